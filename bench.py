@@ -7,7 +7,9 @@ Every rank runs its own independent synthetic 1080p stream (weak scaling, no dat
 stream).  A step = one pass of the hot path over one batch of `--batch` consecutive frames: stretch-resize
 + /255, Darknet, decode, NMS, class mask, crop + ReID CNN, Kalman / cost / Hungarian association, int32 outputs.
 Rank 0 prints ONE JSON line:
-  value               frames/s with the frames already resident in HBM when the timed region starts (the contract's metric)
+  value               frames/s with the frames already resident in HBM when the timed region starts (the contract's metric);
+                      ms_per_step = the milliseconds of one timed step.  A plain run measures only this: set-up (plan-time conv
+                      autotune, schedule trial), W warm-up steps, K timed steps, the line.  Every field below needs --full
   value_with_upload   the same K steps with the frames handed over as pinned HOST memory and uploaded inside the step
                       (yds_pipeline_step_host: copy stream, double buffered) - the PCIe-inclusive rate
   value_other_schedule  the same K steps under the other stream schedule (config.schedule names the one `value` ran under:
@@ -31,6 +33,8 @@ Rank 0 prints ONE JSON line:
   roofline_f32        the same record for the value_f32_math leg (exact fp32 MFMA kernels, the reference's own arithmetic)
                       against the fp32-input MFMA peak of 157.3 TFLOP/s
   cpu_baseline        the oracle pipeline (C + OpenMP / BLAS) on the host cores over a bounded sample of the same stream
+--dump-outputs DIR writes the int32 result rows of the last timed step as float64 .npy files; the inputs are seeded (same
+arguments, same inputs), so that two builds can be compared output for output.
 N > 1: every rank runs its own stream (cfg4 = cfg3 per rank, seeds = rank); after each step the ranks all-gather their
 result rows ({count, rows[256][6]} per frame, RCCL through libydsort's yds_comm_*) so rank 0 holds every stream's output.
 """
@@ -64,9 +68,10 @@ def cpu_baseline(config, n_frames):
     return rec
 
 
-def timed_steps(wl, ranks, sync, K, W, first, host_frames, lookahead=True, keep=None, own=None):
+def timed_steps(wl, ranks, sync, K, W, first, host_frames, lookahead=True, keep=None, own=None, last=None):
     """W untimed warm-up steps, then exactly K timed steps bracketed by barrier + device sync; max over ranks.
-    Every step ends with the exchange step of the multi-GPU run: the all-gather of this batch's result rows (no-op for one rank)."""
+    Every step ends with the exchange step of the multi-GPU run: the all-gather of this batch's result rows (no-op for one rank).
+    last: a dict that receives the gathered rows of the last timed step (key "streams")."""
     for i in range(first, first + W):
         wl.step(i, prefetch=lookahead and i + 1 < first + W, host_frames=host_frames, prefetch2=i + 2 < first + W)   # nothing of the timed region is enqueued before the clock starts
     sync()
@@ -80,12 +85,31 @@ def timed_steps(wl, ranks, sync, K, W, first, host_frames, lookahead=True, keep=
         n_out += sum(0 if o is None else len(o) for st in streams for o in st)
         if keep is not None:
             keep.append(streams)
+        if last is not None:
+            last["streams"] = streams
     sync()
     if own is not None:
         own["dt"] = time.perf_counter() - t0        # this rank's own K steps (before the closing barrier)
     ranks.barrier()
     sync()
     return ranks.max_over_ranks(time.perf_counter() - t0), n_out
+
+
+def dump_outputs(path, streams):
+    """--dump-outputs: the result rows one timed step returned ([stream][frame] -> int32 [n, 6] or None) as float64 arrays."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    counts = np.full((len(streams), max(len(st) for st in streams)), -1.0)
+    rows = [np.zeros((0, 8))]
+    for s, frames in enumerate(streams):
+        for f, o in enumerate(frames):
+            if o is None:
+                continue
+            o = np.asarray(o, np.int32).reshape(-1, 6)
+            counts[s, f] = len(o)
+            rows.append(np.concatenate([np.tile([float(s), float(f)], (len(o), 1)), o.astype(np.float64)], 1))
+    np.save(os.path.join(path, "track_rows.npy"), np.concatenate(rows, 0))
+    np.save(os.path.join(path, "track_counts.npy"), counts)
 
 
 class _ClipCapture:
@@ -300,13 +324,21 @@ def main():
     ap.add_argument("--half", action="store_true", help="Darknet.half(): single-term fp16 kernels (reported under dtype f16)")
     ap.add_argument("--math", default="f16x3", choices=["f16x3", "f32"], help="conv arithmetic of the WHOLE run: f16x3 (default: split-fp16 operands, exact products, "
                                                                               "fp32 accumulate) or f32 (exact fp32 MFMA kernels; profiles of the value_f32_math leg)")
-    ap.add_argument("--weights", default=os.environ.get("YDS_WEIGHTS"), help="a real Darknet .weights file of the config's network (weights/yolov3.weights ...): adds the "
+    ap.add_argument("--weights", default=os.environ.get("YDS_WEIGHTS"), help="a real Darknet .weights file of the config's network (weights/yolov3.weights ...): adds (with --full) the "
                                                                             "UN-INJECTED leg value_real_weights (SURVEY 8d 'Weights'): same steps, the detector sees what it sees")
     ap.add_argument("--ckpt", default=os.environ.get("YDS_CKPT"), help="a real DeepSORT ckpt.t7 for that leg (default: the synthetic state dict)")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement: upload-inclusive and other-schedule legs, roofline / "
+                                                        "per-kernel records, power experiment, frame-by-frame and VideoDetector legs, f32 and half "
+                                                        "modes, --weights leg, CPU baseline, rank 0 alone (N > 1).  Without it a run sets up, warms "
+                                                        "up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the timed path returned in its LAST timed step: "
+                                                                      "DIR/track_rows.npy (float64 [rows, 8]: stream, frame, x1, y1, x2, y2, "
+                                                                      "track id, class - every int32 row of every frame) and DIR/track_counts.npy "
+                                                                      "(float64 [streams, frames]: rows per frame, -1 where the frame returned None)")
     args = ap.parse_args()
 
-    # `python bench.py --gpus N` on its own launches the N ranks itself (one process per GPU, rendezvous on 127.0.0.1);
-    # under torch.distributed.run (the driver's launch line) WORLD_SIZE is already set and this is one of the ranks
+    # `python bench.py --gpus N` on its own launches the N ranks itself (one process per GPU, rendezvous on 127.0.0.1) as a child
+    # process; under torch.distributed.run (the driver's launch line) WORLD_SIZE is already set and this is one of the ranks
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
         with socket.socket() as so:
@@ -314,7 +346,7 @@ def main():
             port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.call(cmd))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if world_env != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}; launch one rank per GPU")
@@ -367,7 +399,7 @@ def main():
     #      itself: efficiency_vs_rank0_single = value / (N x this rate).  It runs on a workload OF ITS OWN (same construction, same seed):
     #      the job's stream and tracker state must start untouched - every stream's rows equal a single-rank run of its seed bit for bit.
     solo = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             w1 = Workload(args.config, B, seed=ranks.stream_seed(args.seed_base), half=args.half)
             w1.to_device()
@@ -402,9 +434,11 @@ def main():
         ranks.shutdown()
         raise SystemExit(3)
     kept = [] if args.dump_rows else None
-    own = {}
-    dt, n_out = timed_steps(wl, ranks, sync, K, W, n_set, host_frames=False, keep=kept, own=own)     # n_out: rows of ALL streams (gathered on every rank)
+    own, last = {}, {}
+    dt, n_out = timed_steps(wl, ranks, sync, K, W, n_set, host_frames=False, keep=kept, own=own, last=last)     # n_out: rows of ALL streams (gathered on every rank)
     dt_own = own["dt"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["streams"])
     clock_ghz, clock_ms = 0.0, 0.0
     if kept is not None and rank == 0:
         import numpy as np
@@ -427,7 +461,7 @@ def main():
     # ---- the same steps with the frames coming from pinned host memory (PCIe inside the timed region)
     dt_up, trial_up = None, None
     base = n_set + W + K
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         n_up, trial_up = settle_schedule(wl, base, True)
         base += n_up
         dt_up, _ = timed_steps(wl, ranks, sync, K, W, base, host_frames=True)
@@ -436,7 +470,7 @@ def main():
 
     # ---- the same K steps under the OTHER schedule (results are identical; the line carries both rates)
     other = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         wl.pipe.set_schedule(-1 if schedule == "serialized" else 0)
         dt_o, _ = timed_steps(wl, ranks, sync, K, W, base, host_frames=False)
         other = {"schedule": wl.pipe.last_schedule(), "value": round(ranks.total_frames(K, B) / dt_o, 2)}
@@ -444,7 +478,7 @@ def main():
         base += W + K
 
     roofline, variants = None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (every rank runs the leg - its steps contain the exchange step - rank 0 reports)
         f16x3 = lib.yds_get_conv_math() == 1 and not args.half
         peak = PEAK_F16_MFMA_TFLOPS / 3 if f16x3 else (PEAK_F16_MFMA_TFLOPS if args.half else PEAK_F32_MFMA_TFLOPS)
@@ -484,7 +518,7 @@ def main():
     # ---- power experiment: the dominant layer alone, random operands vs operands that never toggle (same binary, same instruction
     #      stream; the chip is power limited)
     power = None
-    if rank == 0 and not args.no_roofline and not args.half and math_name != "f32":
+    if rank == 0 and args.full and not args.no_roofline and not args.half and math_name != "f32":
         import ctypes as C
         shape = (76, 76, 128, 256, 3, 1, 1, 0)
         rec = {}
@@ -501,7 +535,7 @@ def main():
 
     # ---- frame by frame: batch_frames = 1 (the reference's loop: one frame in, one result out)
     fbf, fbf_ahead, fbf_stage = None, None, None
-    if args.latency_steps > 0 and not args.half:
+    if args.full and args.latency_steps > 0 and not args.half:
         wl1 = Workload(args.config, 1, seed=ranks.stream_seed(args.seed_base), n_distinct=64)
         wl1.to_device()
         n1 = args.latency_steps
@@ -515,7 +549,7 @@ def main():
 
     # ---- the generator: VideoDetector.detect as the unchanged demo drives it (default arguments, shim import paths, BGR result images)
     vd_fps, vd_rec, vd_host_fps, vd_host_rec = None, None, None, None
-    if args.latency_steps > 0 and not args.half and world == 1 and math_name != "f32":
+    if args.full and args.latency_steps > 0 and not args.half and world == 1 and math_name != "f32":
         try:
             vd_fps, vd_rec = video_detector_leg(args.config, B, ranks.stream_seed(args.seed_base), 40 * B, device_overlay=True)
             vd_host_fps, vd_host_rec = video_detector_leg(args.config, B, ranks.stream_seed(args.seed_base), 4 * B, device_overlay=False)
@@ -526,7 +560,7 @@ def main():
     # ---- exact-fp32 kernels (the reference's own arithmetic), short run; the network is re-planned: tensor formats depend on the
     #      conv math.  Its roofline block is measured like the default one, against the fp32-input MFMA peak.
     f32_fps, roofline_f32 = None, None
-    if not args.no_extras and not args.half and math_name != "f32":
+    if args.full and not args.no_extras and not args.half and math_name != "f32":
         del wl
         gc.collect()                                               # (the handles sit in reference cycles: free the device buffers NOW - a crowd workload is ~80 GB)
         sync()
@@ -556,7 +590,7 @@ def main():
     # ---- Darknet.half() (ImageDetector(half=True), img_detect.py:49-50): single-term fp16 operands AND 2-byte activations in the
     #      detector; fp16-class accuracy, never the metric - reported so that the half / default ratio comes from one box and one run
     half_fps, half_err = None, None
-    if not args.no_extras and not args.half and math_name != "f32":
+    if args.full and not args.no_extras and not args.half and math_name != "f32":
         # A side leg: its failure must not cost the line its metric.  The part that can fail per rank (building the half-mode network: memory,
         # a format check) runs first; the ranks then VOTE, and only if every rank built its workload do they enter timed_steps, whose
         # barriers and gathers are collectives - a rank skipping them alone would leave its peers blocked.
@@ -582,7 +616,7 @@ def main():
 
     # ---- the un-injected leg (SURVEY 8d "Weights"): real .weights / ckpt.t7 files, nothing written into the head tensors
     real, real_err = None, None
-    if args.weights:
+    if args.full and args.weights:
         wlr, dtr = None, None
         try:
             if not os.path.exists(args.weights) or (args.ckpt and not os.path.exists(args.ckpt)):
@@ -614,7 +648,7 @@ def main():
         sync()
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:      # rank 0 at N = 1 only (bench contract)
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:      # rank 0 at N = 1 only (bench contract)
         cpu = cpu_baseline("cfg3" if args.config == "cfg4" else args.config, args.cpu_frames)
 
     if rank == 0:
@@ -635,35 +669,38 @@ def main():
                                 "between the returns of the step call) under either schedule on this box, per rank; `schedule` is what the timed steps then ran under",
                            per_rank=trial, with_upload=trial_up, set_up_steps=n_set),
                        **ranks.describe()},
-            "value_definition": "frames resident in HBM when the timed region starts (bench contract); value_with_upload is the PCIe-inclusive rate",
-            "value_with_upload": None if dt_up is None else round(frames_total / dt_up, 2),
-            "value_with_upload_schedule": None if dt_up is None else schedule_up,
-            "value_with_upload_note": "same K steps, frames handed over as pinned host memory and uploaded inside the timed region (copy stream, three staging buffers, each batch announced two steps ahead like a decoder queue)",
-            "value_other_schedule": other,
-            "value_f32_math": None if f32_fps is None else round(f32_fps, 2),
-            "value_half_mode": None if half_fps is None else round(half_fps, 2),
-            **({"value_half_mode_error": half_err} if half_err else {}),
-            "value_half_mode_note": "Darknet.half(): detector on single-term fp16 operands with 2-byte activations (the reference's ImageDetector(half=True)); fp16-class accuracy, not the metric",
-            **({"value_real_weights": real} if args.weights else {}), **({"value_real_weights_error": real_err} if real_err else {}),
-            "value_frame_by_frame": None if fbf is None else round(fbf, 2),
-            "value_frame_by_frame_lookahead1": None if fbf_ahead is None else round(fbf_ahead, 2),
-            "value_frame_by_frame_note": "batch_frames = 1: one frame in, one result out, nothing enqueued ahead (video_detect.py:124-157); "
-                                         "lookahead1 = the next frame is handed over one step early (its detector pass overlaps this frame's association)",
-            "stage_us_frame_by_frame": None if fbf_stage is None else {k: round(v, 1) for k, v in fbf_stage.items()},
-            "value_video_detector": None if vd_fps is None else round(vd_fps, 2),
-            "value_video_detector_note": "VideoDetector.detect exactly as the unchanged demo calls it (video_deepsort.py:13-45: reference import paths, default "
-                                         "arguments, no batch_frames keyword) on a file-like source serving 1080p BGR frames from memory: read-ahead "
-                                         "batching by default (the reference decodes 128 frames ahead, video_detect.py:86), frames uploaded inside, "
-                                         "overlay + RGB->BGR + FPS text on the device, every BGR result image delivered to the consumer",
-            "video_detector": vd_rec,
-            "value_video_detector_host_overlay": None if vd_host_fps is None else round(vd_host_fps, 2),
-            "video_detector_host_overlay": vd_host_rec,
+            "value_definition": "frames resident in HBM when the timed region starts (bench contract); value_with_upload (--full) is the PCIe-inclusive rate",
             "exchange": None if world == 1 else "all-gather of {count, rows[256][6]} per frame per rank after every step (%s)" % (
                 "RCCL via yds_comm_*" if ranks.comm is not None else ("gloo" + (f"; RCCL unavailable: {ranks.fallback_reason}" if ranks.fallback_reason else ""))),
             "stage_us_last_step": {k: round(v, 1) for k, v in stage.items()},
             "algorithmic_gflop_per_frame": round(flops_frame / 1e9, 2),
-            "roofline": roofline, "roofline_f32": roofline_f32, "power_experiment": power, "conv_variants": variants, "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update({
+                "value_with_upload": None if dt_up is None else round(frames_total / dt_up, 2),
+                "value_with_upload_schedule": None if dt_up is None else schedule_up,
+                "value_with_upload_note": "same K steps, frames handed over as pinned host memory and uploaded inside the timed region (copy stream, three staging buffers, each batch announced two steps ahead like a decoder queue)",
+                "value_other_schedule": other,
+                "value_f32_math": None if f32_fps is None else round(f32_fps, 2),
+                "value_half_mode": None if half_fps is None else round(half_fps, 2),
+                **({"value_half_mode_error": half_err} if half_err else {}),
+                "value_half_mode_note": "Darknet.half(): detector on single-term fp16 operands with 2-byte activations (the reference's ImageDetector(half=True)); fp16-class accuracy, not the metric",
+                **({"value_real_weights": real} if args.weights else {}), **({"value_real_weights_error": real_err} if real_err else {}),
+                "value_frame_by_frame": None if fbf is None else round(fbf, 2),
+                "value_frame_by_frame_lookahead1": None if fbf_ahead is None else round(fbf_ahead, 2),
+                "value_frame_by_frame_note": "batch_frames = 1: one frame in, one result out, nothing enqueued ahead (video_detect.py:124-157); "
+                                             "lookahead1 = the next frame is handed over one step early (its detector pass overlaps this frame's association)",
+                "stage_us_frame_by_frame": None if fbf_stage is None else {k: round(v, 1) for k, v in fbf_stage.items()},
+                "value_video_detector": None if vd_fps is None else round(vd_fps, 2),
+                "value_video_detector_note": "VideoDetector.detect exactly as the unchanged demo calls it (video_deepsort.py:13-45: reference import paths, default "
+                                             "arguments, no batch_frames keyword) on a file-like source serving 1080p BGR frames from memory: read-ahead "
+                                             "batching by default (the reference decodes 128 frames ahead, video_detect.py:86), frames uploaded inside, "
+                                             "overlay + RGB->BGR + FPS text on the device, every BGR result image delivered to the consumer",
+                "video_detector": vd_rec,
+                "value_video_detector_host_overlay": None if vd_host_fps is None else round(vd_host_fps, 2),
+                "video_detector_host_overlay": vd_host_rec,
+                "roofline": roofline, "roofline_f32": roofline_f32, "power_experiment": power, "conv_variants": variants, "cpu_baseline": cpu,
+            })
         print(json.dumps(line))
     ranks.shutdown()
 

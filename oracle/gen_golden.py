@@ -3,8 +3,9 @@
 Run in the build container only (needs /root/reference):
     python -m oracle.gen_golden [name ...]
 Every fixture stores inputs (or the seed that regenerates them through
-yolo_deepsort_amd.synth) and the reference's outputs.  Nothing from the
-reference tree is copied; it is imported through oracle/ref_harness.py.
+yolo_deepsort_amd.synth) and the reference's outputs.  No program text of the
+reference is copied (its network cfg files, settings only, are stored as test
+inputs under tests/golden/cfg/); it is imported through oracle/ref_harness.py.
 """
 
 import importlib
@@ -215,6 +216,57 @@ def gen_cfg_parse(ns):
     with open(os.path.join(GOLD, "cfg_parse.json"), "w") as f:
         json.dump(out, f, separators=(",", ":"))
     print("  wrote cfg_parse.json")
+
+
+CFG_FILES = ("yolov3", "yolov3-tiny", "yolov4", "yolov4-tiny")
+
+
+def gen_cfg_files(ns):
+    """The reference's own network cfg files (settings only, comments and spacing as shipped), stored as test inputs under
+    tests/golden/cfg/ so that the parse test of cfg_parse.json runs without the reference tree."""
+    os.makedirs(os.path.join(GOLD, "cfg"), exist_ok=True)
+    for name in CFG_FILES:
+        with open(os.path.join(ref_harness.REF_ROOT, "config", name + ".cfg")) as f:
+            text = f.read()
+        with open(os.path.join(GOLD, "cfg", name + ".cfg"), "w") as f:
+            f.write(text)
+    print("  wrote cfg/*.cfg")
+
+
+def public_signatures():
+    """Parameter names and defaults (repr) of the drop-in boundary, read with inspect from whichever yolo3 / deep_sort packages
+    are importable: the reference's under import_reference(), the repo's own drop-in packages otherwise."""
+    import inspect
+    import yolo3.detect.video_detect as a, yolo3.detect.img_detect as b, deep_sort as c, yolo3.models as d
+    import deep_sort.sort.nn_matching as e, deep_sort.sort.tracker as f, deep_sort.sort.kalman_filter as k
+    import deep_sort.sort.linear_assignment as la, yolo3.utils.model_build as mb, deep_sort.sort.preprocessing as pp
+    import deep_sort.sort.detection as dt
+
+    def sig(fn):
+        return [[p.name, repr(p.default) if p.default is not inspect.Parameter.empty else "<req>"] for p in inspect.signature(fn).parameters.values()]
+    return {
+        "VideoDetector.__init__": sig(a.VideoDetector.__init__), "VideoDetector.detect": sig(a.VideoDetector.detect),
+        "ImageDetector.__init__": sig(b.ImageDetector.__init__), "ImageDetector.detect": sig(b.ImageDetector.detect),
+        "DeepSort.__init__": sig(c.DeepSort.__init__), "DeepSort.update": sig(c.DeepSort.update),
+        "Darknet.__init__": sig(d.Darknet.__init__), "Darknet.load_darknet_weights": sig(d.Darknet.load_darknet_weights),
+        "Darknet.save_darknet_weights": sig(d.Darknet.save_darknet_weights),
+        "NNMetric.__init__": sig(e.NearestNeighborDistanceMetric.__init__), "NNMetric.distance": sig(e.NearestNeighborDistanceMetric.distance),
+        "NNMetric.partial_fit": sig(e.NearestNeighborDistanceMetric.partial_fit),
+        "Tracker.__init__": sig(f.Tracker.__init__), "Tracker.update": sig(f.Tracker.update), "Tracker.predict": sig(f.Tracker.predict),
+        "KalmanFilter.gating_distance": sig(k.KalmanFilter.gating_distance), "KalmanFilter.update": sig(k.KalmanFilter.update),
+        "min_cost_matching": sig(la.min_cost_matching), "gate_cost_matrix": sig(la.gate_cost_matrix),
+        "soft_non_max_suppression": sig(mb.soft_non_max_suppression), "bbox_iou": sig(mb.bbox_iou), "resize_boxes": sig(mb.resize_boxes),
+        "non_max_suppression": sig(pp.non_max_suppression), "Detection.__init__": sig(dt.Detection.__init__),
+    }
+
+
+def gen_signatures(ns):
+    """Public constructor / method signatures of the reference (names, order, defaults) under the oracle's shims."""
+    import yolo3.models as chk
+    assert chk.__file__.startswith(ref_harness.REF_ROOT)
+    with open(os.path.join(GOLD, "ref_signatures.json"), "w") as f:
+        json.dump(public_signatures(), f, indent=0)
+    print("  wrote ref_signatures.json")
 
 
 def gen_mini_darknet(ns):
@@ -1139,6 +1191,22 @@ def gen_action(ns):
     with open(os.path.join(GOLD, "action_trace.json"), "w") as f:
         json.dump(dict(frames=out, none_returns_none=none_case is None), f)
     print("    action events:", sum(len(o) for o in out))
+    # the position-only action set (no speed test), same scene and clock
+    time.time = fake_time
+    try:
+        A = rai.ActionIdentify(action_set_positional(ra), max_age=3, max_size=4)
+        out = [[[int(a), int(b), str(c)] for a, b, c in A.update(det)] for det in action_scene()]
+        none_case = A.update(None)
+    finally:
+        time.time = real
+    with open(os.path.join(GOLD, "action_trace_positional.json"), "w") as f:
+        json.dump(dict(frames=out, none_returns_none=none_case is None), f)
+    print("    positional action events:", sum(len(o) for o in out))
+
+
+def action_set_positional(mod):
+    """TakeOff / Landing / Glide / BreakInto instances of the action module `mod` (reference's or the repo's)."""
+    return [mod.TakeOff(0, (1, 2)), mod.Landing(0, (1, 2)), mod.Glide(0, (2, 4)), mod.BreakInto(0, 2), mod.BreakInto(2, 1)]
 
 
 # ---- wide dynamic range (VERDICT r5 'next' #2): BatchNorm statistics over decades, black / saturated inputs --------------------
@@ -1464,7 +1532,7 @@ def _ref_darknet_profile(ns, cfg_text, img_size, seed, obj_bias):
 
 ALL = dict(long_stream=gen_long_stream, wide=gen_wide_range, wide_mish=gen_wide_mish, rect=gen_rect, video_detect=gen_video_detect, action=gen_action, bench_shape=gen_bench_shape, options=gen_track_options, tiled=gen_tiled, cfg_parse=gen_cfg_parse, mini=gen_mini_darknet, tiny416=gen_tiny416, full608=gen_full608,
            nms=gen_nms, plumbing=gen_detect_plumbing, reid=gen_reid, kalman=gen_kalman,
-           traces=gen_track_traces)
+           traces=gen_track_traces, cfg_files=gen_cfg_files, signatures=gen_signatures)
 
 
 def main(argv):

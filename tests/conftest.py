@@ -13,7 +13,6 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "ref: needs /root/reference (build container only)")
 
 
 def golden(name):
@@ -23,10 +22,6 @@ def golden(name):
 @pytest.fixture(scope="session")
 def gold():
     return golden
-
-
-def has_reference():
-    return os.path.isdir("/root/reference/yolo3")
 
 
 TRACE_PARAMS = dict(max_dist=0.3, nn_budget=30, n_init=3, max_iou_distance=0.7, max_age=30)

@@ -58,7 +58,7 @@ def test_two_ranks_use_two_gpus():
     """bench.py --gpus 2 launches itself under torch.distributed.run; each rank must sit on its own GPU."""
     if _lib.load().yds_device_count() < 2:
         pytest.skip("needs 2 GPUs (the driver's 8-GPU node runs the scaling bench)")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-frames", "0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--cpu-frames", "0",
                           "--no-roofline"], capture_output=True, text=True, timeout=1200)
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and len(set(line["config"]["rank_pci_bus_ids"])) == 2, line
@@ -66,11 +66,38 @@ def test_two_ranks_use_two_gpus():
 
 
 def _bench(tmp, extra, env=None, launcher=None):
-    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py")] + extra + ["--cpu-frames", "0", "--no-extras", "--no-roofline", "--latency-steps", "0"]
+    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, "bench.py")] + extra + ["--full", "--cpu-frames", "0", "--no-extras", "--no-roofline", "--latency-steps", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env or os.environ)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-500:] + out.stderr[-1500:]          # rank 0 prints ONE line
     return json.loads(lines[0])
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A run without --full measures the headline only; --dump-outputs holds the rows its LAST timed step returned (the same rows
+    --dump-rows records for that step)."""
+    import numpy as np
+    outs, rows = tmp_path / "outs", str(tmp_path / "rows.npz")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "cfg2", "--steps", "3", "--warmup", "1", "--batch", "4",
+           "--dump-rows", rows, "--dump-outputs", str(outs)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stdout[-500:] + out.stderr[-1500:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "frames/s" and line["dtype"] == "f16x3" and line["config"]["frames_per_step"] == 4
+    assert abs(line["ms_per_step"] - 4e3 / line["value"]) < 1e-2 * line["ms_per_step"]
+    assert not {"roofline", "cpu_baseline", "value_with_upload", "value_frame_by_frame", "value_video_detector"} & set(line)
+    r, c = np.load(outs / "track_rows.npy"), np.load(outs / "track_counts.npy")
+    assert r.dtype == c.dtype == np.float64 and r.shape[1] == 8 and c.shape == (1, 4) and r.shape[0] > 0
+    g = np.load(rows)
+    for f in range(4):
+        want = g[f"s0_k2_f{f}"]
+        if c[0, f] < 0:
+            assert np.array_equal(want, np.full((1, 6), -1, np.int32))
+        else:
+            got = r[r[:, 1] == f]
+            assert len(got) == c[0, f] and (got[:, 0] == 0).all() and np.array_equal(got[:, 2:].astype(np.int32), want), f
 
 
 def test_two_rank_bench_path_on_one_gpu(tmp_path):
@@ -153,7 +180,7 @@ def test_rccl_failure_fails_the_multi_gpu_bench(tmp_path):
     env.pop("YDS_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29583",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "cfg4", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--cpu-frames", "0", "--no-extras", "--no-roofline", "--latency-steps", "0"]
+           "--full", "--cpu-frames", "0", "--no-extras", "--no-roofline", "--latency-steps", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode != 0, out.stdout[-500:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@ import tempfile
 import numpy as np
 import pytest
 
-from conftest import ROOT, has_reference
+from conftest import ROOT
 from yolo_deepsort_amd import cfgs, loaders, synth
 
 
@@ -120,39 +120,28 @@ def test_head_injection_decodes_back_to_boxes():
         np.testing.assert_allclose(box, want, rtol=2e-3, atol=0.05)
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not has_reference(), reason="reference tree not present")
-def test_action_module_matches_reference():
-    code = r'''
-import sys, numpy as np
-sys.path.insert(0, %r)
-from oracle import ref_harness
-from yolo_deepsort_amd import action as mine
-ref_harness.install_shims()
-sys.path.insert(0, ref_harness.REF_ROOT)
-for k in [k for k in sys.modules if k.split(".")[0] == "action"]:
-    del sys.modules[k]
-import action.action_Identify as rai, action.actions as ra
-assert ra.__file__.startswith(ref_harness.REF_ROOT)
-def mk(mod):
-    return [mod.TakeOff(0, (1, 2)), mod.Landing(0, (1, 2)), mod.Glide(0, (2, 4)), mod.BreakInto(0, 2), mod.BreakInto(2, 1)]
-A = rai.ActionIdentify(mk(ra), max_age=3, max_size=4)
-B = mine.ActionIdentify(mk(mine), max_age=3, max_size=4)
-rng = np.random.RandomState(0)
-pos = rng.randint(0, 500, (6, 2)).astype(float)
-vel = rng.randint(-6, 7, (6, 2)).astype(float)
-for t in range(40):
-    pos += vel
-    if t %% 7 == 0: vel = rng.randint(-6, 7, (6, 2)).astype(float)
-    vis = [i for i in range(6) if rng.rand() > 0.25]
-    det = np.array([[pos[i, 0], pos[i, 1], pos[i, 0] + 20, pos[i, 1] + 40, i + 1, (i %% 2) * 2] for i in vis], np.int32).reshape(-1, 6)
-    ra_out, rb_out = A.update(det), B.update(det)
-    assert [(int(a), int(b), c) for a, b, c in ra_out] == [(int(a), int(b), c) for a, b, c in rb_out], (t, ra_out, rb_out)
-assert A.update(None) is None and B.update(None) is None
-print("OK")
-''' % ROOT
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "OK" in out.stdout, out.stderr[-2000:]
+def test_action_module_matches_reference(monkeypatch):
+    """action/ against the reference's ActionIdentify on the position-only action set (TakeOff, Landing, Glide, BreakInto), 40
+    frames of scripted tracker rows: the reference's trace is recorded by oracle/gen_golden.py (same scene, stepped clock)."""
+    import json
+    import time
+    from conftest import GOLD
+    from oracle.gen_golden import action_scene, action_set_positional
+    from yolo_deepsort_amd import action as mine
+    want = json.load(open(os.path.join(GOLD, "action_trace_positional.json")))
+    tick = [1000.0]
+
+    def fake_time():
+        tick[0] += 0.04
+        return tick[0]
+    monkeypatch.setattr(time, "time", fake_time)
+    B = mine.ActionIdentify(action_set_positional(mine), max_age=3, max_size=4)
+    frames = action_scene()
+    assert len(want["frames"]) == len(frames) == 40 and sum(map(len, want["frames"])) > 0
+    for t, det in enumerate(frames):
+        got = [[int(a), int(b), str(c)] for a, b, c in B.update(det)]
+        assert got == want["frames"][t], (t, got, want["frames"][t])
+    assert want["none_returns_none"] and B.update(None) is None
 
 
 def test_two_rank_gloo_stream_sharding():
@@ -321,61 +310,33 @@ def test_reference_import_paths_resolve_without_a_gpu():
     np.testing.assert_allclose(bbox_iou(np.array([[0., 0., 9., 9.]]), np.array([[5., 5., 14., 14.]])), [25. / 175.])
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not has_reference(), reason="reference tree not present")
 def test_public_signatures_match_the_reference():
     """Constructor / method parameter names (and defaults) of the drop-in classes vs the reference's, read with inspect from the
-    reference sources imported under the oracle's shims."""
+    reference sources imported under the oracle's shims (tests/golden/ref_signatures.json, oracle/gen_golden.py)."""
+    import json
+    from conftest import GOLD
     code = r'''
-import inspect, sys
+import json, sys
 sys.path.insert(0, %r)
-from oracle import ref_harness
-ref_harness.install_shims()
-import importlib
-def sig(f):
-    return [(p.name, p.default if p.default is not inspect._empty else "<req>") for p in inspect.signature(f).parameters.values()]
-mine = {}
-import yolo3.detect.video_detect as a, yolo3.detect.img_detect as b, deep_sort as c, yolo3.models as d, deep_sort.sort.nn_matching as e, deep_sort.sort.tracker as f
-import deep_sort.sort.kalman_filter as k, deep_sort.sort.linear_assignment as la, yolo3.utils.model_build as mb, deep_sort.sort.preprocessing as pp
-assert a.__file__.startswith(%r)
-def collect():
-    import yolo3.detect.video_detect as a, yolo3.detect.img_detect as b, deep_sort as c, yolo3.models as d, deep_sort.sort.nn_matching as e, deep_sort.sort.tracker as f
-    import deep_sort.sort.kalman_filter as k, deep_sort.sort.linear_assignment as la, yolo3.utils.model_build as mb, deep_sort.sort.preprocessing as pp
-    import deep_sort.sort.detection as dt
-    return {
-        "VideoDetector.__init__": sig(a.VideoDetector.__init__), "VideoDetector.detect": sig(a.VideoDetector.detect),
-        "ImageDetector.__init__": sig(b.ImageDetector.__init__), "ImageDetector.detect": sig(b.ImageDetector.detect),
-        "DeepSort.__init__": sig(c.DeepSort.__init__), "DeepSort.update": sig(c.DeepSort.update),
-        "Darknet.__init__": sig(d.Darknet.__init__), "Darknet.load_darknet_weights": sig(d.Darknet.load_darknet_weights),
-        "Darknet.save_darknet_weights": sig(d.Darknet.save_darknet_weights),
-        "NNMetric.__init__": sig(e.NearestNeighborDistanceMetric.__init__), "NNMetric.distance": sig(e.NearestNeighborDistanceMetric.distance),
-        "NNMetric.partial_fit": sig(e.NearestNeighborDistanceMetric.partial_fit),
-        "Tracker.__init__": sig(f.Tracker.__init__), "Tracker.update": sig(f.Tracker.update), "Tracker.predict": sig(f.Tracker.predict),
-        "KalmanFilter.gating_distance": sig(k.KalmanFilter.gating_distance), "KalmanFilter.update": sig(k.KalmanFilter.update),
-        "min_cost_matching": sig(la.min_cost_matching), "gate_cost_matrix": sig(la.gate_cost_matrix),
-        "soft_non_max_suppression": sig(mb.soft_non_max_suppression), "bbox_iou": sig(mb.bbox_iou), "resize_boxes": sig(mb.resize_boxes),
-        "non_max_suppression": sig(pp.non_max_suppression), "Detection.__init__": sig(dt.Detection.__init__),
-    }
-mine = collect()
-for key in [m for m in sys.modules if m.split(".")[0] in ("yolo3", "deep_sort", "action")]:
-    del sys.modules[key]
-sys.path.insert(0, ref_harness.REF_ROOT)
-ref = collect()
+from oracle.gen_golden import public_signatures
 import yolo3.models as chk
-assert chk.__file__.startswith(ref_harness.REF_ROOT)
-extra_ok = {"VideoDetector.__init__": {"batch_frames", "device_overlay"}, "DeepSort.__init__": {"metric"}, "Darknet.__init__": {"batch_max", "cfg_text"},
-            "Darknet.load_darknet_weights": {"blob"}}
-for name, r in ref.items():
-    m = mine[name]
-    if name == "VideoDetector.__init__":                      # (cv2.VideoWriter_fourcc('m','p','4','v') in the reference; the string here)
-        m = [(n, "mp4v" if n == "fourcc" else d) for n, d in m]
-        r = [(n, "mp4v" if n == "fourcc" else d) for n, d in r]
-    assert m[:len(r)] == r, (name, m, r)                      # same names, order and defaults; additions only at the end
-    assert {n for n, _ in m[len(r):]} <= extra_ok.get(name, set()), (name, m[len(r):])
-print("OK", len(ref))
+assert chk.__file__.startswith(%r)
+print(json.dumps(public_signatures()))
 ''' % (ROOT, ROOT)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "OK" in out.stdout, out.stdout[-1500:] + out.stderr[-3000:]
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    mine = json.loads(out.stdout.splitlines()[-1])
+    ref = json.load(open(os.path.join(GOLD, "ref_signatures.json")))
+    assert len(ref) == 24 and sorted(mine) == sorted(ref)
+    extra_ok = {"VideoDetector.__init__": {"batch_frames", "device_overlay"}, "DeepSort.__init__": {"metric"}, "Darknet.__init__": {"batch_max", "cfg_text"},
+                "Darknet.load_darknet_weights": {"blob"}}
+    for name, r in ref.items():
+        m = mine[name]
+        if name == "VideoDetector.__init__":                      # (cv2.VideoWriter_fourcc('m','p','4','v') in the reference; the string here)
+            m = [[n, "'mp4v'" if n == "fourcc" else d] for n, d in m]
+            r = [[n, "'mp4v'" if n == "fourcc" else d] for n, d in r]
+        assert m[:len(r)] == r, (name, m, r)                      # same names, order and defaults; additions only at the end
+        assert {n for n, _ in m[len(r):]} <= extra_ok.get(name, set()), (name, m[len(r):])
 
 
 def test_checkpoint_reader_refuses_out_of_bounds_tensor_geometry():
@@ -772,3 +733,16 @@ def test_auto_batch_follows_the_clip_length_and_sclk_parsing(tmp_path):
     assert s.ghz() == 2.0                                   # the sleep state between legs is not a sample of the loaded clock
     s.path = str(tmp_path / "absent")
     assert s._read() is None
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: every int32 row of a step's frames (stream, frame prepended) and the rows per frame (-1 = None)."""
+    import bench
+    streams = [[np.array([[1, 2, 3, 4, 7, 0]], np.int32), None, np.zeros((0, 6), np.int32)],
+               [np.arange(12, dtype=np.int32).reshape(2, 6), None, None]]
+    bench.dump_outputs(str(tmp_path / "o"), streams)
+    r = np.load(tmp_path / "o" / "track_rows.npy")
+    c = np.load(tmp_path / "o" / "track_counts.npy")
+    assert r.dtype == c.dtype == np.float64
+    assert c.tolist() == [[1, -1, 0], [2, -1, -1]]
+    assert r.tolist() == [[0, 0, 1, 2, 3, 4, 7, 0], [1, 0, 0, 1, 2, 3, 4, 5], [1, 0, 6, 7, 8, 9, 10, 11]]

@@ -50,6 +50,8 @@ def test_init_binds_one_device_per_process(monkeypatch):
     monkeypatch.setattr(_lib, "_bound", None)
     monkeypatch.setenv("LOCAL_RANK", "1")
     monkeypatch.delenv("YDS_DEVICE", raising=False)
+    for k in _lib.VISIBILITY_MASKS:              # (unmasked launch: a mask in the caller's environment would make LOCAL_RANK no ordinal)
+        monkeypatch.delenv(k, raising=False)
     assert _lib.init() == 1                      # rank 1 of torch.distributed.run -> GPU 1
     assert _lib.init() == 1 and _lib.init(1) == 1
     assert fake.calls == [1]                     # what Darknet/Extractor/DeepSort constructors do: no second yds_init

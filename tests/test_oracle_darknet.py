@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLD, golden, has_reference
+from conftest import GOLD, golden
 from oracle.cfg import parse_model_config_text
 from oracle.darknet import DarknetOracle, conv_flops
 from oracle import nms as onms
@@ -140,15 +140,23 @@ def test_rectangular_input_and_the_scale_pairing_quirk():
     assert np.abs(yq[..., 0] * (8.0 / 8.8) - g["quirk_out"][..., 0]).max() > 1.0
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not has_reference(), reason="reference tree not present")
 def test_real_cfg_files_parse_identically():
+    """cfg_parse.json holds what the reference's parser read from its own four cfg files.  The cfg texts this package
+    generates must parse to the same blocks, keys and values - also after the file-format noise the shipped files carry
+    (comment lines, indentation, blanks, spaces around '=' and trailing spaces)."""
+    from yolo_deepsort_amd import loaders
     ref = json.load(open(os.path.join(GOLD, "cfg_parse.json")))
+    assert sorted(ref) == sorted(cfgs.CFG_BUILDERS)
     for name in ref:
-        text = open(f"/root/reference/config/{name}.cfg").read()
-        mine = parse_model_config_text(text)
-        red = [{k: v for k, v in d.items() if k in ref[name][i]} for i, d in enumerate(mine)]
-        assert red == ref[name]
+        text = cfgs.cfg_text(name)
+        noisy = "# " + name + "\n\n" + "\n".join(
+            ("#" + l + "\n" + l + "  ") if l.startswith("[") else ("  " + l.replace("=", " = ", 1) if "=" in l else l)
+            for l in text.split("\n"))
+        for t in (text, noisy):
+            mine = parse_model_config_text(t)
+            assert len(mine) == len(ref[name]) and loaders.parse_model_config(None, text=t) == mine, name
+            red = [{k: v for k, v in d.items() if k in ref[name][i]} for i, d in enumerate(mine)]
+            assert red == ref[name], name
 
 
 def test_tiled_detection_and_merge_quirk():

@@ -1,4 +1,4 @@
-B="python bench.py --cpu-frames 0 --latency-steps 0 --no-roofline --steps 30 --warmup 4"
+B="python bench.py --full --cpu-frames 0 --latency-steps 0 --no-roofline --steps 30 --warmup 4"
 for m in serialized two-stream serialized two-stream; do
   $B --schedule $m > gpurun_out/up_$m.json 2>gpurun_out/up_err.log
   python - <<P

@@ -1,10 +1,10 @@
 #!/bin/bash
 # the bench lines of a round on one box (run on the GPU box): cfg2 / cfg3 / cfg5 + the sustained cfg2 run -> gpurun_out/lines/
 O=gpurun_out/lines; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python bench.py --config cfg3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python bench.py --config cfg5 --steps 20 --warmup 5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-python bench.py --steps 600 --warmup 5 --no-extras --latency-steps 0 --cpu-frames 0 > $O/bench_cfg2_sustained.json 2> $O/bench_cfg2_sustained.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python bench.py --full --config cfg3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python bench.py --full --config cfg5 --steps 20 --warmup 5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+python bench.py --full --steps 600 --warmup 5 --no-extras --latency-steps 0 --cpu-frames 0 > $O/bench_cfg2_sustained.json 2> $O/bench_cfg2_sustained.err
 python - <<'P'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/lines/bench_cfg*.json')):

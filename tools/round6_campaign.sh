@@ -10,10 +10,10 @@ copy() {
 PMC=1 MFMA=1 TIMELINE=1 tools/profile_bench.sh cfg2 $O > $O/log_cfg2.txt 2>&1; copy cfg2
 PMC=1 MFMA=1 tools/profile_bench.sh cfg3 $O > $O/log_cfg3.txt 2>&1; copy cfg3
 MFMA=1 TIMELINE=1 tools/profile_bench.sh cfg5 $O > $O/log_cfg5.txt 2>&1; copy cfg5
-python bench.py --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err; cp $O/bench_cfg2.json profiles/r06_bench_cfg2.json
-python bench.py --config cfg3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err; cp $O/bench_cfg3.json profiles/r06_bench_cfg3.json
-python bench.py --config cfg5 --steps 20 --warmup 5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; cp $O/bench_cfg5.json profiles/r06_bench_cfg5.json
-python bench.py --steps 600 --warmup 5 --no-extras --latency-steps 0 --cpu-frames 0 > $O/bench_cfg2_sustained.json 2> $O/bench_cfg2_sustained.err; cp $O/bench_cfg2_sustained.json profiles/r06_bench_cfg2_sustained.json
+python bench.py --full --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err; cp $O/bench_cfg2.json profiles/r06_bench_cfg2.json
+python bench.py --full --config cfg3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err; cp $O/bench_cfg3.json profiles/r06_bench_cfg3.json
+python bench.py --full --config cfg5 --steps 20 --warmup 5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; cp $O/bench_cfg5.json profiles/r06_bench_cfg5.json
+python bench.py --full --steps 600 --warmup 5 --no-extras --latency-steps 0 --cpu-frames 0 > $O/bench_cfg2_sustained.json 2> $O/bench_cfg2_sustained.err; cp $O/bench_cfg2_sustained.json profiles/r06_bench_cfg2_sustained.json
 mkdir -p $O/profiles_r06; cp profiles/r06_* $O/profiles_r06/
 python - <<'P'
 import json,glob
