@@ -101,15 +101,24 @@ struct ConvArgs {
     // results do not depend on it.  launch_conv takes it from bits 8.. of its `variant` argument (what conv_autotune returns).
     int tile_gn = 0;
 };
+// Tile-variant ids: 0-6 fp32 MFMA, 7-22 f16x3 (register-staged, LDS-DMA ring of NS stages, window-resident 3x3, split-K), 23 direct RGB
+// 3x3.  They are an external contract (YDS_CONV_FORCE, YDS_TUNE_CACHE files, yds_conv_variant_name, the per-variant statistics,
+// bench.py's conv_variants record): new variants are appended, ids never change.  conv.hip holds the table behind them.
+enum ConvVariant {
+    VAR_F32_128x128_K32, VAR_F32_128x64_K32, VAR_F32_64x64_K32, VAR_F32_128x32_K32, VAR_F32_128x128_K16, VAR_F32_128x64_K16, VAR_F32_64x128_K16,
+    VAR_STAGED_128x128, VAR_STAGED_64x128, VAR_STAGED_128x64, VAR_STAGED_64x64,
+    VAR_DMA_128x128_NS2, VAR_DMA_256x128_NS3, VAR_DMA_128x256_NS3, VAR_DMA_128x128_NS3, VAR_WIN_256x128, VAR_WIN_256x64, VAR_WIN_128x64,
+    VAR_DMA_128x64_NS2, VAR_DMA_64x128_NS2, VAR_WIN2_128x128, VAR_SPLITK_64x128, VAR_SPLITK_128x128, VAR_DIRECT_RGB, kConvVariants
+};
+static_assert(VAR_STAGED_128x128 == 7 && VAR_WIN_256x128 == 15 && VAR_SPLITK_64x128 == 21 && kConvVariants == 24, "variant ids are fixed");
 // returns the tile-variant id that was launched (see conv_variant_name)
 int launch_conv(const ConvArgs &a, hipStream_t s, int variant = -1);   // variant < 0: built-in default choice; bits 8..: tile order (conv_autotune's packed result); returns the plain id
 constexpr int kVariantMask = 0xff, kTileGnShift = 8;
-int conv_default_variant(const ConvArgs &a);
 bool conv_presplit_input(const ConvArgs &a);   // H16, or F16 in half mode: what the LDS-DMA / window kernels fetch as opaque chunks
 // 3x3 RGB stem + MaxPool2d(3, 2, 1) in one kernel (ReID); a.y is the pooled view.  Returns false when the layer does not qualify.
 bool launch_conv_maxpool3s2(const ConvArgs &a, hipStream_t s);
-int conv_autotune(const ConvArgs &a, hipStream_t s, float *best_us);   // measured fastest variant
-constexpr int kF32Variants = 7, kDirectVariant = 23, kConvVariants = 24;   // ids 0-6: fp32 MFMA tiles, 7-22: f16x3 tiles, 23: direct RGB 3x3
+int conv_autotune(const ConvArgs &a, hipStream_t s, float *best_us);   // measured fastest variant; -1 (default choice) under YDS_NO_AUTOTUNE
+std::vector<int> conv_candidates(const ConvArgs &a);                  // the variants conv_autotune times, in timing order
 enum ConvMath { MATH_F32 = 0, MATH_F16X3 = 1 };
 int conv_math();                 // process-wide arithmetic mode (env YDS_CONV_MATH=f32|f16x3, default f16x3)
 void set_conv_math(int m);

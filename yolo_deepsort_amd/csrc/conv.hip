@@ -294,16 +294,6 @@ double conv_bytes(const ConvArgs &a) {
     return conv_bytes_io(a.x) + conv_bytes_io(a.y) + (a.res.p ? conv_bytes_io(a.res) : 0.0) + (double)a.y.c * a.kpad * 4.0;
 }
 
-const char *conv_variant_name(int v) {
-    if (v >= 0) v &= kVariantMask;                                  // (a packed conv_autotune result names its tile variant)
-    static const char *names[kF32Variants] = {"conv_igemm_f32<128,128,2,2,32>", "conv_igemm_f32<128,64,2,2,32>", "conv_igemm_f32<64,64,2,2,32>",
-                                               "conv_igemm_f32<128,32,4,1,32>", "conv_igemm_f32<128,128,2,2,16>", "conv_igemm_f32<128,64,2,2,16>",
-                                               "conv_igemm_f32<64,128,2,2,16>"};
-    if (v == kDirectVariant) return "conv3x3_rgb_direct";
-    if (v >= kF32Variants) return conv_f16x3_variant_name(v - kF32Variants);
-    return v >= 0 ? names[v] : "?";
-}
-
 ConvKernelArgs make_conv_args(const ConvArgs &a) {
     ConvKernelArgs k;
     k.x = a.x.p; k.w = a.w; k.bias = a.bias; k.res = a.res.p; k.y = a.y.p;
@@ -341,15 +331,16 @@ bool conv_presplit_input(const ConvArgs &a) {
     return (a.x.fmt == FMT_H16 && a.x.c % 32 == 0) || (a.x.fmt == FMT_F16 && a.terms == 1 && a.x.c % 64 == 0);
 }
 
-// default tile choice when no measured choice is supplied: widest tile whose grid still fills the chip
-int conv_default_variant(const ConvArgs &a) {
+// default choice when no measured choice is supplied: widest tile whose grid still fills the chip, in the arithmetic's register-staged kernel
+static int conv_default_variant(const ConvArgs &a) {
+    if (a.x.fmt == FMT_F16) return VAR_DMA_128x128_NS2;          // 2-byte activations: the LDS-DMA kernel reads them, the staged one does not
+    // [ConvMath][tile]: 128x128, 128x64, 64x64, 128x32 (the f16x3 staged kernel has no 128x32 tile: 64x64)
+    static const int by_tile[2][4] = {{VAR_F32_128x128_K32, VAR_F32_128x64_K32, VAR_F32_64x64_K32, VAR_F32_128x32_K32},
+                                      {VAR_STAGED_128x128, VAR_STAGED_128x64, VAR_STAGED_64x64, VAR_STAGED_64x64}};
     const long M = (long)a.y.pixels(), N = a.y.c;
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    if (N <= 32) return 3;
-    if (N <= 64) return blocks(128, 64) >= 256 ? 1 : 2;
-    if (blocks(128, 128) >= 384) return 0;
-    if (blocks(128, 64) >= 384) return 1;
-    return 2;
+    const int t = N <= 32 ? 3 : N <= 64 ? (blocks(128, 64) >= 256 ? 1 : 2) : blocks(128, 128) >= 384 ? 0 : blocks(128, 64) >= 384 ? 1 : 2;
+    return by_tile[conv_math()][t];
 }
 
 bool launch_conv_maxpool3s2(const ConvArgs &a, hipStream_t s) {
@@ -372,33 +363,23 @@ int conv_math() {
 }
 void set_conv_math(int m) { g_math = m == MATH_F32 ? MATH_F32 : MATH_F16X3; }
 
-int launch_conv(const ConvArgs &a, hipStream_t s, int variant) {
-    ConvKernelArgs k = make_conv_args(a);
-    if (variant >= 0) {                                             // conv_autotune's packed result: tile variant | tile order << 8
-        k.gn_req = std::max(a.tile_gn, (variant >> kTileGnShift) & 0xff);
-        variant &= kVariantMask;
-    } else {
-        k.gn_req = a.tile_gn;
-    }
-    if (variant < 0 || variant >= kConvVariants) {
-        variant = conv_default_variant(a);
-        if (conv_math() == MATH_F16X3) variant = kF32Variants + (variant == 0 ? 0 : variant == 1 ? 2 : 3);
-        if (a.x.fmt == FMT_F16) variant = kF32Variants + 4;          // 2-byte activations: the LDS-DMA kernel reads them, the staged one does not
-    }
-    if (variant == kDirectVariant) {
-        if (!conv_direct_applicable(k)) fail("conv: the direct RGB kernel does not apply to this layer");
-        launch_conv_direct(k, s);
-        return variant;
-    }
-    if (variant < kF32Variants && (k.fmt_x != FMT_F32 || k.fmt_y != FMT_F32 || k.fmt_r != FMT_F32))
-        fail("conv: the fp32 MFMA kernel takes fp32 tensors only");
-    if (variant >= kF32Variants) {
-        if (!a.w16) fail("conv: f16x3 variant requested but the layer has no split weights");
-        k.w = reinterpret_cast<const float *>(a.w16);
-        launch_conv_f16x3(k, variant - kF32Variants, s);
-        return variant;
-    }
-    switch (variant) {
+// ---- tile variants -----------------------------------------------------------------------------------------------------------
+// One row per ConvVariant id (common.h): the kernel's name, its arithmetic, its family launcher + tile index, and two rules:
+//   runs(a, k)  the kernel takes the layer.  YDS_CONV_FORCE pins an id where this holds; launch_conv does not consult it (a launcher
+//               refuses what it cannot run, with its own message).
+//   timed(a)    the stopwatch tries it on the layer as well: narrower where a tile only pays off on some layers.
+enum ConvArith { ARITH_F32 = MATH_F32, ARITH_F16X3 = MATH_F16X3, ARITH_DIRECT };   // the direct kernel is a candidate in either arithmetic
+struct ConvVariantInfo {
+    const char *name;
+    int arith;
+    void (*launch)(ConvKernelArgs k, int tile, hipStream_t s);
+    int tile;
+    bool (*runs)(const ConvArgs &a, const ConvKernelArgs &k);
+    bool (*timed)(const ConvArgs &a);
+};
+
+static void launch_f32(ConvKernelArgs k, int tile, hipStream_t s) {
+    switch (tile) {
         case 0: launch_cfg<128, 128, 2, 2, 32>(k, s); break;
         case 1: launch_cfg<128, 64, 2, 2, 32>(k, s); break;
         case 2: launch_cfg<64, 64, 2, 2, 32>(k, s); break;
@@ -407,12 +388,95 @@ int launch_conv(const ConvArgs &a, hipStream_t s, int variant) {
         case 5: launch_cfg<128, 64, 2, 2, 16>(k, s); break;
         default: launch_cfg<64, 128, 2, 2, 16>(k, s); break;
     }
+}
+static void launch_win2(ConvKernelArgs k, int, hipStream_t s) { launch_conv_win2(k, s); }
+static void launch_direct(ConvKernelArgs k, int, hipStream_t s) {
+    if (!conv_direct_applicable(k)) fail("conv: the direct RGB kernel does not apply to this layer");
+    launch_conv_direct(k, s);
+}
+
+// (2-byte F16 activations: only the LDS-DMA and window kernels read them; the win2, split-K and direct conditions exclude them too)
+static bool runs_not_f16(const ConvArgs &a, const ConvKernelArgs &) { return a.x.fmt != FMT_F16; }
+static bool runs_presplit(const ConvArgs &a, const ConvKernelArgs &) { return conv_presplit_input(a); }
+static bool runs_win(const ConvArgs &a, const ConvKernelArgs &k) { return conv_presplit_input(a) && conv_win_applicable(k); }
+static bool runs_win_small(const ConvArgs &a, const ConvKernelArgs &k) { return runs_win(a, k) && a.terms != 1 && conv_win16_small_applicable(k); }
+static bool runs_win2(const ConvArgs &a, const ConvKernelArgs &k) { return conv_presplit_input(a) && conv_win2_applicable(k); }
+template <int TILE> static bool runs_splitk(const ConvArgs &a, const ConvKernelArgs &k) { return conv_presplit_input(a) && conv_splitk_applicable(k, TILE); }
+static bool runs_direct(const ConvArgs &, const ConvKernelArgs &k) { return conv_direct_applicable(k); }
+
+static bool timed_always(const ConvArgs &) { return true; }
+static bool timed_narrow(const ConvArgs &a) { return a.y.c <= 64; }     // 128x32 and the 64-wide window tiles: layers of <= 64 filters
+static bool timed_wide(const ConvArgs &a) { return a.y.c >= 128; }      // the two-workgroup window kernel
+static bool timed_never(const ConvArgs &) { return false; }             // split-K: selected by rule in conv_autotune, never by timing
+static bool timed_unmerged(const ConvArgs &a) { return !a.n_split; }    // the direct kernel has no second output
+
+static const ConvVariantInfo kVariants[kConvVariants] = {
+    /*  0 */ {"conv_igemm_f32<128,128,2,2,32>", ARITH_F32, launch_f32, 0, runs_not_f16, timed_always},
+    /*  1 */ {"conv_igemm_f32<128,64,2,2,32>", ARITH_F32, launch_f32, 1, runs_not_f16, timed_always},
+    /*  2 */ {"conv_igemm_f32<64,64,2,2,32>", ARITH_F32, launch_f32, 2, runs_not_f16, timed_always},
+    /*  3 */ {"conv_igemm_f32<128,32,4,1,32>", ARITH_F32, launch_f32, 3, runs_not_f16, timed_narrow},
+    /*  4 */ {"conv_igemm_f32<128,128,2,2,16>", ARITH_F32, launch_f32, 4, runs_not_f16, timed_always},
+    /*  5 */ {"conv_igemm_f32<128,64,2,2,16>", ARITH_F32, launch_f32, 5, runs_not_f16, timed_always},
+    /*  6 */ {"conv_igemm_f32<64,128,2,2,16>", ARITH_F32, launch_f32, 6, runs_not_f16, timed_always},
+    /*  7 */ {"conv_igemm_f16x3<128,128>", ARITH_F16X3, launch_conv_f16x3_staged, 0, runs_not_f16, timed_always},
+    /*  8 */ {"conv_igemm_f16x3<64,128>", ARITH_F16X3, launch_conv_f16x3_staged, 1, runs_not_f16, timed_always},
+    /*  9 */ {"conv_igemm_f16x3<128,64>", ARITH_F16X3, launch_conv_f16x3_staged, 2, runs_not_f16, timed_always},
+    /* 10 */ {"conv_igemm_f16x3<64,64>", ARITH_F16X3, launch_conv_f16x3_staged, 3, runs_not_f16, timed_always},
+    /* 11 */ {"conv_igemm_f16x3_dma<128,128,2x2,2>", ARITH_F16X3, launch_conv_f16x3_dma, 0, runs_presplit, timed_always},
+    /* 12 */ {"conv_igemm_f16x3_dma<256,128,4x2,3>", ARITH_F16X3, launch_conv_f16x3_dma, 1, runs_presplit, timed_always},
+    /* 13 */ {"conv_igemm_f16x3_dma<128,256,2x4,3>", ARITH_F16X3, launch_conv_f16x3_dma, 2, runs_presplit, timed_always},
+    /* 14 */ {"conv_igemm_f16x3_dma<128,128,2x2,3>", ARITH_F16X3, launch_conv_f16x3_dma, 3, runs_presplit, timed_always},
+    /* 15 */ {"conv3x3_f16x3_win<256,128,4x2>", ARITH_F16X3, launch_conv_f16x3_win, 0, runs_win, timed_always},
+    /* 16 */ {"conv3x3_f16x3_win<256,64,8x1>", ARITH_F16X3, launch_conv_f16x3_win, 1, runs_win, timed_narrow},
+    /* 17 */ {"conv3x3_f16x3_win<128,64,4x1>", ARITH_F16X3, launch_conv_f16x3_win, 2, runs_win_small, timed_narrow},
+    /* 18 */ {"conv_igemm_f16x3_dma<128,64,2x2,2>", ARITH_F16X3, launch_conv_f16x3_dma, 4, runs_presplit, timed_always},
+    /* 19 */ {"conv_igemm_f16x3_dma<64,128,2x2,2>", ARITH_F16X3, launch_conv_f16x3_dma, 5, runs_presplit, timed_always},
+    /* 20 */ {"conv3x3_f16x3_win2<128,128,2x2>", ARITH_F16X3, launch_win2, 0, runs_win2, timed_wide},
+    /* 21 */ {"conv_igemm_f16x3_dma<64,128,2x2,2>+splitK", ARITH_F16X3, launch_conv_f16x3_splitk, 0, runs_splitk<0>, timed_never},
+    /* 22 */ {"conv_igemm_f16x3_dma<128,128,2x2,2>+splitK", ARITH_F16X3, launch_conv_f16x3_splitk, 1, runs_splitk<1>, timed_never},
+    /* 23 */ {"conv3x3_rgb_direct", ARITH_DIRECT, launch_direct, 0, runs_direct, timed_unmerged},
+};
+
+const char *conv_variant_name(int v) {
+    if (v >= 0) v &= kVariantMask;                                  // (a packed conv_autotune result names its tile variant)
+    return v >= 0 && v < kConvVariants ? kVariants[v].name : "?";
+}
+
+int launch_conv(const ConvArgs &a, hipStream_t s, int variant) {
+    ConvKernelArgs k = make_conv_args(a);
+    if (variant >= 0) {                                             // conv_autotune's packed result: tile variant | tile order << 8
+        k.gn_req = std::max(a.tile_gn, (variant >> kTileGnShift) & 0xff);
+        variant &= kVariantMask;
+    } else {
+        k.gn_req = a.tile_gn;
+    }
+    if (variant < 0 || variant >= kConvVariants) variant = conv_default_variant(a);
+    const ConvVariantInfo &e = kVariants[variant];
+    if (e.arith == ARITH_F32 && (k.fmt_x != FMT_F32 || k.fmt_y != FMT_F32 || k.fmt_r != FMT_F32))
+        fail("conv: the fp32 MFMA kernel takes fp32 tensors only");
+    if (e.arith == ARITH_F16X3) {
+        if (!a.w16) fail("conv: f16x3 variant requested but the layer has no split weights");
+        k.w = reinterpret_cast<const float *>(a.w16);
+    }
+    e.launch(k, e.tile, s);
     return variant;
 }
 
-// Measured tile choice: times every instantiation on the real buffers (HIP events, median of 3) and returns the
-// fastest.  Wave quantisation on 256 CUs makes the best tile shape a function of (M, N, K, batch) that a closed
-// form predicts poorly, and the measurement costs a few milliseconds per layer at plan time.
+// the variants the stopwatch tries on a layer: those of the current arithmetic (and the direct kernel) that take it and are worth
+// timing there, in id order - the direct kernel last
+std::vector<int> conv_candidates(const ConvArgs &a) {
+    const ConvKernelArgs k = make_conv_args(a);
+    std::vector<int> cand;
+    for (int v = 0; v < kConvVariants; ++v) {
+        const ConvVariantInfo &e = kVariants[v];
+        if ((e.arith == conv_math() || e.arith == ARITH_DIRECT) && e.runs(a, k) && e.timed(a)) cand.push_back(v);
+    }
+    return cand;
+}
+
+// Measured tile choice: times every candidate on the real buffers and returns the fastest.  Wave quantisation on 256 CUs makes the
+// best tile shape a function of (M, N, K, batch) that a closed form predicts poorly, and the measurement costs a few milliseconds per
+// layer at plan time.
 static int conv_autotune_measured(const ConvArgs &a, hipStream_t s, float *best_us);
 
 // Optional on-disk cache of measured choices (env YDS_TUNE_CACHE=<file>): lets a profiled run reuse the choices of a
@@ -448,20 +512,13 @@ static std::string tune_key(const ConvArgs &a) {
 }
 
 int conv_autotune(const ConvArgs &a, hipStream_t s, float *best_us) {
-    if (const char *f = getenv("YDS_CONV_FORCE")) {      // tuning aid: pin a variant id where it is applicable
-        int v = atoi(f);
-        const bool f16v = v >= kF32Variants && v != kDirectVariant;
-        const bool presplit = f16v && (f16_variant_is_dma(v - kF32Variants) || f16_variant_is_win(v - kF32Variants) || f16_variant_is_win2(v - kF32Variants) ||
-                                       f16_variant_is_splitk(v - kF32Variants));
-        if (f16v && f16_variant_is_splitk(v - kF32Variants) && !conv_splitk_applicable(make_conv_args(a), v - kF32Variants)) return conv_autotune_measured(a, s, best_us);
-        if (v == kDirectVariant && !conv_direct_applicable(make_conv_args(a))) return conv_autotune_measured(a, s, best_us);
-        if (f16v && f16_variant_is_win(v - kF32Variants) && !conv_win_applicable(make_conv_args(a))) return conv_autotune_measured(a, s, best_us);
-        if (f16v && v - kF32Variants == 10 && (a.terms == 1 || !conv_win16_small_applicable(make_conv_args(a)))) return conv_autotune_measured(a, s, best_us);
-        if (f16v && f16_variant_is_win2(v - kF32Variants) && !conv_win2_applicable(make_conv_args(a))) return conv_autotune_measured(a, s, best_us);
-        if (a.x.fmt == FMT_F16 && !(f16v && (f16_variant_is_dma(v - kF32Variants) || f16_variant_is_win(v - kF32Variants)))) return conv_autotune_measured(a, s, best_us);
-        if (!(presplit && !conv_presplit_input(a))) return v;
+    if (getenv("YDS_NO_AUTOTUNE")) return -1;            // the default choice everywhere
+    if (const char *f = getenv("YDS_CONV_FORCE")) {      // tuning aid: pin a variant id where its kernel takes the layer, else measure
+        const int v = atoi(f);
+        if (v >= 0 && v < kConvVariants && kVariants[v].runs(a, make_conv_args(a))) return v;
+        return conv_autotune_measured(a, s, best_us);
     }
-    if (conv_math() == MATH_F16X3 && a.w16 && a.terms != 1 && a.n_split == 0 && conv_splitk_preferred(make_conv_args(a))) return kF32Variants + 14;   // by rule (see there)
+    if (conv_math() == MATH_F16X3 && a.w16 && a.terms != 1 && a.n_split == 0 && conv_splitk_preferred(make_conv_args(a))) return VAR_SPLITK_64x128;   // by rule (see there)
     const std::string key = tune_key(a);
     auto &cache = tune_cache();
     auto it = cache.find(key);
@@ -474,88 +531,54 @@ int conv_autotune(const ConvArgs &a, hipStream_t s, float *best_us) {
     return v;
 }
 
-static int conv_autotune_measured(const ConvArgs &a, hipStream_t s, float *best_us) {
-    // Every applicable variant is timed in ONE uninterrupted stream sequence (two rounds of six back-to-back launches per
-    // variant, a single host sync at the end): the chip then sits in its sustained clock state, like in the real
-    // detector pass.  Timing variants one by one with a host sync in between measured boost clocks and mis-ranked near ties.
-    const bool direct_ok = conv_direct_applicable(make_conv_args(a));
-    const int v_lo = conv_math() == MATH_F16X3 ? kF32Variants : 0, v_hi = conv_math() == MATH_F16X3 ? kDirectVariant : kF32Variants;
-    std::vector<int> cand;
-    for (int v = v_lo; v <= v_hi; ++v) {
-        if (v == v_hi) {                                 // last candidate: the direct first-layer kernel
-            if (!direct_ok || a.n_split) break;
-            v = kDirectVariant;
-        }
-        if (v == 3 && a.y.c > 64) continue;             // 128x32 only makes sense for narrow layers
-        const int fv = v - kF32Variants;                // f16x3 variant index (meaningful for kF32Variants <= v < kDirectVariant)
-        const bool f16v = v >= kF32Variants && v != kDirectVariant;
-        if (f16v && (f16_variant_is_dma(fv) || f16_variant_is_win(fv) || f16_variant_is_win2(fv) || f16_variant_is_splitk(fv)) && !conv_presplit_input(a)) continue;   // need a pre-split input
-        if (f16v && f16_variant_is_splitk(fv)) continue;                                  // selected by rule in conv_autotune, never by timing
-        if (a.x.fmt == FMT_F16 && !(f16v && (f16_variant_is_dma(fv) || f16_variant_is_win(fv)))) continue;   // 2-byte activations: LDS-DMA and window kernels only
-        if (f16v && f16_variant_is_win2(fv) && (!conv_win2_applicable(make_conv_args(a)) || a.y.c < 128)) continue;
-        if (f16v && f16_variant_is_win(fv) && !conv_win_applicable(make_conv_args(a))) continue;
-        if (f16v && f16_variant_is_win(fv) && fv > 8 && a.y.c > 64) continue;          // 64-wide window tiles are for 64-filter layers
-        if (f16v && fv == 10 && (a.terms == 1 || !conv_win16_small_applicable(make_conv_args(a)))) continue;   // the 128x64 tile exists in the default arithmetic only
-        cand.push_back(v);
-    }
+// Times launch(i), i < n, in ONE uninterrupted stream sequence - two rounds of six back-to-back launches per item, a single host sync at
+// the end - and returns each item's time per launch in ms (its faster round).  The chip then sits in its sustained clock state, like in
+// the real detector pass; timing items one by one with a host sync in between measured boost clocks and mis-ranked near ties.
+template <class Launch> static std::vector<float> time_launches(size_t n, Launch launch, hipStream_t s) {
     constexpr int ROUNDS = 2, REPS = 6;
-    std::vector<hipEvent_t> ev(cand.size() * ROUNDS * 2);
+    std::vector<hipEvent_t> ev(n * ROUNDS * 2);
     for (auto &e : ev) YDS_HIP(hipEventCreate(&e));
-    for (int v : cand) launch_conv(a, s, v);            // first-use setup (function attributes) outside the timed sequence
     for (int r = 0; r < ROUNDS; ++r)
-        for (size_t i = 0; i < cand.size(); ++i) {
+        for (size_t i = 0; i < n; ++i) {
             YDS_HIP(hipEventRecord(ev[(i * ROUNDS + r) * 2], s));
-            for (int k = 0; k < REPS; ++k) launch_conv(a, s, cand[i]);
+            for (int k = 0; k < REPS; ++k) launch(i);
             YDS_HIP(hipEventRecord(ev[(i * ROUNDS + r) * 2 + 1], s));
         }
     YDS_HIP(hipStreamSynchronize(s));
-    int best = -1;
-    float best_t = 0.f;
-    std::vector<float> times(cand.size());
-    for (size_t i = 0; i < cand.size(); ++i) {
-        float t = 1e30f;
+    std::vector<float> t(n, 1e30f);
+    for (size_t i = 0; i < n; ++i)
         for (int r = 0; r < ROUNDS; ++r) {
             float ms = 0.f;
             YDS_HIP(hipEventElapsedTime(&ms, ev[(i * ROUNDS + r) * 2], ev[(i * ROUNDS + r) * 2 + 1]));
-            t = fminf(t, ms / REPS);
+            t[i] = fminf(t[i], ms / REPS);
         }
-        times[i] = t;
-        if (best < 0 || t < best_t) { best = cand[i]; best_t = t; }
-    }
+    for (auto &e : ev) (void)hipEventDestroy(e);
+    return t;
+}
+
+static int conv_autotune_measured(const ConvArgs &a, hipStream_t s, float *best_us) {
+    const std::vector<int> cand = conv_candidates(a);
+    for (int v : cand) launch_conv(a, s, v);            // first-use setup (function attributes) outside the timed sequence
+    const std::vector<float> times = time_launches(cand.size(), [&](size_t i) { launch_conv(a, s, cand[i]); }, s);
+    int best = -1;
+    float best_t = 0.f;
+    for (size_t i = 0; i < cand.size(); ++i)
+        if (best < 0 || times[i] < best_t) { best = cand[i]; best_t = times[i]; }
     // near ties (within 1.5 %, the run-to-run noise of this measurement) go to the window-resident kernel: it fetches each
     // input pixel once instead of nine times, and a stable choice keeps per-tile statistics comparable between runs
     for (size_t i = 0; i < cand.size(); ++i)
-        if (cand[i] == kF32Variants + 8 && best != cand[i] && times[i] <= best_t * 1.015f) { best = cand[i]; best_t = times[i]; }
-    for (auto &e : ev) (void)hipEventDestroy(e);
+        if (cand[i] == VAR_WIN_256x128 && best != cand[i] && times[i] <= best_t * 1.015f) { best = cand[i]; best_t = times[i]; }
     // Second measurement (round 6): the ORDER in which an XCD walks its rectangle of tiles - column by column, or 2 / 4 filter tiles
     // together so that the workgroups of one pixel tile share its input through the L2 (conv_common.h tile_of_block).  Same
     // protocol, same sequence for all three; the result is a placement, never a different sum.  Measured on one box at 68 frames:
     // 19x19 1024->512 1x1 -11 %, 76->38 strided 3x3 -4 %, 76x76 window layers -2 %, 38x38 layers +1 % (kept column by column there).
     int best_gn = 0;
-    if (a.y.c > 128 && best != kDirectVariant) {
+    if (a.y.c > 128 && best != VAR_DIRECT_RGB) {
         const int gns[3] = {0, 2, 4};
-        hipEvent_t e2[3][ROUNDS][2];
-        for (auto &g : e2) for (auto &r : g) for (auto &e : r) YDS_HIP(hipEventCreate(&e));
-        for (int r = 0; r < ROUNDS; ++r)
-            for (int g = 0; g < 3; ++g) {
-                YDS_HIP(hipEventRecord(e2[g][r][0], s));
-                for (int k = 0; k < REPS; ++k) launch_conv(a, s, best | (gns[g] << kTileGnShift));
-                YDS_HIP(hipEventRecord(e2[g][r][1], s));
-            }
-        YDS_HIP(hipStreamSynchronize(s));
-        float tg[3];
-        for (int g = 0; g < 3; ++g) {
-            tg[g] = 1e30f;
-            for (int r = 0; r < ROUNDS; ++r) {
-                float ms = 0.f;
-                YDS_HIP(hipEventElapsedTime(&ms, e2[g][r][0], e2[g][r][1]));
-                tg[g] = fminf(tg[g], ms / REPS);
-            }
-        }
+        const std::vector<float> tg = time_launches(3, [&](size_t g) { launch_conv(a, s, best | (gns[g] << kTileGnShift)); }, s);
         for (int g = 1; g < 3; ++g)
             if (tg[g] < tg[0] * 0.985f && (best_gn == 0 || tg[g] < best_t)) { best_gn = gns[g]; best_t = tg[g]; }   // beyond the noise only
         if (best_gn == 0) best_t = fminf(best_t, tg[0]);
-        for (auto &g : e2) for (auto &r : g) for (auto &e : r) (void)hipEventDestroy(e);
     }
     if (best_us) *best_us = best_t * 1e3f;
     return best | (best_gn << kTileGnShift);

@@ -332,27 +332,24 @@ void launch_conv_direct(const ConvKernelArgs &k, hipStream_t s);
 bool conv_pool_applicable(const ConvKernelArgs &k);
 void launch_conv_pool(const ConvKernelArgs &k, hipStream_t s);
 
-// split-fp16 path (conv_f16x3.hip)
-constexpr int kF16Variants = 16;           // 0-3 register-staged tiles, 4-7 and 11-12 LDS-DMA ring, 8-10 window-resident 3x3, 13 window-resident with two workgroups per CU, 14-15 LDS-DMA ring with split-K + reduce pass (pre-split inputs only)
-inline bool f16_variant_is_dma(int v) { return (v >= 4 && v <= 7) || v == 11 || v == 12; }
-inline bool f16_variant_is_win(int v) { return v >= 8 && v <= 10; }
-inline bool f16_variant_is_win2(int v) { return v == 13; }
-inline bool f16_variant_is_splitk(int v) { return v == 14 || v == 15; }
-bool conv_splitk_applicable(const ConvKernelArgs &k, int fv);     // a split of >= 2 K ranges exists
-bool conv_splitk_preferred(const ConvKernelArgs &k);              // the deterministic rule that selects variant 14 (never timed against the others)
+// split-fp16 path (conv_f16x3.hip): one launcher per kernel family, `tile` picks the instantiation (conv.hip's variant table)
+void launch_conv_f16x3_staged(ConvKernelArgs k, int tile, hipStream_t s);   // 0: 128x128, 1: 64x128, 2: 128x64, 3: 64x64
+void launch_conv_f16x3_dma(ConvKernelArgs k, int tile, hipStream_t s);      // 0: 128x128 NS2, 1: 256x128 NS3, 2: 128x256 NS3, 3: 128x128 NS3, 4: 128x64 NS2, 5: 64x128 NS2
+void launch_conv_f16x3_win(ConvKernelArgs k, int tile, hipStream_t s);      // 0: 256x128, 1: 256x64, 2: 128x64 (default arithmetic only)
+void launch_conv_f16x3_splitk(ConvKernelArgs k, int tile, hipStream_t s);   // 0: 64x128, 1: 128x128
+bool conv_splitk_applicable(const ConvKernelArgs &k, int tile);   // a split of >= 2 K ranges exists
+bool conv_splitk_preferred(const ConvKernelArgs &k);              // the deterministic rule that selects split-K tile 0 (never timed against the others)
 // two-workgroup window kernel (conv_win2.hip): 128x128 tiles, 4 waves, 16-channel K steps
 bool conv_win2_applicable(const ConvKernelArgs &k);
 void launch_conv_win2(ConvKernelArgs k, hipStream_t s);
-// window-resident 3x3 stride-1 kernel (conv_win.hip)
+// window-resident 3x3 stride-1 kernel: launch_conv_f16x3_win runs half mode (terms == 1) on conv_win.hip, the default arithmetic on conv_win16.hip
 bool conv_win_applicable(const ConvKernelArgs &k);
-void launch_conv_win(ConvKernelArgs k, int shape, hipStream_t s);   // shape 0: 256x128 (4x2 waves), 1: 256x64 (8x1), 2: 128x64 (4x1, two workgroups per CU; default arithmetic only)
-const char *conv_f16x3_variant_name(int v);
-void launch_conv_f16x3(ConvKernelArgs k, int variant, hipStream_t s);
+void launch_conv_win(ConvKernelArgs k, int shape, hipStream_t s);   // half mode; shape 0: 256x128 (4x2 waves), otherwise 256x64
 // sampled (shader cycles, 100 MHz ticks) accumulated inside the window kernels since the last reset
 void conv_win_clock(unsigned long long *cycles_ticks, bool reset);   // in-kernel sampling: -DYDS_CLOCK_PROBE builds only (zeros otherwise)
 void conv_win16_clock(unsigned long long *cycles_ticks, bool reset);
 bool conv_win16_small_applicable(const ConvKernelArgs &k);           // shape 2 below
-void launch_conv_win16(ConvKernelArgs k, int shape, hipStream_t s);  // the f16x3 (default arithmetic) form on v_mfma_f32_16x16x32_f16 (conv_win16.hip)
+void launch_conv_win16(ConvKernelArgs k, int shape, hipStream_t s);  // default arithmetic, v_mfma_f32_16x16x32_f16; shape 0: 256x128 (4x2 waves), 1: 256x64 (8x1), 2: 128x64 (4x1, two workgroups per CU)
 void conv_win2_clock(unsigned long long *cycles_ticks, bool reset);
 
 }  // namespace yds

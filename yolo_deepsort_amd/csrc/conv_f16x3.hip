@@ -477,7 +477,7 @@ template <int BM, int BN, int WM, int WN, int NS> static void launch_cfg_dma(con
     const bool xs = k.fmt_x == FMT_F16;                          // 2-byte activations (half mode): the 64-channel K steps read them in place
     if (xs ? (k.terms != 1 || k.Cin % 64) : (k.fmt_x != FMT_H16 || k.Cin % 32)) fail("conv: the LDS-DMA kernel needs a pre-split (H16, or F16 in half mode) input");
     if ((size_t)k.Cin * 4 + 128 > (size_t)ZERO_PAGE_BYTES) fail("conv: %d input channels exceed the zero page of the LDS-DMA kernel", k.Cin);
-    if (k.terms == 1 && k.Cin % 64 == 0 && (xs || !getenv("YDS_HALF_NARROW"))) {      // half mode, 64 channels per K step
+    if (k.terms == 1 && k.Cin % 64 == 0) {                      // half mode, 64 channels per K step
 #define YDS_CALL(A, R) launch_inst_dma<BM, BN, WM, WN, NS, A, R, 4>(k, s)
         YDS_DISPATCH_ACT_RES(k, YDS_CALL)
 #undef YDS_CALL
@@ -582,9 +582,9 @@ bool conv_splitk_preferred(const ConvKernelArgs &k) {
     return tiles <= 128 && k.K / 32 >= 32 && conv_splitk_factor(k, 64, 128) >= 2;
 }
 
-bool conv_splitk_applicable(const ConvKernelArgs &k, int fv) {
+bool conv_splitk_applicable(const ConvKernelArgs &k, int tile) {
     if (k.fmt_x != FMT_H16 || k.Cin % 32) return false;
-    return fv == 14 ? conv_splitk_factor(k, 64, 128) >= 2 : conv_splitk_factor(k, 128, 128) >= 2;
+    return tile == 0 ? conv_splitk_factor(k, 64, 128) >= 2 : conv_splitk_factor(k, 128, 128) >= 2;
 }
 
 template <int BM, int BN, int ACT, int RES, int AIN> static void launch_inst16(ConvKernelArgs k, hipStream_t s) {
@@ -613,37 +613,37 @@ template <int BM, int BN> static void launch_cfg16(const ConvKernelArgs &k, hipS
     }
 }
 
-const char *conv_f16x3_variant_name(int v) {
-    static const char *names[kF16Variants] = {"conv_igemm_f16x3<128,128>", "conv_igemm_f16x3<64,128>", "conv_igemm_f16x3<128,64>",
-                                              "conv_igemm_f16x3<64,64>", "conv_igemm_f16x3_dma<128,128,2x2,2>", "conv_igemm_f16x3_dma<256,128,4x2,3>",
-                                              "conv_igemm_f16x3_dma<128,256,2x4,3>", "conv_igemm_f16x3_dma<128,128,2x2,3>", "conv3x3_f16x3_win<256,128,4x2>",
-                                              "conv3x3_f16x3_win<256,64,8x1>", "conv3x3_f16x3_win<128,64,4x1>",
-                                              "conv_igemm_f16x3_dma<128,64,2x2,2>", "conv_igemm_f16x3_dma<64,128,2x2,2>", "conv3x3_f16x3_win2<128,128,2x2>",
-                                              "conv_igemm_f16x3_dma<64,128,2x2,2>+splitK", "conv_igemm_f16x3_dma<128,128,2x2,2>+splitK"};
-    return v >= 0 && v < kF16Variants ? names[v] : "?";
-}
-
-void launch_conv_f16x3(ConvKernelArgs k, int variant, hipStream_t s) {
-    switch (variant) {
+void launch_conv_f16x3_staged(ConvKernelArgs k, int tile, hipStream_t s) {
+    switch (tile) {
         case 0: launch_cfg16<128, 128>(k, s); break;
         case 1: launch_cfg16<64, 128>(k, s); break;
         case 2: launch_cfg16<128, 64>(k, s); break;
-        case 3: launch_cfg16<64, 64>(k, s); break;
-        case 4: launch_cfg_dma<128, 128, 2, 2, 2>(k, s); break;
-        case 5: launch_cfg_dma<256, 128, 4, 2, 3>(k, s); break;
-        case 6: launch_cfg_dma<128, 256, 2, 4, 3>(k, s); break;
-        case 7: launch_cfg_dma<128, 128, 2, 2, 3>(k, s); break;
-        case 8: launch_conv_win(k, 0, s); break;
-        case 9: launch_conv_win(k, 1, s); break;
-        case 10: launch_conv_win(k, 2, s); break;
+        default: launch_cfg16<64, 64>(k, s); break;
+    }
+}
+
+void launch_conv_f16x3_dma(ConvKernelArgs k, int tile, hipStream_t s) {
+    switch (tile) {
+        case 0: launch_cfg_dma<128, 128, 2, 2, 2>(k, s); break;
+        case 1: launch_cfg_dma<256, 128, 4, 2, 3>(k, s); break;
+        case 2: launch_cfg_dma<128, 256, 2, 4, 3>(k, s); break;
+        case 3: launch_cfg_dma<128, 128, 2, 2, 3>(k, s); break;
         // small LDS-DMA tiles (48 KB of LDS: three workgroups per CU): layers whose 128x128 tile count leaves a long tail -
         // the 1x1 layers at 76^2 / 38^2 / 19^2 run 1.4 rounds of 128x128 tiles on 512 slots, i.e. pay for 2
-        case 11: launch_cfg_dma<128, 64, 2, 2, 2>(k, s); break;
-        case 13: launch_conv_win2(k, s); break;
-        case 14: launch_splitk<64, 128>(k, s); break;
-        case 15: launch_splitk<128, 128>(k, s); break;
+        case 4: launch_cfg_dma<128, 64, 2, 2, 2>(k, s); break;
         default: launch_cfg_dma<64, 128, 2, 2, 2>(k, s); break;
     }
+}
+
+void launch_conv_f16x3_win(ConvKernelArgs k, int tile, hipStream_t s) {
+    if (!conv_win_applicable(k)) fail("conv: the window-resident kernel needs a 3x3 stride-1 layer with a pre-split input and W <= 95 (W <= 318 for 32 input channels)");
+    if (k.terms == 1) launch_conv_win(k, tile, s);               // half mode: 256x128, or 256x64 for narrow layers
+    else launch_conv_win16(k, tile, s);                           // default arithmetic: the v_mfma_f32_16x16x32_f16 form
+}
+
+void launch_conv_f16x3_splitk(ConvKernelArgs k, int tile, hipStream_t s) {
+    if (tile == 0) launch_splitk<64, 128>(k, s);
+    else launch_splitk<128, 128>(k, s);
 }
 
 // host: fold-free split of already BN-folded fp32 weights [cout][kpad] into [cout][kpad/32][32 hi | 32 lo] fp16

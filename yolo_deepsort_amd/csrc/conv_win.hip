@@ -315,7 +315,7 @@ bool conv_win_applicable(const ConvKernelArgs &k) {
     const bool presplit = (k.fmt_x == FMT_H16 && k.Cin % 32 == 0) || (k.fmt_x == FMT_F16 && k.terms == 1 && k.Cin % 64 == 0);
     if (!(k.ksize == 3 && k.stride == 1 && k.pad == 1 && presplit && k.H == k.Ho && k.W == k.Wo)) return false;
     // (half mode runs 64 channels per K step - launch_conv_win below - so a 64-channel layer is a single group there)
-    const bool wide_step = k.terms == 1 && k.Cin % 64 == 0 && (k.fmt_x == FMT_F16 || !getenv("YDS_HALF_NARROW"));
+    const bool wide_step = k.terms == 1 && k.Cin % 64 == 0;
     const int wrows = window_rows(k.W), nbuf = k.Cin == (wide_step ? 64 : 32) ? 1 : 2;
     // several channel groups: the next group's window is fetched by at most APW instructions per wave while this one is
     // consumed (two buffers); a single group needs one buffer only, which admits much wider images
@@ -324,9 +324,9 @@ bool conv_win_applicable(const ConvKernelArgs &k) {
     return (size_t)nbuf * wrows * ROW + (size_t)NSB * 128 * ROW + ROW <= 160 * 1024 && (size_t)k.M * (k.ldx / 4) < (1ull << 32);
 }
 
+// half mode (launch_conv_f16x3_win checks applicability): 256x128, or 256x64 for narrow layers; 64 channels per K step where Cin allows
 void launch_conv_win(ConvKernelArgs k, int shape, hipStream_t s) {
-    if (!conv_win_applicable(k)) fail("conv: the window-resident kernel needs a 3x3 stride-1 layer with a pre-split input and W <= 95 (W <= 318 for 32 input channels)");
-    if (k.terms == 1 && k.Cin % 64 == 0 && (k.fmt_x == FMT_F16 || !getenv("YDS_HALF_NARROW"))) {   // half mode, 64 channels per step (YDS_HALF_NARROW: tuning aid, the 32-channel form)
+    if (k.Cin % 64 == 0) {
         if (shape == 0) {
 #define YDS_CALL(A, R) launch_inst_win<128, 4, 2, A, R, 4>(k, s)
             YDS_DISPATCH_ACT_RES(k, YDS_CALL)
@@ -336,18 +336,14 @@ void launch_conv_win(ConvKernelArgs k, int shape, hipStream_t s) {
             YDS_DISPATCH_ACT_RES(k, YDS_CALL)
 #undef YDS_CALL
         }
-    } else if (k.terms == 1) {                                   // half mode: one instantiation family (256x128, or 256x64 for narrow layers)
-        if (shape == 0) {
+    } else if (shape == 0) {
 #define YDS_CALL(A, R) launch_inst_win<128, 4, 2, A, R, 1>(k, s)
-            YDS_DISPATCH_ACT_RES(k, YDS_CALL)
+        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
 #undef YDS_CALL
-        } else {
+    } else {
 #define YDS_CALL(A, R) launch_inst_win<64, 4, 2, A, R, 1>(k, s)
-            YDS_DISPATCH_ACT_RES(k, YDS_CALL)
+        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
 #undef YDS_CALL
-        }
-    } else {                                                     // default arithmetic: the v_mfma_f32_16x16x32_f16 form (conv_win16.hip)
-        launch_conv_win16(k, shape, s);
     }
 }
 

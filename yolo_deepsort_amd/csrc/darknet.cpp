@@ -519,13 +519,12 @@ ConvArgs Darknet::merged_conv_args(int i, int batch) const {
 }
 
 void Darknet::autotune(int batch) {
-    static const bool off = getenv("YDS_NO_AUTOTUNE") != nullptr;
     for (int i = 0; i < (int)layers.size(); ++i) {
         Layer &l = layers[i];
         const int mode = conv_math() + (half_mode ? 10 : 0);
         if (l.type != "convolutional" || !l.loaded || (l.tuned_batch == batch && l.tuned_math == mode)) continue;
         if (l.merged_into >= 0 && layers[l.merged_into].wt_m.p) { l.tuned_batch = batch; l.tuned_math = mode; continue; }   // launched by its partner
-        l.variant = off ? -1 : conv_autotune(l.merge_next >= 0 && l.wt_m.p ? merged_conv_args(i, batch) : conv_args(i, batch), stream, nullptr);
+        l.variant = conv_autotune(l.merge_next >= 0 && l.wt_m.p ? merged_conv_args(i, batch) : conv_args(i, batch), stream, nullptr);
         l.tuned_batch = batch;
         l.tuned_math = mode;
     }
@@ -615,7 +614,7 @@ void Darknet::run_lane(int first, int batch, hipStream_t stream, int l0, int l1)
                 ConvKernelArgs k0 = make_conv_args(a0), k1 = make_conv_args(a);
                 k1.w = reinterpret_cast<const float *>(a.w16);
                 launch_conv_stem2(k0, k1, stream);
-                variant = kDirectVariant;                           // accounted with the direct first-layer kernel
+                variant = VAR_DIRECT_RGB;                           // accounted with the direct first-layer kernel
                 extra_flops = conv_flops(a0);
                 extra_bytes = conv_bytes(a0) - conv_bytes_io(a0.y) - conv_bytes_io(a.x);     // the intermediate tensor never reaches HBM
             } else if (i == block1_at + 1 && block1_at >= 0 && block1_fused(batch)) {
@@ -624,7 +623,7 @@ void Darknet::run_lane(int first, int batch, hipStream_t stream, int l0, int l1)
                 k2.w = reinterpret_cast<const float *>(a2.w16);
                 k3.w = reinterpret_cast<const float *>(a.w16);
                 launch_conv_block1(k2, k3, stream);
-                variant = kF32Variants + 8;                         // accounted with the window-resident 3x3 kernel
+                variant = VAR_WIN_256x128;                          // accounted with the window-resident 3x3 kernel
                 extra_flops = conv_flops(a2);
                 // the block input is read once (it is also the residual), the 32-channel intermediate never reaches HBM
                 extra_bytes = conv_bytes(a2) - conv_bytes_io(a2.y) - conv_bytes_io(a.x) - (a.res.p ? conv_bytes_io(a.res) : 0.0);
@@ -1019,7 +1018,7 @@ int yds_conv_bench(int n, int h, int w, int cin, int cout, int ksize, int stride
     YDS_HIP(hipStreamCreate(&st));
     hipEvent_t e0, e1;
     YDS_HIP(hipEventCreate(&e0)); YDS_HIP(hipEventCreate(&e1));
-    int tuned = getenv("YDS_NO_AUTOTUNE") ? -1 : conv_autotune(a, st, nullptr);
+    int tuned = conv_autotune(a, st, nullptr);
     for (int i = 0; i < 3; ++i) *variant = launch_conv(a, st, tuned);
     YDS_HIP(hipEventRecord(e0, st));
     for (int i = 0; i < iters; ++i) launch_conv(a, st, tuned);

@@ -154,7 +154,7 @@ void ReidNet::forward(int D) {
         if (tuned_math != conv_math()) { tuned.clear(); tuned_math = conv_math(); }
         auto it = tuned.find(ci);
         if (it == tuned.end() || D > 2 * it->second.first || 2 * D < it->second.first) {
-            int v = getenv("YDS_NO_AUTOTUNE") ? -1 : conv_autotune(a, stream, nullptr);
+            int v = conv_autotune(a, stream, nullptr);
             tuned[ci] = std::make_pair(D, v);
             it = tuned.find(ci);
         }
