@@ -266,23 +266,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32(ConvKernelArgs p) {
     conv_epilogue<BM, BN, WM, WN, ACT, RES>(p, acc, smem, m0, n0, tid);
 }
 
-template <int BM, int BN, int WM, int WN, int BK, int ACT, int RES> static void launch_inst(ConvKernelArgs k, hipStream_t s) {
-    constexpr size_t smem = 2ull * (BM + BN) * (BK + 4) * sizeof(float);
-    static bool attr_set = false;
-    auto kern = conv_igemm_f32<BM, BN, WM, WN, BK, ACT, RES>;
-    if (!attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
-    dim3 grid(plan_tile_map(k, BM, BN));
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, k);
-    YDS_HIP(hipGetLastError());
-}
-
 template <int BM, int BN, int WM, int WN, int BK> static void launch_cfg(const ConvKernelArgs &k, hipStream_t s) {
-#define YDS_CALL(A, R) launch_inst<BM, BN, WM, WN, BK, A, R>(k, s)
-    YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
+    constexpr size_t smem = 2ull * (BM + BN) * (BK + 4) * sizeof(float);
+    dispatch_act_res(k, [&](auto A, auto R) { launch_conv_tiles<conv_igemm_f32<BM, BN, WM, WN, BK, A, R>>(k, BM, BN, 1, 256, smem, s); });
 }
 
 double conv_flops(const ConvArgs &a) {

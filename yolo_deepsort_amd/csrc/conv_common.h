@@ -312,18 +312,42 @@ void launch_conv_stem2(const ConvKernelArgs &k0, const ConvKernelArgs &k1, hipSt
 bool conv_block1_applicable(const ConvKernelArgs &k2, const ConvKernelArgs &k3);
 void launch_conv_block1(const ConvKernelArgs &k2, const ConvKernelArgs &k3, hipStream_t s);
 
-// dispatch on (activation, residual mode) to the compile-time epilogue instantiation of launcher L<ACT, RES>
-#define YDS_DISPATCH_ACT_RES(k, CALL)                                                                     \
-    switch ((k).act * 4 + (k).res_mode) {                                                                 \
-        case ACT_LINEAR * 4 + RES_NONE: CALL(ACT_LINEAR, RES_NONE); break;                                \
-        case ACT_LEAKY * 4 + RES_NONE: CALL(ACT_LEAKY, RES_NONE); break;                                  \
-        case ACT_LEAKY * 4 + RES_AFTER_ACT: CALL(ACT_LEAKY, RES_AFTER_ACT); break;                        \
-        case ACT_MISH * 4 + RES_NONE: CALL(ACT_MISH, RES_NONE); break;                                    \
-        case ACT_MISH * 4 + RES_AFTER_ACT: CALL(ACT_MISH, RES_AFTER_ACT); break;                          \
-        case ACT_RELU * 4 + RES_NONE: CALL(ACT_RELU, RES_NONE); break;                                    \
-        case ACT_RELU * 4 + RES_BEFORE_ACT: CALL(ACT_RELU, RES_BEFORE_ACT); break;                        \
-        default: fail("conv: unsupported activation/residual combination (%d, %d)", (k).act, (k).res_mode); \
+// dispatch on (activation, residual mode): f(A, R) is called with the pair as std::integral_constant values, so that a generic
+// lambda can name the compile-time epilogue instantiation:  dispatch_act_res(k, [&](auto A, auto R) { launch<..., A, R>(k, s); });
+template <class F> void dispatch_act_res(const ConvKernelArgs &k, F f) {
+    using Linear = std::integral_constant<int, ACT_LINEAR>;
+    using Leaky = std::integral_constant<int, ACT_LEAKY>;
+    using Mish = std::integral_constant<int, ACT_MISH>;
+    using Relu = std::integral_constant<int, ACT_RELU>;
+    using None = std::integral_constant<int, RES_NONE>;
+    using After = std::integral_constant<int, RES_AFTER_ACT>;
+    using Before = std::integral_constant<int, RES_BEFORE_ACT>;
+    switch (k.act * 4 + k.res_mode) {
+        case ACT_LINEAR * 4 + RES_NONE: f(Linear{}, None{}); break;
+        case ACT_LEAKY * 4 + RES_NONE: f(Leaky{}, None{}); break;
+        case ACT_LEAKY * 4 + RES_AFTER_ACT: f(Leaky{}, After{}); break;
+        case ACT_MISH * 4 + RES_NONE: f(Mish{}, None{}); break;
+        case ACT_MISH * 4 + RES_AFTER_ACT: f(Mish{}, After{}); break;
+        case ACT_RELU * 4 + RES_NONE: f(Relu{}, None{}); break;
+        case ACT_RELU * 4 + RES_BEFORE_ACT: f(Relu{}, Before{}); break;
+        default: fail("conv: unsupported activation/residual combination (%d, %d)", k.act, k.res_mode);
     }
+}
+
+// Launch of one instantiation KERN(ConvKernelArgs, args...) of a dynamic-LDS convolution kernel over the BM x BN tiles of k (times
+// grid_y K ranges): raises the kernel's dynamic-LDS limit when this launch needs more than every earlier one (grow-only, one
+// high-water mark per instantiation), plans the tile map, launches, checks the launch.
+template <auto KERN, class... Args>
+void launch_conv_tiles(ConvKernelArgs k, int BM, int BN, int grid_y, int threads, size_t smem, hipStream_t s, Args... args) {
+    static size_t attr_set = 0;
+    if (smem > attr_set) {
+        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        attr_set = smem;
+    }
+    dim3 grid(plan_tile_map(k, BM, BN), grid_y);
+    hipLaunchKernelGGL(KERN, grid, dim3(threads), smem, s, k, args...);
+    YDS_HIP(hipGetLastError());
+}
 
 // direct first-layer kernel (conv_first.hip)
 bool conv_direct_applicable(const ConvKernelArgs &k);

@@ -460,38 +460,20 @@ static const char *zero_page_dev() {
     return static_cast<const char *>(z);
 }
 
-template <int BM, int BN, int WM, int WN, int NS, int ACT, int RES, int TERMS> static void launch_inst_dma(ConvKernelArgs k, hipStream_t s) {
-    constexpr size_t smem = dma_smem_bytes(BM, BN, NS);
-    static bool attr_set = false;
-    auto kern = conv_igemm_f16x3_dma<BM, BN, WM, WN, NS, ACT, RES, TERMS>;
-    if (!attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
-    dim3 grid(plan_tile_map(k, BM, BN), k.ksplit > 1 ? k.ksplit : 1);
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, s, k, zero_page_dev());
-    YDS_HIP(hipGetLastError());
-}
-
 template <int BM, int BN, int WM, int WN, int NS> static void launch_cfg_dma(const ConvKernelArgs &k, hipStream_t s) {
     const bool xs = k.fmt_x == FMT_F16;                          // 2-byte activations (half mode): the 64-channel K steps read them in place
     if (xs ? (k.terms != 1 || k.Cin % 64) : (k.fmt_x != FMT_H16 || k.Cin % 32)) fail("conv: the LDS-DMA kernel needs a pre-split (H16, or F16 in half mode) input");
     if ((size_t)k.Cin * 4 + 128 > (size_t)ZERO_PAGE_BYTES) fail("conv: %d input channels exceed the zero page of the LDS-DMA kernel", k.Cin);
-    if (k.terms == 1 && k.Cin % 64 == 0) {                      // half mode, 64 channels per K step
-#define YDS_CALL(A, R) launch_inst_dma<BM, BN, WM, WN, NS, A, R, 4>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-        return;
-    }
-    if (k.terms == 1) {
-#define YDS_CALL(A, R) launch_inst_dma<BM, BN, WM, WN, NS, A, R, 1>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-        return;
-    }
-#define YDS_CALL(A, R) launch_inst_dma<BM, BN, WM, WN, NS, A, R, 3>(k, s)
-    YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
+    auto launch = [&](auto A, auto R, auto terms_c) {
+        constexpr int TERMS = decltype(terms_c)::value;
+        launch_conv_tiles<conv_igemm_f16x3_dma<BM, BN, WM, WN, NS, A, R, TERMS>>(k, BM, BN, k.ksplit > 1 ? k.ksplit : 1, WM * WN * 64, dma_smem_bytes(BM, BN, NS), s,
+                                                                                  zero_page_dev());
+    };
+    dispatch_act_res(k, [&](auto A, auto R) {
+        if (k.terms == 1 && k.Cin % 64 == 0) launch(A, R, std::integral_constant<int, 4>{});   // half mode, 64 channels per K step
+        else if (k.terms == 1) launch(A, R, std::integral_constant<int, 1>{});
+        else launch(A, R, std::integral_constant<int, 3>{});
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -587,30 +569,13 @@ bool conv_splitk_applicable(const ConvKernelArgs &k, int tile) {
     return tile == 0 ? conv_splitk_factor(k, 64, 128) >= 2 : conv_splitk_factor(k, 128, 128) >= 2;
 }
 
-template <int BM, int BN, int ACT, int RES, int AIN> static void launch_inst16(ConvKernelArgs k, hipStream_t s) {
-    constexpr size_t smem = 2ull * (BM + BN) * ROWB;
-    static bool attr_set = false;
-    auto kern = conv_igemm_f16x3<BM, BN, ACT, RES, AIN>;
-    if (!attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
-    dim3 grid(plan_tile_map(k, BM, BN));
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, k);
-    YDS_HIP(hipGetLastError());
-}
-
 template <int BM, int BN> static void launch_cfg16(const ConvKernelArgs &k, hipStream_t s) {
     if (k.fmt_x == FMT_F16) fail("conv: the register-staged kernel does not read 2-byte (F16) activations");
-    if (k.fmt_x == FMT_H16) {
-#define YDS_CALL(A, R) launch_inst16<BM, BN, A, R, FMT_H16>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    } else {
-#define YDS_CALL(A, R) launch_inst16<BM, BN, A, R, FMT_F32>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    }
+    constexpr size_t smem = 2ull * (BM + BN) * ROWB;
+    dispatch_act_res(k, [&](auto A, auto R) {
+        if (k.fmt_x == FMT_H16) launch_conv_tiles<conv_igemm_f16x3<BM, BN, A, R, FMT_H16>>(k, BM, BN, 1, 256, smem, s);
+        else launch_conv_tiles<conv_igemm_f16x3<BM, BN, A, R, FMT_F32>>(k, BM, BN, 1, 256, smem, s);
+    });
 }
 
 void launch_conv_f16x3_staged(ConvKernelArgs k, int tile, hipStream_t s) {

@@ -1,4 +1,5 @@
-// Window-resident 3x3 / stride-1 convolution on the fp16 matrix cores (f16x3 arithmetic, see conv_f16x3.hip).
+// Window-resident 3x3 / stride-1 convolution on the fp16 matrix cores: the data movement all three window kernels share, and the
+// half-mode tiers (the default f16x3 arithmetic, see conv_f16x3.hip, runs conv_win16.hip; two workgroups per CU: conv_win2.hip).
 //
 // The LDS-DMA implicit-GEMM kernel fetches the activation tile once per filter tap: nine times the same pixels,
 // shifted.  Its K loop is bound by the number of global->LDS instructions a wave has to issue between its MFMAs
@@ -15,30 +16,18 @@
 //   buffer, W <= 318)
 // Same swizzle as the DMA kernel: row r keeps its 16-byte chunk c at position c ^ ((r >> 1) & 7), applied on the source
 // address of the DMA and again by the fragment reads; 16 consecutive rows hit 16 distinct bank slots at any base.
-#include "conv_common.h"
+#include "conv_win_common.h"
 
 namespace yds {
-
-// Sustained shader clock INSIDE the kernel: one workgroup in 32 samples the shader-cycle counter (s_memtime) and the constant
-// 100 MHz counter (s_memrealtime) at its start and end; cycles / ticks is the clock the chip really ran at while every CU
-// was busy with this kernel (it is power limited: ~1.55 GHz, not the 2.4 GHz the MFMA peak is quoted at).
-#ifdef YDS_CLOCK_PROBE
-__device__ unsigned long long yds_clk_win[2];
-#endif
 namespace {
 
 constexpr int BM = 256, NW = 8, NT = NW * 64;
-constexpr int NSB = 3;                         // filter-stage ring depth
-constexpr int ROW = 128;
-constexpr int APW = 7;                         // window DMA instructions per wave per channel group (8 rows each)
-constexpr int MAX_WROWS = APW * NW * 8;        // 448 window rows
+constexpr int BN_MAX = 128;                    // the widest tile (shape 0): conv_win_applicable plans for it
 
-// BN x (WM x WN waves): 128 x (4x2) = 64x64 accumulator tiles per wave; 64 x (8x1) / 64 x (4x2) for 64-filter layers
-// This file holds the HALF-MODE tiers of the window kernel (Darknet.half()); the default f16x3 arithmetic runs conv_win16.hip.
-// TERMS: 1 = half mode (hi halves of both operands only: no lo fragment reads, one MFMA per product block - compile-time
-// pruning of the three-term slot plan; a round-3 tier that computed the cross terms in fp8, TERMS = 2, was removed in round 4:
-// with the default kernel on v_mfma_f32_16x16x32_f16 it was no longer faster - 1487 against 1508 frames/s);
-// 4 = half mode with 64 channels per K step: the LDS rows (window and filter stages alike) are GATHERED by the DMA from the hi halves
+// This file holds the HALF-MODE tiers of the window kernel (Darknet.half()), on v_mfma_f32_32x32x16_f16; the default f16x3 arithmetic
+// runs conv_win16.hip.  BN x (WM x WN waves): 128 x (4x2) = 64x64 accumulator tiles per wave, 64 x (4x2) for 64-filter layers.
+// TERMS: 1 = hi halves of both operands only: no lo fragment reads, one MFMA per product block;
+// 4 = 64 channels per K step: the LDS rows (window and filter stages alike) are GATHERED by the DMA from the hi halves
 // of two consecutive 32-channel groups (a DMA lane's global address is free), [hi of group 2q | hi of group 2q+1], so the "lo" fragment
 // slots hold the second group's hi values and the step does A_hi x B_hi + A_lo x B_lo - the same DMA instructions, fragment reads and
 // barrier per step as TERMS = 1 for twice the channels, i.e. half the steps (a K step is bound by those, not by its MFMAs, once two
@@ -67,11 +56,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
         n0 = tn * BN;
     }
     if (tid < 32) reinterpret_cast<float *>(smem + zoff)[tid] = 0.f;
-#ifdef YDS_CLOCK_PROBE
-    const bool clk_sample = tid == 0 && (blockIdx.x & 31) == 0;
-    unsigned long long clk_c0 = 0, clk_w0 = 0;
-    if (clk_sample) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = wall_clock64(); }
-#endif
+    const ClockProbe clk(tid);
 
     const int W = p.W, G = TERMS == 4 ? p.Cin / 64 : p.Cin / 32;       // channel groups per K step
     constexpr int GROUP_BYTES = TERMS == 4 ? 256 : 128;
@@ -109,32 +94,19 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
     // per-lane validity of the nine taps for the two A fragments of this wave (rows wm*64 + i*32 + (lane & 31))
     int r_row[TM];
     unsigned ok9[TM];
-    {
-        const int HW = p.H * W;
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int r = wm * (BM / WM) + i * 32 + (lane & 31), m = m0 + r;
-            r_row[i] = r;
-            unsigned bits = 0;
-            if (m < p.M) {
-                const int rem = m % HW, y = rem / W, x = rem - y * W;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-                    bits |= ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)W ? 1u : 0u) << t;
-                }
-            }
-            ok9[i] = bits;
-        }
+    for (int i = 0; i < TM; ++i) {
+        r_row[i] = wm * (BM / WM) + i * 32 + (lane & 31);
+        ok9[i] = tap_valid_bits(p, m0 + r_row[i]);
     }
 
-    f32x16 acc1[TM][TN], acc2[TM][TN];
+    f32x16 acc1[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { acc1[i][j][e] = 0.f; acc2[i][j][e] = 0.f; }
+            for (int e = 0; e < 16; ++e) acc1[i][j][e] = 0.f;
 
     // filter fragment addressing (as in the DMA kernel)
     const int swz = (lane >> 1) & 7, kb = lane >> 5;
@@ -156,19 +128,12 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
             fr[s][f] = *reinterpret_cast<const h8 *>(bst + b_frag + (which - TM) * 32 * ROW + (lo ? bpos_lo[s] : bpos_hi[s]));
         }
     };
-    auto mfma = [&](int s, int m0) {
-        const int m = m0;
+    // slot m of a substep: product block m / 3, term m % 3 of the three-term slot plan the schedule below is laid out for; the half
+    // tiers fill term 0 (hi x hi) and, TERMS = 4, term 1 (the "lo" slots hold the second channel group's hi values)
+    auto mfma = [&](int s, int m) {
         const int ij = m / 3, term = m % 3, i = ij / TN, j = ij % TN;
-        if (TERMS == 1 && term != 0) return;
-        const h8 ah = fr[s][2 * i], al = fr[s][2 * i + 1], bh = fr[s][2 * (TM + j)], bl = fr[s][2 * (TM + j) + 1];
-        if (TERMS == 4) {                                        // both slots hold hi values (of two channel groups)
-            if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
-            else if (term == 1) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bl, acc1[i][j], 0, 0, 0);
-            return;
-        }
-        if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
-        else if (term == 1) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc2[i][j], 0, 0, 0);
-        else acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc2[i][j], 0, 0, 0);
+        if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[s][2 * i], fr[s][2 * (TM + j)], acc1[i][j], 0, 0, 0);
+        else if (TERMS == 4 && term == 1) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[s][2 * i + 1], fr[s][2 * (TM + j) + 1], acc1[i][j], 0, 0, 0);
     };
     // substep-1 fragment order: the operands of accumulator tile (0,0) first
     auto frag_order = [&](int k) {
@@ -198,7 +163,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
             a_sw[i] = ok ? (j >> 1) & 7 : 0;
         }
     };
-    auto step = [&](int g, auto tap_c, auto last_c) {
+    auto step = [&](auto tap_c, int g, auto last_c) {
         constexpr int TAP = decltype(tap_c)::value;
         constexpr bool LAST = decltype(last_c)::value;          // last channel group: no window prefetch, filter refills stop
         constexpr int AHEAD = 2;             // prefetch distance of the filter stages, in steps
@@ -234,17 +199,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
         }
     };
 
-    auto group = [&](int g, auto last_c) {
-        step(g, std::integral_constant<int, 0>{}, last_c);
-        step(g, std::integral_constant<int, 1>{}, last_c);
-        step(g, std::integral_constant<int, 2>{}, last_c);
-        step(g, std::integral_constant<int, 3>{}, last_c);
-        step(g, std::integral_constant<int, 4>{}, last_c);
-        step(g, std::integral_constant<int, 5>{}, last_c);
-        step(g, std::integral_constant<int, 6>{}, last_c);
-        step(g, std::integral_constant<int, 7>{}, last_c);
-        step(g, std::integral_constant<int, 8>{}, last_c);
-    };
+    auto group = [&](int g, auto last_c) { for_each_tap(step, g, last_c); };
 
     // prologue: window of group 0, filter stages of steps 0 and 1, fragments of step 0 / substep 0
     for (int k = 0; k < (npieces + NW - 1) / NW; ++k) a_piece(0, k);
@@ -269,82 +224,46 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_f16x3_win(ConvKernelArgs p, int
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                acc1[i][j][e] *= 1.f / A_SCALE;                       // every tier of this kernel keeps one accumulator set
+                acc1[i][j][e] *= 1.f / A_SCALE;
     conv_epilogue<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true>(p, acc1, reinterpret_cast<float *>(smem), m0, n0, tid);   // whole-tile staging
-#ifdef YDS_CLOCK_PROBE
-    if (clk_sample) {
-        atomicAdd(&yds_clk_win[0], __builtin_amdgcn_s_memtime() - clk_c0);
-        atomicAdd(&yds_clk_win[1], wall_clock64() - clk_w0);
-    }
-#endif
+    clk.end();
 }
 
-int window_rows(int W) { return (BM + 2 * W + 2 + 7) / 8 * 8; }
+// 64 channels per K step where Cin allows (TERMS = 4): a 64-channel layer is a single group there
+constexpr int step_channels(const ConvKernelArgs &k) { return k.terms == 1 && k.Cin % 64 == 0 ? 64 : 32; }
 
 template <int BN, int WM, int WN, int ACT, int RES, int TERMS> void launch_inst_win(ConvKernelArgs k, hipStream_t s) {
-    const int wrows = window_rows(k.W), nbuf = k.Cin == (TERMS == 4 ? 64 : 32) ? 1 : 2;
-    // (the epilogue stages the whole 256 x BN tile in the same LDS: narrow images need more than their windows + ring)
-    const size_t smem = std::max((size_t)nbuf * wrows * ROW + (size_t)NSB * BN * ROW + ROW, conv_stage_bytes(BM, BN));
-    static size_t attr_set = 0;
-    auto kern = conv3x3_f16x3_win<BN, WM, WN, ACT, RES, TERMS>;
-    if (smem > attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = smem;
-    }
-    dim3 grid(plan_tile_map(k, BM, BN));
-    hipLaunchKernelGGL(kern, grid, dim3(NT), smem, s, k, wrows, nbuf);
-    YDS_HIP(hipGetLastError());
+    const int nbuf = win_buffers(k.Cin, TERMS == 4 ? 64 : 32);
+    const WinPlan plan = win_plan(WIN128, BM, BN, NW, k.W, nbuf);
+    launch_conv_tiles<conv3x3_f16x3_win<BN, WM, WN, ACT, RES, TERMS>>(k, BM, BN, 1, NT, plan.launch_bytes, s, plan.wrows, nbuf);
 }
 
 }  // namespace
 
-void conv_win_clock(unsigned long long *cycles_ticks, bool reset) {
-#ifdef YDS_CLOCK_PROBE
-    YDS_HIP(hipMemcpyFromSymbol(cycles_ticks, HIP_SYMBOL(yds_clk_win), 2 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[2] = {};
-        YDS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(yds_clk_win), z, sizeof z));
-    }
-#else
-    cycles_ticks[0] = cycles_ticks[1] = 0;     // product build: no sampling inside the kernel (clock_probe.hip measures beside it)
-    (void)reset;
-#endif
-}
+void conv_win_clock(unsigned long long *cycles_ticks, bool reset) { clock_probe_read(cycles_ticks, reset); }
 
+// the 256-row tiles of this file and of conv_win16.hip (its shapes 0 / 1: same LDS plan), planned for the widest one
 bool conv_win_applicable(const ConvKernelArgs &k) {
     const bool presplit = (k.fmt_x == FMT_H16 && k.Cin % 32 == 0) || (k.fmt_x == FMT_F16 && k.terms == 1 && k.Cin % 64 == 0);
     if (!(k.ksize == 3 && k.stride == 1 && k.pad == 1 && presplit && k.H == k.Ho && k.W == k.Wo)) return false;
-    // (half mode runs 64 channels per K step - launch_conv_win below - so a 64-channel layer is a single group there)
-    const bool wide_step = k.terms == 1 && k.Cin % 64 == 0;
-    const int wrows = window_rows(k.W), nbuf = k.Cin == (wide_step ? 64 : 32) ? 1 : 2;
+    const WinPlan plan = win_plan(WIN128, BM, BN_MAX, NW, k.W, win_buffers(k.Cin, step_channels(k)));
     // several channel groups: the next group's window is fetched by at most APW instructions per wave while this one is
     // consumed (two buffers); a single group needs one buffer only, which admits much wider images
-    if (nbuf == 2 && wrows > MAX_WROWS) return false;
     // (the epilogue stages BM x (BN+4) floats in the same LDS: 135 KB at BN = 128)
-    return (size_t)nbuf * wrows * ROW + (size_t)NSB * 128 * ROW + ROW <= 160 * 1024 && (size_t)k.M * (k.ldx / 4) < (1ull << 32);
+    return plan.prefetch_fits && plan.launch_bytes <= 160 * 1024 && (size_t)k.M * (k.ldx / 4) < (1ull << 32);
 }
 
 // half mode (launch_conv_f16x3_win checks applicability): 256x128, or 256x64 for narrow layers; 64 channels per K step where Cin allows
 void launch_conv_win(ConvKernelArgs k, int shape, hipStream_t s) {
-    if (k.Cin % 64 == 0) {
-        if (shape == 0) {
-#define YDS_CALL(A, R) launch_inst_win<128, 4, 2, A, R, 4>(k, s)
-            YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
+    dispatch_act_res(k, [&](auto A, auto R) {
+        if (k.Cin % 64 == 0) {
+            if (shape == 0) launch_inst_win<128, 4, 2, A, R, 4>(k, s);
+            else launch_inst_win<64, 4, 2, A, R, 4>(k, s);
         } else {
-#define YDS_CALL(A, R) launch_inst_win<64, 4, 2, A, R, 4>(k, s)
-            YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
+            if (shape == 0) launch_inst_win<128, 4, 2, A, R, 1>(k, s);
+            else launch_inst_win<64, 4, 2, A, R, 1>(k, s);
         }
-    } else if (shape == 0) {
-#define YDS_CALL(A, R) launch_inst_win<128, 4, 2, A, R, 1>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    } else {
-#define YDS_CALL(A, R) launch_inst_win<64, 4, 2, A, R, 1>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    }
+    });
 }
 
 }  // namespace yds

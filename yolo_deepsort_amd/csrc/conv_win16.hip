@@ -26,20 +26,10 @@
 // Fragments: lane l holds 8 consecutive channels (chunk l >> 4 of the hi or lo half) of row l & 15 of its block - the 16 lanes
 // of one chunk read 16 consecutive rows, which the swizzle spreads over 16 distinct 16-byte bank slots at any base.
 // C/D layout of the instruction: column (filter) = lane & 15, row (pixel) = 4 * (lane >> 4) + e, e = 0..3.
-#include "conv_common.h"
+#include "conv_win_common.h"
 
 namespace yds {
-
-#ifdef YDS_CLOCK_PROBE
-__device__ unsigned long long yds_clk_win16[2];        // sampled (shader cycles, 100 MHz ticks) inside the kernel, see conv_win.hip
-#endif
-
 namespace {
-
-constexpr int NSB = 3;                         // filter-stage ring depth
-constexpr int ROW = 128;
-constexpr int APW = 7;                         // window DMA instructions per wave per channel group (8 rows each): taps 0-6 of a group carry one
-constexpr int max_wrows(int nw) { return APW * nw * 8; }   // 448 window rows for eight waves, 224 for four
 
 // BM x BN tile on WM x WN waves.  256 x 128 / 256 x 64 on eight waves: one workgroup per CU (its LDS holds two windows + the
 // ring: 154 KB at W = 76).  128 x 64 on four waves (round 4): 76 KB at W = 32, so TWO workgroups share a CU and one computes
@@ -72,11 +62,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
         n0 = tn * BN;
     }
     if (tid < 32) reinterpret_cast<float *>(smem + zoff)[tid] = 0.f;
-#ifdef YDS_CLOCK_PROBE
-    const bool clk_sample = tid == 0 && (blockIdx.x & 31) == 0;
-    unsigned long long clk_c0 = 0, clk_w0 = 0;
-    if (clk_sample) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = wall_clock64(); }
-#endif
+    const ClockProbe clk(tid);
 
     const int W = p.W, G = p.Cin / 32;
     const int drow = lane >> 3, dpos = lane & 7;
@@ -105,25 +91,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
     // blocks per register
     const int r0 = wm * RW + (lane & 15);
     unsigned okbits[(TM + 2) / 3];
-    {
-        const int HW = p.H * W;
 #pragma unroll
-        for (int q = 0; q < (TM + 2) / 3; ++q) okbits[q] = 0;
+    for (int q = 0; q < (TM + 2) / 3; ++q) okbits[q] = 0;
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + r0 + i * 16;
-            unsigned bits = 0;
-            if (m < p.M) {
-                const int rem = m % HW, y = rem / W, x = rem - y * W;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-                    bits |= ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)W ? 1u : 0u) << t;
-                }
-            }
-            okbits[i / 3] |= bits << (9 * (i % 3));
-        }
-    }
+    for (int i = 0; i < TM; ++i) okbits[i / 3] |= tap_valid_bits(p, m0 + r0 + i * 16) << (9 * (i % 3));
 
     f32x4 acc1[TM][TN], acc2[TM][TN];                           // hi x hi; hi x lo + lo x hi
 #pragma unroll
@@ -171,7 +142,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
             a_hi[i] = ok ? wbase + j * ROW + ((kq ^ ((j >> 1) & 7)) << 4) : zoff + (kq << 4);
         }
     };
-    auto step = [&](int g, auto tap_c, auto last_c) {
+    auto step = [&](auto tap_c, int g, auto last_c) {
         constexpr int TAP = decltype(tap_c)::value;
         constexpr bool LAST = decltype(last_c)::value;          // last channel group: no window prefetch, filter refills stop
         constexpr bool REFILL = !(LAST && TAP + 2 > 8);         // a step t+2 exists
@@ -221,17 +192,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto group = [&](int g, auto last_c) {
-        step(g, std::integral_constant<int, 0>{}, last_c);
-        step(g, std::integral_constant<int, 1>{}, last_c);
-        step(g, std::integral_constant<int, 2>{}, last_c);
-        step(g, std::integral_constant<int, 3>{}, last_c);
-        step(g, std::integral_constant<int, 4>{}, last_c);
-        step(g, std::integral_constant<int, 5>{}, last_c);
-        step(g, std::integral_constant<int, 6>{}, last_c);
-        step(g, std::integral_constant<int, 7>{}, last_c);
-        step(g, std::integral_constant<int, 8>{}, last_c);
-    };
+    auto group = [&](int g, auto last_c) { for_each_tap(step, g, last_c); };
 
     // prologue: window of group 0, filter stages of steps 0 and 1, H0 fragments of step 0
     for (int k = 0; k < (npieces + NW - 1) / NW; ++k) a_piece(0, k);
@@ -257,77 +218,38 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc1[i][j][e] = (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
     conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true>(p, acc1, reinterpret_cast<float *>(smem), m0, n0, tid);   // whole-tile staging
-#ifdef YDS_CLOCK_PROBE
-    if (clk_sample) {
-        atomicAdd(&yds_clk_win16[0], __builtin_amdgcn_s_memtime() - clk_c0);
-        atomicAdd(&yds_clk_win16[1], wall_clock64() - clk_w0);
-    }
-#endif
-}
-
-int window_rows16(int BM, int W) { return (BM + 2 * W + 2 + 7) / 8 * 8; }
-size_t win16_smem(int BM, int BN, int W, int Cin) {
-    const int wrows = window_rows16(BM, W), nbuf = Cin == 32 ? 1 : 2;
-    // (the epilogue stages the whole BM x BN tile in the same LDS: narrow images need more than their windows + ring)
-    return std::max((size_t)nbuf * wrows * ROW + (size_t)NSB * BN * ROW + ROW, conv_stage_bytes(BM, BN));
+    clk.end();
 }
 
 template <int BM, int BN, int WM, int WN, int ACT, int RES> void launch_inst_win16(ConvKernelArgs k, hipStream_t s) {
-    constexpr int NT = WM * WN * 64;
-    const int wrows = window_rows16(BM, k.W), nbuf = k.Cin == 32 ? 1 : 2;
-    const size_t smem = win16_smem(BM, BN, k.W, k.Cin);
-    static size_t attr_set = 0;
-    auto kern = conv3x3_f16x3_win16<BM, BN, WM, WN, ACT, RES>;
-    if (smem > attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = smem;
-    }
-    dim3 grid(plan_tile_map(k, BM, BN));
-    hipLaunchKernelGGL(kern, grid, dim3(NT), smem, s, k, wrows, nbuf);
-    YDS_HIP(hipGetLastError());
+    const int nbuf = win_buffers(k.Cin, 32);
+    const WinPlan plan = win_plan(WIN128, BM, BN, WM * WN, k.W, nbuf);
+    launch_conv_tiles<conv3x3_f16x3_win16<BM, BN, WM, WN, ACT, RES>>(k, BM, BN, 1, WM * WN * 64, plan.launch_bytes, s, plan.wrows, nbuf);
 }
+
+constexpr int SMALL_BM = 128, SMALL_BN = 64, SMALL_NW = 4;       // shape 2
 
 }  // namespace
 
-void conv_win16_clock(unsigned long long *cycles_ticks, bool reset) {
-#ifdef YDS_CLOCK_PROBE
-    YDS_HIP(hipMemcpyFromSymbol(cycles_ticks, HIP_SYMBOL(yds_clk_win16), 2 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[2] = {};
-        YDS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(yds_clk_win16), z, sizeof z));
-    }
-#else
-    cycles_ticks[0] = cycles_ticks[1] = 0;     // product build: no sampling inside the kernel (clock_probe.hip measures beside it)
-    (void)reset;
-#endif
-}
+void conv_win16_clock(unsigned long long *cycles_ticks, bool reset) { clock_probe_read(cycles_ticks, reset); }
 
 // the 128 x 64 tile with two workgroups per CU: 64-filter layers whose two windows + ring fit 80 KB and whose window is fetched by
 // at most APW instructions per wave (W <= 43 with several channel groups: 216 window rows)
 bool conv_win16_small_applicable(const ConvKernelArgs &k) {
-    if (!conv_win_applicable(k) || k.Cout > 64) return false;
-    const int wrows = window_rows16(128, k.W), nbuf = k.Cin == 32 ? 1 : 2;
-    if (nbuf == 2 && wrows > max_wrows(4)) return false;
-    return win16_smem(128, 64, k.W, k.Cin) <= 80 * 1024;
+    if (!conv_win_applicable(k) || k.Cout > SMALL_BN) return false;
+    const WinPlan plan = win_plan(WIN128, SMALL_BM, SMALL_BN, SMALL_NW, k.W, win_buffers(k.Cin, 32));
+    return plan.prefetch_fits && plan.launch_bytes <= 80 * 1024;
 }
 
 // default arithmetic (f16x3) of the window-resident kernel; shapes 0 / 1: applicability is conv_win_applicable's (same LDS plan),
 // shape 2: conv_win16_small_applicable
 void launch_conv_win16(ConvKernelArgs k, int shape, hipStream_t s) {
-    if (shape == 0) {
-#define YDS_CALL(A, R) launch_inst_win16<256, 128, 4, 2, A, R>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    } else if (shape == 1) {
-#define YDS_CALL(A, R) launch_inst_win16<256, 64, 8, 1, A, R>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    } else {
-        if (!conv_win16_small_applicable(k)) fail("conv: the 128x64 window-resident tile needs a 3x3 stride-1 layer with a pre-split input, at most 64 filters and W <= 43");
-#define YDS_CALL(A, R) launch_inst_win16<128, 64, 4, 1, A, R>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    }
+    if (shape != 0 && shape != 1 && !conv_win16_small_applicable(k)) fail("conv: the 128x64 window-resident tile needs a 3x3 stride-1 layer with a pre-split input, at most 64 filters and W <= 43");
+    dispatch_act_res(k, [&](auto A, auto R) {
+        if (shape == 0) launch_inst_win16<256, 128, 4, 2, A, R>(k, s);
+        else if (shape == 1) launch_inst_win16<256, 64, 8, 1, A, R>(k, s);
+        else launch_inst_win16<SMALL_BM, SMALL_BN, SMALL_NW, 1, A, R>(k, s);
+    });
 }
 
 }  // namespace yds

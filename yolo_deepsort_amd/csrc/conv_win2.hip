@@ -12,22 +12,17 @@
 // Swizzle for 64-byte rows: row r keeps its 16-byte chunk c at position c ^ ((r >> 2) & 3); a ds_read_b128 lane group
 // covers 16 rows with distinct residues mod 16, i.e. all 16 (r & 3, (r >> 2) & 3) pairs once: 16 distinct bank slots at
 // ANY base row, which is what the shifted tap windows need.
-#include "conv_common.h"
+#include "conv_win_common.h"
 
 namespace yds {
-
-#ifdef YDS_CLOCK_PROBE
-__device__ unsigned long long yds_clk_win2[2];  // sustained shader clock inside the kernel: (cycles, 100 MHz ticks) of one workgroup in 32 (see conv_win.hip)
-#endif
-
 namespace {
 
 constexpr int BM2 = 128, BN2 = 128, NW2 = 4, NT2 = NW2 * 64;
-constexpr int ROW2 = 64;                        // bytes per LDS row (one pixel or one filter, one half group: 16 hi + 16 lo fp16)
-constexpr int NSB2 = 4;                         // filter-stage ring depth
+constexpr int ROW2 = WIN64.row;                 // bytes per LDS row (one pixel or one filter, one half group: 16 hi + 16 lo fp16)
+constexpr int NSB2 = WIN64.nsb;                 // filter-stage ring depth
+constexpr int APW2 = WIN64.apw;                 // window pieces per wave and half group: taps 0-5 carry one (two resident workgroups: <= 80 KB each)
 constexpr int B_STAGE2 = BN2 * ROW2;            // 8 KB
 constexpr int B_INST2 = BN2 / (16 * NW2);       // filter DMA instructions per wave per stage (16 rows each): 2
-constexpr int MAX_WROWS2 = 384;
 
 template <int ACT, int RES, int TERMS>
 __global__ __launch_bounds__(NT2, 2) void conv3x3_f16x3_win2(ConvKernelArgs p, int wrows, int apw) {
@@ -49,11 +44,7 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_f16x3_win2(ConvKernelArgs p, i
         n0 = tn * BN2;
     }
     if (tid < 16) reinterpret_cast<float *>(smem + zoff)[tid] = 0.f;
-#ifdef YDS_CLOCK_PROBE
-    const bool clk_sample = tid == 0 && (blockIdx.x & 31) == 0;
-    unsigned long long clk_c0 = 0, clk_w0 = 0;
-    if (clk_sample) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_w0 = wall_clock64(); }
-#endif
+    const ClockProbe clk(tid);
     const int W = p.W, G = p.Cin / 32, HG = 2 * G;               // half groups
     const int drow = lane >> 2, dpos = lane & 3;
     const int npieces = wrows / 16;
@@ -83,23 +74,10 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_f16x3_win2(ConvKernelArgs p, i
     // per-lane validity of the nine taps for the two A fragments of this wave (rows wm*64 + i*32 + (lane & 31))
     int r_row[TM];
     unsigned ok9[TM];
-    {
-        const int HW = p.H * W;
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int r = wm * (BM2 / WM) + i * 32 + (lane & 31), m = m0 + r;
-            r_row[i] = r;
-            unsigned bits = 0;
-            if (m < p.M) {
-                const int rem = m % HW, y = rem / W, x = rem - y * W;
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-                    bits |= ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)W ? 1u : 0u) << t;
-                }
-            }
-            ok9[i] = bits;
-        }
+    for (int i = 0; i < TM; ++i) {
+        r_row[i] = wm * (BM2 / WM) + i * 32 + (lane & 31);
+        ok9[i] = tap_valid_bits(p, m0 + r_row[i]);
     }
 
     f32x16 acc1[TM][TN], acc2[TM][TN];
@@ -190,13 +168,15 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_f16x3_win2(ConvKernelArgs p, i
             mfma(PAR, m);
             __builtin_amdgcn_sched_barrier(0);
             const int o = m < NF ? m + NDMA : (m - NF < NDMA ? m - NF : NDMA + NF);   // operation: 0 window, 1..2 filter, 3..10 fragments; the next step's fragments go first
-            if (o == 0) { if (!LAST && TAP < 6 && TAP < apw) a_piece(hg + 1, TAP); }
+            if (o == 0) { if (!LAST && TAP < APW2 && TAP < apw) a_piece(hg + 1, TAP); }
             else if (o - 1 < B_INST2) { if (REFILL) b_piece(hg4, TAP4, slot0, o - 1); }
             else if (o - NDMA < NF) { if (NEXT) frag_read(bst1, PAR ^ 1, frag_order(o - NDMA)); }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
     // nine taps of one half group; the step parity alternates and 9 is odd, so half groups alternate between two bodies
+    // (written out, not for_each_tap: with the fold the compiler stopped inlining half_group<not last, parity 0>, which has two call
+    // sites, and forcing it inline laid the loop bodies out in another order)
     auto half_group = [&](int hg, auto last_c, auto par_c) {
         constexpr int P0 = decltype(par_c)::value;
         step(hg, std::integral_constant<int, 0>{}, last_c, std::integral_constant<int, P0>{});
@@ -240,64 +220,31 @@ __global__ __launch_bounds__(NT2, 2) void conv3x3_f16x3_win2(ConvKernelArgs p, i
             for (int e = 0; e < 16; ++e)
                 acc1[i][j][e] = TERMS == 1 ? acc1[i][j][e] * (1.f / A_SCALE) : (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
     conv_epilogue<BM2, BN2, WM, WN, ACT, RES, TM, TN, NT2, true>(p, acc1, reinterpret_cast<float *>(smem), m0, n0, tid);   // whole-tile staging
-#ifdef YDS_CLOCK_PROBE
-    if (clk_sample) {
-        atomicAdd(&yds_clk_win2[0], __builtin_amdgcn_s_memtime() - clk_c0);
-        atomicAdd(&yds_clk_win2[1], wall_clock64() - clk_w0);
-    }
-#endif
+    clk.end();
 }
 
-int window_rows2(int W) { return (BM2 + 2 * W + 2 + 15) / 16 * 16; }
-
-template <int ACT, int RES, int TERMS = 3> void launch_inst_win2(ConvKernelArgs k, hipStream_t s) {
-    const int wrows = window_rows2(k.W);
-    const int apw = (wrows / 16 + NW2 - 1) / NW2;
-    const size_t smem = std::max((size_t)2 * wrows * ROW2 + (size_t)NSB2 * B_STAGE2 + ROW2, conv_stage_bytes(BM2, BN2));
-    static size_t attr_set = 0;
-    auto kern = conv3x3_f16x3_win2<ACT, RES, TERMS>;
-    if (smem > attr_set) {
-        YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = smem;
-    }
-    dim3 grid(plan_tile_map(k, BM2, BN2));
-    hipLaunchKernelGGL(kern, grid, dim3(NT2), smem, s, k, wrows, apw);
-    YDS_HIP(hipGetLastError());
+template <int ACT, int RES, int TERMS> void launch_inst_win2(ConvKernelArgs k, hipStream_t s) {
+    const WinPlan plan = win_plan(WIN64, BM2, BN2, NW2, k.W, 2);
+    const int apw = (plan.wrows / WIN64.piece() + NW2 - 1) / NW2;   // window pieces per wave
+    launch_conv_tiles<conv3x3_f16x3_win2<ACT, RES, TERMS>>(k, BM2, BN2, 1, NT2, plan.launch_bytes, s, plan.wrows, apw);
 }
 
 }  // namespace
 
 bool conv_win2_applicable(const ConvKernelArgs &k) {
     if (!(k.ksize == 3 && k.stride == 1 && k.pad == 1 && k.fmt_x == FMT_H16 && k.Cin % 32 == 0 && k.H == k.Ho && k.W == k.Wo)) return false;
-    const int wrows = window_rows2(k.W);
-    if (wrows > MAX_WROWS2) return false;                        // two resident workgroups: <= 80 KB each; <= 6 window pieces per wave and half group
+    if (!win_plan(WIN64, BM2, BN2, NW2, k.W, 2).prefetch_fits) return false;   // <= APW2 window pieces per wave and half group (W <= 127)
     return (size_t)k.M * ((size_t)k.ldx / 4) < (1ull << 32) && (size_t)k.Cout * (k.Kpad / 4) < (1ull << 32);
 }
 
-void conv_win2_clock(unsigned long long *cycles_ticks, bool reset) {
-#ifdef YDS_CLOCK_PROBE
-    YDS_HIP(hipMemcpyFromSymbol(cycles_ticks, HIP_SYMBOL(yds_clk_win2), 2 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[2] = {};
-        YDS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(yds_clk_win2), z, sizeof z));
-    }
-#else
-    cycles_ticks[0] = cycles_ticks[1] = 0;     // product build: no sampling inside the kernel (clock_probe.hip measures beside it)
-    (void)reset;
-#endif
-}
+void conv_win2_clock(unsigned long long *cycles_ticks, bool reset) { clock_probe_read(cycles_ticks, reset); }
 
 void launch_conv_win2(ConvKernelArgs k, hipStream_t s) {
     if (!conv_win2_applicable(k)) fail("conv: the two-workgroup window-resident kernel needs a 3x3 stride-1 layer with a pre-split input and W <= 127");
-    if (k.terms == 1) {
-#define YDS_CALL(A, R) launch_inst_win2<A, R, 1>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    } else {
-#define YDS_CALL(A, R) launch_inst_win2<A, R>(k, s)
-        YDS_DISPATCH_ACT_RES(k, YDS_CALL)
-#undef YDS_CALL
-    }
+    dispatch_act_res(k, [&](auto A, auto R) {
+        if (k.terms == 1) launch_inst_win2<A, R, 1>(k, s);
+        else launch_inst_win2<A, R, 3>(k, s);
+    });
 }
 
 }  // namespace yds
