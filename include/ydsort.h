@@ -121,6 +121,13 @@ int yds_detect_tiled(yds_net *, const uint8_t *rgb_hwc_host, int h, int w, const
                      float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out);
 int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres,
                        float *out6_host, int cap, int *n_out);
+/* yds_nms_merge_pred_batched <- the same function for n_frames images in ONE launch sequence, entirely on the device: the launch the
+ *                        window-mode pipeline uses (yds_pipeline_set_windows) - corner-form candidates, blockIdx.y = image, the merge
+ *                        branch as a kernel (one workgroup per image, sums in candidate order like the host loop of
+ *                        yds_nms_merge_pred, so NaN rows agree) before the results are published; no candidate copy to the host.
+ *                        pred_host [n_frames, n_boxes, attrs]; out6_host [n_frames, cap, 6]; n_out[n_frames] rows per image. */
+int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
+                               float *out6_host, int cap, int *n_out);
 
 /* ---- ReID: crop + Extractor + Net(reid=True) --------------------------------------------
  * yds_reid_load_tensor <- Extractor.__init__ load_state_dict  feature_extractor.py:13-17
@@ -267,6 +274,20 @@ int yds_pipeline_set_schedule(yds_pipe *, int min_crops);
  * decoded frame before the detector sees it), 1 = B, G, R as a decoder delivers them - the resize front end and the ReID crops then
  * read channel c from byte 2 - c, the same integers as on the reversed copy the reference makes, without making it. */
 int yds_pipeline_set_frame_order(yds_pipe *, int bgr);
+/* Window mode <- ImageDetector(win_size=(win_w, win_h), overlap) yolo3/detect/img_detect.py:97-151 for every frame of a step.  Each
+ * frame is cut into T windows on a win_w x win_h grid (x-major, then y: `for x: for y:`), every window extended by
+ * ox = int(win_w * overlap), oy = int(win_h * overlap) and clipped to the frame; the B * T windows of a step are stretched to the model
+ * size straight from the frames in HBM (frame order honoured) and run through the network in chunks of at most batch_max; behind every
+ * chunk the boxes go to corner form, are scaled to the window (resize_boxes) and shifted by its origin into per-frame storage in the
+ * order of the concatenation at :142; ONE NMS launch per step does soft_non_max_suppression(merge=True, is_p1p2=True) for all frames
+ * (yds_nms_merge_pred_batched), the merge branch included, on the device.  ReID, association, look-ahead, host-frame entries,
+ * prefetch, multi-stream and stage times work as without windows (stage_us[0] is 0: the resize is part of the detector's figure;
+ * the serialized schedule applies, with the whole detector pass behind the ReID pass instead of split around it).  A frame with
+ * w < win_w and h < win_h takes the plain path (:68).  win_w <= 0: window mode off (the default).  Valid for single- and multi-stream
+ * pipelines; refused while a look-ahead pass is in flight (after a step that was given next frames: run the step that consumes them
+ * first).  Memory: the shifted predictions of a step stay resident, B * T * boxes * attrs * 4 bytes (yolov3-608: 7.73 MB per window).
+ * Bench-only logit injection (yds_darknet_load_injection_sets) addresses the slots of a chunk: slot b * T + t while B * T <= batch_max. */
+int yds_pipeline_set_windows(yds_pipe *, int win_w, int win_h, double overlap);
 int yds_pipeline_last_schedule(yds_pipe *);
 int yds_pipeline_schedule_trial(yds_pipe *, int uploaded, int *decided, double *serialized_s, double *two_stream_s);
 /* last step, microseconds: resize (device), detector (device: the detector pass alone - a ReID pass the serialized schedule puts

@@ -74,6 +74,7 @@ SIGNATURES = {
     "yds_nms": (_I, [_P, _I, _F, _F, _I, _I, _P, _I, _P]),
     "yds_nms_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),
     "yds_nms_merge_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),
+    "yds_nms_merge_pred_batched": (_I, [_P, _I, _I, _I, _F, _F, _P, _I, _P]),
     "yds_detect_tiled": (_I, [_P, _P, _I, _I, _P, _I, _F, _F, _P, _I, _P]),
     "yds_reid_create": (_P, [_I]),
     "yds_reid_destroy": (None, [_P]),
@@ -139,6 +140,7 @@ SIGNATURES = {
     "yds_swap_rb": (_I, [_P, _SZ]),
     "yds_overlay_tracks_bgr": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "yds_pipeline_set_frame_order": (_I, [_P, _I]),
+    "yds_pipeline_set_windows": (_I, [_P, _I, _I, C.c_double]),
 }
 
 _lib = None

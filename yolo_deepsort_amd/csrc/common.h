@@ -146,9 +146,11 @@ void launch_inject_batch(const View &head, int batch, const float *table_dev, co
                          int num_classes, float logit, hipStream_t s);
 // stretch-resize uint8 HWC frames to NHWC4 fp32 in [0,1] (4th channel 0)
 void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y, hipStream_t s, bool bgr = false);   // bgr: frames in a decoder's B, G, R byte order
-void launch_tile_resize(const uint8_t *frame, int w, const int *tiles_dev, int n_tiles, const View &y, hipStream_t s);
-void launch_tile_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int n_tiles, float *dst,
-                       hipStream_t s);
+// sliding windows: slots [slot0, slot0 + n) of B frames x T windows (slot = b * T + t; one host frame: B = 1), layers.hip
+void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_dev, int T, int slot0, int n, const View &y, hipStream_t s,
+                          bool bgr);
+void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int T, int slot0, int n,
+                         float *dst, hipStream_t s);
 // ReID: crop + resize to 64x128 + /255 + mean/std -> NHWC4
 // boxes: [D,5] = x1,y1,x2,y2,frame index (frames are h*w*3 bytes apart)
 void launch_crop_resize(const uint8_t *frames, int h, int w, const int *boxes5_dev, int D, const View &y,

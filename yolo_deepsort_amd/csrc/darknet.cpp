@@ -735,10 +735,9 @@ void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *
     YDS_HIP(hipMemcpyAsync(tile_scale.p, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     for (int t0 = 0; t0 < n_tiles; t0 += batch_max) {
         const int nb = std::min(batch_max, n_tiles - t0);
-        launch_tile_resize(stage_u8.p, w, tile_rects.p + (size_t)t0 * 4, nb, input_view(nb), stream);
+        launch_window_resize(stage_u8.p, h, w, tile_rects.p, n_tiles, t0, nb, input_view(nb), stream, false);
         run_graph(nb);
-        launch_tile_boxes(out.p, total_boxes, attrs, tile_rects.p + (size_t)t0 * 4, tile_scale.p + (size_t)t0 * 2, nb,
-                          tiled_pred.p + (size_t)t0 * total_boxes * attrs, stream);
+        launch_window_boxes(out.p, total_boxes, attrs, tile_rects.p, tile_scale.p, n_tiles, t0, nb, tiled_pred.p, stream);
     }
     YDS_HIP(hipStreamSynchronize(stream));          // `scale` and the caller's buffers may go away
 }

@@ -153,9 +153,10 @@ public:
     ~NmsWorkspace();
     NmsWorkspace(const NmsWorkspace &) = delete;
     // asynchronous form: launch() enqueues the kernels and the copies into pinned host memory, collect() reads
-    // them after the caller synchronised the stream
+    // them after the caller synchronised the stream.  corner: the predictions already hold x1,y1,x2,y2 (is_p1p2=True);
+    // merge: the reference's merge branch as a kernel behind the sweep (nms_merge_kernel) - both per launch, no state
     void launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                float sx, float sy, int cap, hipStream_t s);
+                float sx, float sy, int cap, hipStream_t s, bool corner = false, bool merge = false);
     int collect(int frame, float *out6_host, int cap);
     void resize(int max_candidates, int n_frames);       // (re)allocates; contents are lost
     int needed(int n_frames) const;                       // largest candidate count of the last launch (after the caller's sync)
@@ -167,7 +168,6 @@ public:
     // merge=True / is_p1p2=True form used by the sliding-window detector: corner-form boxes, the reference's merge branch
     int run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap, hipStream_t s);
     int max_cand, frames;
-    bool corner = false;         // predictions already hold x1,y1,x2,y2
     DevBuf<float> cand;          // [max_cand, 6]   x1,y1,x2,y2,score,cls in candidate order
     DevBuf<float> sorted;        // [max_cand, 6]   score order
     DevBuf<int> counts;          // [0] n candidates, [1] n kept

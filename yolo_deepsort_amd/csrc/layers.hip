@@ -419,49 +419,60 @@ void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y,
     YDS_HIP(hipGetLastError());
 }
 
-// Sliding-window front end (img_detect.py:103-111): window `b` of the frame (x, y, th, tw) is stretched to the model
-// size into batch slot b, same bilinear arithmetic as resize_u8_kernel.
-__global__ void tile_resize_kernel(const uint8_t *frame, int W, const int *tiles, int n_tiles, float *y, int Ho, int Wo) {
-    const size_t total = (size_t)n_tiles * Ho * Wo;
+// Sliding-window front end (img_detect.py:103-111): every window (x, y, th, tw) is stretched to the model size into its batch slot,
+// same bilinear arithmetic as resize_u8_kernel.  A step of the batched pipeline (pipeline.cpp window mode) holds B frames of T
+// windows each, window t of frame b is slot b * T + t; `tiles` is the table of ONE frame's T windows - every frame of a step is cut
+// alike.  A launch covers the slots [slot0, slot0 + n) of one network chunk (which may straddle frames) and reads the frames where
+// they lie in HBM; bgr as resize_u8_kernel.  One host frame (Darknet::forward_tiles_host) is the case B = 1.
+__global__ void window_resize_kernel(const uint8_t *frames, int H, int W, const int *tiles, int T, int slot0, int n, float *y, int Ho, int Wo,
+                                     int bgr) {
+    const size_t total = (size_t)n * Ho * Wo;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         int ox = idx % Wo;
-        size_t t = idx / Wo;
-        int oy = t % Ho;
-        int n = t / Ho;
-        const int x0 = tiles[n * 4 + 0], y0 = tiles[n * 4 + 1], th = tiles[n * 4 + 2], tw = tiles[n * 4 + 3];
+        size_t r = idx / Wo;
+        int oy = r % Ho;
+        const int slot = slot0 + (int)(r / Ho), b = slot / T, t = slot - b * T;
+        const int x0 = tiles[t * 4 + 0], y0 = tiles[t * 4 + 1], th = tiles[t * 4 + 2], tw = tiles[t * 4 + 3];
         float o[3];
-        resize_px(frame + ((size_t)y0 * W + x0) * 3, (size_t)W * 3, th, tw, Ho, Wo, oy, ox, o);
+        resize_px(frames + ((size_t)b * H * W + (size_t)y0 * W + x0) * 3, (size_t)W * 3, th, tw, Ho, Wo, oy, ox, o);
+        if (bgr) { const float v = o[0]; o[0] = o[2]; o[2] = v; }
         *reinterpret_cast<float4 *>(y + idx * 4) = make_float4(__fdiv_rn(o[0], 255.f), __fdiv_rn(o[1], 255.f), __fdiv_rn(o[2], 255.f), 0.f);
     }
 }
 
-void launch_tile_resize(const uint8_t *frame, int w, const int *tiles_dev, int n_tiles, const View &y, hipStream_t s) {
+void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_dev, int T, int slot0, int n, const View &y, hipStream_t s,
+                          bool bgr) {
     if (y.c != 4 || y.ld != 4) fail("resize: destination must be NHWC4");
-    hipLaunchKernelGGL(tile_resize_kernel, dim3(grid_for((size_t)n_tiles * y.h * y.w)), dim3(256), 0, s, frame, w, tiles_dev, n_tiles, y.p, y.h, y.w);
+    hipLaunchKernelGGL(window_resize_kernel, dim3(grid_for((size_t)n * y.h * y.w)), dim3(256), 0, s, frames, h, w, tiles_dev, T, slot0, n, y.p,
+                       y.h, y.w, bgr ? 1 : 0);
     YDS_HIP(hipGetLastError());
 }
 
-// img_detect.py:131-139: centre form -> corner form (x -+ w/2), resize_boxes to the window's own size (python-double
-// ratio rounded to fp32, passed in `scale`), shift by the window origin; the other attributes are copied.
-__global__ void tile_boxes_kernel(const float *pred, int n_boxes, int attrs, const int *tiles, const float *scale, int n_tiles, float *dst) {
-    const size_t total = (size_t)n_tiles * n_boxes;
+// img_detect.py:131-139 for the predictions of one chunk: centre form -> corner form (x -+ w/2), resize_boxes to the window's own
+// size (python-double ratio rounded to fp32, passed in `scale`), shift by the window origin; the other attributes are copied.  Row r
+// of `pred` is a box of slot slot0 + r / n_boxes, whose window is slot % T; `dst` is the step's whole [B * T * n_boxes, attrs] block,
+// so a frame's rows lie window-major, then in box order - the concatenation of img_detect.py:142.
+__global__ void window_boxes_kernel(const float *pred, int n_boxes, int attrs, const int *tiles, const float *scale, int T, int slot0, int n,
+                                    float *dst) {
+    const size_t total = (size_t)n * n_boxes;
     for (size_t row = blockIdx.x * (size_t)(blockDim.x / 32) + threadIdx.x / 32; row < total; row += (size_t)gridDim.x * (blockDim.x / 32)) {
-        const int b = row / n_boxes, lane = threadIdx.x % 32;
+        const int t = (slot0 + (int)(row / n_boxes)) % T, lane = threadIdx.x % 32;
         const float *p = pred + row * attrs;
-        float *d = dst + row * attrs;
+        float *d = dst + ((size_t)slot0 * n_boxes + row) * attrs;
         for (int j = 4 + lane; j < attrs; j += 32) d[j] = p[j];
         if (lane < 4) {
             const float half = __fdiv_rn(p[2 + (lane & 1)], 2.f);
             float v = lane < 2 ? __fsub_rn(p[lane & 1], half) : __fadd_rn(p[lane & 1], half);
-            v = __fmul_rn(v, scale[b * 2 + (lane & 1)]);
-            d[lane] = __fadd_rn(v, (float)tiles[b * 4 + (lane & 1)]);
+            v = __fmul_rn(v, scale[t * 2 + (lane & 1)]);
+            d[lane] = __fadd_rn(v, (float)tiles[t * 4 + (lane & 1)]);
         }
     }
 }
 
-void launch_tile_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int n_tiles, float *dst, hipStream_t s) {
-    hipLaunchKernelGGL(tile_boxes_kernel, dim3(grid_for((size_t)n_tiles * n_boxes * 32)), dim3(256), 0, s, pred, n_boxes, attrs, tiles_dev, scale_dev,
-                       n_tiles, dst);
+void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int T, int slot0, int n,
+                         float *dst, hipStream_t s) {
+    hipLaunchKernelGGL(window_boxes_kernel, dim3(grid_for((size_t)n * n_boxes * 32)), dim3(256), 0, s, pred, n_boxes, attrs, tiles_dev, scale_dev,
+                       T, slot0, n, dst);
     YDS_HIP(hipGetLastError());
 }
 

@@ -233,6 +233,50 @@ NmsWorkspace::~NmsWorkspace() {
     if (h_kept) (void)hipHostFree(h_kept);
 }
 
+// The merge branch of soft_non_max_suppression(merge=True, is_p1p2=True) on the device, one workgroup per image: what the host loop
+// of run_merge() does (model_build.py:122-131; see the comment there), for the batched launch of the window-mode pipeline.  It fires
+// when 1 < n < 3000 and the kept count k is n or 1: every kept row's box becomes the weighted mean of ALL candidates whose +1-pixel
+// IoU (model_build.py:354-381, on class-offset boxes) with the paired kept box - kept row j when k == n, kept row 0 when k == 1 -
+// exceeds the threshold, weights = the candidates' scores.  The IoUs are computed by all threads; the sums are taken by ONE thread in
+// candidate order (fp32 weight sum, fp64 box sums, like the host loop), so that the rounding and the rows where 0/0 gives NaN are
+// the host's.  `cand` holds the candidates in emit order, `sorted` in kept (score) order; runs behind the sweep, before publish.
+constexpr int MERGE_MAX = 3000;
+__global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
+                                                        float iou_thres, float *kept_all) {
+    const float *cand = cand_all + (size_t)blockIdx.x * max_cand * 6;
+    const float *sorted = sorted_all + (size_t)blockIdx.x * max_cand * 6;
+    float *kept = kept_all + (size_t)blockIdx.x * MAX_DET * 6;
+    const int n = counts_all[blockIdx.x * 4], k = counts_all[blockIdx.x * 4 + 1];
+    if (!(n > 1 && n < MERGE_MAX && n <= max_cand && (k == n || k == 1))) return;
+    __shared__ float wgt[MERGE_MAX];
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        float a[4], b[4];
+        offset_box(sorted + (size_t)(k == 1 ? 0 : j) * 6, a);
+        offset_box(cand + (size_t)j * 6, b);
+        float iw = __fadd_rn(__fsub_rn(fminf(a[2], b[2]), fmaxf(a[0], b[0])), 1.f);
+        float ih = __fadd_rn(__fsub_rn(fminf(a[3], b[3]), fmaxf(a[1], b[1])), 1.f);
+        iw = iw > 0.f ? iw : 0.f; ih = ih > 0.f ? ih : 0.f;
+        const float inter = __fmul_rn(iw, ih);
+        const float a1 = __fmul_rn(__fadd_rn(__fsub_rn(a[2], a[0]), 1.f), __fadd_rn(__fsub_rn(a[3], a[1]), 1.f));
+        const float a2 = __fmul_rn(__fadd_rn(__fsub_rn(b[2], b[0]), 1.f), __fadd_rn(__fsub_rn(b[3], b[1]), 1.f));
+        const float iou = __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(a1, a2), inter), 1e-16f));
+        wgt[j] = iou > iou_thres ? cand[(size_t)j * 6 + 4] : 0.f;
+    }
+    __syncthreads();
+    __shared__ float mean[4];
+    if (threadIdx.x < 4) {                                       // one coordinate per thread, each sum in candidate order
+        double acc = 0.0;
+        float wsum = 0.f;
+        for (int j = 0; j < n; ++j) {
+            wsum = __fadd_rn(wsum, wgt[j]);
+            acc = __dadd_rn(acc, __dmul_rn((double)wgt[j], (double)cand[(size_t)j * 6 + threadIdx.x]));
+        }
+        mean[threadIdx.x] = __fdiv_rn((float)acc, wsum);         // 0/0 -> NaN like the reference
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < k * 4; i += blockDim.x) kept[(size_t)(i >> 2) * 6 + (i & 3)] = mean[i & 3];
+}
+
 // Results go to the host through a KERNEL that stores into the pinned buffers (host-coherent memory the device writes in place),
 // not through copy commands: a device-to-host hipMemcpyAsync is a copy-engine job and queues behind a frame upload that is in
 // flight (200 MB, 3.6 ms) - the host then learns the detections late, which the pipeline's serialized schedule cannot hide
@@ -248,7 +292,7 @@ __global__ __launch_bounds__(256) void nms_publish_kernel(const int *counts, con
 
 // All `n_frames` images go through each stage in ONE launch (blockIdx.y = image).
 void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                          float sx, float sy, int cap, hipStream_t s) {
+                          float sx, float sy, int cap, hipStream_t s, bool corner, bool merge) {
     if (attrs < 6) fail("nms: predictions need at least one class");
     if (n_frames < 1) fail("nms: no frames");
     if (n_frames > frames) resize(max_cand, n_frames);
@@ -263,6 +307,7 @@ void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frame
     hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
     hipLaunchKernelGGL(nms_sweep_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
                        counts.p, max_cand, sx, sy, kept.p, cap);
+    if (merge) hipLaunchKernelGGL(nms_merge_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, kept.p);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
     hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
     YDS_HIP(hipGetLastError());
@@ -294,17 +339,13 @@ int NmsWorkspace::run(const float *pred_dev, int n_boxes, int attrs, float conf_
 // by one weighted-mean box before the following line raises into the bare except; otherwise the plain result stands.
 int NmsWorkspace::run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap,
                             hipStream_t s) {
-    corner = true;
-    try {
-        launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s);
+    launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s, true);
+    YDS_HIP(hipStreamSynchronize(s));
+    if (needed(1) > max_cand) {
+        resize(needed(1), frames);
+        launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s, true);
         YDS_HIP(hipStreamSynchronize(s));
-        if (needed(1) > max_cand) {
-            resize(needed(1), frames);
-            launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s);
-            YDS_HIP(hipStreamSynchronize(s));
-        }
-    } catch (...) { corner = false; throw; }
-    corner = false;
+    }
     const int n = h_counts[0], k = h_counts[1];
     if (n > 1 && n < 3000 && (k == n || k == 1)) {
         std::vector<float> c((size_t)n * 6);
@@ -382,6 +423,27 @@ int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float con
     pred.upload(pred_host, (size_t)n_boxes * attrs);
     YDS_HIP(hipStreamSynchronize(nullptr));
     *n_out = workspace().run_merge(pred.p, n_boxes, attrs, conf_thres, iou_thres, out6_host, cap, nullptr);
+    YDS_API_END
+}
+
+int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host,
+                               int cap, int *n_out) {
+    YDS_API_BEGIN
+    if (n_frames < 1 || n_boxes < 1) yds::fail("nms: %d frames of %d boxes", n_frames, n_boxes);
+    static thread_local std::unique_ptr<yds::NmsWorkspace> ws;           // own workspace: sized by the number of frames
+    if (!ws) ws.reset(new yds::NmsWorkspace(4096, n_frames));
+    yds::DevBuf<float> pred;
+    const size_t stride = (size_t)n_boxes * attrs;
+    pred.upload(pred_host, (size_t)n_frames * stride);
+    YDS_HIP(hipStreamSynchronize(nullptr));
+    for (int pass = 0; pass < 2; ++pass) {
+        // corner-form boxes, the merge branch as a kernel behind the sweep: the launch of the window-mode pipeline
+        ws->launch(pred.p, stride, n_frames, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, yds::MAX_DET, nullptr, true, true);
+        YDS_HIP(hipStreamSynchronize(nullptr));
+        if (ws->needed(n_frames) <= ws->max_cand) break;
+        ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again
+    }
+    for (int f = 0; f < n_frames; ++f) n_out[f] = ws->collect(f, out6_host + (size_t)f * cap * 6, cap);
     YDS_API_END
 }
 

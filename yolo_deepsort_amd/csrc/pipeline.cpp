@@ -142,6 +142,11 @@ public:
             if (stage[b].p && frames_dev == stage[b].p && hipEventQuery(up_done[b]) != hipSuccess)
                 YDS_HIP(hipStreamWaitEvent(net->stream, up_done[b], 0));   // (only while the copy is still running: see step())
         YDS_HIP(hipEventRecord(e0[k], net->stream));
+        if (windows_for(h, w)) {                                    // window mode: the whole pass (resize included) is the tail's
+            YDS_HIP(hipEventRecord(e1[k], net->stream));
+            head_split = false;
+            return;
+        }
         launch_resize_u8(frames_dev, batch, h, w, net->input_view(batch), net->stream, frames_bgr);
         YDS_HIP(hipEventRecord(e1[k], net->stream));
         if (const int sl = slot_of(frames_dev); sl >= 0) { YDS_HIP(hipEventRecord(rd_det[sl], net->stream)); rd_det_set[sl] = true; }
@@ -149,6 +154,12 @@ public:
     }
     void launch_detector_tail(const uint8_t *frames_dev, int h, int w, int batch) {
         const int k = head_slot;
+        if (const int T = windows_for(h, w)) {
+            launch_windows_tail(frames_dev, h, w, batch, T, k);
+            in_flight = frames_dev;
+            in_flight_batch = batch;
+            return;
+        }
         if (head_split) (void)net->forward_resized_part(batch, 1);
         else net->forward_resized(batch);
         YDS_HIP(hipEventRecord(e2[k], net->stream));
@@ -158,6 +169,67 @@ public:
         YDS_HIP(hipEventRecord(e_nms[k], net->stream));
         in_flight = frames_dev;
         in_flight_batch = batch;
+    }
+
+    // ---- window mode (yds_pipeline_set_windows; ImageDetector(win_size, overlap), img_detect.py:97-151, for a batch of frames) ----
+    // Every frame of a step is cut into the same T windows (the reference's grid: x-major, then y; each window extended by the
+    // overlap and clipped to the frame); window t of frame b is slot b * T + t.  The slots run through the network in chunks of at
+    // most batch_max (a chunk may straddle frames); behind every chunk its predictions go - corner form, resize_boxes to the window's
+    // own size, shifted by the window origin (window_boxes_kernel, as yds_detect_tiled does) - into win_pred [batch * T * total_boxes, attrs], a
+    // frame's rows window-major then in box order: the concatenation of img_detect.py:142, which the stable ranking and the merge
+    // branch depend on.  ONE NMS launch per step over n_boxes = T * total_boxes per frame, merge branch as a kernel (nms.hip); no
+    // copy of candidates to the host and no synchronisation inside the pass.  win_pred holds the FULL shifted predictions (no
+    // compaction per chunk): batch * T * total_boxes * attrs * 4 bytes - yolov3-608 (22743 boxes x 85): 7.73 MB per window, 8 frames of
+    // 1080p (T = 8) 495 MB.  One buffer serves both NMS slots: the NMS of a pass and the box kernels of the next are ordered by the
+    // detector's stream.  The window table (T rectangles + scales) is rebuilt when the frame size or the window setting changes.
+    // Bench-only logit injection addresses the slots of a CHUNK (tables [0, batch_max) of the selected set serve every chunk).
+    void set_windows(int ww, int wh, double overlap) {
+        if (in_flight || ahead.reid_in_flight) fail("pipeline: set_windows while a look-ahead pass is in flight (consume it with a step first)");
+        if (ww > 0 && wh <= 0) fail("pipeline: window %d x %d", ww, wh);
+        if (ww > 0 && !(overlap >= 0)) fail("pipeline: window overlap %g", overlap);
+        win_w = ww > 0 ? ww : 0; win_h = ww > 0 ? wh : 0; win_overlap = overlap;
+        win_tab_h = win_tab_w = 0;
+    }
+    // number of windows T of an h x w frame; 0 = the plain path (window mode off, or a frame smaller than the window: img_detect.py:68)
+    int windows_for(int h, int w) {
+        if (win_w <= 0 || (w < win_w && h < win_h)) return 0;
+        if (h == win_tab_h && w == win_tab_w) return win_T;
+        const int ox = (int)(win_w * win_overlap), oy = (int)(win_h * win_overlap);
+        std::vector<int> rects;
+        std::vector<float> scale;
+        for (int x = 0; x < w; x += win_w)
+            for (int y = 0; y < h; y += win_h) {
+                const int th = std::min(y + win_h + oy, h) - y, tw = std::min(x + win_w + ox, w) - x;
+                rects.insert(rects.end(), {x, y, th, tw});
+                scale.push_back((float)((double)tw / net->img_w));      // resize_boxes: python-double ratio, fp32 multiply
+                scale.push_back((float)((double)th / net->img_h));
+            }
+        YDS_HIP(hipStreamSynchronize(net->stream));                 // a pass that reads the previous table may still run
+        win_rects.ensure(rects.size());
+        win_scale.ensure(scale.size());
+        YDS_HIP(hipMemcpy(win_rects.p, rects.data(), rects.size() * sizeof(int), hipMemcpyHostToDevice));
+        YDS_HIP(hipMemcpy(win_scale.p, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice));
+        win_tab_h = h; win_tab_w = w; win_T = (int)rects.size() / 4;
+        return win_T;
+    }
+    void launch_windows_tail(const uint8_t *frames_dev, int h, int w, int batch, int T, int k) {
+        const int slots = batch * T, nb_max = net->batch_max;
+        const size_t per_slot = (size_t)net->total_boxes * net->attrs;
+        if (win_pred.n < (size_t)slots * per_slot) {
+            YDS_HIP(hipStreamSynchronize(net->stream));             // (an NMS of the previous pass may still read the old buffer)
+            win_pred.alloc((size_t)slots * per_slot);
+        }
+        for (int slot0 = 0; slot0 < slots; slot0 += nb_max) {
+            const int nb = std::min(nb_max, slots - slot0);
+            launch_window_resize(frames_dev, h, w, win_rects.p, T, slot0, nb, net->input_view(nb), net->stream, frames_bgr);
+            net->forward_resized(nb);
+            launch_window_boxes(net->out.p, net->total_boxes, net->attrs, win_rects.p, win_scale.p, T, slot0, nb, win_pred.p, net->stream);
+        }
+        if (const int sl = slot_of(frames_dev); sl >= 0) { YDS_HIP(hipEventRecord(rd_det[sl], net->stream)); rd_det_set[sl] = true; }
+        YDS_HIP(hipEventRecord(e2[k], net->stream));
+        nms[k]->launch(win_pred.p, (size_t)T * per_slot, batch, T * net->total_boxes, net->attrs, conf, nms_thres, 1.f, 1.f, 300, net->stream,
+                       true, true);
+        YDS_HIP(hipEventRecord(e_nms[k], net->stream));
     }
 
     // detections of one batch after NMS + class mask + p1p2Toxywh, ready for the extractor and the tracker
@@ -460,6 +532,11 @@ public:
     int head_slot = 0;                 // NMS slot of the pass whose head was enqueued last
     bool head_split = false, head_stale = false;
     float stage_us[5] = {0, 0, 0, 0, 0};
+    // window mode (set_windows): setting, the table on the device and the frame size it was built for, the shifted predictions
+    int win_w = 0, win_h = 0, win_T = 0, win_tab_h = 0, win_tab_w = 0;
+    double win_overlap = 0;
+    DevBuf<int> win_rects;
+    DevBuf<float> win_scale, win_pred;
 };
 
 }  // namespace yds
@@ -540,6 +617,11 @@ int yds_pipeline_set_next_injection(yds_pipe *p, int set) {
 int yds_pipeline_set_frame_order(yds_pipe *p, int bgr) {
     YDS_API_BEGIN
     p->p->frames_bgr = bgr != 0;
+    YDS_API_END
+}
+int yds_pipeline_set_windows(yds_pipe *p, int win_w, int win_h, double overlap) {
+    YDS_API_BEGIN
+    p->p->set_windows(win_w, win_h, overlap);
     YDS_API_END
 }
 int yds_pipeline_set_schedule(yds_pipe *p, int min_crops) {

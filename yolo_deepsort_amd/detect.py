@@ -209,13 +209,17 @@ def _transform(frame):
 class VideoDetector:
     def __init__(self, model, class_path, thickness=2, font_path=None, font_size=10, thres=0.7, nms_thres=0.4,
                  skip_frames=-1, fourcc="mp4v", class_mask=None, win_size=None, overlap=0.15, tracker=None,
-                 action_id=None, half=False, batch_frames=None, device_overlay=True):
+                 action_id=None, half=False, batch_frames=None, device_overlay=True, batch_windows=False):
         # batch_frames (not in the reference): with a tracker, read that many frames ahead and run them through the batched device
         # pipeline (csrc/pipeline.cpp) - same results per frame, yielded in order, several times the frame rate of the frame-by-frame
         # path.  None (default, round 5) = by source: AUTO_BATCH frames for a file / an .npy / an iterable of frames - the reference
         # itself decodes up to 128 frames ahead of the detector for those (FileVideoStream queue, video_detect.py:86) - and 1 for a
         # live source (a camera index, a stream URL), where reading ahead would be waiting.  1 = the reference's latency (one frame
         # in, one result out).  device_overlay: the output stage (overlay, RGB -> BGR, FPS text) of the batched path on the device.
+        # batch_windows (not in the reference): with win_size set, run the batched pipeline in window mode (pipeline.Pipeline(win_size=...):
+        # windows cut, merged and tracked on the device) wherever a detector without win_size would take the batched path.  False
+        # (default): a detector with win_size keeps the frame-by-frame loop, as before.
+        self.batch_windows = bool(batch_windows)
         self.batch_frames = None if batch_frames is None else max(1, int(batch_frames))
         self.device_overlay = bool(device_overlay) and not os.environ.get("YDS_HOST_OVERLAY")
         self._pipe = None
@@ -256,6 +260,18 @@ class VideoDetector:
         return (isinstance(t, DeepSort) and isinstance(getattr(t, "extractor", None), Extractor)
                 and hasattr(t.extractor, "_h") and hasattr(getattr(t, "tracker", None), "_h")
                 and self.image_detector.win_size is None and getattr(t, "nms_max_overlap", 1) == 1)
+
+    def _batchable_windows(self):
+        """_batchable() with the sliding-window condition lifted: every other condition holds and win_size is set (the batched
+        pipeline then runs in window mode: detect() with batch_windows=True, detect_streams)."""
+        det = self.image_detector
+        if det.win_size is None:
+            return False
+        keep, det.win_size = det.win_size, None
+        try:
+            return self._batchable()
+        finally:
+            det.win_size = keep
 
     def _frames(self, video_path, skip_secs=0, transform=True):
         """RGB frames of the source (transform=False: a capture / file source's frames as decoded, BGR)."""
@@ -427,7 +443,8 @@ class VideoDetector:
             from . import pipeline as pl
             if det.model.batch_max < bf:
                 det.model.set_batch_max(bf)
-            self._pipe = pl.Pipeline(det.model, self.tracker, det.thres, det.nms_thres, class_mask=self.class_mask)
+            self._pipe = pl.Pipeline(det.model, self.tracker, det.thres, det.nms_thres, class_mask=self.class_mask,
+                                     win_size=det.win_size, overlap=det.overlap)
         self._batch_now = bf
         iterable = hasattr(video_path, "__iter__") and not isinstance(video_path, (str, bytes)) and not hasattr(video_path, "isOpened")
         if hasattr(self._pipe, "set_frame_order"):
@@ -586,15 +603,15 @@ class VideoDetector:
         step: one detector pass, one ReID pass, all trackers advanced in the same launches.  A stream that ends drops out, the
         others go on.  frames_per_stream=None: 1 when any source is live (_is_live), else max(1, AUTO_BATCH // len(sources)).
         Limits: every frame of every source must have one uint8 [h, w, 3] shape, and action_id is not supported - both raise
-        ValueError; the tracker must be this package's DeepSort around its Extractor, with nms_max_overlap=1 and no sliding window."""
+        ValueError; the tracker must be this package's DeepSort around its Extractor, with nms_max_overlap=1.  A detector with
+        win_size runs the pipeline in window mode (MultiStreamPipeline(win_size=...))."""
         from . import _lib, pipeline as pl
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
         if self.action_id is not None:
             raise ValueError("VideoDetector.detect_streams does not support action_id")
-        if not self._batchable():
-            raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor, nms_max_overlap=1 and no "
-                             "sliding window (win_size=None)")
+        if not (self._batchable() or self._batchable_windows()):
+            raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         sources = list(sources)
         S = len(sources)
         if S == 0:
@@ -603,7 +620,8 @@ class VideoDetector:
         det = self.image_detector
         if det.model.batch_max < S * F:
             det.model.set_batch_max(S * F)
-        pipe = pl.MultiStreamPipeline(det.model, [self.tracker.clone() for _ in range(S)], det.thres, det.nms_thres, class_mask=self.class_mask)
+        pipe = pl.MultiStreamPipeline(det.model, [self.tracker.clone() for _ in range(S)], det.thres, det.nms_thres, class_mask=self.class_mask,
+                                      win_size=det.win_size, overlap=det.overlap)
         lib = _lib.load()
         its = [iter(self._frames(src)) for src in sources]
         since, hold, alive = [0] * S, [None] * S, [True] * S
@@ -668,7 +686,7 @@ class VideoDetector:
             n = self._source_len(video_path)                          # a clip shorter than the default read-ahead: no buffers for frames
             if n is not None:                                         # that will never come (every capacity follows the batch size)
                 bf = max(1, min(bf, n))
-        if bf > 1 and self._batchable():
+        if bf > 1 and (self._batchable() or (getattr(self, "batch_windows", False) and self._batchable_windows())):
             yield from self._detect_batched(video_path, show_fps, skip_secs, bf)
             return
         hold_detections, actions, frames = None, [], 0

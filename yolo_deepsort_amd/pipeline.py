@@ -11,8 +11,9 @@ from . import _lib
 
 
 class Pipeline:
-    def __init__(self, net, deepsort, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512):
+    def __init__(self, net, deepsort, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         self.net, self.ds, self.cap = net, deepsort, int(cap)
+        self._h = None
         # the batched path hands the tracker handle to the C pipeline and never passes through DeepSort.update: the
         # tracker-side NMS (deep_sort.py:52-57, a host-ordered reordering of the detections) is not part of it
         if getattr(deepsort, "nms_max_overlap", 1) != 1:
@@ -22,6 +23,16 @@ class Pipeline:
         self._h = _lib.check_ptr(_lib.load().yds_pipeline_create(net._h, deepsort.extractor._h, deepsort.tracker._h,
                                                                  conf_thres, nms_thres,
                                                                  _lib.ptr(mask) if mask.size else None, int(mask.size)))
+        self.set_windows(win_size, overlap)
+
+    def set_windows(self, win_size=None, overlap=0.15):
+        """Window mode, ImageDetector(win_size=(win_w, win_h), overlap) (img_detect.py:97-151) for every frame of a step: the frames
+        are cut into windows on the device, all windows of the step run through the detector in chunks of net.batch_max, one NMS
+        launch merges them per frame (yds_pipeline_set_windows).  None = off (the default).  Refused (YdsError) while a look-ahead
+        pass is in flight, i.e. between a step that was given next frames and the step that consumes them."""
+        ww, wh = (0, 0) if win_size is None else (int(win_size[0]), int(win_size[1]))
+        _lib.check(_lib.load().yds_pipeline_set_windows(self._h, ww, wh, float(overlap)))
+        self.win_size, self.overlap = (None if win_size is None else (ww, wh)), overlap
 
     def step(self, frames_dev, h, w, batch, next_frames_dev=None, select_next=None):
         """frames_dev: device pointer to uint8 [batch,h,w,3]; next_frames_dev (optional): the frames of the next
@@ -99,8 +110,9 @@ class MultiStreamPipeline(Pipeline):
     launches (a stream's k-th frame of the step in round k).  Per stream the results are those of that stream run alone through
     Pipeline.  Schedule, frame order, prefetch and stage times: as Pipeline."""
 
-    def __init__(self, net, deepsorts, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512):
+    def __init__(self, net, deepsorts, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         from .deep_sort import Extractor
+        self._h = None
         deepsorts = list(deepsorts)
         if not deepsorts:
             raise ValueError("MultiStreamPipeline: no streams")
@@ -119,6 +131,7 @@ class MultiStreamPipeline(Pipeline):
         trks = (C.c_void_p * self.n_streams)(*[d.tracker._h for d in deepsorts])
         self._h = _lib.check_ptr(_lib.load().yds_pipeline_create_multi(net._h, ex._h, trks, self.n_streams, conf_thres, nms_thres,
                                                                        _lib.ptr(mask) if mask.size else None, int(mask.size)))
+        self.set_windows(win_size, overlap)
 
     def _streams(self, stream_of_frame):
         s = np.ascontiguousarray(stream_of_frame, dtype=np.int32).reshape(-1)
