@@ -219,3 +219,83 @@ def test_pipeline_nms_workspace_overflow_redoes_the_batch():
         assert g is not None and g.shape == w.shape, t
         assert np.array_equal(g[:, 4:], w[:, 4:]), t
         assert np.abs(g[:, :4] - w[:, :4]).max(initial=0) <= 1, t
+
+
+def _iou_matrix(tlwh):
+    a = np.asarray(tlwh, np.float64)
+    x1, y1, x2, y2 = a[:, 0], a[:, 1], a[:, 0] + a[:, 2], a[:, 1] + a[:, 3]
+    iw = np.clip(np.minimum(x2[:, None], x2[None]) - np.maximum(x1[:, None], x1[None]), 0, None)
+    ih = np.clip(np.minimum(y2[:, None], y2[None]) - np.maximum(y1[:, None], y1[None]), 0, None)
+    area = a[:, 2] * a[:, 3]
+    return iw * ih / (area[:, None] + area[None] - iw * ih)
+
+
+def test_pipeline_step_with_uneven_detection_counts_matches_oracle_stream(monkeypatch):
+    # The association driver plans a whole step before its first launch: rounds, capacities and every buffer.  Two things can only go
+    # wrong there: (1) inside ONE step a frame brings >= 8 times the detections of the frame before it, so the lists and the cost
+    # matrix of a later round outgrow everything sized so far, and (2) live tracks plus the detections of one later step exceed the
+    # tracker's initial 256 slots, so the capacity grows with live state between two steps.  Recipe of
+    # test_pipeline_matches_oracle_stream (yolov3-tiny 416, 480x640 frames, batch 4, frames in HBM, injected detections, expected rows
+    # from the oracle pipeline); what differs is the detections per frame: the first k[t] of a fixed list of persons.
+    # That list: walkers of a crowded PersonScene, taken in scene order, whose box never overlaps a listed one of its class by 0.3 in any
+    # frame of the test - so NMS at 0.4 (class aware) removes none of them and the tracker sees exactly k[t] detections.
+    # (383 crops: the oracle embeds them through its C form, oracle/fast.py ReidFast, which tests/test_oracle_fast.py holds to the numpy one.)
+    monkeypatch.setenv("YDS_PIPE_DEEP_MIN", "1000000")
+    from oracle import nms as onms
+    from oracle.darknet import DarknetOracle
+    from oracle.fast import ReidFast
+    from oracle.pipeline import run_stream
+    from yolo_deepsort_amd import _lib, pipeline as pl
+    from yolo_deepsort_amd.deep_sort import DeepSort
+    from yolo_deepsort_amd.models import Darknet
+    _lib.init(0)
+    size, batch, K = 416, 4, 54
+    k_of = [5, K, K, K, K, K, K, K]                     # step 0: 5 then 54 detections; step 1: 4 x 54 on top of the 54 live tracks
+    n = len(k_of)
+    cfg = cfgs.cfg_text("yolov3-tiny", size, size)
+    blob = synth.darknet_weights_blob(cfg, 0)
+    net = Darknet(None, img_size=(size, size), batch_max=batch, cfg_text=cfg)
+    net.load_darknet_weights(None, blob=blob)
+    heads = net.yolo_heads()
+    scene = synth.PersonScene(250, frame_hw=(480, 640), seed=0, occlude_frac=0.0)
+    boxes = np.stack([scene.boxes(t)[1] for t in range(n)])                     # [n, 250, 4]: everybody is visible in every frame
+    assert all(np.array_equal(scene.boxes(t)[0], np.arange(250)) for t in range(n))
+    cls_of = np.where(np.arange(250) % 3 == 0, 2, 0)                            # every third person is a "car" (class 2)
+    worst = np.max([_iou_matrix(boxes[t]) for t in range(n)], 0)
+    cells = np.stack([synth.head_injection(boxes[t], (480, 640), (size, size), heads)[:, :4] for t in range(n)])       # head, anchor, gy, gx
+    same_cell = (cells[:, :, None] == cells[:, None]).all(-1).any(0)               # [250, 250]: two persons would be injected into one cell
+    persons = []
+    for p in range(250):
+        if len(persons) < K and all(not same_cell[p, q] and (cls_of[q] != cls_of[p] or worst[p, q] < 0.3) for q in persons):
+            persons.append(p)
+    assert len(persons) == K
+    inj = []
+    for t in range(n):
+        sel = persons[:k_of[t]]
+        rows = synth.head_injection(boxes[t, sel], (480, 640), (size, size), heads)
+        rows[:, 8] = cls_of[sel]
+        assert len({tuple(r[:4]) for r in rows.tolist()}) == len(sel), t        # one head cell per person: no injection overwrites another
+        # the oracle's NMS over the injected boxes (equal scores, class offset as soft_non_max_suppression): every one survives 0.4
+        p1p2 = np.concatenate([boxes[t, sel, :2], boxes[t, sel, :2] + boxes[t, sel, 2:]], 1) + cls_of[sel, None] * 4096.
+        assert len(onms.nms_greedy(p1p2.astype(F32), np.ones(len(sel), F32), 0.4)) == k_of[t], t
+        inj.append(rows)
+    frames = np.stack([scene.frame(t) for t in range(n)], 0)
+    sd = synth.reid_state_dict(0)
+    ref_net = DarknetOracle(cfg, size, is_text=True)
+    ref_net.load_weights_array(np.frombuffer(blob, dtype=F32, offset=20))
+    want = [np.array(w, np.int32).reshape(-1, 6) for w in run_stream(ref_net, sd, DS, frames, inj, reid_fn=ReidFast(sd))]
+    # (1) inside step 0, (2) between step 0 and step 1: the rows of frame 3 are confirmed, hence live, tracks when step 1 is planned
+    assert any(k_of[t + 1] >= 8 * k_of[t] for t in range(batch - 1))
+    assert len(want[batch - 1]) + sum(k_of[batch:2 * batch]) > 256
+    pl.load_injection_sets(net, [[inj[s * batch + b] for b in range(batch)] for s in range(n // batch)])
+    pipe = pl.Pipeline(net, DeepSort(sd, use_cuda=True, **DS), 0.5, 0.4, class_mask=[0, 2, 4])
+    dev = _lib.DeviceBuffer.from_array(frames)
+    pl.select_injection_set(net, 0)
+    got = pipe.step(dev.offset(0), 480, 640, batch, dev.offset(batch * frames[0].nbytes), select_next=1)
+    got += pipe.step(dev.offset(batch * frames[0].nbytes), 480, 640, batch)
+    assert len(got) == n
+    for t, (g, w) in enumerate(zip(got, want)):
+        assert g.shape == w.shape, (t, g, w)
+        assert np.array_equal(g[:, 4:], w[:, 4:]), t              # track ids and classes: bit exact
+        assert np.abs(g[:, :4] - w[:, :4]).max(initial=0) <= 1, t
+    assert len(want[-1]) == K                                     # every person is a confirmed track at the end

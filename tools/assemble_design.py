@@ -39,7 +39,7 @@ def sustained():
     if d is None:
         return "(not measured yet)"
     r = d.get("roofline") or {}
-    return ("`bench.py --steps {} --warmup 5` = {} frames in {:.1f} s: **{} frames/s**, dominant kernel `frac` {} at {} GHz sclk "
+    return ("`bench.py --full --steps {} --warmup 5 --no-extras --latency-steps 0 --cpu-frames 0` = {} frames in {:.1f} s: **{} frames/s**, dominant kernel `frac` {} at {} GHz sclk "
             "(`profiles/r06_bench_cfg2_sustained.json`) - the 20-step headline does not ride boost headroom.").format(
         d["steps"], d["steps"] * d["config"]["frames_per_step"], d["steps"] * d["ms_per_step"] / 1e3, d["value"], r.get("frac"), r.get("sustained_clock_ghz"))
 

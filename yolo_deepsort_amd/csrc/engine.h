@@ -227,26 +227,25 @@ public:
 };
 
 // --------------------------------------------------------------------------------------------- tracker
-// Implemented in tracker.hip; the pipeline drives it through this interface.
+// Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
 struct TrackerIface {
     virtual ~TrackerIface() {}
-    // feats: [D,512] on device when feats_on_device, else host.  Returns rows written to out6 (int32 [m,6]).
+    // stand-alone call, one frame through a driver of the tracker's own.  feats: [D,512] on device when feats_on_device, else host.
+    // Returns rows written to out6 (int32 [m,6]).
     virtual int step(const float *tlwh_host, const float *feats, bool feats_on_device, const float *payload_host, int D,
                      int32_t *out6_host, int cap) = 0;
-    // the frames of one batch in order with ONE host synchronisation: detections of frame b are rows [first[b], first[b+1])
-    // of tlwh / feats_dev / payload; skip[b] != 0: tracker not called for that frame (counts[b] = -1)
-    virtual void step_batch(int n, const float *tlwh_host, const int *first, const float *feats_dev, const float *payload_host, const char *skip,
-                            int32_t *out6_host, int cap, int32_t *counts) = 0;
     virtual int num_tracks() const = 0;
-    // the next step / step_batch starts behind `ev` on the tracker's own stream (features produced on another stream: no host wait)
-    virtual void wait_for(hipEvent_t ev) = 0;
 };
-// Several trackers (one per video stream) advanced together (tracker.hip TrackerGroup): frame b of the batch belongs to tracker
-// stream_of[b], each tracker's frames in time order; the other arguments as in TrackerIface::step_batch.  ONE host synchronisation.
+// The association driver (tracker.hip TrackerGroup): S trackers (one per video stream; the pipeline of a single stream has S = 1)
+// advanced together through the frames of one batch with ONE host synchronisation.  Frame b belongs to tracker stream_of[b], each
+// tracker's frames in time order; detections of frame b are rows [first[b], first[b+1]) of tlwh / feats_dev / payload; skip[b] != 0:
+// its tracker is not called for that frame (counts[b] = -1).
 struct TrackerGroupIface {
     virtual ~TrackerGroupIface() {}
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
+    // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)
+    virtual void wait_for(hipEvent_t ev) = 0;
 };
 TrackerGroupIface *make_tracker_group();
 

@@ -24,8 +24,10 @@ namespace yds {
 
 class Pipeline {
 public:
-    Pipeline(Darknet *net, ReidNet *reid, TrackerIface *trk, float conf, float nms_iou, const int32_t *mask, int n_mask)
-        : net(net), reid(reid), trk(trk), conf(conf), nms_thres(nms_iou), class_mask(mask, mask + n_mask) {
+    // trks: the tracker of every stream; multi: made by yds_pipeline_create_multi (a step names the stream of each frame)
+    Pipeline(Darknet *net, ReidNet *reid, std::vector<TrackerIface *> trks, bool multi, float conf, float nms_iou, const int32_t *mask, int n_mask)
+        : net(net), reid(reid), trks(std::move(trks)), group(make_tracker_group()), multi(multi), conf(conf), nms_thres(nms_iou),
+          class_mask(mask, mask + n_mask) {
         for (int k = 0; k < 2; ++k) {
             for (hipEvent_t *e : {&e0[k], &e1[k], &e2[k], &e_nms[k]}) YDS_HIP(hipEventCreate(e));
             nms[k].reset(new NmsWorkspace(4096, net->batch_max));
@@ -456,7 +458,7 @@ public:
         // for the event - instead of by a host wake-up between the two (round 6: one round trip less on the latency path; stage_us[3]
         // then holds the enqueue only and stage_us[4] the ReID pass + association).  Batches keep the host wait: it is what lets the
         // host start the next batch's work in the right order below.
-        if (D_all) { if (batch == 1 && !next_frames_dev && !group) trk->wait_for(ev_feat); else YDS_HIP(hipEventSynchronize(ev_feat)); }
+        if (D_all) { if (batch == 1 && !next_frames_dev) group->wait_for(ev_feat); else YDS_HIP(hipEventSynchronize(ev_feat)); }
         auto t_reid = clk::now();
         // Crowded scenes (the association of a batch takes long and is all small latency-bound kernels and host syncs):
         // before associating, finish the next batch's detector + NMS and start its ReID pass, so that the matrix
@@ -467,14 +469,13 @@ public:
             in_flight = nullptr;
             launch_reid(ahead, h, w, serial ? net->stream : nullptr);
         }
-        // association of the whole batch, frame after frame on the tracker's stream, one host synchronisation
+        // association of the whole batch on the group's stream, one host synchronisation: frame b advances tracker stream_of[b] (a
+        // single stream: all zeros), every tracker in the same launches
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
-        if (group)              // several streams: frame b advances tracker stream_of[b], every tracker in the same launches
-            group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
-                              cur.payload.data(), skip.data(), out6, cap, counts);
-        else
-            trk->step_batch(batch, cur.tlwh.data(), cur.first.data(), feat_cur.p, cur.payload.data(), skip.data(), out6, cap, counts);
+        if (!multi) stream_of.assign(batch, 0);
+        group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
+                          cur.payload.data(), skip.data(), out6, cap, counts);
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
@@ -484,7 +485,7 @@ public:
     // Several video streams through one pipeline (yds_pipeline_create_multi): one tracker per stream, advanced together by `group`;
     // stream_of[b] = stream of frame b of the step being run (set_streams before step / step_host)
     void set_streams(const int32_t *stream_of_frame, int n) {
-        if (!group) fail("pipeline: created by yds_pipeline_create: it has no streams (use yds_pipeline_step)");
+        if (!multi) fail("pipeline: created by yds_pipeline_create: it has no streams (use yds_pipeline_step)");
         if (n < 1 || n > net->batch_max) fail("pipeline: batch %d outside [1,%d]", n, net->batch_max);
         for (int b = 0; b < n; ++b)
             if (stream_of_frame[b] < 0 || stream_of_frame[b] >= (int)trks.size())
@@ -494,9 +495,9 @@ public:
 
     Darknet *net;
     ReidNet *reid;
-    TrackerIface *trk;
-    std::vector<TrackerIface *> trks;             // multi-stream pipeline: tracker of each stream (trk = trks[0])
-    std::unique_ptr<TrackerGroupIface> group;
+    std::vector<TrackerIface *> trks;             // tracker of each stream
+    std::unique_ptr<TrackerGroupIface> group;     // the association driver of all of them
+    const bool multi;                             // yds_pipeline_create_multi: the step_multi entries, else the plain ones
     std::vector<int32_t> stream_of;
     float conf, nms_thres;
     std::vector<int32_t> class_mask;
@@ -548,7 +549,7 @@ extern "C" {
 yds_pipe *yds_pipeline_create(yds_net *n, yds_reid *r, yds_trk *t, float conf_thres, float nms_thres, const int32_t *class_mask, int n_mask) {
     YDS_API_BEGIN
     if (!n || !r || !t) yds::fail("pipeline: NULL handle");
-    return new yds_pipe{new yds::Pipeline(n->d, r->r, t->t, conf_thres, nms_thres, class_mask, class_mask ? n_mask : 0)};
+    return new yds_pipe{new yds::Pipeline(n->d, r->r, {t->t}, false, conf_thres, nms_thres, class_mask, class_mask ? n_mask : 0)};
     YDS_API_END_PTR
 }
 yds_pipe *yds_pipeline_create_multi(yds_net *n, yds_reid *r, yds_trk *const *trks, int n_streams, float conf_thres, float nms_thres,
@@ -563,10 +564,7 @@ yds_pipe *yds_pipeline_create_multi(yds_net *n, yds_reid *r, yds_trk *const *trk
         for (int q = 0; q < s; ++q)
             if (trks[q] == trks[s] || t[q] == t[s]) yds::fail("pipeline: streams %d and %d share one tracker (one tracker per stream: DeepSort.clone())", q, s);
     }
-    std::unique_ptr<yds::Pipeline> p(new yds::Pipeline(n->d, r->r, t[0], conf_thres, nms_thres, class_mask, class_mask ? n_mask : 0));
-    p->trks = t;
-    p->group.reset(yds::make_tracker_group());
-    return new yds_pipe{p.release()};
+    return new yds_pipe{new yds::Pipeline(n->d, r->r, t, true, conf_thres, nms_thres, class_mask, class_mask ? n_mask : 0)};
     YDS_API_END_PTR
 }
 void yds_pipeline_destroy(yds_pipe *p) {
@@ -575,7 +573,7 @@ void yds_pipeline_destroy(yds_pipe *p) {
 int yds_pipeline_step(yds_pipe *p, const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int batch, int32_t *out6_host,
                       int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    if (p->p->group) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi");
+    if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi");
     p->p->step(frames_dev, next_frames_dev, p->p->next_inject_set, h, w, batch, out6_host, cap, counts_host);
     p->p->next_inject_set = -1;
     YDS_API_END
@@ -583,7 +581,7 @@ int yds_pipeline_step(yds_pipe *p, const uint8_t *frames_dev, const uint8_t *nex
 int yds_pipeline_step_host(yds_pipe *p, const uint8_t *frames_host, const uint8_t *next_frames_host, int h, int w, int batch,
                            int32_t *out6_host, int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    if (p->p->group) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi_host");
+    if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi_host");
     p->p->step_host(frames_host, next_frames_host, p->p->next_inject_set, h, w, batch, out6_host, cap, counts_host);
     p->p->next_inject_set = -1;
     YDS_API_END

@@ -11,8 +11,9 @@
 // table (ids, hits, age, time_since_update, Tentative/Confirmed/Deleted, ring position, payload) in track-list order.
 // The order-sensitive list bookkeeping (linear_assignment.py:58-72, tracker.py:56-93,115-176, track.py) runs in two
 // single-workgroup kernels built from ordered compactions (ballot + prefix), so a frame is a fixed sequence of launches
-// whose sizes are read from device memory: the host synchronises ONCE per frame - or once per batch of frames
-// (step_batch, used by the pipeline) - to fetch the int32 rows.
+// whose sizes are read from device memory.  ONE host driver (TrackerGroup) advances any number of trackers through the
+// frames of a step - a stand-alone tracker call is a step of one tracker and one frame - and synchronises ONCE per step
+// to fetch the int32 rows.
 #include "tracker_lsap_dev.h"
 
 namespace yds {
@@ -95,6 +96,7 @@ template <class Pred, class Emit> __device__ __forceinline__ int compact_ordered
 //                                                     bookkeeping, the IOU cost in between, Tracker.update on the integer table,
 //                                                     output selection, output rows of the tracks that were not updated
 //   trk_back_kernel    (one workgroup per match / new track)  Kalman update / initiate, gallery row, output row of updated tracks
+// (grids per tracker; the entries - behind the bodies - carry the trackers of a round as one more grid axis)
 
 // deep_sort.py:73-87: state mean -> clipped corner box, int32 truncation, id, payload
 __device__ __forceinline__ void write_out_row(const float *m, int id, float payload, int *o) {
@@ -130,7 +132,6 @@ __device__ __forceinline__ void trk_front_body(const TrkDev &d, int D, int t, in
     appearance_cost_block(d.gallery, slot, d.tab.n_feat[t], d.budget, d.feats_n, D, slab * 16, pm, pP, d.tlwh, d.max_dist, d.flood_a, 1, d.euclid,
                           d.cost + (size_t)row * D);
 }
-__global__ __launch_bounds__(256) void trk_front_kernel(TrkDev d, int D) { trk_front_body(d, D, blockIdx.x, blockIdx.y); }
 
 // min_cost_matching list bookkeeping (linear_assignment.py:58-72) for one solved assignment problem:
 //   unmatched detections = [columns not assigned, ascending] then [rejected pairs in row order], unmatched tracks likewise,
@@ -298,7 +299,6 @@ __device__ __forceinline__ void trk_assoc_body(const TrkDev &d, int D, char *lsa
         for (int k = 0; k < M_COUNT; ++k) d.res[k] = d.meta[k];
     }
 }
-__global__ __launch_bounds__(256) void trk_assoc_kernel(TrkDev d, int D, char *lsap_state, int smem_bytes) { trk_assoc_body(d, D, lsap_state, smem_bytes); }
 
 // Workgroup k: entry k of the update list - KalmanFilter.update for a match (kalman_filter.py:161-204 via tracker.py:143-150) or
 // initiate for a new track (:54-87) on one thread, the gallery row (tracker.py:165-176 + nn_matching.py:152-155) on all of them,
@@ -324,34 +324,42 @@ __device__ __forceinline__ void trk_back_body(const TrkDev &d, int k) {
     const float *src = d.feats_n + (size_t)det * EMB;
     for (int c = threadIdx.x; c < EMB; c += 128) dst[c] = src[c];
 }
-__global__ __launch_bounds__(128) void trk_back_kernel(TrkDev d) { trk_back_body(d, blockIdx.x); }
 
-// -------------------------------------------------------------------------------------------- several trackers, three launches per round
-// The same three bodies over the trackers of several streams (step_group): the stream axis of the grid selects the tracker's TrkDev in
-// a device array; sizes are the largest of the round, and the guards above (live count and list lengths read from each tracker's own
-// meta) retire the workgroups a smaller tracker does not need.  A tracker stepped in a group runs the instruction sequence it runs alone.
+// -------------------------------------------------------------------------------------------- the three entries
+// One round of a step = the three bodies over the trackers that have a frame in it (TrackerGroup::step_group; a single tracker is a
+// group of one): the stream axis of the grid selects the tracker's TrkDev in a device array; sizes are the largest of the round, and the
+// guards above (live count and list lengths read from each tracker's own meta) retire the workgroups a smaller tracker does not need.
+// A tracker stepped in a group runs the instruction sequence it runs alone.
 struct alignas(16) TrkGroupDev {
     TrkDev d;
     int D;
     char *lsap_state;       // this tracker's region of global LSAP scratch (nullptr: its problems fit the LDS)
 };
 static_assert(sizeof(TrkGroupDev) % 16 == 0, "the host packs TrkGroupDev arrays at a stride of sizeof(TrkGroupDev)");
-__global__ __launch_bounds__(256) void trk_front_group_kernel(const TrkGroupDev *g) {
+__global__ __launch_bounds__(256) void trk_front_kernel(const TrkGroupDev *g) {
     const TrkGroupDev &e = g[blockIdx.z];
     if ((int)blockIdx.y * 16 >= e.D) return;
     trk_front_body(e.d, e.D, blockIdx.x, blockIdx.y);
 }
-__global__ __launch_bounds__(256) void trk_assoc_group_kernel(const TrkGroupDev *g, int smem_bytes) {
+__global__ __launch_bounds__(256) void trk_assoc_kernel(const TrkGroupDev *g, int smem_bytes) {
     const TrkGroupDev &e = g[blockIdx.x];
     trk_assoc_body(e.d, e.D, e.lsap_state, smem_bytes);
 }
-__global__ __launch_bounds__(128) void trk_back_group_kernel(const TrkGroupDev *g) {
+__global__ __launch_bounds__(128) void trk_back_kernel(const TrkGroupDev *g) {
     const TrkGroupDev &e = g[blockIdx.y];
     if ((int)blockIdx.x >= e.D) return;
     trk_back_body(e.d, blockIdx.x);
 }
 
 // ============================================================================================ host
+// ALLOCATION: a step (TrackerGroup::step_group) allocates only before its first launch and ends with a synchronise of the stream it
+// ran on, whichever driver runs it.  So nothing that uses a tracker's or a driver's buffers is in flight when a step is entered, and
+// every buffer may be freed and reallocated there without draining anything.
+template <class T> static void grow_to(DevBuf<T> &b, size_t count) { if (count > b.n) b.alloc(count + count / 2); }
+
+class TrackerGroup;
+
+// The state of one DeepSORT tracker and the buffers sized by it.  It launches nothing itself: TrackerGroup advances it.
 class Tracker : public TrackerIface {
 public:
     // budget <= 0: nn_budget=None, every track keeps all its features (nn_matching.py:152-154) - the per-track row
@@ -360,19 +368,11 @@ public:
         : max_dist(max_dist), max_iou(max_iou), max_age(max_age), n_init(n_init), budget(budget > 0 ? budget : 32), unbounded(budget <= 0),
           metric(metric) {
         if (metric != METRIC_COSINE && metric != METRIC_EUCLIDEAN) fail("Invalid metric; must be either 'euclidean' or 'cosine'");
-        stream = make_stream(true);
-        feats_stage.st = feats_n.st = cost_dev.st = &stream;
-        det_lists.st = &stream;
         meta.alloc(M_COUNT);
         int init[M_COUNT] = {};
         init[M_NEXT_ID] = 1;
         YDS_HIP(hipMemcpy(meta.p, init, sizeof init, hipMemcpyHostToDevice));
         grow(256);
-    }
-    ~Tracker() override {
-        if (res_host) (void)hipHostFree(res_host);
-        if (in_host) (void)hipHostFree(in_host);
-        if (stream) (void)hipStreamDestroy(stream);
     }
     int num_tracks() const override { return T_host; }
 
@@ -383,9 +383,8 @@ public:
         return t;
     }
 
-    // capacity = number of slots = maximum number of live tracks.  Nothing may be in flight on the stream.
+    // capacity = number of slots = maximum number of live tracks (at the entry of a step: see ALLOCATION)
     void grow(int cap) {
-        YDS_HIP(hipStreamSynchronize(stream));
         DevBuf<float> m((size_t)cap * 8), c((size_t)cap * 64), g((size_t)cap * budget * EMB);
         DevBuf<int> tab((size_t)cap * TAB_FIELDS), tmp((size_t)cap * TAB_FIELDS), fs(cap), lists((size_t)cap * 13);
         if (capacity) {
@@ -409,7 +408,6 @@ public:
     }
     // nn_budget=None: double the per-track row capacity, keeping every slot's rows
     void grow_budget() {
-        YDS_HIP(hipStreamSynchronize(stream));
         const int nb = budget * 2;
         size_t free_b = 0, total_b = 0;
         YDS_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -425,62 +423,18 @@ public:
 
     struct FrameIn { const float *tlwh; const float *feats; bool feats_on_device; const int *feat_rows; const float *payload; int D; };
 
-    // Enqueues one frame (three launches, see the kernels); T_ub = host-side upper bound of the live track count when it starts.
-    // feats_n_frame: this frame's normalised embeddings when the caller has normalised the whole batch in one launch, else nullptr.
-    // Returns the int offset of this frame's result block inside res_host (pinned host memory the kernels store into: no copy
-    // command at the end).
-    size_t enqueue(const FrameIn &f, int T_ub, size_t in_off, size_t res_off, size_t *res_len, int *out_cap, float *feats_n_frame) {
-        const int D = f.D, Dn = std::max(D, 1), Tn = std::max(T_ub, 1);
-        const TrkDev d = frame_dev(f, T_ub, in_dev.p + in_off, res_host + res_off, res_len, out_cap, feats_n_frame);
-        const int *feat_rows_dev = f.feat_rows ? reinterpret_cast<const int *>(d.payload + D) : nullptr;
-
-        // ---- kernels (sizes come from device memory; the grids use the host-side upper bounds)
-        if (!feats_n_frame && D) {
-            const float *feats_dev = f.feats;
-            if (!f.feats_on_device) {
-                int n_rows = D;
-                if (f.feat_rows) for (int k = 0; k < D; ++k) n_rows = std::max(n_rows, f.feat_rows[k] + 1);
-                feats_stage.ensure_keep((size_t)n_rows * EMB);
-                YDS_HIP(hipMemcpyAsync(feats_stage.p, f.feats, (size_t)n_rows * EMB * 4, hipMemcpyHostToDevice, stream));
-                feats_dev = feats_stage.p;
-            }
-            hipLaunchKernelGGL(normalize_rows_kernel, dim3((D + 3) / 4), dim3(256), 0, stream, feats_dev, feat_rows_dev, feats_n.p, D,
-                               metric == METRIC_COSINE ? 1 : 0);     // x / ||x|| once per frame (nn_matching.py:50-52); euclidean: as is
-        }
-        if (T_ub && D) hipLaunchKernelGGL(trk_front_kernel, dim3(T_ub, (D + 15) / 16), dim3(256), 0, stream, d, D);
-        // the assignment solvers get the whole LDS; their state moves to a global scratch when even that is too small (~3000 rows)
-        static bool attr_set = false;
-        if (!attr_set) {
-            YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(trk_assoc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LSAP_LDS_MAX));
-            attr_set = true;
-        }
-        const size_t lsap_state = (size_t)std::max(Tn, Dn) * LSAP_STATE_BYTES;
-        if (lsap_state > LSAP_LDS_MAX && lsap_scratch.n < lsap_state) {
-            YDS_HIP(hipStreamSynchronize(stream));                   // nothing may still use the old scratch
-            lsap_scratch.alloc(lsap_state);
-        }
-        hipLaunchKernelGGL(trk_assoc_kernel, dim3(1), dim3(256), LSAP_LDS_MAX, stream, d, D, lsap_state > LSAP_LDS_MAX ? lsap_scratch.p : (char *)nullptr,
-                           (int)LSAP_LDS_MAX);
-        if (D) hipLaunchKernelGGL(trk_back_kernel, dim3(D), dim3(128), 0, stream, d);
-        YDS_HIP(hipGetLastError());
-        return res_off;
-    }
-
-    // Device view of one frame (enqueue, step_group): this tracker's buffers - grown for the frame when needed (GrowBuf drains the
-    // tracker's own stream first) - the frame's inputs at `in` (tlwh [D,4], payload [D], feat_rows [D] as ints) and its result
-    // block at `res` (pinned host memory).  feats_n_frame: this frame's normalised embeddings, else the tracker's own feats_n.
-    TrkDev frame_dev(const FrameIn &f, int T_ub, const int *in, int *res, size_t *res_len, int *out_cap, float *feats_n_frame) {
-        const int D = f.D, Dn = std::max(D, 1), Tn = std::max(T_ub, 1);
-        // ---- inputs: tlwh, payload (and feat_rows) were packed into in_host by the caller; one H2D per batch
+    // Device view of one frame, the one place that builds a TrkDev: this tracker's buffers (the driver has sized them for the whole
+    // step), the frame's inputs at `in` (tlwh [D,4], payload [D], then feat_rows [D] as ints), its result block at `res` (pinned host
+    // memory the kernels store into: no copy command at the end) and its embeddings as the kernels read them at `feats_n`.
+    // T_ub = host-side upper bound of the live track count when the frame starts.
+    TrkDev frame_dev(int D, int T_ub, const int *in, int *res, float *feats_n) {
+        const int Dn = std::max(D, 1), Tn = std::max(T_ub, 1);
         TrkDev d;
         d.tab = table_at(table.p, capacity); d.tmp = table_at(table_tmp.p, capacity);
         d.meta = meta.p; d.free_slots = free_slots.p;
         d.mean = mean.p; d.cov = cov.p; d.gallery = gallery.p;
-        if (!feats_n_frame) feats_n.ensure_keep((size_t)Dn * EMB);
         const size_t cost_n = (size_t)(Tn + Dn) * Dn;
-        cost_dev.ensure_keep(2 * cost_n);
-        det_lists.ensure_keep((size_t)Dn * 8 + (size_t)(Tn + Dn) * 8);
-        d.feats_n = feats_n_frame ? feats_n_frame : feats_n.p;
+        d.feats_n = feats_n;
         d.cost = cost_dev.p; d.cost_b = cost_dev.p + cost_n;
         d.tlwh = reinterpret_cast<const float *>(in);
         d.payload = d.tlwh + (size_t)D * 4;
@@ -498,106 +452,18 @@ public:
         d.max_dist = (float)max_dist; d.max_iou = (float)max_iou;
         d.flood_a = (float)(max_dist + 1e-5); d.flood_b = (float)(max_iou + 1e-5);           // linear_assignment.py:52
         d.euclid = metric == METRIC_EUCLIDEAN ? 1 : 0;
-        // ---- result block layout: header | out6 rows | matches | unmatched tracks | unmatched detections
-        const int rows_cap = T_ub + D, mcap = T_ub + D;
-        d.res_out6 = M_COUNT; d.res_matches = d.res_out6 + rows_cap * 6; d.res_um_t = d.res_matches + 2 * mcap; d.res_um_d = d.res_um_t + T_ub + D;
-        *res_len = (size_t)d.res_um_d + D + 1;
-        *out_cap = rows_cap;
+        // ---- result block layout: header | out6 rows | matches | unmatched tracks | unmatched detections (absorb_last reads it back)
+        const int rows_cap = T_ub + D;
+        d.res_out6 = M_COUNT; d.res_matches = d.res_out6 + rows_cap * 6; d.res_um_t = d.res_matches + 2 * rows_cap; d.res_um_d = d.res_um_t + rows_cap;
         d.res = res;
         return d;
     }
+    // ints of the input block / the result block of a frame laid out by frame_dev
+    static size_t in_ints(int D) { return (size_t)D * 6 + 4; }
+    static size_t res_ints(int D, int T_ub) { return (size_t)M_COUNT + (size_t)(T_ub + D) * 10 + D + 8; }
 
-    // One or several frames, in order, with ONE host synchronisation at the end.  counts[b] = rows of frame b.
-    void run(const FrameIn *frames, int n_frames, int32_t *const *out6, const int *caps, int *counts) {
-        // ---- capacity for the worst case: every detection of the batch starts a track, every frame adds a gallery row
-        int D_sum = 0;
-        for (int b = 0; b < n_frames; ++b) D_sum += frames[b].D;
-        if (T_host + D_sum > capacity) { int c = capacity; while (c < T_host + D_sum) c *= 2; grow(c); }
-        // (max_rows = the largest gallery any LIVE track held after the last synchronised frame, from the result header;
-        //  every frame of this call can add one row to it)
-        if (unbounded) while (max_rows + n_frames + 1 > budget) grow_budget();
-        // ---- inputs of all frames in one pinned block, one upload
-        std::vector<size_t> in_off(n_frames);
-        size_t in_total = 0;
-        for (int b = 0; b < n_frames; ++b) { in_off[b] = in_total; in_total += (size_t)frames[b].D * 6 + 4; }
-        if (in_total > in_cap) {
-            if (in_host) (void)hipHostFree(in_host);
-            in_cap = in_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&in_host, in_cap * sizeof(int)));
-            in_dev.alloc(in_cap);
-        }
-        for (int b = 0; b < n_frames; ++b) {
-            const FrameIn &f = frames[b];
-            float *dst = reinterpret_cast<float *>(in_host + in_off[b]);
-            if (f.D) {
-                memcpy(dst, f.tlwh, (size_t)f.D * 16);
-                memcpy(dst + (size_t)f.D * 4, f.payload, (size_t)f.D * 4);
-                if (f.feat_rows) memcpy(dst + (size_t)f.D * 5, f.feat_rows, (size_t)f.D * 4);
-            }
-        }
-        YDS_HIP(hipMemcpyAsync(in_dev.p, in_host, in_total * sizeof(int), hipMemcpyHostToDevice, stream));
-        // ---- result blocks
-        std::vector<size_t> res_off(n_frames), res_len(n_frames);
-        std::vector<int> out_cap(n_frames);
-        size_t res_total = 0;
-        {
-            int T_ub = T_host;
-            for (int b = 0; b < n_frames; ++b) { res_off[b] = res_total; res_total += (size_t)M_COUNT + (size_t)(T_ub + frames[b].D) * 10 + frames[b].D + 8; T_ub += frames[b].D; }
-        }
-        if (res_total > res_cap) {
-            YDS_HIP(hipStreamSynchronize(stream));
-            if (res_host) (void)hipHostFree(res_host);
-            res_cap = res_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&res_host, res_cap * sizeof(int)));
-        }
-        // ---- embeddings of the whole batch normalised in ONE launch when they already sit back to back on the device (the
-        //      pipeline's ReID pass writes them that way): x / ||x|| once per frame in the reference (nn_matching.py:50-52)
-        bool batch_norm = n_frames > 1 && D_sum > 0;
-        {
-            const float *expect = nullptr;
-            for (int b = 0; b < n_frames && batch_norm; ++b) {
-                const FrameIn &f = frames[b];
-                if (!f.D) continue;
-                if (!f.feats_on_device || f.feat_rows || (expect && f.feats != expect)) batch_norm = false;
-                expect = f.feats + (size_t)f.D * EMB;
-            }
-        }
-        std::vector<float *> fn(n_frames, nullptr);
-        if (batch_norm) {
-            feats_n.ensure_keep((size_t)D_sum * EMB);
-            const float *first_feats = nullptr;
-            size_t off = 0;
-            for (int b = 0; b < n_frames; ++b) {
-                if (frames[b].D && !first_feats) first_feats = frames[b].feats;
-                fn[b] = feats_n.p + off * EMB;
-                off += frames[b].D;
-            }
-            hipLaunchKernelGGL(normalize_rows_kernel, dim3((D_sum + 3) / 4), dim3(256), 0, stream, first_feats, (const int *)nullptr, feats_n.p, D_sum,
-                               metric == METRIC_COSINE ? 1 : 0);
-        }
-        int T_ub = T_host;
-        for (int b = 0; b < n_frames; ++b) {
-            enqueue(frames[b], T_ub, in_off[b], res_off[b], &res_len[b], &out_cap[b], fn[b]);
-            T_ub += frames[b].D;
-        }
-        // (the result blocks are in host memory already: a device-to-host copy command would queue behind frame uploads)
-        YDS_HIP(hipStreamSynchronize(stream));
-        for (int b = 0; b < n_frames; ++b) {
-            const int *r = res_host + res_off[b];
-            const int m = r[M_NOUT];
-            if (m > caps[b]) fail("tracker: %d output rows exceed the caller's capacity %d", m, caps[b]);
-            if (m) memcpy(out6[b], r + M_COUNT, (size_t)m * 6 * sizeof(int));
-            counts[b] = m;
-        }
-        // ---- host-side mirror of the last frame (debug lists for the parity tests, live track count)
-        {
-            const int b = n_frames - 1;
-            int T_before = T_host;
-            for (int k = 0; k < b; ++k) T_before += frames[k].D;         // upper bound used for that frame's layout
-            absorb_last(res_host + res_off[b], T_before + frames[b].D);
-        }
-    }
-    // r: result block of the last frame this tracker ran, rows_cap: its row capacity (T_ub + D of that frame)
+    // host-side mirror of the last frame this tracker ran (debug lists for the parity tests, live track count).
+    // r: that frame's result block, rows_cap: its row capacity (T_ub + D of that frame)
     void absorb_last(const int *r, int rows_cap) {
         const int *pm = r + M_COUNT + rows_cap * 6, *pt = pm + 2 * rows_cap, *pd = pt + rows_cap;
         last_matches.assign(r[M_NM], {0, 0});
@@ -609,36 +475,13 @@ public:
         max_rows = r[M_MAXFEAT];
     }
 
+    // stand-alone calls (yds_tracker_step*, DeepSort.update): a step of one frame through a driver of this tracker's own
     int step(const float *tlwh_host, const float *feats, bool feats_on_device, const float *payload, int D, int32_t *out6, int cap) override {
         return step_sel(tlwh_host, feats, feats_on_device, nullptr, payload, D, out6, cap);
     }
     // feat_rows (optional): detection d uses row feat_rows[d] of `feats` (tracker-side NMS keeps a subset in pick order)
     int step_sel(const float *tlwh_host, const float *feats, bool feats_on_device, const int *feat_rows, const float *payload, int D,
-                 int32_t *out6, int cap) {
-        FrameIn f{tlwh_host, feats, feats_on_device, feat_rows, payload, D};
-        int count = 0;
-        run(&f, 1, &out6, &cap, &count);
-        return count;
-    }
-    // frames of one batch, in order, one synchronisation (the pipeline's association stage); skip[b]: tracker not called
-    void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
-    void step_batch(int n, const float *tlwh_host, const int *first, const float *feats_dev, const float *payload, const char *skip, int32_t *out6,
-                    int cap, int32_t *counts) override {
-        std::vector<FrameIn> fr;
-        std::vector<int32_t *> outs;
-        std::vector<int> caps, cnt, which;
-        for (int b = 0; b < n; ++b) {
-            if (skip && skip[b]) { counts[b] = -1; continue; }
-            const int D = first[b + 1] - first[b];
-            fr.push_back(FrameIn{tlwh_host + (size_t)first[b] * 4, feats_dev + (size_t)first[b] * EMB, true, nullptr, payload + first[b], D});
-            outs.push_back(out6 + (size_t)b * cap * 6);
-            caps.push_back(cap);
-            which.push_back(b);
-        }
-        cnt.assign(fr.size(), 0);
-        if (!fr.empty()) run(fr.data(), (int)fr.size(), outs.data(), caps.data(), cnt.data());
-        for (size_t k = 0; k < which.size(); ++k) counts[which[k]] = cnt[k];
-    }
+                 int32_t *out6, int cap);
 
     // host copy of the integer table (parity tests, DeepSort.tracker.tracks)
     struct HostTable { std::vector<int> slot, id, hits, age, tsu, state, n_feat; };
@@ -660,33 +503,21 @@ public:
     int capacity = 0;
     int T_host = 0;                 // live tracks after the last synchronised frame
     int max_rows = 1;               // largest gallery row count of a live track after the last synchronised frame
-    template <class T> struct GrowBuf : DevBuf<T> {
-        // ensure() that never shrinks and - unlike DevBuf::ensure - may only be called while nothing that uses the old buffer is
-        // in flight; growth is rare (sizes follow the largest frame seen), so it simply drains the stream first
-        hipStream_t *st = nullptr;
-        void ensure_keep(size_t count) {
-            if (count <= this->n) return;
-            if (st && *st) (void)hipStreamSynchronize(*st);
-            this->alloc(count + count / 2);
-        }
-    };
-    DevBuf<float> mean, cov, gallery /* cosine: rows stored normalised */;
-    DevBuf<int> table, table_tmp, free_slots, track_lists, meta, in_dev;
-    GrowBuf<float> feats_stage, feats_n, cost_dev;
-    GrowBuf<int> det_lists;
+    DevBuf<float> mean, cov, gallery /* cosine: rows stored normalised */, cost_dev;
+    DevBuf<int> table, table_tmp, free_slots, track_lists, meta, det_lists;
     DevBuf<char> lsap_scratch;
-    int *res_host = nullptr, *in_host = nullptr;
-    size_t res_cap = 0, in_cap = 0;
     std::vector<std::pair<int, int>> last_matches;
     std::vector<int> last_um_t, last_um_d;
-    hipStream_t stream = nullptr;
+    std::unique_ptr<TrackerGroupIface> solo;    // driver of the stand-alone calls (a TrackerGroup), made by the first of them
 };
 
-// ============================================================================================ several trackers in one step
-// The association of S independent trackers (one per video stream) advanced together: frame b belongs to tracker stream_of[b], a
-// tracker's frames come in time order and take rounds 0, 1, ... of the step; each round is the three launches of a frame with the
-// stream as an extra grid axis (trk_*_group_kernel), so S trackers cost three launches per round instead of three per frame.  Every
-// tracker keeps its own device state and buffers; the group owns the stream, the input / result blocks and the normalised embeddings.
+// ============================================================================================ the association driver
+// Advances S independent trackers (one per video stream; S = 1: a single tracker) through the frames of a step: frame b belongs to
+// tracker stream_of[b], a tracker's frames come in time order and take rounds 0, 1, ... of the step; each round is the three launches
+// with the stream as a grid axis, so S trackers cost three launches per round instead of three per frame.  The whole step is planned
+// before its first launch - rounds, capacities, every buffer, one input block - and the host synchronises ONCE, to fetch the int32
+// rows.  Every tracker keeps its own device state and the buffers sized by it; the driver owns the stream, the input / result blocks
+// and the embeddings as the kernels read them.
 class TrackerGroup : public TrackerGroupIface {
 public:
     TrackerGroup() { stream = make_stream(true); }
@@ -695,6 +526,7 @@ public:
         if (in_host) (void)hipHostFree(in_host);
         if (stream) (void)hipStreamDestroy(stream);
     }
+    void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
                     const float *payload, const char *skip, int32_t *out6, int cap, int32_t *counts) override {
@@ -718,7 +550,8 @@ public:
         for (size_t k = 0; k < which.size(); ++k) counts[which[k]] = cnt[k];
     }
 
-    // frames[i] (embeddings on the device, back to back in frame order) belongs to trk[stream_of[i]].  ONE host synchronisation.
+    // frames[i] belongs to trk[stream_of[i]]; counts[i] = its rows.  Embeddings: on the device, back to back in frame order, no row
+    // selection; a step of ONE frame (the stand-alone calls) may also bring them in host memory and select rows (feat_rows).
     void step_group(Tracker *const *trk, int S, const Tracker::FrameIn *frames, const int *stream_of, int n, int32_t *const *out6, const int *caps,
                     int *counts) {
         for (int a = 0; a < S; ++a)
@@ -734,8 +567,8 @@ public:
             last[s] = i;
             n_rounds = std::max(n_rounds, round[i] + 1);
         }
-        // ---- per tracker, as Tracker::run: capacity for the worst case, then every buffer its frames need (growth drains the tracker's
-        //      own stream; nothing of this step is in flight yet)
+        // ---- per tracker: capacity for the worst case - every detection of the step starts a track, every frame adds a gallery row
+        //      (max_rows = the largest gallery any LIVE track held after its last frame, from the result header) ...
         std::vector<int> T_run(S);
         for (int s = 0; s < S; ++s) {
             if (!n_of[s]) continue;
@@ -744,6 +577,9 @@ public:
             if (k.unbounded) while (k.max_rows + n_of[s] + 1 > k.budget) k.grow_budget();
             T_run[s] = k.T_host;
         }
+        // ---- ... then the buffers its largest frame needs.  The assignment solvers get the whole LDS; their state moves to a global
+        //      scratch when even that is too small (~3000 rows)
+        auto lsap_bytes = [](int T, int D) { return (size_t)std::max(std::max(T, D), 1) * LSAP_STATE_BYTES; };
         std::vector<size_t> cost_need(S, 0), lists_need(S, 0), lsap_need(S, 0);
         for (int i = 0; i < n; ++i) {
             const int s = stream_of[i], D = frames[i].D, Dn = std::max(D, 1);
@@ -752,34 +588,38 @@ public:
             const int Tn = std::max(T_ub[i], 1);
             cost_need[s] = std::max(cost_need[s], 2 * (size_t)(Tn + Dn) * Dn);
             lists_need[s] = std::max(lists_need[s], (size_t)Dn * 8 + (size_t)(Tn + Dn) * 8);
-            lsap_need[s] = std::max(lsap_need[s], (size_t)std::max(Tn, Dn) * LSAP_STATE_BYTES);
+            lsap_need[s] = std::max(lsap_need[s], lsap_bytes(T_ub[i], D));
         }
         for (int s = 0; s < S; ++s) {
             if (!n_of[s]) continue;
-            Tracker &k = *trk[s];
-            k.cost_dev.ensure_keep(cost_need[s]);
-            k.det_lists.ensure_keep(lists_need[s]);
-            if (lsap_need[s] > LSAP_LDS_MAX && k.lsap_scratch.n < lsap_need[s]) {           // this tracker's region of LSAP scratch
-                YDS_HIP(hipStreamSynchronize(k.stream));
-                k.lsap_scratch.alloc(lsap_need[s]);
-            }
+            grow_to(trk[s]->cost_dev, cost_need[s]);
+            grow_to(trk[s]->det_lists, lists_need[s]);
+            if (lsap_need[s] > LSAP_LDS_MAX) trk[s]->lsap_scratch.ensure(lsap_need[s]);
         }
-        // ---- embeddings: the frames' rows sit back to back on the device (the pipeline's ReID pass); cosine trackers read them
-        //      normalised by ONE launch over the whole step, euclidean trackers read them as they are (normalize_rows_kernel divides
-        //      by 1.f there: the same values)
+        // ---- embeddings: cosine trackers read them normalised, x / ||x|| once per frame (nn_matching.py:50-52), by ONE launch over the
+        //      whole step; euclidean trackers read the rows in place.  gather (one frame, rows in host memory or selected by feat_rows):
+        //      the same launch gathers the rows, for either metric (divisor 1.f for the euclidean one: the same values)
+        const bool gather = n == 1 && frames[0].D && (!frames[0].feats_on_device || frames[0].feat_rows);
         const float *feats0 = nullptr, *expect = nullptr;
         bool any_cos = false;
         for (int i = 0; i < n; ++i) {
             const Tracker::FrameIn &f = frames[i];
             if (!f.D) continue;
-            if (!f.feats_on_device || f.feat_rows || (expect && f.feats != expect)) fail("tracker group: embeddings must sit back to back on the device");
+            if (!gather && (!f.feats_on_device || f.feat_rows || (expect && f.feats != expect)))
+                fail("tracker group: embeddings must sit back to back on the device");
             if (!feats0) feats0 = f.feats;
             expect = f.feats + (size_t)f.D * EMB;
             any_cos |= trk[stream_of[i]]->metric == METRIC_COSINE;
         }
         const int rows_all = feats0 ? (int)((expect - feats0) / EMB) : 0;
-        if (any_cos) feats_n.ensure((size_t)rows_all * EMB);
-        // ---- input block: the TrkGroupDev of every (round, stream) pair (round-major), then each frame's tlwh | payload
+        if (any_cos || gather) grow_to(feats_n, (size_t)rows_all * EMB);
+        size_t stage_rows = 0;                                               // rows of host memory that go through feats_stage
+        if (gather && !frames[0].feats_on_device) {
+            stage_rows = rows_all;
+            if (frames[0].feat_rows) for (int k = 0; k < rows_all; ++k) stage_rows = std::max(stage_rows, (size_t)frames[0].feat_rows[k] + 1);
+            grow_to(feats_stage, stage_rows * EMB);
+        }
+        // ---- input block: the TrkGroupDev of every (round, stream) pair (round-major), then each frame's tlwh | payload | feat_rows
         std::vector<int> order(n), r_first(n_rounds + 1, 0);
         for (int i = 0; i < n; ++i) ++r_first[round[i] + 1];
         for (int r = 0; r < n_rounds; ++r) r_first[r + 1] += r_first[r];
@@ -791,60 +631,63 @@ public:
         std::vector<size_t> in_off(n), res_off(n);
         size_t in_total = (size_t)n * dev_ints, res_total = 0;
         for (int i = 0; i < n; ++i) {
-            in_off[i] = in_total; in_total += (size_t)frames[i].D * 6 + 4;
-            res_off[i] = res_total; res_total += (size_t)M_COUNT + (size_t)(T_ub[i] + frames[i].D) * 10 + frames[i].D + 8;
+            in_off[i] = in_total; in_total += Tracker::in_ints(frames[i].D);
+            res_off[i] = res_total; res_total += Tracker::res_ints(frames[i].D, T_ub[i]);
         }
         if (in_total > in_cap) {
-            YDS_HIP(hipStreamSynchronize(stream));
             if (in_host) (void)hipHostFree(in_host);
             in_cap = in_total * 2;
             YDS_HIP(hipHostMalloc((void **)&in_host, in_cap * sizeof(int)));
             in_dev.alloc(in_cap);
         }
         if (res_total > res_cap) {
-            YDS_HIP(hipStreamSynchronize(stream));
             if (res_host) (void)hipHostFree(res_host);
             res_cap = res_total * 2;
             YDS_HIP(hipHostMalloc((void **)&res_host, res_cap * sizeof(int)));
         }
-        std::vector<size_t> res_len(n);
-        std::vector<int> out_cap(n);
         std::vector<int> r_maxT(n_rounds, 0), r_maxD(n_rounds, 0);
         for (int e = 0; e < n; ++e) {
-            const int i = order[e], s = stream_of[i];
+            const int i = order[e];
             const Tracker::FrameIn &f = frames[i];
-            Tracker &k = *trk[s];
+            Tracker &k = *trk[stream_of[i]];
             float *dst = reinterpret_cast<float *>(in_host + in_off[i]);
             if (f.D) {
                 memcpy(dst, f.tlwh, (size_t)f.D * 16);
                 memcpy(dst + (size_t)f.D * 4, f.payload, (size_t)f.D * 4);
+                if (f.feat_rows) memcpy(dst + (size_t)f.D * 5, f.feat_rows, (size_t)f.D * 4);
             }
-            float *fn = nullptr;
-            if (f.D) fn = k.metric == METRIC_COSINE ? feats_n.p + (f.feats - feats0) : const_cast<float *>(f.feats);
+            float *fn = feats_n.p;
+            if (f.D) fn = gather || k.metric == METRIC_COSINE ? feats_n.p + (f.feats - feats0) : const_cast<float *>(f.feats);
             TrkGroupDev g;
-            g.d = k.frame_dev(f, T_ub[i], in_dev.p + in_off[i], res_host + res_off[i], &res_len[i], &out_cap[i], fn ? fn : feats_n.p);
+            g.d = k.frame_dev(f.D, T_ub[i], in_dev.p + in_off[i], res_host + res_off[i], fn);
             g.D = f.D;
-            g.lsap_state = (size_t)std::max(std::max(T_ub[i], 1), std::max(f.D, 1)) * LSAP_STATE_BYTES > LSAP_LDS_MAX ? k.lsap_scratch.p : nullptr;
+            g.lsap_state = lsap_bytes(T_ub[i], f.D) > LSAP_LDS_MAX ? k.lsap_scratch.p : nullptr;
             memcpy(in_host + (size_t)e * dev_ints, &g, sizeof g);
             r_maxT[round[i]] = std::max(r_maxT[round[i]], T_ub[i]);
             r_maxD[round[i]] = std::max(r_maxD[round[i]], f.D);
         }
+        // ---- launches (sizes come from device memory; the grids use the host-side upper bounds)
         YDS_HIP(hipMemcpyAsync(in_dev.p, in_host, in_total * sizeof(int), hipMemcpyHostToDevice, stream));
-        if (any_cos && rows_all)
-            hipLaunchKernelGGL(normalize_rows_kernel, dim3((rows_all + 3) / 4), dim3(256), 0, stream, feats0, (const int *)nullptr, feats_n.p, rows_all, 1);
+        if (stage_rows) YDS_HIP(hipMemcpyAsync(feats_stage.p, feats0, stage_rows * EMB * 4, hipMemcpyHostToDevice, stream));
+        if ((any_cos || gather) && rows_all) {
+            const int *rows_dev = gather && frames[0].feat_rows ? in_dev.p + in_off[0] + (size_t)rows_all * 5 : nullptr;
+            hipLaunchKernelGGL(normalize_rows_kernel, dim3((rows_all + 3) / 4), dim3(256), 0, stream, stage_rows ? feats_stage.p : feats0, rows_dev,
+                               feats_n.p, rows_all, any_cos ? 1 : 0);
+        }
         static bool attr_set = false;
         if (!attr_set) {
-            YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(trk_assoc_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LSAP_LDS_MAX));
+            YDS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(trk_assoc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LSAP_LDS_MAX));
             attr_set = true;
         }
         for (int r = 0; r < n_rounds; ++r) {
             const TrkGroupDev *g = reinterpret_cast<const TrkGroupDev *>(in_dev.p + (size_t)r_first[r] * dev_ints);
             const int Sr = r_first[r + 1] - r_first[r], maxT = r_maxT[r], maxD = r_maxD[r];
-            if (maxT && maxD) hipLaunchKernelGGL(trk_front_group_kernel, dim3(maxT, (maxD + 15) / 16, Sr), dim3(256), 0, stream, g);
-            hipLaunchKernelGGL(trk_assoc_group_kernel, dim3(Sr), dim3(256), LSAP_LDS_MAX, stream, g, (int)LSAP_LDS_MAX);
-            if (maxD) hipLaunchKernelGGL(trk_back_group_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
+            if (maxT && maxD) hipLaunchKernelGGL(trk_front_kernel, dim3(maxT, (maxD + 15) / 16, Sr), dim3(256), 0, stream, g);
+            hipLaunchKernelGGL(trk_assoc_kernel, dim3(Sr), dim3(256), LSAP_LDS_MAX, stream, g, (int)LSAP_LDS_MAX);
+            if (maxD) hipLaunchKernelGGL(trk_back_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
         }
         YDS_HIP(hipGetLastError());
+        // (the result blocks are in host memory already: a device-to-host copy command would queue behind frame uploads)
         YDS_HIP(hipStreamSynchronize(stream));
         for (int i = 0; i < n; ++i) {
             const int *r = res_host + res_off[i];
@@ -853,17 +696,27 @@ public:
             if (m) memcpy(out6[i], r + M_COUNT, (size_t)m * 6 * sizeof(int));
             counts[i] = m;
         }
-        // ---- each tracker's host mirror from its last frame, as Tracker::run leaves it
         for (int s = 0; s < S; ++s)
             if (last[s] >= 0) trk[s]->absorb_last(res_host + res_off[last[s]], T_ub[last[s]] + frames[last[s]].D);
     }
 
     hipStream_t stream = nullptr;
     DevBuf<int> in_dev;
-    DevBuf<float> feats_n;
+    DevBuf<float> feats_n, feats_stage;
     int *res_host = nullptr, *in_host = nullptr;
     size_t res_cap = 0, in_cap = 0;
 };
+
+int Tracker::step_sel(const float *tlwh_host, const float *feats, bool feats_on_device, const int *feat_rows, const float *payload, int D,
+                      int32_t *out6, int cap) {
+    if (!solo) solo.reset(new TrackerGroup());
+    const FrameIn f{tlwh_host, feats, feats_on_device, feat_rows, payload, D};
+    Tracker *self = this;
+    const int stream_of = 0;
+    int count = 0;
+    static_cast<TrackerGroup *>(solo.get())->step_group(&self, 1, &f, &stream_of, 1, &out6, &cap, &count);
+    return count;
+}
 
 TrackerGroupIface *make_tracker_group() { return new TrackerGroup(); }
 
@@ -881,6 +734,15 @@ struct Scratch {
 };
 Scratch g_scratch;
 std::vector<int> iota(int n) { std::vector<int> v(n); for (int i = 0; i < n; ++i) v[i] = i; return v; }
+// matches of the tracker's last frame for the parity tests (n_matches == nullptr: not asked for)
+void copy_debug_matches(const yds::Tracker &t, int32_t *dbg_matches, int dbg_cap, int *n_matches) {
+    if (!n_matches) return;
+    const auto &lm = t.last_matches;
+    *n_matches = (int)lm.size();
+    if (!dbg_matches) return;
+    if ((int)lm.size() > dbg_cap) yds::fail("tracker: %zu matches exceed dbg_cap %d", lm.size(), dbg_cap);
+    for (size_t k = 0; k < lm.size(); ++k) { dbg_matches[2 * k] = lm[k].first; dbg_matches[2 * k + 1] = lm[k].second; }
+}
 }  // namespace
 
 extern "C" {
@@ -899,14 +761,7 @@ int yds_tracker_step_sel(yds_trk *t, const float *tlwh, const float *feats, int 
                          int D, int32_t *out6, int cap, int *m_out, int32_t *dbg_matches, int dbg_cap, int *n_matches) {
     YDS_API_BEGIN
     *m_out = impl(t)->step_sel(tlwh, feats, feats_on_device != 0, feat_rows, payload, D, out6, cap);
-    if (n_matches) {
-        const auto &lm = impl(t)->last_matches;
-        *n_matches = (int)lm.size();
-        if (dbg_matches) {
-            if ((int)lm.size() > dbg_cap) yds::fail("tracker: %zu matches exceed dbg_cap %d", lm.size(), dbg_cap);
-            for (size_t k = 0; k < lm.size(); ++k) { dbg_matches[2 * k] = lm[k].first; dbg_matches[2 * k + 1] = lm[k].second; }
-        }
-    }
+    copy_debug_matches(*impl(t), dbg_matches, dbg_cap, n_matches);
     YDS_API_END
 }
 void yds_tracker_destroy(yds_trk *t) {
@@ -916,14 +771,7 @@ int yds_tracker_step(yds_trk *t, const float *tlwh, const float *feats, const fl
                      int32_t *dbg_matches, int dbg_cap, int *n_matches) {
     YDS_API_BEGIN
     *m_out = impl(t)->step(tlwh, feats, false, payload, D, out6, cap);
-    if (n_matches) {
-        const auto &lm = impl(t)->last_matches;
-        *n_matches = (int)lm.size();
-        if (dbg_matches) {
-            if ((int)lm.size() > dbg_cap) yds::fail("tracker: %zu matches exceed dbg_cap %d", lm.size(), dbg_cap);
-            for (size_t k = 0; k < lm.size(); ++k) { dbg_matches[2 * k] = lm[k].first; dbg_matches[2 * k + 1] = lm[k].second; }
-        }
-    }
+    copy_debug_matches(*impl(t), dbg_matches, dbg_cap, n_matches);
     YDS_API_END
 }
 int yds_tracker_step_dev(yds_trk *t, const float *tlwh, const float *feats_dev, const float *payload, int D, int32_t *out6, int cap, int *m_out) {

@@ -10,15 +10,26 @@ import numpy as np
 from . import _lib
 
 
+def _refuse_tracker_nms(deepsort, message):
+    # the batched path hands the tracker handle to the C pipeline and never passes through DeepSort.update: the
+    # tracker-side NMS (deep_sort.py:52-57, a host-ordered reordering of the detections) is not part of it
+    if getattr(deepsort, "nms_max_overlap", 1) != 1:
+        raise ValueError(message % (deepsort.nms_max_overlap,))
+
+
+def _check_host_frames(frames, next_frames=None):
+    assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.flags["C_CONTIGUOUS"]
+    if next_frames is not None:
+        assert next_frames.shape == frames.shape and next_frames.dtype == np.uint8 and next_frames.flags["C_CONTIGUOUS"]
+    return frames.shape[:3]
+
+
 class Pipeline:
     def __init__(self, net, deepsort, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         self.net, self.ds, self.cap = net, deepsort, int(cap)
         self._h = None
-        # the batched path hands the tracker handle to the C pipeline and never passes through DeepSort.update: the
-        # tracker-side NMS (deep_sort.py:52-57, a host-ordered reordering of the detections) is not part of it
-        if getattr(deepsort, "nms_max_overlap", 1) != 1:
-            raise ValueError("Pipeline: DeepSort(nms_max_overlap=%r) needs the frame-by-frame path (DeepSort.update / "
-                             "VideoDetector(batch_frames=1)); the batched pipeline has no tracker-side NMS" % (deepsort.nms_max_overlap,))
+        _refuse_tracker_nms(deepsort, "Pipeline: DeepSort(nms_max_overlap=%r) needs the frame-by-frame path (DeepSort.update / "
+                                      "VideoDetector(batch_frames=1)); the batched pipeline has no tracker-side NMS")
         mask = np.ascontiguousarray(class_mask if class_mask is not None else [], dtype=np.int32)
         self._h = _lib.check_ptr(_lib.load().yds_pipeline_create(net._h, deepsort.extractor._h, deepsort.tracker._h,
                                                                  conf_thres, nms_thres,
@@ -38,29 +49,25 @@ class Pipeline:
         """frames_dev: device pointer to uint8 [batch,h,w,3]; next_frames_dev (optional): the frames of the next
         call, whose detector pass is enqueued early.  Returns a list of int32 [m,6] (None when the detector found
         nothing and the tracker was not called)."""
-        out = np.zeros((batch, self.cap, 6), np.int32)
-        counts = np.zeros(batch, np.int32)
+        return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step(
+            self._h, frames_dev, next_frames_dev, h, w, batch, out, self.cap, counts))
+
+    def _run(self, n, select_next, call):
+        """One step of n frames: call(out, counts) is the library entry that fills int32 out [n,cap,6] and counts [n]."""
+        out = np.zeros((n, self.cap, 6), np.int32)
+        counts = np.zeros(n, np.int32)
         if select_next is not None:
             _lib.check(_lib.load().yds_pipeline_set_next_injection(self._h, int(select_next)))
-        _lib.check(_lib.load().yds_pipeline_step(self._h, frames_dev, next_frames_dev, h, w, batch, _lib.ptr(out), self.cap,
-                                                 _lib.ptr(counts)))
-        return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(batch)]
+        _lib.check(call(_lib.ptr(out), _lib.ptr(counts)))
+        return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(n)]
 
     def step_host(self, frames, next_frames=None, select_next=None):
         """frames / next_frames: uint8 [batch,h,w,3] HOST arrays (C-contiguous; views of a _lib.PinnedArray upload
         asynchronously).  The upload of next_frames overlaps this call's work; the next call must pass the same array
         object's memory as `frames`."""
-        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.flags["C_CONTIGUOUS"]
-        batch, h, w, _ = frames.shape
-        if next_frames is not None:
-            assert next_frames.shape == frames.shape and next_frames.dtype == np.uint8 and next_frames.flags["C_CONTIGUOUS"]
-        out = np.zeros((batch, self.cap, 6), np.int32)
-        counts = np.zeros(batch, np.int32)
-        if select_next is not None:
-            _lib.check(_lib.load().yds_pipeline_set_next_injection(self._h, int(select_next)))
-        _lib.check(_lib.load().yds_pipeline_step_host(self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, batch, _lib.ptr(out),
-                                                      self.cap, _lib.ptr(counts)))
-        return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(batch)]
+        batch, h, w = _check_host_frames(frames, next_frames)
+        return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step_host(
+            self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, batch, out, self.cap, counts))
 
     def set_frame_order(self, bgr):
         """bgr=True: the frames handed to step / step_host are B, G, R as a decoder delivers them (read in place, no reversed copy)."""
@@ -69,8 +76,7 @@ class Pipeline:
     def prefetch_host(self, frames):
         """Start uploading a batch that a LATER step_host call will receive (one per step; the array must stay alive and
         unchanged until the next step_host call returns)."""
-        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.flags["C_CONTIGUOUS"]
-        batch, h, w, _ = frames.shape
+        batch, h, w = _check_host_frames(frames)
         _lib.check(_lib.load().yds_pipeline_prefetch_host(self._h, _lib.ptr(frames), h, w, batch))
 
     def set_schedule(self, min_crops=None):
@@ -122,9 +128,8 @@ class MultiStreamPipeline(Pipeline):
         if len({id(d) for d in deepsorts}) != len(deepsorts) or len({id(d.tracker) for d in deepsorts}) != len(deepsorts):
             raise ValueError("MultiStreamPipeline: a DeepSort (or its tracker) is given for more than one stream; use DeepSort.clone()")
         for d in deepsorts:
-            if getattr(d, "nms_max_overlap", 1) != 1:
-                raise ValueError("MultiStreamPipeline: DeepSort(nms_max_overlap=%r) needs the frame-by-frame path; the batched pipeline "
-                                 "has no tracker-side NMS" % (d.nms_max_overlap,))
+            _refuse_tracker_nms(d, "MultiStreamPipeline: DeepSort(nms_max_overlap=%r) needs the frame-by-frame path; the batched pipeline "
+                                   "has no tracker-side NMS")
         self.net, self.ds, self.deepsorts, self.cap = net, deepsorts[0], deepsorts, int(cap)
         self.n_streams = len(deepsorts)
         mask = np.ascontiguousarray(class_mask if class_mask is not None else [], dtype=np.int32)
@@ -146,31 +151,17 @@ class MultiStreamPipeline(Pipeline):
         next_frames_dev (optional): the next call's n frames, whose detector pass is enqueued early.  Returns a list per frame of
         int32 [m,6] (None when the detector found nothing and that stream's tracker was not called)."""
         s = self._streams(stream_of_frame)
-        n = s.size
-        out = np.zeros((n, self.cap, 6), np.int32)
-        counts = np.zeros(n, np.int32)
-        if select_next is not None:
-            _lib.check(_lib.load().yds_pipeline_set_next_injection(self._h, int(select_next)))
-        _lib.check(_lib.load().yds_pipeline_step_multi(self._h, frames_dev, next_frames_dev, h, w, n, _lib.ptr(s), _lib.ptr(out), self.cap,
-                                                       _lib.ptr(counts)))
-        return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(n)]
+        return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi(
+            self._h, frames_dev, next_frames_dev, h, w, s.size, _lib.ptr(s), out, self.cap, counts))
 
     def step_host(self, frames, stream_of_frame, next_frames=None, select_next=None):
         """frames / next_frames: uint8 [n,h,w,3] HOST arrays, as Pipeline.step_host; frame i of stream stream_of_frame[i]."""
-        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.flags["C_CONTIGUOUS"]
-        n, h, w, _ = frames.shape
+        n, h, w = _check_host_frames(frames, next_frames)
         s = self._streams(stream_of_frame)
         if s.size != n:
             raise ValueError("MultiStreamPipeline: %d frames but %d stream ids" % (n, s.size))
-        if next_frames is not None:
-            assert next_frames.shape == frames.shape and next_frames.dtype == np.uint8 and next_frames.flags["C_CONTIGUOUS"]
-        out = np.zeros((n, self.cap, 6), np.int32)
-        counts = np.zeros(n, np.int32)
-        if select_next is not None:
-            _lib.check(_lib.load().yds_pipeline_set_next_injection(self._h, int(select_next)))
-        _lib.check(_lib.load().yds_pipeline_step_multi_host(self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, n, _lib.ptr(s),
-                                                            _lib.ptr(out), self.cap, _lib.ptr(counts)))
-        return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(n)]
+        return self._run(n, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_host(
+            self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, n, _lib.ptr(s), out, self.cap, counts))
 
 
 def conv_timing(net, mode=0):
