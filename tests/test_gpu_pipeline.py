@@ -299,3 +299,117 @@ def test_pipeline_step_with_uneven_detection_counts_matches_oracle_stream(monkey
         assert np.array_equal(g[:, 4:], w[:, 4:]), t              # track ids and classes: bit exact
         assert np.abs(g[:, :4] - w[:, :4]).max(initial=0) <= 1, t
     assert len(want[-1]) == K                                     # every person is a confirmed track at the end
+
+
+# ---- look-ahead that the caller abandons, and the per-pipeline crowded-scene threshold -------------------------------------
+# yolov3-tiny at 416 with a head bias that leaves a handful of content-dependent detections per frame (as
+# test_video_detector_batched_lookahead_equals_frame_by_frame); four batches A, B, C, D of two 480x640 frames, rolled copies of one
+# random image.  Seed and roll were chosen on the parent commit so that the runs below produce rows and B's rows differ from D's.
+_LA_SEED, _LA_ROLL = 0, 1
+
+
+def _la_batches(seed=_LA_SEED, roll=_LA_ROLL):
+    base = np.random.RandomState(seed).randint(0, 256, (480, 640, 3)).astype(np.uint8)
+    return {name: np.stack([np.roll(base, roll * (2 * i + b), axis=1) for b in range(2)]) for i, name in enumerate("ABCD")}
+
+
+def _la_pipeline():
+    """A fresh detector, DeepSort and pipeline (the pipeline keeps the other two alive)."""
+    from yolo_deepsort_amd import _lib, pipeline as pl
+    from yolo_deepsort_amd.deep_sort import DeepSort
+    from yolo_deepsort_amd.models import Darknet
+    _lib.init(0)
+    cfg = cfgs.cfg_text("yolov3-tiny", 416, 416)
+    net = Darknet(None, img_size=(416, 416), batch_max=2, cfg_text=cfg)
+    net.load_darknet_weights(None, blob=synth.darknet_weights_blob(cfg, 0, -1.45))
+    return pl.Pipeline(net, DeepSort(synth.reid_state_dict(0), use_cuda=True, **DS), 0.5, 0.4)
+
+
+_la_refs = {}
+
+
+def _la_reference(order, batches=None):
+    """Rows of the batches named in `order` stepped one by one, no look-ahead, frames in HBM: computed once, read only."""
+    from yolo_deepsort_amd import _lib
+    if batches is not None or order not in _la_refs:
+        b = batches or _la_batches()
+        pipe = _la_pipeline()
+        rows = []
+        for name in order:
+            dev = _lib.DeviceBuffer.from_array(b[name])
+            rows += pipe.step(dev.offset(0), 480, 640, 2)
+            dev.free()
+        if batches is not None:
+            return rows
+        _la_refs[order] = rows
+    return _la_refs[order]
+
+
+def _la_count(rows):
+    return sum(len(r) for r in rows if r is not None)
+
+
+def _la_assert_equal(got, want):
+    assert len(got) == len(want)
+    for t, (g, w) in enumerate(zip(got, want)):
+        assert (g is None) == (w is None), t
+        if w is not None:
+            assert g.shape == w.shape and np.array_equal(g, w), (t, g, w)      # same kernels, same inputs: element for element
+
+
+@pytest.mark.parametrize("deep_min", [0, 1000000])
+def test_abandoned_lookahead_in_hbm_equals_no_lookahead(deep_min, monkeypatch):
+    """step(A, next=B), step(C), step(B): B's detector pass was enqueued and never consumed; at threshold 0 its NMS had been waited
+    for and its ReID pass started early as well, and both are dropped.  Rows equal the run that never announced B."""
+    from yolo_deepsort_amd import _lib
+    monkeypatch.setenv("YDS_PIPE_DEEP_MIN", str(deep_min))
+    want = _la_reference("ACB")
+    assert _la_count(want) > 0
+    b = _la_batches()
+    dev = {k: _lib.DeviceBuffer.from_array(b[k]) for k in "ABC"}
+    pipe = _la_pipeline()
+    got = pipe.step(dev["A"].offset(0), 480, 640, 2, dev["B"].offset(0))
+    got += pipe.step(dev["C"].offset(0), 480, 640, 2)
+    got += pipe.step(dev["B"].offset(0), 480, 640, 2)
+    _la_assert_equal(got, want)
+
+
+def test_abandoned_lookahead_of_host_frames_expires():
+    """step_host(P=A, next=Q=B), P <- C, step_host(P), Q <- D, step_host(Q): the announced upload of B out of Q was never consumed
+    and must have been forgotten, so the last step uploads Q again and returns D's rows."""
+    from yolo_deepsort_amd import _lib
+    want = _la_reference("ACD")
+    with_b = _la_reference("ACB")
+    assert _la_count(want) > 0
+    assert not all((g is None) == (w is None) and (g is None or (g.shape == w.shape and np.array_equal(g, w)))
+                   for g, w in zip(want[4:], with_b[4:]))           # B's rows differ from D's: a stale B would be seen
+    b = _la_batches()
+    P, Q = _lib.PinnedArray((2, 480, 640, 3)), _lib.PinnedArray((2, 480, 640, 3))
+    pipe = _la_pipeline()
+    P.array[:] = b["A"]
+    Q.array[:] = b["B"]
+    got = pipe.step_host(P.array, Q.array)
+    P.array[:] = b["C"]
+    got += pipe.step_host(P.array)
+    Q.array[:] = b["D"]
+    got += pipe.step_host(Q.array)
+    _la_assert_equal(got, want)
+
+
+def test_crowded_scene_threshold_is_read_per_pipeline(monkeypatch):
+    """Two pipelines of one process, the first built under YDS_PIPE_DEEP_MIN=1000000 and the second under 0: the second construction
+    reads the variable again; the same stream with look-ahead gives the same rows under both orders."""
+    from yolo_deepsort_amd import _lib
+    b = _la_batches()
+    dev = {k: _lib.DeviceBuffer.from_array(b[k]) for k in "ABC"}
+    runs = []
+    for deep_min in (1000000, 0):
+        monkeypatch.setenv("YDS_PIPE_DEEP_MIN", str(deep_min))
+        pipe = _la_pipeline()
+        rows = pipe.step(dev["A"].offset(0), 480, 640, 2, dev["B"].offset(0))
+        rows += pipe.step(dev["B"].offset(0), 480, 640, 2, dev["C"].offset(0))
+        rows += pipe.step(dev["C"].offset(0), 480, 640, 2)
+        assert "reid_host" in pipe.stage_us()
+        runs.append(rows)
+    assert _la_count(runs[0]) > 0
+    _la_assert_equal(runs[1], runs[0])

@@ -714,32 +714,48 @@ void Darknet::forward_u8_host(const uint8_t *frames, int h, int w, int batch, fl
     YDS_HIP(hipStreamSynchronize(stream));
 }
 
-void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *tiles, int n_tiles) {
+void WindowTable::build(const int *rects_xyhw, int n, int img_h, int img_w, hipStream_t s) {
+    scale_host.resize((size_t)n * 2);
+    for (int t = 0; t < n; ++t) {
+        const int th = rects_xyhw[t * 4 + 2], tw = rects_xyhw[t * 4 + 3];
+        scale_host[t * 2] = (float)((double)tw / img_w);       // resize_boxes: python-double ratio, fp32 multiply
+        scale_host[t * 2 + 1] = (float)((double)th / img_h);
+    }
+    rects.ensure((size_t)n * 4);
+    scale.ensure((size_t)n * 2);
+    // s: enqueued on s; nullptr: synchronous
+    YDS_HIP(s ? hipMemcpyAsync(rects.p, rects_xyhw, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, s)
+              : hipMemcpy(rects.p, rects_xyhw, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice));
+    YDS_HIP(s ? hipMemcpyAsync(scale.p, scale_host.data(), scale_host.size() * sizeof(float), hipMemcpyHostToDevice, s)
+              : hipMemcpy(scale.p, scale_host.data(), scale_host.size() * sizeof(float), hipMemcpyHostToDevice));
+    T = n;
+}
+
+void Darknet::forward_windows(const uint8_t *frames_dev, int h, int w, int n_frames, const WindowTable &tab, float *pred, bool bgr) {
+    const int slots = n_frames * tab.T;
+    for (int slot0 = 0; slot0 < slots; slot0 += batch_max) {
+        const int nb = std::min(batch_max, slots - slot0);
+        launch_window_resize(frames_dev, h, w, tab.rects.p, tab.T, slot0, nb, input_view(nb), stream, bgr);
+        run_graph(nb);
+        launch_window_boxes(out.p, total_boxes, attrs, tab.rects.p, tab.scale.p, tab.T, slot0, nb, pred, stream);
+    }
+}
+
+void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *tiles_xyhw, int n_tiles) {
     if (in_channels != 3) fail("forward_tiles: network expects %d channels", in_channels);
     if (n_tiles < 1) fail("forward_tiles: no windows");
-    std::vector<float> scale((size_t)n_tiles * 2);
     for (int t = 0; t < n_tiles; ++t) {
-        const int x = tiles[t * 4], y = tiles[t * 4 + 1], th = tiles[t * 4 + 2], tw = tiles[t * 4 + 3];
+        const int x = tiles_xyhw[t * 4], y = tiles_xyhw[t * 4 + 1], th = tiles_xyhw[t * 4 + 2], tw = tiles_xyhw[t * 4 + 3];
         if (x < 0 || y < 0 || th < 1 || tw < 1 || x + tw > w || y + th > h) fail("forward_tiles: window %d (%d,%d,%d,%d) outside the %dx%d frame", t, x, y, th, tw, w, h);
-        scale[t * 2] = (float)((double)tw / img_w);            // resize_boxes: python-double ratio, fp32 multiply
-        scale[t * 2 + 1] = (float)((double)th / img_h);
     }
     const size_t nbytes = (size_t)h * w * 3;
     stage_u8.ensure(nbytes);
-    tile_rects.ensure((size_t)n_tiles * 4);
-    tile_scale.ensure((size_t)n_tiles * 2);
     tiled_pred.ensure((size_t)n_tiles * total_boxes * attrs);
     YDS_HIP(hipMemcpyAsync(stage_u8.p, frame, nbytes, hipMemcpyHostToDevice, stream));
     stage_h = h; stage_w = w; stage_n = 1;                      // stage_u8 now holds exactly this frame
-    YDS_HIP(hipMemcpyAsync(tile_rects.p, tiles, (size_t)n_tiles * 4 * sizeof(int), hipMemcpyHostToDevice, stream));
-    YDS_HIP(hipMemcpyAsync(tile_scale.p, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    for (int t0 = 0; t0 < n_tiles; t0 += batch_max) {
-        const int nb = std::min(batch_max, n_tiles - t0);
-        launch_window_resize(stage_u8.p, h, w, tile_rects.p, n_tiles, t0, nb, input_view(nb), stream, false);
-        run_graph(nb);
-        launch_window_boxes(out.p, total_boxes, attrs, tile_rects.p, tile_scale.p, n_tiles, t0, nb, tiled_pred.p, stream);
-    }
-    YDS_HIP(hipStreamSynchronize(stream));          // `scale` and the caller's buffers may go away
+    tiles.build(tiles_xyhw, n_tiles, img_h, img_w, stream);
+    forward_windows(stage_u8.p, h, w, 1, tiles, tiled_pred.p, false);
+    YDS_HIP(hipStreamSynchronize(stream));          // the caller's buffers may go away
 }
 
 bool Darknet::stem_fused(int batch) {

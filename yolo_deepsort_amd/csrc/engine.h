@@ -55,6 +55,16 @@ struct Storage {
     int into = -1, coff = 0;
 };
 
+// Rectangles (x, y, th, tw) of T windows of a frame and each window's resize_boxes scale (tw / img_w, th / img_h), on the device.
+struct WindowTable {
+    DevBuf<int> rects;
+    DevBuf<float> scale;
+    int T = 0;
+    // s: the two copies are enqueued on s (the caller synchronises s before rects_xyhw goes away); nullptr: synchronous copies
+    void build(const int *rects_xyhw, int n, int img_h, int img_w, hipStream_t s);
+    std::vector<float> scale_host;                          // source of the enqueued copy
+};
+
 class Darknet {
 public:
     Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_max);
@@ -72,6 +82,10 @@ public:
     // sliding-window front end (img_detect.py:97-139): windows (x, y, th, tw) of one host frame -> corner-form, window-
     // shifted predictions [n_tiles * total_boxes, attrs] in tiled_pred (windows run in chunks of batch_max)
     void forward_tiles_host(const uint8_t *frame, int h, int w, const int *tiles_xyhw, int n_tiles);
+    // window slots [0, n_frames * tab.T) of n_frames frames in HBM (slot = frame * T + window) through the network in chunks of
+    // batch_max (a chunk may straddle frames): resize -> network -> boxes in corner form, resize_boxes to the window's own size,
+    // shifted by the window origin, to pred [slots * total_boxes, attrs].  Asynchronous on `stream`.
+    void forward_windows(const uint8_t *frames_dev, int h, int w, int n_frames, const WindowTable &tab, float *pred, bool bgr);
     void layer_output_host(int layer, int batch, float *nchw);
     void get_input_host(int batch, float *nchw);
     void set_injection(int image, const float *rows, int n, float logit);
@@ -100,8 +114,8 @@ public:
     DevBuf<float> input, out, stage_f32;
     DevBuf<uint8_t> stage_u8;
     int stage_h = 0, stage_w = 0, stage_n = 0;               // frames last uploaded by forward_u8_host (device copy in stage_u8)
-    DevBuf<float> tiled_pred, tile_scale;
-    DevBuf<int> tile_rects;
+    DevBuf<float> tiled_pred;
+    WindowTable tiles;
     hipStream_t stream = nullptr;
     int32_t header[5] = {0, 0, 0, 0, 0};
     bool weights_loaded = false;

@@ -19,174 +19,221 @@
 #include <stdlib.h>
 
 #include <chrono>
+#include <utility>
 
 namespace yds {
+
+// One NMS slot: workspace + pinned results, and the events of the detector pass that uses it.  Two slots alternate, so that the
+// pass of batch i+1 can be enqueued before the host has waited for and read the results of batch i: the detector stream never
+// drains between passes.
+struct DetSlot {
+    std::unique_ptr<NmsWorkspace> nms;
+    hipEvent_t e0, e1, e2, e_nms;      // pass start, resize (+ head) done, network done, NMS done
+    hipEvent_t e_r0, e_r1;             // around a ReID pass enqueued inside this slot's detector pass
+    bool reid_in_pass = false;
+    DetSlot() { for (hipEvent_t *e : {&e0, &e1, &e2, &e_nms, &e_r0, &e_r1}) YDS_HIP(hipEventCreate(e)); }
+    ~DetSlot() { for (hipEvent_t e : {e0, e1, e2, e_nms, e_r0, e_r1}) (void)hipEventDestroy(e); }
+};
+
+// One detector pass (+ NMS) over a batch, as far as it has been enqueued.
+struct Pass {
+    const uint8_t *frames = nullptr;   // nullptr: no pass (slot still names the DetSlot used last)
+    int h = 0, w = 0, batch = 0;
+    int slot = 0;                      // DetSlot
+    enum { NOTHING, HEAD, WHOLE } done = NOTHING;     // NOTHING with frames set: the head is still to be (re-)enqueued
+    bool split = false;                // HEAD: the first layers went with the head, the tail runs the rest
+    bool open() const { return frames && done != WHOLE; }
+    bool is_whole(const uint8_t *f, int n) const { return frames == f && batch == n && done == WHOLE; }
+};
+
+// ---- frames handed over as HOST memory (img_detect.py:70-71 starts from a host frame) ------------------------------
+// Three device staging buffers take turns; the copy runs on its own stream (SDMA engine), so uploads overlap the detector /
+// ReID / association of earlier batches.  A batch is matched by its host pointer for a BOUNDED time: the slot is forgotten
+// when the step that consumed it returns, and an announced batch that is never consumed is forgotten too (`next` must be the
+// following call's `frames`, a prefetch_host batch must be consumed within two calls: Slot::ttl) - so a caller may reuse a
+// host buffer for new frames and a later buffer at the same address can never match stale device frames.  A slot is only
+// overwritten after the kernels that read it (the detector's resize, the extractor's crops) have passed: the copy stream
+// waits on their events.  Pinned source memory (yds_host_alloc) makes the copy asynchronous and full speed.
+// Depth: step_host(frames, next) starts the upload of `next` when it is called - but the detector stream runs a whole pass
+// ahead of the host chain (NMS -> ReID -> association), so it wants `next` at that very moment and would idle for the
+// 1.7 ms of a 100 MB copy (1352 vs 1447 frames/s).  prefetch_host(frames of the step after next) starts that copy one
+// step earlier; step_host then finds both of its batches resident.
+class FrameStager {
+public:
+    enum Reader { DET, REID };
+    FrameStager(hipStream_t det_stream, hipStream_t reid_stream) : det_stream(det_stream), reid_stream(reid_stream) {
+        YDS_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    }
+    ~FrameStager() { (void)hipStreamDestroy(copy_stream); }
+    // slot holding the batch uploaded from `host` / the slot whose device buffer is `dev`; -1: none
+    int find(const uint8_t *host) const {
+        for (int k = 0; k < N; ++k)
+            if (host && slots[k].host == host) return k;
+        return -1;
+    }
+    int slot_of(const uint8_t *dev) const {
+        for (int k = 0; k < N; ++k)
+            if (slots[k].dev.p && dev == slots[k].dev.p) return k;
+        return -1;
+    }
+    const uint8_t *dev(int k) const { return slots[k].dev.p; }
+    // ttl: step_host calls the batch survives unconsumed (1 = this step's frames, 2 = its `next`, 3 = a prefetch)
+    int upload(const uint8_t *host, size_t bytes, int ttl, int keep_a = -1, int keep_b = -1) {
+        int k = -1;
+        for (int pass = 0; pass < 2 && k < 0; ++pass)               // next slot in turn: an empty one first, else any not in use
+            for (int t = 1; t <= N; ++t) {
+                const int c = (turn + t) % N;
+                if (c == keep_a || c == keep_b || (pass == 0 && slots[c].host)) continue;
+                k = c;
+                break;
+            }
+        if (k < 0) fail("pipeline: no staging buffer free");
+        turn = k;
+        Slot &s = slots[k];
+        // the previous tenant's readers (a prefetched detector pass, an early ReID pass) may still be running on their streams
+        for (Read &r : s.rd)
+            if (r.set) { YDS_HIP(hipStreamWaitEvent(copy_stream, r.ev, 0)); r.set = false; }
+        if (s.dev.n < bytes) {                                      // (re)allocation frees the old buffer: its readers must be done
+            YDS_HIP(hipStreamSynchronize(det_stream));
+            YDS_HIP(hipStreamSynchronize(reid_stream));
+        }
+        s.dev.ensure(bytes);
+        s.ttl = ttl;
+        YDS_HIP(hipMemcpyAsync(s.dev.p, host, bytes, hipMemcpyHostToDevice, copy_stream));
+        YDS_HIP(hipEventRecord(s.up_done, copy_stream));
+        s.host = host;
+        s.up_pending = true;
+        return k;
+    }
+    // `dev` is a staging buffer whose copy is still running: `stream` waits for the copy engine (only then: see Pipeline::step)
+    void wait_uploaded(const uint8_t *dev, hipStream_t stream) {
+        if (const int k = slot_of(dev); k >= 0 && hipEventQuery(slots[k].up_done) != hipSuccess)
+            YDS_HIP(hipStreamWaitEvent(stream, slots[k].up_done, 0));
+    }
+    // the last kernels of `who` that read staging buffer `dev` have just been enqueued on `stream`
+    void mark_read(const uint8_t *dev, hipStream_t stream, Reader who) {
+        if (const int k = slot_of(dev); k >= 0) { YDS_HIP(hipEventRecord(slots[k].rd[who].ev, stream)); slots[k].rd[who].set = true; }
+    }
+    // every host buffer handed over so far may be reused by the caller when the step returns; the consumed batch is forgotten
+    void end_of_step(int consumed) {
+        for (Slot &s : slots)
+            if (s.up_pending) { YDS_HIP(hipEventSynchronize(s.up_done)); s.up_pending = false; }
+        slots[consumed].host = nullptr;
+        for (int k = 0; k < N; ++k)                                 // announced but never consumed: forget it (its address may be reused)
+            if (k != consumed && slots[k].host && --slots[k].ttl <= 0) slots[k].host = nullptr;
+        cur = -1;
+    }
+    int cur = -1, next = -1;           // slots of the running step's frames and of its `next` (the last step's, between steps)
+
+private:
+    static constexpr int N = 3;
+    struct Read { hipEvent_t ev = nullptr; bool set = false; };       // recorded behind the last kernels that read a slot
+    struct Slot {
+        DevBuf<uint8_t> dev;           // device copy of the host frames
+        const uint8_t *host = nullptr; // where they came from; nullptr: forgotten
+        bool up_pending = false;
+        int ttl = 0;
+        hipEvent_t up_done = nullptr;
+        Read rd[2];                    // by Reader
+        Slot() { for (hipEvent_t *e : {&up_done, &rd[DET].ev, &rd[REID].ev}) YDS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming)); }
+        ~Slot() { for (hipEvent_t e : {up_done, rd[DET].ev, rd[REID].ev}) (void)hipEventDestroy(e); }
+    };
+    Slot slots[N];
+    int turn = 0;
+    hipStream_t copy_stream = nullptr, det_stream, reid_stream;
+};
 
 class Pipeline {
 public:
     // trks: the tracker of every stream; multi: made by yds_pipeline_create_multi (a step names the stream of each frame)
     Pipeline(Darknet *net, ReidNet *reid, std::vector<TrackerIface *> trks, bool multi, float conf, float nms_iou, const int32_t *mask, int n_mask)
         : net(net), reid(reid), trks(std::move(trks)), group(make_tracker_group()), multi(multi), conf(conf), nms_thres(nms_iou),
-          class_mask(mask, mask + n_mask) {
-        for (int k = 0; k < 2; ++k) {
-            for (hipEvent_t *e : {&e0[k], &e1[k], &e2[k], &e_nms[k]}) YDS_HIP(hipEventCreate(e));
-            nms[k].reset(new NmsWorkspace(4096, net->batch_max));
-        }
-        for (int k = 0; k < NSTAGE; ++k)
-            for (hipEvent_t *e : {&up_done[k], &rd_det[k], &rd_reid[k]}) YDS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        YDS_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+          class_mask(mask, mask + n_mask), deep_min(getenv("YDS_PIPE_DEEP_MIN") ? atoi(getenv("YDS_PIPE_DEEP_MIN")) : 64),
+          stager(net->stream, reid->stream) {
+        for (DetSlot &s : det) s.nms.reset(new NmsWorkspace(4096, net->batch_max));
         YDS_HIP(hipEventCreateWithFlags(&ev_feat, hipEventDisableTiming));
         YDS_HIP(hipEventCreateWithFlags(&ev_reid_done, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k)
-            for (hipEvent_t *e : {&e_r0[k], &e_r1[k]}) YDS_HIP(hipEventCreate(e));
     }
     ~Pipeline() {
-        for (int k = 0; k < 2; ++k) {
-            for (hipEvent_t e : {e0[k], e1[k], e2[k], e_nms[k]}) (void)hipEventDestroy(e);
-        }
-        for (int k = 0; k < NSTAGE; ++k)
-            for (hipEvent_t e : {up_done[k], rd_det[k], rd_reid[k]}) (void)hipEventDestroy(e);
-        (void)hipStreamDestroy(copy_stream);
         (void)hipEventDestroy(ev_feat);
         (void)hipEventDestroy(ev_reid_done);
-        for (int k = 0; k < 2; ++k)
-            for (hipEvent_t e : {e_r0[k], e_r1[k]}) (void)hipEventDestroy(e);
     }
 
-    // ---- frames handed over as HOST memory (img_detect.py:70-71 starts from a host frame) ------------------------------
-    // Three device staging buffers take turns; the copy runs on its own stream (SDMA engine), so uploads overlap the detector /
-    // ReID / association of earlier batches.  A batch is matched by its host pointer for a BOUNDED time: the slot is forgotten
-    // when the step that consumed it returns, and an announced batch that is never consumed is forgotten too (`next` must be the
-    // following call's `frames`, a prefetch_host batch must be consumed within two calls: stage_ttl) - so a caller may reuse a
-    // host buffer for new frames and a later buffer at the same address can never match stale device frames.  A slot is only
-    // overwritten after the kernels that read it (the detector's resize, the extractor's crops) have passed: the copy stream
-    // waits on their events.  Pinned source memory (yds_host_alloc) makes the copy asynchronous and full speed.
-    // Depth: step_host(frames, next) starts the upload of `next` when it is called - but the detector stream runs a whole pass
-    // ahead of the host chain (NMS -> ReID -> association), so it wants `next` at that very moment and would idle for the
-    // 1.7 ms of a 100 MB copy (1352 vs 1447 frames/s).  prefetch_host(frames of the step after next) starts that copy one
-    // step earlier; step_host then finds both of its batches resident.
-    int staged(const uint8_t *host) const {
-        for (int k = 0; k < NSTAGE; ++k)
-            if (host && stage_host[k] == host) return k;
-        return -1;
-    }
-    int upload(const uint8_t *host, size_t bytes, int ttl, int keep_a = -1, int keep_b = -1) {
-        int k = -1;
-        for (int pass = 0; pass < 2 && k < 0; ++pass)               // next slot in turn: an empty one first, else any not in use
-            for (int t = 1; t <= NSTAGE; ++t) {
-                const int c = (stage_turn + t) % NSTAGE;
-                if (c == keep_a || c == keep_b || (pass == 0 && stage_host[c])) continue;
-                k = c;
-                break;
-            }
-        if (k < 0) fail("pipeline: no staging buffer free");
-        stage_turn = k;
-        // the previous tenant's readers (a prefetched detector pass, an early ReID pass) may still be running on their streams
-        if (rd_det_set[k]) { YDS_HIP(hipStreamWaitEvent(copy_stream, rd_det[k], 0)); rd_det_set[k] = false; }
-        if (rd_reid_set[k]) { YDS_HIP(hipStreamWaitEvent(copy_stream, rd_reid[k], 0)); rd_reid_set[k] = false; }
-        if (stage[k].n < bytes) {                                    // (re)allocation frees the old buffer: its readers must be done
-            YDS_HIP(hipStreamSynchronize(net->stream));
-            YDS_HIP(hipStreamSynchronize(reid->stream));
-        }
-        stage[k].ensure(bytes);
-        stage_ttl[k] = ttl;
-        YDS_HIP(hipMemcpyAsync(stage[k].p, host, bytes, hipMemcpyHostToDevice, copy_stream));
-        YDS_HIP(hipEventRecord(up_done[k], copy_stream));
-        stage_host[k] = host;
-        up_pending[k] = true;
-        return k;
-    }
+    // frames handed over as host memory: see FrameStager
     void prefetch_host(const uint8_t *frames_host, int h, int w, int batch) {
-        if (staged(frames_host) >= 0) return;
-        upload(frames_host, (size_t)batch * h * w * 3, 3, cur_k, next_k);      // survives this call's step and the next: consumed by the one after
+        if (stager.find(frames_host) >= 0) return;
+        stager.upload(frames_host, (size_t)batch * h * w * 3, 3, stager.cur, stager.next);      // survives this call's step and the next: consumed by the one after
     }
-    void step_host(const uint8_t *frames_host, const uint8_t *next_host, int next_inject_set, int h, int w, int batch, int32_t *out6, int cap,
-                   int32_t *counts) {
+    void step_host(const uint8_t *frames_host, const uint8_t *next_host, int h, int w, int batch, int32_t *out6, int cap, int32_t *counts) {
         const size_t bytes = (size_t)batch * h * w * 3;
         // batches handed over earlier (as `next` of the previous call, or through prefetch_host) are already resident or on their way
-        cur_k = staged(frames_host);
-        if (cur_k < 0) cur_k = upload(frames_host, bytes, 1, staged(next_host));
-        next_k = -1;
-        if (next_host) {
-            next_k = staged(next_host);
-            if (next_k < 0) next_k = upload(next_host, bytes, 2, cur_k);              // survives this step: the next call's `frames`
-        }
-        step(stage[cur_k].p, next_k >= 0 ? stage[next_k].p : nullptr, next_inject_set, h, w, batch, out6, cap, counts, true);
-        // every host buffer handed over so far may be reused by the caller when this returns; the consumed batch is forgotten
-        for (int k = 0; k < NSTAGE; ++k)
-            if (up_pending[k]) { YDS_HIP(hipEventSynchronize(up_done[k])); up_pending[k] = false; }
-        stage_host[cur_k] = nullptr;
-        for (int k = 0; k < NSTAGE; ++k)                            // announced but never consumed: forget it (its address may be reused)
-            if (k != cur_k && stage_host[k] && --stage_ttl[k] <= 0) stage_host[k] = nullptr;
-        cur_k = -1;
-    }
-    int slot_of(const uint8_t *frames_dev) const {
-        for (int b = 0; b < NSTAGE; ++b)
-            if (stage[b].p && frames_dev == stage[b].p) return b;
-        return -1;
+        stager.cur = stager.find(frames_host);
+        if (stager.cur < 0) stager.cur = stager.upload(frames_host, bytes, 1, stager.find(next_host));
+        stager.next = next_host ? stager.find(next_host) : -1;
+        if (next_host && stager.next < 0) stager.next = stager.upload(next_host, bytes, 2, stager.cur);      // survives this step: the next call's `frames`
+        step(stager.dev(stager.cur), stager.next >= 0 ? stager.dev(stager.next) : nullptr, h, w, batch, out6, cap, counts, true);
+        stager.end_of_step(stager.cur);
     }
 
-    // One detector pass over a batch AND its NMS, all asynchronous on the detector stream.  Two NMS workspaces (and
-    // their pinned result buffers) alternate, so that the pass of batch i+1 can be enqueued before the host has waited
-    // for and read the results of batch i: the detector stream never drains between passes.
-    void launch_detector(const uint8_t *frames_dev, int h, int w, int batch, int slot = -1) {
-        launch_detector_head(frames_dev, h, w, batch, slot, false);
-        launch_detector_tail(frames_dev, h, w, batch);
+    // One detector pass over a batch AND its NMS, all asynchronous on the detector stream, in two pieces (serialized schedule, see
+    // step()): head = upload wait + resize + the first layers (Darknet::head_layers), tail = the remaining layers + NMS.  split =
+    // false (or a network that cannot be split) puts the whole network into the tail.  launch_detector enqueues what is missing.
+    void launch_detector(Pass &p, bool split = false) {
+        if (p.done == Pass::NOTHING) launch_detector_head(p, split);
+        if (p.done == Pass::HEAD) launch_detector_tail(p);
     }
-    // The pass in two pieces (serialized schedule, see step()): head = upload wait + resize + the first layers
-    // (Darknet::head_layers), tail = the remaining layers + NMS.  split = false (or a network that cannot be split) puts the whole
-    // network into the tail.
-    void launch_detector_head(const uint8_t *frames_dev, int h, int w, int batch, int slot, bool split) {
-        const int k = slot >= 0 ? slot : (in_flight_slot ^= 1);
-        head_slot = k;
-        reid_in_pass[k] = false;                                    // (a head re-recorded for this slot: no ReID interval of an earlier pass belongs to it)
-        for (int b = 0; b < NSTAGE; ++b)                            // frames uploaded by step_host: wait for the copy engine
-            if (stage[b].p && frames_dev == stage[b].p && hipEventQuery(up_done[b]) != hipSuccess)
-                YDS_HIP(hipStreamWaitEvent(net->stream, up_done[b], 0));   // (only while the copy is still running: see step())
-        YDS_HIP(hipEventRecord(e0[k], net->stream));
-        if (windows_for(h, w)) {                                    // window mode: the whole pass (resize included) is the tail's
-            YDS_HIP(hipEventRecord(e1[k], net->stream));
-            head_split = false;
+    void launch_detector_head(Pass &p, bool split) {
+        DetSlot &s = det[p.slot];
+        s.reid_in_pass = false;                                     // (a head re-recorded for this slot: no ReID interval of an earlier pass belongs to it)
+        stager.wait_uploaded(p.frames, net->stream);                // frames uploaded by step_host: wait for the copy engine
+        YDS_HIP(hipEventRecord(s.e0, net->stream));
+        p.done = Pass::HEAD;
+        p.split = false;
+        if (windows_for(p.h, p.w)) {                                // window mode: the whole pass (resize included) is the tail's
+            YDS_HIP(hipEventRecord(s.e1, net->stream));
             return;
         }
-        launch_resize_u8(frames_dev, batch, h, w, net->input_view(batch), net->stream, frames_bgr);
-        YDS_HIP(hipEventRecord(e1[k], net->stream));
-        if (const int sl = slot_of(frames_dev); sl >= 0) { YDS_HIP(hipEventRecord(rd_det[sl], net->stream)); rd_det_set[sl] = true; }
-        head_split = split && net->forward_resized_part(batch, 0);
+        launch_resize_u8(p.frames, p.batch, p.h, p.w, net->input_view(p.batch), net->stream, frames_bgr);
+        YDS_HIP(hipEventRecord(s.e1, net->stream));
+        stager.mark_read(p.frames, net->stream, FrameStager::DET);
+        p.split = split && net->forward_resized_part(p.batch, 0);
     }
-    void launch_detector_tail(const uint8_t *frames_dev, int h, int w, int batch) {
-        const int k = head_slot;
-        if (const int T = windows_for(h, w)) {
-            launch_windows_tail(frames_dev, h, w, batch, T, k);
-            in_flight = frames_dev;
-            in_flight_batch = batch;
-            return;
+    void launch_detector_tail(Pass &p) {
+        DetSlot &s = det[p.slot];
+        const size_t per_slot = (size_t)net->total_boxes * net->attrs;
+        if (const int T = windows_for(p.h, p.w)) {
+            if (win_pred.n < (size_t)p.batch * T * per_slot) {
+                YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
+                win_pred.alloc((size_t)p.batch * T * per_slot);
+            }
+            net->forward_windows(p.frames, p.h, p.w, p.batch, win, win_pred.p, frames_bgr);
+            stager.mark_read(p.frames, net->stream, FrameStager::DET);
+            YDS_HIP(hipEventRecord(s.e2, net->stream));
+            s.nms->launch(win_pred.p, (size_t)T * per_slot, p.batch, T * net->total_boxes, net->attrs, conf, nms_thres, 1.f, 1.f, 300, net->stream,
+                          true, true);
+        } else {
+            if (p.split) (void)net->forward_resized_part(p.batch, 1);
+            else net->forward_resized(p.batch);
+            YDS_HIP(hipEventRecord(s.e2, net->stream));
+            const float sx = (float)((double)p.w / net->img_w), sy = (float)((double)p.h / net->img_h);
+            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream);
         }
-        if (head_split) (void)net->forward_resized_part(batch, 1);
-        else net->forward_resized(batch);
-        YDS_HIP(hipEventRecord(e2[k], net->stream));
-        const float sx = (float)((double)w / net->img_w), sy = (float)((double)h / net->img_h);
-        nms[k]->launch(net->out.p, (size_t)net->total_boxes * net->attrs, batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300,
-                       net->stream);
-        YDS_HIP(hipEventRecord(e_nms[k], net->stream));
-        in_flight = frames_dev;
-        in_flight_batch = batch;
+        YDS_HIP(hipEventRecord(s.e_nms, net->stream));
+        p.done = Pass::WHOLE;
     }
 
     // ---- window mode (yds_pipeline_set_windows; ImageDetector(win_size, overlap), img_detect.py:97-151, for a batch of frames) ----
     // Every frame of a step is cut into the same T windows (the reference's grid: x-major, then y; each window extended by the
     // overlap and clipped to the frame); window t of frame b is slot b * T + t.  The slots run through the network in chunks of at
-    // most batch_max (a chunk may straddle frames); behind every chunk its predictions go - corner form, resize_boxes to the window's
-    // own size, shifted by the window origin (window_boxes_kernel, as yds_detect_tiled does) - into win_pred [batch * T * total_boxes, attrs], a
-    // frame's rows window-major then in box order: the concatenation of img_detect.py:142, which the stable ranking and the merge
-    // branch depend on.  ONE NMS launch per step over n_boxes = T * total_boxes per frame, merge branch as a kernel (nms.hip); no
+    // most batch_max (Darknet::forward_windows) into win_pred [batch * T * total_boxes, attrs], a frame's rows window-major then in
+    // box order: the concatenation of img_detect.py:142, which the stable ranking and the merge branch depend on.  ONE NMS launch per step over n_boxes = T * total_boxes per frame, merge branch as a kernel (nms.hip); no
     // copy of candidates to the host and no synchronisation inside the pass.  win_pred holds the FULL shifted predictions (no
     // compaction per chunk): batch * T * total_boxes * attrs * 4 bytes - yolov3-608 (22743 boxes x 85): 7.73 MB per window, 8 frames of
     // 1080p (T = 8) 495 MB.  One buffer serves both NMS slots: the NMS of a pass and the box kernels of the next are ordered by the
     // detector's stream.  The window table (T rectangles + scales) is rebuilt when the frame size or the window setting changes.
     // Bench-only logit injection addresses the slots of a CHUNK (tables [0, batch_max) of the selected set serve every chunk).
     void set_windows(int ww, int wh, double overlap) {
-        if (in_flight || ahead.reid_in_flight) fail("pipeline: set_windows while a look-ahead pass is in flight (consume it with a step first)");
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_windows while a look-ahead pass is in flight (consume it with a step first)");
         if (ww > 0 && wh <= 0) fail("pipeline: window %d x %d", ww, wh);
         if (ww > 0 && !(overlap >= 0)) fail("pipeline: window overlap %g", overlap);
         win_w = ww > 0 ? ww : 0; win_h = ww > 0 ? wh : 0; win_overlap = overlap;
@@ -195,43 +242,16 @@ public:
     // number of windows T of an h x w frame; 0 = the plain path (window mode off, or a frame smaller than the window: img_detect.py:68)
     int windows_for(int h, int w) {
         if (win_w <= 0 || (w < win_w && h < win_h)) return 0;
-        if (h == win_tab_h && w == win_tab_w) return win_T;
+        if (h == win_tab_h && w == win_tab_w) return win.T;
         const int ox = (int)(win_w * win_overlap), oy = (int)(win_h * win_overlap);
         std::vector<int> rects;
-        std::vector<float> scale;
         for (int x = 0; x < w; x += win_w)
-            for (int y = 0; y < h; y += win_h) {
-                const int th = std::min(y + win_h + oy, h) - y, tw = std::min(x + win_w + ox, w) - x;
-                rects.insert(rects.end(), {x, y, th, tw});
-                scale.push_back((float)((double)tw / net->img_w));      // resize_boxes: python-double ratio, fp32 multiply
-                scale.push_back((float)((double)th / net->img_h));
-            }
+            for (int y = 0; y < h; y += win_h)
+                rects.insert(rects.end(), {x, y, std::min(y + win_h + oy, h) - y, std::min(x + win_w + ox, w) - x});
         YDS_HIP(hipStreamSynchronize(net->stream));                 // a pass that reads the previous table may still run
-        win_rects.ensure(rects.size());
-        win_scale.ensure(scale.size());
-        YDS_HIP(hipMemcpy(win_rects.p, rects.data(), rects.size() * sizeof(int), hipMemcpyHostToDevice));
-        YDS_HIP(hipMemcpy(win_scale.p, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice));
-        win_tab_h = h; win_tab_w = w; win_T = (int)rects.size() / 4;
-        return win_T;
-    }
-    void launch_windows_tail(const uint8_t *frames_dev, int h, int w, int batch, int T, int k) {
-        const int slots = batch * T, nb_max = net->batch_max;
-        const size_t per_slot = (size_t)net->total_boxes * net->attrs;
-        if (win_pred.n < (size_t)slots * per_slot) {
-            YDS_HIP(hipStreamSynchronize(net->stream));             // (an NMS of the previous pass may still read the old buffer)
-            win_pred.alloc((size_t)slots * per_slot);
-        }
-        for (int slot0 = 0; slot0 < slots; slot0 += nb_max) {
-            const int nb = std::min(nb_max, slots - slot0);
-            launch_window_resize(frames_dev, h, w, win_rects.p, T, slot0, nb, net->input_view(nb), net->stream, frames_bgr);
-            net->forward_resized(nb);
-            launch_window_boxes(net->out.p, net->total_boxes, net->attrs, win_rects.p, win_scale.p, T, slot0, nb, win_pred.p, net->stream);
-        }
-        if (const int sl = slot_of(frames_dev); sl >= 0) { YDS_HIP(hipEventRecord(rd_det[sl], net->stream)); rd_det_set[sl] = true; }
-        YDS_HIP(hipEventRecord(e2[k], net->stream));
-        nms[k]->launch(win_pred.p, (size_t)T * per_slot, batch, T * net->total_boxes, net->attrs, conf, nms_thres, 1.f, 1.f, 300, net->stream,
-                       true, true);
-        YDS_HIP(hipEventRecord(e_nms[k], net->stream));
+        win.build(rects.data(), (int)rects.size() / 4, net->img_h, net->img_w, nullptr);
+        win_tab_h = h; win_tab_w = w;
+        return win.T;
     }
 
     // detections of one batch after NMS + class mask + p1p2Toxywh, ready for the extractor and the tracker
@@ -244,47 +264,44 @@ public:
         hipStream_t reid_on = nullptr;            // stream the ReID pass of this batch was enqueued on
     };
 
-    // wait for the detector pass + NMS enqueued in slot k, build the detection lists
-    void finish_detector(Dets &d, int k, const uint8_t *frames_dev, int batch) {
-        YDS_HIP(hipEventSynchronize(e_nms[k]));
-        if (nms[k]->needed(batch) > nms[k]->max_cand) {
+    // wait for the detector pass + NMS `p` (whole), build the detection lists
+    void finish_detector(Dets &d, const Pass &p) {
+        DetSlot &s = det[p.slot];
+        const int batch = p.batch;
+        YDS_HIP(hipEventSynchronize(s.e_nms));
+        if (s.nms->needed(batch) > s.nms->max_cand) {
             // More candidates than the workspace holds (the reference has no limit): grow it and redo this batch.  The
             // prefetched pass of the next batch may already have overwritten the predictions, so the detector runs again
             // after that pass has drained (its NMS results sit in the other slot's pinned buffers and stay valid).
             // Rare slow path; bench-only logit injection is not re-selected for it.
             YDS_HIP(hipStreamSynchronize(net->stream));
-            nms[k]->resize(nms[k]->needed(batch), nms[k]->frames);
-            const uint8_t *keep = in_flight;
-            const int keep_batch = in_flight_batch, keep_head = head_slot;
-            const bool keep_split = head_split;
-            launch_detector(frames_dev, last_h, last_w, batch, k);
-            in_flight = keep; in_flight_batch = keep_batch;      // the prefetched pass (if any) is still the one in flight
-            head_slot = keep_head; head_split = keep_split;
-            head_stale = true;                                   // ... but a head enqueued for the next pass has been overwritten
-            YDS_HIP(hipEventSynchronize(e_nms[k]));
+            s.nms->resize(s.nms->needed(batch), s.nms->frames);
+            Pass redo{p.frames, p.h, p.w, batch, p.slot};
+            launch_detector(redo);
+            if (pending.done == Pass::HEAD) pending.done = Pass::NOTHING;      // a head enqueued for the next pass has been overwritten
+            YDS_HIP(hipEventSynchronize(s.e_nms));
         }
         float ms01 = 0, ms12 = 0;
-        YDS_HIP(hipEventElapsedTime(&ms01, e0[k], e1[k]));
-        YDS_HIP(hipEventElapsedTime(&ms12, e1[k], e2[k]));
-        if (reid_in_pass[k]) {
+        YDS_HIP(hipEventElapsedTime(&ms01, s.e0, s.e1));
+        YDS_HIP(hipEventElapsedTime(&ms12, s.e1, s.e2));
+        if (s.reid_in_pass) {
             // serialized schedule: the ReID pass of the PREVIOUS batch ran on this stream between the head and the tail of this
             // pass (between e1 and e2); its own event pair takes it out of the detector's figure again, so that stage_us[1]
             // means the same under both schedules
             float msr = 0;
-            YDS_HIP(hipEventElapsedTime(&msr, e_r0[k], e_r1[k]));
+            YDS_HIP(hipEventElapsedTime(&msr, s.e_r0, s.e_r1));
             ms12 -= msr;
-            reid_in_pass[k] = false;
+            s.reid_in_pass = false;
         }
         stage_us[0] = ms01 * 1e3f; stage_us[1] = ms12 * 1e3f;
-        NmsWorkspace *nmsw = nms[k].get();
-        std::vector<float> det(300 * 6);
+        std::vector<float> det_rows(300 * 6);
         d.tlwh.clear(); d.payload.clear(); d.frame_of.clear();
         d.first.assign(batch + 1, 0); d.n_det.assign(batch, 0);
-        d.frames = frames_dev; d.batch = batch; d.reid_in_flight = false;
+        d.frames = p.frames; d.batch = batch; d.reid_in_flight = false;
         for (int b = 0; b < batch; ++b) {
-            d.n_det[b] = nmsw->collect(b, det.data(), 300);
+            d.n_det[b] = s.nms->collect(b, det_rows.data(), 300);
             for (int i = 0; i < d.n_det[b]; ++i) {
-                const float *r = &det[i * 6];
+                const float *r = &det_rows[i * 6];
                 bool keep = class_mask.empty();
                 for (int m : class_mask) keep |= (r[5] == (float)m);
                 if (!keep) continue;
@@ -298,9 +315,9 @@ public:
     // one ReID pass over the crops of the whole batch, asynchronous on the extractor's stream
     // `on` = the detector's stream: the pass is SERIALIZED with the detector passes (stream order) instead of sharing the CUs
     // with them from the extractor's own stream
-    // inside_pass >= 0: the pass sits between the head and the tail of the detector pass in NMS slot `inside_pass` (serialized
-    // schedule) and gets an event pair of its own (see finish_detector).
-    void launch_reid(Dets &d, int h, int w, hipStream_t on = nullptr, int inside_pass = -1) {
+    // inside: the pass sits between the head and the tail of that detector pass (serialized schedule) and gets an event pair of
+    // its own in the pass's DetSlot (see finish_detector).
+    void launch_reid(Dets &d, int h, int w, hipStream_t on = nullptr, const Pass *inside = nullptr) {
         d.reid_on = on ? on : reid->stream;
         if (!d.payload.empty()) {
             struct Swap { hipStream_t &s; hipStream_t keep; ~Swap() { s = keep; } } swap{reid->stream, reid->stream};
@@ -310,13 +327,13 @@ public:
             if (reid_last_on && reid_last_on != d.reid_on) YDS_HIP(hipStreamWaitEvent(d.reid_on, ev_reid_done, 0));
             reid->stream = d.reid_on;
             if (reid_last_on && reid_last_on != d.reid_on) reid->sync_before_regrow = reid_last_on;
-            if (inside_pass >= 0) YDS_HIP(hipEventRecord(e_r0[inside_pass], d.reid_on));
+            if (inside) YDS_HIP(hipEventRecord(det[inside->slot].e_r0, d.reid_on));
             reid->embed_multi_dev(d.frames, h, w, d.tlwh.data(), d.frame_of.data(), (int)d.payload.size(), frames_bgr);
             reid->sync_before_regrow = nullptr;
-            if (inside_pass >= 0) { YDS_HIP(hipEventRecord(e_r1[inside_pass], d.reid_on)); reid_in_pass[inside_pass] = true; }
+            if (inside) { YDS_HIP(hipEventRecord(det[inside->slot].e_r1, d.reid_on)); det[inside->slot].reid_in_pass = true; }
             YDS_HIP(hipEventRecord(ev_reid_done, d.reid_on));
             reid_last_on = d.reid_on;
-            if (const int sl = slot_of(d.frames); sl >= 0) { YDS_HIP(hipEventRecord(rd_reid[sl], d.reid_on)); rd_reid_set[sl] = true; }
+            stager.mark_read(d.frames, d.reid_on, FrameStager::REID);
         }
         d.reid_in_flight = true;
     }
@@ -324,51 +341,50 @@ public:
     // ---- stream schedule by measurement (round 5) ----------------------------------------------------------------------
     // Which schedule is faster is a property of the box (round 4: serialized +1.2 % on one, two-stream +1.3-3.1 % on four others),
     // so the pipeline times both on the caller's own steps, like conv_autotune times tile variants: steady-state steps (a next
-    // batch handed over, >= 256 crops) run in groups of TRIAL_SKIP + TRIAL_STEPS - serialized, two-stream, serialized, two-stream; the first
-    // step of a group absorbs the transition - the wall time of the three measured steps is taken between the returns of step(), and the
-    // schedule whose better group is shorter is kept (20 steps in all; round 6: see trial_step_done).
+    // batch handed over, >= 256 crops) run in groups of SKIP + STEPS - serialized, two-stream, serialized, two-stream; the first
+    // steps of a group absorb the transition - the wall time of the three measured steps is taken between the returns of step(), and the
+    // schedule whose better group is shorter is kept (20 steps in all; round 6: see step_done).
     // Results do not depend on the schedule (parity tests run both), so the trial is invisible to the caller.  One decision per
     // entry (frames resident in HBM / uploaded inside the step): their balance differs.
-    static constexpr int TRIAL_STEPS = 3, TRIAL_GROUPS = 4;      // groups alternate serialized / two-stream: S T S T
-    // unmeasured steps at the head of a group (round 6: two - with ONE the step after a switch still ran short on work the other
-    // schedule had left in flight, and serialized measured 7 % faster in the trial where the steady rates were equal)
-    static constexpr int TRIAL_SKIP = 2, TRIAL_LEN = TRIAL_SKIP + TRIAL_STEPS;
     struct Trial {
+        static constexpr int STEPS = 3, GROUPS = 4;             // groups alternate serialized / two-stream: S T S T
+        // unmeasured steps at the head of a group (round 6: two - with ONE the step after a switch still ran short on work the other
+        // schedule had left in flight, and serialized measured 7 % faster in the trial where the steady rates were equal)
+        static constexpr int SKIP = 2, LEN = SKIP + STEPS;
         int n = 0;                      // steady-state steps seen
         double t0 = 0, t_serial = 0, t_two = 0;   // t0: start of the running group; t_*: the better group of each schedule (3 measured steps)
         int decided = 0;                // 0 = measuring, 1 = serialized, -1 = two-stream
-    };
-    // Schedule of the NEXT ReID pass for an entry while its trial runs.  A group = TRIAL_SKIP transition steps + TRIAL_STEPS measured steps;
-    // the groups alternate (serialized first) and each schedule is measured twice, once earlier and once later in the run, so that
-    // the clock / temperature drift of the first second under load (the first group ran 7 % faster than steady state on one box)
-    // does not decide the comparison.
-    bool trial_wants_serial(const Trial &t) const { return t.decided ? t.decided > 0 : (t.n / TRIAL_LEN) % 2 == 0; }
-    // A group is timed by the wall clock between the RETURNS of step() - the steady-state period, which is what the schedules differ in
-    // (round 6 first timed the seconds spent INSIDE step(): that is not the period - the serialized schedule returns earlier relative to
-    // the device's work - and it preferred serialized by 8 % where the frame rates were equal; profiles/r06_bench_cfg3.json of that tree).
-    // Per schedule the BETTER of its two groups counts (round 6): one hiccup of the caller inside a three-step group - a slow
-    // decoder, a consumer rendering - no longer fixes the decision; a steadily slow caller stretches both schedules alike.
-    void trial_step_done(Trial &t) {
-        using clk = std::chrono::steady_clock;
-        if (t.decided) return;
-        const double now = std::chrono::duration<double>(clk::now().time_since_epoch()).count();
-        const int group = t.n / TRIAL_LEN, k = t.n % TRIAL_LEN;
-        if (k == TRIAL_SKIP - 1) t.t0 = now;                      // the group's transition steps have returned
-        if (k == TRIAL_LEN - 1) {
-            double &best = group % 2 == 0 ? t.t_serial : t.t_two;
-            best = best > 0 ? std::min(best, now - t.t0) : now - t.t0;
+        // Schedule of the NEXT ReID pass while the trial runs.  A group = SKIP transition steps + STEPS measured steps;
+        // the groups alternate (serialized first) and each schedule is measured twice, once earlier and once later in the run, so that
+        // the clock / temperature drift of the first second under load (the first group ran 7 % faster than steady state on one box)
+        // does not decide the comparison.
+        bool wants_serial() const { return decided ? decided > 0 : (n / LEN) % 2 == 0; }
+        // A group is timed by the wall clock between the RETURNS of step() - the steady-state period, which is what the schedules differ in
+        // (round 6 first timed the seconds spent INSIDE step(): that is not the period - the serialized schedule returns earlier relative to
+        // the device's work - and it preferred serialized by 8 % where the frame rates were equal; profiles/r06_bench_cfg3.json of that tree).
+        // Per schedule the BETTER of its two groups counts (round 6): one hiccup of the caller inside a three-step group - a slow
+        // decoder, a consumer rendering - no longer fixes the decision; a steadily slow caller stretches both schedules alike.
+        void step_done() {
+            if (decided) return;
+            const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+            const int group = n / LEN, k = n % LEN;
+            if (k == SKIP - 1) t0 = now;                            // the group's transition steps have returned
+            if (k == LEN - 1) {
+                double &best = group % 2 == 0 ? t_serial : t_two;
+                best = best > 0 ? std::min(best, now - t0) : now - t0;
+            }
+            ++n;
+            if (n == GROUPS * LEN) decided = t_serial <= t_two ? 1 : -1;
         }
-        ++t.n;
-        if (t.n == TRIAL_GROUPS * TRIAL_LEN) t.decided = t.t_serial <= t.t_two ? 1 : -1;
-    }
+    };
 
-    void step(const uint8_t *frames_dev, const uint8_t *next_frames_dev, int next_inject_set, int h, int w, int batch, int32_t *out6,
-              int cap, int32_t *counts, bool uploaded = false) {
+    void step(const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int batch, int32_t *out6, int cap, int32_t *counts,
+              bool uploaded = false) {
         using clk = std::chrono::steady_clock;
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<float, std::micro>(b - a).count(); };
         if (batch < 1 || batch > net->batch_max) fail("pipeline: batch %d outside [1,%d]", batch, net->batch_max);
         auto t_begin = clk::now();
-        last_h = h; last_w = w;
+        const int inject_set = std::exchange(next_inject_set, -1); // bench-only: applies to the pass this step enqueues for `next`
         const bool resumed = ahead.reid_in_flight && ahead.frames == frames_dev && ahead.batch == batch;
         // Serialized schedule (round 4).  The ReID pass of batch i and the detector pass of batch i+1 are both chip-filling
         // sequences of matrix-core kernels; from two streams they time-share the CUs, every launch stretched by the other
@@ -389,8 +405,6 @@ public:
         // A detector in half mode keeps two streams as well: its pass is half as long, the (default-arithmetic) ReID pass is 40 % of
         // the step, and its kernels are no longer power bound - running beside the ReID network's gains 3.5 % there (cfg2 --half,
         // alternating runs on one box: 2210-2214 serialized, 2287-2295 two-stream).
-        // Policy: serialize from 256 crops per batch when the frames are already in HBM and the detector runs the default arithmetic.
-        // yds_pipeline_set_schedule / YDS_PIPE_SERIAL=<crops> force a threshold for either entry, -1 = never.
         // Policy (round 5): yds_pipeline_set_schedule / YDS_PIPE_SERIAL=<crops> force a threshold (-1 = never serialize); otherwise a
         // ReID pass of >= 256 crops takes the schedule the trial measured faster on THIS box (serialized while none has been
         // decided: see Trial), smaller passes keep two streams.
@@ -398,26 +412,14 @@ public:
         Trial &trial = trials[uploaded ? 1 : 0];
         const int serial_min = schedule_min_crops != INT_MIN ? schedule_min_crops
                                : getenv("YDS_PIPE_SERIAL")  ? atoi(getenv("YDS_PIPE_SERIAL"))
-                               : (trial_wants_serial(trial) ? 256 : -1);
-        int next_slot = -1;
-        bool next_head_only = false;
-        auto launch_next = [&](bool head_only) {                    // detector (+ NMS) of the next batch goes in flight
+                               : (trial.wants_serial() ? 256 : -1);
+        // detector (+ NMS) of the next batch goes in flight, in the DetSlot this batch's pass does not use
+        auto launch_next = [&](int this_slot, bool head_only) {
+            pending = next_frames_dev ? Pass{next_frames_dev, h, w, batch, this_slot ^ 1} : Pass{nullptr, 0, 0, 0, this_slot};
             if (!next_frames_dev) return;
-            if (next_inject_set >= 0) net->select_injection_set(next_inject_set);      // bench-only logit injection
-            if (head_only) {
-                head_stale = false;
-                launch_detector_head(next_frames_dev, h, w, batch, -1, true);
-                next_head_only = true;
-            } else {
-                launch_detector(next_frames_dev, h, w, batch);
-            }
-            next_slot = in_flight_slot;
-        };
-        auto launch_next_tail = [&]() {
-            if (!next_head_only) return;
-            if (head_stale) launch_detector_head(next_frames_dev, h, w, batch, head_slot, true);    // (overwritten by a redone pass)
-            launch_detector_tail(next_frames_dev, h, w, batch);
-            next_head_only = false;
+            if (inject_set >= 0) net->select_injection_set(inject_set);
+            if (head_only) launch_detector_head(pending, true);
+            else launch_detector(pending);
         };
         auto copy_feats = [&]() {
             // the tracker reads its own copy so that the extractor can start on the next batch during the association
@@ -432,21 +434,20 @@ public:
             ahead.reid_in_flight = false;
             serial = cur.reid_on == net->stream;
             copy_feats();                                           // (behind that ReID pass, ahead of the next detector pass)
-            launch_next(false);
+            launch_next(pending.slot, false);
         } else {
             ahead.reid_in_flight = false;
-            if (in_flight != frames_dev || in_flight_batch != batch) launch_detector(frames_dev, h, w, batch);
-            const int slot = in_flight_slot;
-            in_flight = nullptr;
-            launch_next(serial_min >= 0);                           // enqueued BEFORE the host waits for this batch's NMS
-            finish_detector(cur, slot, frames_dev, batch);
+            Pass now = pending.is_whole(frames_dev, batch) ? pending : Pass{frames_dev, h, w, batch, pending.slot ^ 1};
+            launch_detector(now);
+            launch_next(now.slot, serial_min >= 0);                 // enqueued BEFORE the host waits for this batch's NMS
+            finish_detector(cur, now);
             serial = serial_min >= 0 && (int)cur.payload.size() >= std::max(serial_min, 1);
             if (serial) {
-                launch_reid(cur, h, w, net->stream, next_head_only ? head_slot : -1);
+                launch_reid(cur, h, w, net->stream, pending.open() ? &pending : nullptr);
                 copy_feats();
-                launch_next_tail();
+                if (pending.open()) launch_detector(pending, true);
             } else {
-                launch_next_tail();
+                if (pending.open()) launch_detector(pending, true); // (the head again first if a redone pass overwrote it)
                 launch_reid(cur, h, w);
                 copy_feats();
             }
@@ -463,10 +464,9 @@ public:
         // Crowded scenes (the association of a batch takes long and is all small latency-bound kernels and host syncs):
         // before associating, finish the next batch's detector + NMS and start its ReID pass, so that the matrix
         // cores stay busy underneath.  Sparse scenes keep the simpler order (the detector alone covers the association).
-        static const int deep_min = getenv("YDS_PIPE_DEEP_MIN") ? atoi(getenv("YDS_PIPE_DEEP_MIN")) : 64;    // detections per frame
         if (next_frames_dev && D_all >= deep_min * batch) {
-            finish_detector(ahead, next_slot, next_frames_dev, batch);
-            in_flight = nullptr;
+            finish_detector(ahead, pending);
+            pending.frames = nullptr;                               // consumed: its detections are in `ahead`
             launch_reid(ahead, h, w, serial ? net->stream : nullptr);
         }
         // association of the whole batch on the group's stream, one host synchronisation: frame b advances tracker stream_of[b] (a
@@ -479,7 +479,7 @@ public:
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
-        if (!forced && next_frames_dev && D_all >= 256) trial_step_done(trial);
+        if (!forced && next_frames_dev && D_all >= 256) trial.step_done();
     }
 
     // Several video streams through one pipeline (yds_pipeline_create_multi): one tracker per stream, advanced together by `group`;
@@ -501,48 +501,40 @@ public:
     std::vector<int32_t> stream_of;
     float conf, nms_thres;
     std::vector<int32_t> class_mask;
-    std::unique_ptr<NmsWorkspace> nms[2];
-    int in_flight_slot = 0;
-    int last_h = 0, last_w = 0;
-    static constexpr int NSTAGE = 3;
-    DevBuf<uint8_t> stage[NSTAGE];            // device copies of host frames (step_host / prefetch_host)
-    const uint8_t *stage_host[NSTAGE] = {nullptr, nullptr, nullptr};
-    bool up_pending[NSTAGE] = {false, false, false};
-    int stage_ttl[NSTAGE] = {0, 0, 0};        // step_host calls an unconsumed slot may still survive
-    hipEvent_t rd_det[NSTAGE] = {}, rd_reid[NSTAGE] = {};     // recorded behind the last kernels that read a slot
-    bool rd_det_set[NSTAGE] = {false, false, false}, rd_reid_set[NSTAGE] = {false, false, false};
-    int cur_k = -1, next_k = -1;
-    hipEvent_t up_done[NSTAGE] = {};
-    hipStream_t copy_stream = nullptr;
-    int stage_turn = 0;
+    const int deep_min;                           // crowded-scene order from this many detections per frame (YDS_PIPE_DEEP_MIN, read per pipeline)
+    DetSlot det[2];
+    Pass pending;                   // the pass enqueued for the next call (whole between steps); a fresh pass takes the other DetSlot
+    FrameStager stager;             // device copies of host frames (step_host / prefetch_host)
     Dets cur, ahead;                // this batch; the next batch when its ReID pass was started early
     DevBuf<float> feat_cur;
-    int next_inject_set = -1;      // bench-only: injection set of the prefetched detector pass
-    const uint8_t *in_flight = nullptr;
-    int in_flight_batch = 0;
-    hipEvent_t e0[2] = {}, e1[2] = {}, e2[2] = {}, e_nms[2] = {};
+    int next_inject_set = -1;      // bench-only: injection set of the next prefetched detector pass (step() takes it)
     hipEvent_t ev_feat = nullptr;      // this batch's embeddings have been copied for the tracker
     int schedule_min_crops = INT_MIN;  // yds_pipeline_set_schedule: crops per batch from which the ReID pass is serialized (INT_MIN: policy)
     Trial trials[2];                   // schedule trial per entry: [0] frames resident in HBM, [1] uploaded inside the step
     hipEvent_t ev_reid_done = nullptr; // behind the last ReID pass, on the stream it ran on
     hipStream_t reid_last_on = nullptr;
-    hipEvent_t e_r0[2] = {}, e_r1[2] = {};     // around a ReID pass enqueued inside the detector pass of NMS slot k
-    bool reid_in_pass[2] = {false, false};
     bool last_serial = false;          // schedule of the last step
     bool frames_bgr = false;           // yds_pipeline_set_frame_order: the frames handed over hold B, G, R bytes (a decoder's order)
-    int head_slot = 0;                 // NMS slot of the pass whose head was enqueued last
-    bool head_split = false, head_stale = false;
     float stage_us[5] = {0, 0, 0, 0, 0};
     // window mode (set_windows): setting, the table on the device and the frame size it was built for, the shifted predictions
-    int win_w = 0, win_h = 0, win_T = 0, win_tab_h = 0, win_tab_w = 0;
+    int win_w = 0, win_h = 0, win_tab_h = 0, win_tab_w = 0;
     double win_overlap = 0;
-    DevBuf<int> win_rects;
-    DevBuf<float> win_scale, win_pred;
+    WindowTable win;
+    DevBuf<float> win_pred;
 };
 
 }  // namespace yds
 
 struct yds_pipe { yds::Pipeline *p; };
+
+// the four step entries: multi_entry = one that names the stream of each frame; host = frames in host memory (uploaded by the pipeline)
+static void pipeline_step(yds_pipe *p, bool multi_entry, bool host, const uint8_t *frames, const uint8_t *next_frames, int h, int w, int n,
+                          const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host) {
+    if (multi_entry) p->p->set_streams(stream_of_frame, n);
+    else if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi%s", host ? "_host" : "");
+    if (host) p->p->step_host(frames, next_frames, h, w, n, out6_host, cap, counts_host);
+    else p->p->step(frames, next_frames, h, w, n, out6_host, cap, counts_host);
+}
 
 extern "C" {
 
@@ -573,33 +565,25 @@ void yds_pipeline_destroy(yds_pipe *p) {
 int yds_pipeline_step(yds_pipe *p, const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int batch, int32_t *out6_host,
                       int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi");
-    p->p->step(frames_dev, next_frames_dev, p->p->next_inject_set, h, w, batch, out6_host, cap, counts_host);
-    p->p->next_inject_set = -1;
+    pipeline_step(p, false, false, frames_dev, next_frames_dev, h, w, batch, nullptr, out6_host, cap, counts_host);
     YDS_API_END
 }
 int yds_pipeline_step_host(yds_pipe *p, const uint8_t *frames_host, const uint8_t *next_frames_host, int h, int w, int batch,
                            int32_t *out6_host, int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi_host");
-    p->p->step_host(frames_host, next_frames_host, p->p->next_inject_set, h, w, batch, out6_host, cap, counts_host);
-    p->p->next_inject_set = -1;
+    pipeline_step(p, false, true, frames_host, next_frames_host, h, w, batch, nullptr, out6_host, cap, counts_host);
     YDS_API_END
 }
 int yds_pipeline_step_multi(yds_pipe *p, const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int n_frames,
                             const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    p->p->set_streams(stream_of_frame, n_frames);
-    p->p->step(frames_dev, next_frames_dev, p->p->next_inject_set, h, w, n_frames, out6_host, cap, counts_host);
-    p->p->next_inject_set = -1;
+    pipeline_step(p, true, false, frames_dev, next_frames_dev, h, w, n_frames, stream_of_frame, out6_host, cap, counts_host);
     YDS_API_END
 }
 int yds_pipeline_step_multi_host(yds_pipe *p, const uint8_t *frames_host, const uint8_t *next_frames_host, int h, int w, int n_frames,
                                  const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host) {
     YDS_API_BEGIN
-    p->p->set_streams(stream_of_frame, n_frames);
-    p->p->step_host(frames_host, next_frames_host, p->p->next_inject_set, h, w, n_frames, out6_host, cap, counts_host);
-    p->p->next_inject_set = -1;
+    pipeline_step(p, true, true, frames_host, next_frames_host, h, w, n_frames, stream_of_frame, out6_host, cap, counts_host);
     YDS_API_END
 }
 int yds_pipeline_prefetch_host(yds_pipe *p, const uint8_t *frames_host, int h, int w, int batch) {
