@@ -1529,8 +1529,178 @@ def _ref_darknet_profile(ns, cfg_text, img_size, seed, obj_bias):
     return model, torch
 
 
+# ------------------------------------------------------------------------------------------ association thresholds
+THRESHOLD_PARAMS = dict(max_dist=0.3, nn_budget=30, n_init=3, max_iou_distance=0.7, max_age=30)
 
-ALL = dict(long_stream=gen_long_stream, wide=gen_wide_range, wide_mish=gen_wide_mish, rect=gen_rect, video_detect=gen_video_detect, action=gen_action, bench_shape=gen_bench_shape, options=gen_track_options, tiled=gen_tiled, cfg_parse=gen_cfg_parse, mini=gen_mini_darknet, tiny416=gen_tiny416, full608=gen_full608,
+
+def pm_feature(signs):
+    """512-d feature with 16 non-zero entries of +-1 (norm 4; products of two normalised rows are +-1/16: every partial sum of a
+    dot product is exact in fp32)."""
+    f = np.zeros(512, F32)
+    f[:16] = np.asarray(signs, F32)
+    return f
+
+
+def pm_patterns():
+    """16 mutually orthogonal +-1 rows (Sylvester-Hadamard): cosine cost exactly 1 between any two, exactly 0 with itself."""
+    h = np.ones((1, 1), np.int8)
+    for _ in range(4):
+        h = np.block([[h, h], [h, -h]])
+    return h
+
+
+class _CostSpy:
+    """Pass-through wrappers (like MarginSpy) that keep, per frame, what the reference's association computed BEFORE its
+    thresholds: the appearance cost (NearestNeighborDistanceMetric.distance), the gating distance and the IOU cost."""
+
+    def __init__(self, ns):
+        self.ns, self.t, self.seen = ns, 0, {}
+
+    def __enter__(self):
+        ns, spy = self.ns, self
+        NN, KF, iou = ns.nn_matching.NearestNeighborDistanceMetric, ns.kalman_filter.KalmanFilter, ns.iou_matching
+        self._orig = (NN.distance, KF.gating_distance, iou.iou_cost)
+        o_dist, o_gd, o_iou = self._orig
+
+        def keep(name, v):
+            spy.seen[(spy.t, name)] = v.detach().cpu().numpy().copy()
+            return v
+        NN.distance = lambda self_, *a, **k: keep("cos", o_dist(self_, *a, **k))
+        KF.gating_distance = lambda self_, *a, **k: keep("gate", o_gd(self_, *a, **k))
+        iou.iou_cost = lambda *a, **k: keep("iou", o_iou(*a, **k))
+        return self
+
+    def __exit__(self, *exc):
+        ns = self.ns
+        ns.nn_matching.NearestNeighborDistanceMetric.distance, ns.kalman_filter.KalmanFilter.gating_distance, ns.iou_matching.iou_cost = self._orig
+
+
+def _threshold_run(ns, frames, params):
+    """frames: [(tlwh [D,4] fp32, signs [D,16] int8)]; the trace of run_reference_trace plus the inputs and the spied costs."""
+    import types
+    spy = _CostSpy(ns)
+
+    def boxes_of(t, feats=False):
+        spy.t = t
+        tlwh, signs = frames[t]
+        if feats:
+            return np.stack([pm_feature(s) for s in signs], 0)
+        return np.arange(len(tlwh)), np.asarray(tlwh, F32).reshape(-1, 4)
+    with spy:
+        rec = run_reference_trace(ns, types.SimpleNamespace(H=1080, W=1920), len(frames), params, boxes_of=boxes_of)
+    for t, r in enumerate(rec):
+        r.pop("mean")
+        r["tlwh"] = np.asarray(frames[t][0], F32).reshape(-1, 4)
+        r["sign16"] = np.asarray(frames[t][1], np.int8).reshape(-1, 16)
+        for name in ("cos", "gate", "iou"):
+            if (t, name) in spy.seen:
+                r[name] = spy.seen[(t, name)]
+    return rec
+
+
+def _ulps(v):
+    v = F32(v)
+    return dict(under=float(np.nextafter(v, F32(0))), on=float(v), over=float(np.nextafter(v, F32(np.inf))))
+
+
+def threshold_id_sets(rec):
+    return frozenset(int(i) for r in rec for i in r["ids"])
+
+
+def gen_assoc_thresholds(ns):
+    """Scripted scenes of 3-8 frames that put ONE decision of the association exactly on (or a stated margin from) its threshold,
+    run through the real DeepSort.update on either side of it: max_dist, max_iou_distance, the chi-square gate, the eviction of
+    the oldest gallery row, the tracker-side NMS.  Keys: <scene>.<run>.param_<name>, <scene>.<run>.n_frames,
+    <scene>.<run>.f<t>_<field>; fields as in the traces plus the inputs (tlwh, sign16: the first 16 feature columns, the rest
+    are zero) and the costs the reference computed in front of its thresholds (cos, gate, iou)."""
+    from oracle import tracker as otrk
+    P = THRESHOLD_PARAMS
+    runs = {}
+    ones = np.ones(16, np.int8)
+    flip4 = ones.copy()
+    flip4[12:] = -1                                                    # agrees with `ones` on 12 of 16: cosine cost exactly 0.5
+    narrow = np.array([[100, 100, 8, 128]], F32)                       # w/h = 1/16; a 9 px step already takes the IOU to 0
+
+    def shifted(box, dx):
+        b = np.array(box, F32, copy=True)
+        b[:, 0] += F32(dx)
+        return b
+
+    def add(scene, run, frames, params):
+        rec = _threshold_run(ns, frames, params)
+        runs[(scene, run)] = (rec, params)
+        return rec
+
+    # -- max_dist: a confirmed track (frames 0-2, feature `ones`), then the same person 16 px to the right carrying `flip4`
+    frames = [(narrow, [ones])] * 3 + [(shifted(narrow, 16), [flip4])] * 2
+    for run, thr in _ulps(0.5).items():
+        rec = add("max_dist", run, frames, dict(P, max_dist=thr))
+        assert rec[3]["cos"].tobytes() == F32(0.5).tobytes() and rec[3]["cos"].shape == (1, 1)
+        assert rec[3]["gate"][0, 0] < 3.0
+        assert len(rec[3]["matches"]) == (0 if run == "under" else 1), run
+        if run == "under":
+            assert rec[3]["iou"][0, 0] == 1.0                          # the IOU stage cannot rescue it: the new id is born
+    # -- max_iou_distance: a tentative track from an integer box with w/h = 1/2, then an integer box: exact areas
+    frames = [(np.array([[100, 100, 32, 64]], F32), [ones]), (np.array([[108, 116, 32, 64]], F32), [ones]),
+              (np.array([[108, 116, 32, 64]], F32), [ones])]
+    c = _threshold_run(ns, frames, P)[1]["iou"]
+    assert c.shape == (1, 1) and c[0, 0] == F32(1) - F32(1225) / F32(2871)
+    for run, thr in _ulps(c[0, 0]).items():
+        rec = add("max_iou_distance", run, frames, dict(P, max_iou_distance=thr))
+        assert rec[1]["iou"].tobytes() == c.tobytes()
+        assert len(rec[1]["matches"]) == (0 if run == "under" else 1), run
+    # -- gate: the confirmed track again, the detection moved so that d^2 sits 2e-3 (relative) inside / outside chi2inv95[2]
+    m, cov = otrk.kf_initiate(otrk.tlwh_to_xyah(narrow)[0])
+    for _ in range(2):
+        m, cov = otrk.kf_update(*otrk.kf_predict(m, cov), otrk.tlwh_to_xyah(narrow))
+    s_post = float(otrk.kf_project(m, cov)[1][0, 0, 0])                # what a gate on the posterior would divide by
+    s_pred = float(otrk.kf_project(*otrk.kf_predict(m, cov))[1][0, 0, 0])
+    chi2 = float(ns.kalman_filter.chi2inv95[2])
+    for run, rel in (("inside", -2e-3), ("outside", 2e-3)):
+        dx = float(np.sqrt(chi2 * (1 + rel) * s_pred))
+        rec = add("gate", run, [(narrow, [ones])] * 3 + [(shifted(narrow, dx), [ones])] * 2, P)
+        d2 = float(rec[3]["gate"][0, 0])
+        assert abs(d2 / chi2 - (1 + rel)) < 5e-4, (run, d2)
+        assert dx * dx / s_post > 2 * chi2                             # a gate on the posterior covariance rejects both runs
+        assert rec[3]["cos"][0, 0] == 0.0
+        assert len(rec[3]["matches"]) == (1 if run == "inside" else 0), run
+    # -- ring eviction: nn_budget 5, a new orthogonal feature every frame (the IOU stage keeps the track); at frame 7 the ring
+    #    holds the features of frames 2..6 and the person reappears 16 px away with the oldest kept / the newest evicted one
+    had = pm_patterns()
+    for run, k in (("kept", 2), ("evicted", 1)):
+        frames = [(narrow, [had[t]]) for t in range(7)] + [(shifted(narrow, 16), [had[k]])]
+        rec = add("ring", run, frames, dict(P, nn_budget=5))
+        assert rec[7]["cos"].shape == (1, 1) and rec[7]["cos"][0, 0] == (0.0 if run == "kept" else 1.0), run
+        assert all(rec[t]["cos"][0, 0] == 1.0 for t in range(3, 7))
+        assert len(rec[7]["matches"]) == (1 if run == "kept" else 0), run
+    # -- tracker-side NMS: inter / area exactly 0.5 under the +1 convention (5 * 10 / (10 * 10))
+    pair = np.array([[0, 0, 9, 9], [5, 0, 9, 9]], F32)
+    for run, thr in (("under", _ulps(0.5)["under"]), ("on", 0.5)):
+        rec = add("nms", run, [(pair, [ones, flip4])] * 4, dict(P, nms_max_overlap=thr))
+        assert len(rec[0]["ids"]) == (1 if run == "under" else 2), run
+    for scene in ("max_dist", "max_iou_distance", "gate", "ring", "nms"):
+        sets = {threshold_id_sets(rec) for (s, _), (rec, _) in runs.items() if s == scene}
+        assert len(sets) >= 2, scene                                   # the outcome really differs across the threshold
+    # one flat store (an .npz entry costs ~250 bytes; 1200 small arrays would be 160 KiB): see the loader in
+    # tests/test_gpu_assoc_thresholds.py
+    names = sorted({k for rec, _ in runs.values() for r in rec for k in r})
+    pnames = sorted({k for _, p in runs.values() for k in p})
+    index, store = [], {0: [], 1: []}
+    for ri, (rec, params) in enumerate(runs.values()):
+        for t, r in enumerate(rec):
+            for k, v in r.items():
+                v = np.asarray(v)
+                kind = 0 if v.dtype.kind in "iu" else 1
+                assert v.ndim in (1, 2) and (kind == 0 or v.dtype == F32)
+                index.append((ri, t, names.index(k), kind, sum(len(x) for x in store[kind]), v.shape[0], v.shape[1] if v.ndim == 2 else 0))
+                store[kind].append(v.reshape(-1))
+    _save("assoc_thresholds", runs=np.array([f"{s}.{r}" for s, r in runs]), fields=np.array(names), param_names=np.array(pnames),
+          params=np.array([[p.get(k, np.nan) for k in pnames] for _, p in runs.values()], np.float64),
+          index=np.array(index, np.int32), ints=np.concatenate(store[0]).astype(np.int32), floats=np.concatenate(store[1]).astype(F32))
+
+
+
+ALL = dict(assoc_thresholds=gen_assoc_thresholds, long_stream=gen_long_stream, wide=gen_wide_range, wide_mish=gen_wide_mish, rect=gen_rect, video_detect=gen_video_detect, action=gen_action, bench_shape=gen_bench_shape, options=gen_track_options, tiled=gen_tiled, cfg_parse=gen_cfg_parse, mini=gen_mini_darknet, tiny416=gen_tiny416, full608=gen_full608,
            nms=gen_nms, plumbing=gen_detect_plumbing, reid=gen_reid, kalman=gen_kalman,
            traces=gen_track_traces, cfg_files=gen_cfg_files, signatures=gen_signatures)
 

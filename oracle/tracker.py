@@ -242,6 +242,7 @@ class TrackerOracle:
             means = np.concatenate([self.tracks[i].mean for i in confirmed], 0)
             covs = np.concatenate([self.tracks[i].cov for i in confirmed], 0)
             gate = kf_gating_distance(means, covs, xyah, True)
+            dbg["cost_a_raw"], dbg["gate"] = cost.copy(), gate
             cost[gate > F32(CHI2_2DOF)] = INFTY_COST
             matches_a, um_t_a, um_d, c1, _ = min_cost_matching(cost, self.max_dist, confirmed, det_idx)
             dbg["cost_a"] = c1
@@ -253,6 +254,7 @@ class TrackerOracle:
             cand = np.stack([tlwh[i] for i in um_d], 0)
             bbs = np.stack([self.tracks[i].to_tlwh() for i in iou_cand], 0)
             cost = (F32(1.) - iou_matrix(bbs, cand)).astype(F32)
+            dbg["cost_b_raw"] = cost.copy()
             for r, k in enumerate(iou_cand):
                 if self.tracks[k].tsu > 1:
                     cost[r, :] = INFTY_COST

@@ -180,3 +180,29 @@ def test_reid_on_wide_range_weights():
     np.testing.assert_allclose(feats, g["reid_feats"], rtol=RTOL, atol=1e-5)
     d = 1.0 - g["reid_feats"] @ g["reid_feats"].T
     assert d[~np.eye(8, dtype=bool)].min() > 1e-3                      # the embeddings still tell the crops apart
+
+
+def test_threshold_fixture_conditions_and_oracle_replay():
+    """tests/golden/assoc_thresholds.npz: every decision threshold of the association with the reference run on either side of it
+    (oracle/gen_golden.py gen_assoc_thresholds).  The fixture's own conditions, then the oracle must take the reference's side."""
+    from test_gpu_assoc_thresholds import check_fixture_conditions, check_frame, feats_of, threshold_runs
+    runs = threshold_runs()
+    check_fixture_conditions(runs)
+    for (scene, run), r in runs.items():
+        trk = otrk.TrackerOracle(**r["params"])
+        for t, fr in enumerate(r["frames"]):
+            if "nms_order" in fr:
+                trk.nms_order = fr["nms_order"]
+            out = trk.update(fr["tlwh"], feats_of(fr), (np.arange(len(fr["tlwh"])) % 3 * 2).astype(F32))
+            out = np.array(out, dtype=np.int32).reshape(-1, 6)
+            check_frame(fr, trk.debug["matches"], trk.debug["unmatched_tracks"], trk.debug["unmatched_detections"], trk.state(), (scene, run, t))
+            ref = fr["out"]
+            assert out.shape == ref.shape and np.array_equal(out[:, 4:], ref[:, 4:]), (scene, run, t)
+            assert np.abs(out[:, :4] - ref[:, :4]).max(initial=0) <= 1, (scene, run, t)
+            # the costs in front of the thresholds: the oracle's own bits where the construction is exact
+            if scene in ("max_dist", "ring") and "cos" in fr:
+                assert trk.debug["cost_a_raw"].tobytes() == fr["cos"].tobytes(), (scene, run, t)
+            if scene == "max_iou_distance" and "iou" in fr:
+                assert trk.debug["cost_b_raw"].tobytes() == fr["iou"].tobytes(), (scene, run, t)
+            if scene == "gate" and "gate" in fr:
+                np.testing.assert_allclose(trk.debug["gate"], fr["gate"], rtol=1e-5)
