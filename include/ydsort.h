@@ -90,6 +90,13 @@ int yds_darknet_forward_f32(yds_net *, const float *nchw_host, int batch, float 
 int yds_darknet_forward_u8(yds_net *, const uint8_t *rgb_hwc_host, int h, int w, int batch,
                            float *out_host_or_null);
 int yds_darknet_forward_u8_dev(yds_net *, const uint8_t *rgb_hwc_dev, int h, int w, int batch);
+/* yds_darknet_forward_u8_dev for frames of DIFFERENT sizes in one batch: frame i is frame_hw[2i] x frame_hw[2i+1] pixels at
+ * rgb_hwc_dev + frame_off[i], somewhere inside a device buffer of frames_bytes bytes (frames may lie in any order, with gaps, at odd
+ * offsets).  Each frame is stretched to the model size by the front end's own rule for its size (equal sizes copy, exact 2x takes the
+ * area mean, everything else is bilinear).  A frame with h or w < 1, or one that ends past frames_bytes, is refused before anything
+ * is enqueued.  frame_off / frame_hw are host arrays, copied before the call returns. */
+int yds_darknet_forward_u8_mixed_dev(yds_net *, const uint8_t *rgb_hwc_dev, const uint64_t *frame_off, const int32_t *frame_hw /* [batch,2] */,
+                                     size_t frames_bytes, int batch);
 /* device copy of the frames the last yds_darknet_forward_u8 call uploaded (valid until the next one; NULL if none):
  * lets DeepSort.update crop from it instead of uploading the same frame again (video_detect.py:134-149 hands the same
  * frame to the detector and to the tracker) */
@@ -150,6 +157,11 @@ int yds_reid_embed_dev(yds_reid *, const uint8_t *frame_rgb_dev, int h, int w, c
 const float *yds_reid_features_dev(yds_reid *);   /* [max_crops,512] device buffer written by embed */
 int yds_reid_preprocess(yds_reid *, const uint8_t *frame_rgb_host, int h, int w, const float *tlwh_host,
                         int D, float *nchw_host);                                  /* parity tests */
+/* parity tests: the crop front end of a pipeline step whose frames differ in size - n_frames device frames laid out as in
+ * yds_darknet_forward_u8_mixed_dev (same refusals), detection d cut from frame frame_of_host[d] and clamped to THAT frame's size;
+ * nchw_host receives the [D,3,128,64] crops */
+int yds_reid_preprocess_mixed(yds_reid *, const uint8_t *frames_rgb_dev, const uint64_t *frame_off, const int32_t *frame_hw /* [n_frames,2] */,
+                              int n_frames, size_t frames_bytes, const float *tlwh_host, const int32_t *frame_of_host, int D, float *nchw_host);
 int yds_reid_forward_f32(yds_reid *, const float *nchw_host, int D, float *out_host);  /* parity tests */
 
 /* ---- tracker: DeepSort.update minus the extractor -----------------------------------------
@@ -237,7 +249,7 @@ int yds_pipeline_step_host(yds_pipe *, const uint8_t *frames_host, const uint8_t
                            int batch, int32_t *out6_host, int cap, int32_t *counts_host);
 /* Many video streams through ONE pipeline: VideoDetector.detect hot glue (video_detect.py:134-157) x n_streams, with a
  * DeepSort.clone() per stream (deep_sort/deep_sort.py:41-44: one tracker per stream, the extractor shared).  trks: one tracker
- * handle per stream, each given once.  A step takes n_frames frames of one h x w size; frame i belongs to stream
+ * handle per stream, each given once.  A step takes n_frames frames of one h x w size (yds_pipeline_step_multi_mixed: of any sizes); frame i belongs to stream
  * stream_of_frame[i] in [0, n_streams); a stream's frames appear in time order (a stream may have none).  The detector, NMS, class
  * mask, crops and ReID run once over all n_frames frames (next_frames_dev: look-ahead as in yds_pipeline_step - it must hold
  * n_frames frames too); the association advances every stream's tracker in the same launches: a stream's k-th frame of the
@@ -252,6 +264,24 @@ int yds_pipeline_step_multi(yds_pipe *, const uint8_t *frames_dev, const uint8_t
 /* Same with the frames in HOST memory: the semantics of yds_pipeline_step_host. */
 int yds_pipeline_step_multi_host(yds_pipe *, const uint8_t *frames_host, const uint8_t *next_frames_host, int h, int w, int n_frames,
                                  const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host);
+/* yds_pipeline_step_multi for cameras of DIFFERENT frame sizes in one step: frame i is frame_hw[2i] x frame_hw[2i+1] pixels at
+ * frames_dev + frame_off[i] inside a device buffer of frames_bytes bytes (host arrays, copied by the call).  Nothing behind the front
+ * end needs one size: every frame is stretched to the model size by its own rule, NMS scales a frame's boxes by that frame's own ratio
+ * (resize_boxes, model_build.py:12-19), a crop is clamped to and cut from its own frame, and a stream's tracker sees boxes in the
+ * pixels of its own frames.  Per stream the results are those of the stream stepped alone at its own size.  next_frames_dev (may be
+ * NULL): the next call's frames in a second buffer with the SAME layout - the same n_frames, offsets and sizes (a steady camera set)
+ * and at least frames_bytes bytes; pass NULL when the layout changes.  A look-ahead pass is reused only when pointer, count and layout
+ * all match.  Refused before anything is enqueued: h or w < 1, a frame that ends past frames_bytes, n_frames outside [1, batch_max],
+ * and any mixed layout while window mode is set (yds_pipeline_set_windows cuts frames of one size).  A layout of equal sizes at
+ * offsets i * h * w * 3 gives exactly the rows of yds_pipeline_step_multi. */
+int yds_pipeline_step_multi_mixed(yds_pipe *, const uint8_t *frames_dev, const uint8_t *next_frames_dev, const uint64_t *frame_off,
+                                  const int32_t *frame_hw /* [n_frames,2] */, size_t frames_bytes, int n_frames,
+                                  const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host);
+/* Same with the frames in HOST memory, packed in one block: the bytes [0, max(frame_off + size)) of frames_host (and of
+ * next_frames_host) are uploaded as yds_pipeline_step_host does.  yds_pipeline_prefetch_host announces uniform batches only. */
+int yds_pipeline_step_multi_mixed_host(yds_pipe *, const uint8_t *frames_host, const uint8_t *next_frames_host, const uint64_t *frame_off,
+                                       const int32_t *frame_hw /* [n_frames,2] */, size_t frames_bytes, int n_frames,
+                                       const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host);
 /* Starts the upload of a batch the caller will hand to yds_pipeline_step_host LATER (as `next_frames_host` of the following call
  * or as `frames_host` of the one after): the detector stream runs a whole pass ahead of the host, so a copy that only starts
  * when a batch becomes `next` arrives ~1.7 ms late per 100 MB; a decoder that is one more batch ahead (FileVideoStream keeps a

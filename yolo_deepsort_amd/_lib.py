@@ -141,6 +141,10 @@ SIGNATURES = {
     "yds_overlay_tracks_bgr": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "yds_pipeline_set_frame_order": (_I, [_P, _I]),
     "yds_pipeline_set_windows": (_I, [_P, _I, _I, C.c_double]),
+    "yds_darknet_forward_u8_mixed_dev": (_I, [_P, _P, _P, _P, _SZ, _I]),
+    "yds_reid_preprocess_mixed": (_I, [_P, _P, _P, _P, _I, _SZ, _P, _P, _I, _P]),
+    "yds_pipeline_step_multi_mixed": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
+    "yds_pipeline_step_multi_mixed_host": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
 }
 
 _lib = None

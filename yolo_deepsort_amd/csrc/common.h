@@ -146,6 +146,12 @@ void launch_inject_batch(const View &head, int batch, const float *table_dev, co
                          int num_classes, float logit, hipStream_t s);
 // stretch-resize uint8 HWC frames to NHWC4 fp32 in [0,1] (4th channel 0)
 void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y, hipStream_t s, bool bgr = false);   // bgr: frames in a decoder's B, G, R byte order
+// One frame of a step whose frames differ in size (the "mixed" entries): h x w pixels at frames + off, rows w * 3 bytes apart.
+struct FrameGeom { uint64_t off; int32_t h, w; };
+// (off[n], h[n], w[n]) from the C ABI's two arrays; refuses h or w < 1 and a frame that ends past `frames_bytes`
+std::vector<FrameGeom> checked_layout(const uint64_t *frame_off, const int32_t *frame_hw, int n, size_t frames_bytes);
+// launch_resize_u8 with the geometry of every frame read from `geom` (n entries, device-readable for as long as the kernel may run)
+void launch_resize_u8_frames(const uint8_t *frames, const FrameGeom *geom, int n, const View &y, hipStream_t s, bool bgr = false);
 // sliding windows: slots [slot0, slot0 + n) of B frames x T windows (slot = b * T + t; one host frame: B = 1), layers.hip
 void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_dev, int T, int slot0, int n, const View &y, hipStream_t s,
                           bool bgr);
@@ -155,6 +161,9 @@ void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *t
 // boxes: [D,5] = x1,y1,x2,y2,frame index (frames are h*w*3 bytes apart)
 void launch_crop_resize(const uint8_t *frames, int h, int w, const int *boxes5_dev, int D, const View &y,
                         hipStream_t s, bool bgr = false);
+// the same with a box's frame index selecting that frame's base, row stride and size from `geom`
+void launch_crop_resize_frames(const uint8_t *frames, const FrameGeom *geom, const int *boxes5_dev, int D, const View &y, hipStream_t s,
+                               bool bgr = false);
 void launch_avgpool_l2norm(const View &x, float *out, hipStream_t s);         // [D,8,4,512] -> [D,512]
 
 }  // namespace yds

@@ -704,6 +704,17 @@ void Darknet::forward_u8_dev(const uint8_t *frames_dev, int h, int w, int batch)
     run_graph(batch);
 }
 
+void Darknet::forward_u8_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom) {
+    const int batch = (int)geom.size();
+    if (in_channels != 3) fail("forward_u8: network expects %d channels", in_channels);
+    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
+    geom_dev.ensure(batch_max);
+    YDS_HIP(hipMemcpyAsync(geom_dev.p, geom.data(), geom.size() * sizeof(FrameGeom), hipMemcpyHostToDevice, stream));
+    YDS_HIP(hipStreamSynchronize(stream));                      // the caller's table may go away
+    launch_resize_u8_frames(frames_dev, geom_dev.p, batch, input_view(batch), stream);
+    run_graph(batch);
+}
+
 void Darknet::forward_u8_host(const uint8_t *frames, int h, int w, int batch, float *out_host) {
     size_t n = (size_t)batch * h * w * 3;
     stage_u8.ensure(n);
@@ -947,6 +958,13 @@ const uint8_t *yds_darknet_last_frames_dev(yds_net *n, int *h, int *w, int *batc
 int yds_darknet_forward_u8_dev(yds_net *n, const uint8_t *rgb_dev, int h, int w, int batch) {
     YDS_API_BEGIN
     n->d->forward_u8_dev(rgb_dev, h, w, batch);
+    YDS_API_END
+}
+int yds_darknet_forward_u8_mixed_dev(yds_net *n, const uint8_t *rgb_dev, const uint64_t *frame_off, const int32_t *frame_hw, size_t frames_bytes,
+                                     int batch) {
+    YDS_API_BEGIN
+    if (!rgb_dev) yds::fail("forward_u8: NULL frames");
+    n->d->forward_u8_frames_dev(rgb_dev, yds::checked_layout(frame_off, frame_hw, batch, frames_bytes));
     YDS_API_END
 }
 int yds_darknet_layer_output(yds_net *n, int layer, int batch, float *nchw_host) {

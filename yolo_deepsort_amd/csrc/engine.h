@@ -74,6 +74,8 @@ public:
     void forward_f32_host(const float *nchw, int batch, float *out_host);
     void forward_u8_host(const uint8_t *frames, int h, int w, int batch, float *out_host);
     void forward_u8_dev(const uint8_t *frames_dev, int h, int w, int batch);
+    // frames of different sizes: frame n at frames_dev + geom[n].off (the table is copied before the call returns)
+    void forward_u8_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom);
     void forward_resized(int batch) { run_graph(batch); }      // input buffer already filled
     // the same pass enqueued in two pieces (layers [0, head_layers()) and the rest): the pipeline puts another stream-ordered
     // job between them (pipeline.cpp, serialized schedule); false = this configuration runs in lanes and cannot be split
@@ -113,6 +115,7 @@ public:
     std::vector<int> yolo_layers;
     DevBuf<float> input, out, stage_f32;
     DevBuf<uint8_t> stage_u8;
+    DevBuf<FrameGeom> geom_dev;                              // table of the last forward_u8_frames_dev
     int stage_h = 0, stage_w = 0, stage_n = 0;               // frames last uploaded by forward_u8_host (device copy in stage_u8)
     DevBuf<float> tiled_pred;
     WindowTable tiles;
@@ -169,8 +172,9 @@ public:
     // asynchronous form: launch() enqueues the kernels and the copies into pinned host memory, collect() reads
     // them after the caller synchronised the stream.  corner: the predictions already hold x1,y1,x2,y2 (is_p1p2=True);
     // merge: the reference's merge branch as a kernel behind the sweep (nms_merge_kernel) - both per launch, no state
+    // scale: (sx, sy) of every frame, [n_frames, 2], read on the device when the sweep runs (frames of different sizes); NULL: sx, sy
     void launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                float sx, float sy, int cap, hipStream_t s, bool corner = false, bool merge = false);
+                float sx, float sy, int cap, hipStream_t s, bool corner = false, bool merge = false, const float *scale = nullptr);
     int collect(int frame, float *out6_host, int cap);
     void resize(int max_candidates, int n_frames);       // (re)allocates; contents are lost
     int needed(int n_frames) const;                       // largest candidate count of the last launch (after the caller's sync)
@@ -202,7 +206,15 @@ public:
     void finalize();
     void embed_dev(const uint8_t *frame_dev, int h, int w, const float *tlwh_host, int D, float *out_host);
     // crops of several frames in one batch: frame_of[d] selects frames_dev + frame_of[d]*h*w*3; asynchronous
-    void embed_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr = false);
+    // geom (n_geom frames): the frames differ in size - frame_of[d] indexes geom instead, h and w are not used, every box is clamped
+    // to its own frame; the table travels in the pinned crop list of the pass
+    void embed_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr = false,
+                         const FrameGeom *geom = nullptr, int n_geom = 0);
+    // the front end of embed_multi_dev alone: crop list + crop kernel into `in`, asynchronous
+    void crop_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
+                        const FrameGeom *geom, int n_geom);
+    void preprocess_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom, const float *tlwh_host, const int *frame_of, int D,
+                               float *nchw_host);
     void embed_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *out_host);
     void preprocess_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *nchw_host);
     void forward_f32_host(const float *nchw, int D, float *out_host);

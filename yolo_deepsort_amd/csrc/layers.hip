@@ -419,6 +419,29 @@ void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y,
     YDS_HIP(hipGetLastError());
 }
 
+// The same front end for a step whose frames differ in size (pipeline.cpp, the mixed entries): frame n = blockIdx.y lies at
+// frames + geom[n].off and is geom[n].h x geom[n].w, so the mode (copy, exact 2x, linear) is that frame's own; arithmetic: resize_px.
+__global__ void resize_u8_frames_kernel(const uint8_t *frames, const FrameGeom *geom, float *y, int Ho, int Wo, int bgr) {
+    const FrameGeom g = geom[blockIdx.y];
+    const int per = Ho * Wo;
+    float *dst = y + (size_t)blockIdx.y * per * 4;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < per; idx += gridDim.x * blockDim.x) {
+        const int oy = idx / Wo, ox = idx - oy * Wo;
+        float o[3];
+        resize_px(frames + g.off, (size_t)g.w * 3, g.h, g.w, Ho, Wo, oy, ox, o);
+        if (bgr) { const float v = o[0]; o[0] = o[2]; o[2] = v; }
+        *reinterpret_cast<float4 *>(dst + (size_t)idx * 4) = make_float4(__fdiv_rn(o[0], 255.f), __fdiv_rn(o[1], 255.f), __fdiv_rn(o[2], 255.f), 0.f);
+    }
+}
+
+void launch_resize_u8_frames(const uint8_t *frames, const FrameGeom *geom, int n, const View &y, hipStream_t s, bool bgr) {
+    if (y.c != 4 || y.ld != 4) fail("resize: destination must be NHWC4");
+    if (n < 1 || n > 65535) fail("resize: %d frames", n);
+    const int per_frame = grid_for((size_t)y.h * y.w), gx = std::min(per_frame, std::max(1, 8192 / n));
+    hipLaunchKernelGGL(resize_u8_frames_kernel, dim3(gx, n), dim3(256), 0, s, frames, geom, y.p, y.h, y.w, bgr ? 1 : 0);
+    YDS_HIP(hipGetLastError());
+}
+
 // Sliding-window front end (img_detect.py:103-111): every window (x, y, th, tw) is stretched to the model size into its batch slot,
 // same bilinear arithmetic as resize_u8_kernel.  A step of the batched pipeline (pipeline.cpp window mode) holds B frames of T
 // windows each, window t of frame b is slot b * T + t; `tiles` is the table of ONE frame's T windows - every frame of a step is cut
@@ -498,6 +521,34 @@ __global__ void crop_resize_kernel(const uint8_t *frames, int H, int W, const in
 void launch_crop_resize(const uint8_t *frame, int h, int w, const int *boxes_xyxy_dev, int D, const View &y, hipStream_t s, bool bgr) {   // boxes: [D,5]
     if (D == 0) return;
     hipLaunchKernelGGL(crop_resize_kernel, dim3(grid_for((size_t)D * y.h * y.w)), dim3(256), 0, s, frame, h, w, boxes_xyxy_dev, D, y.p,
+                       y.h, y.w, bgr ? 1 : 0);
+    YDS_HIP(hipGetLastError());
+}
+
+// crop_resize_kernel for frames of different sizes: boxes[d * 5 + 4] indexes `geom` (the box was clamped to that frame on the host)
+__global__ void crop_resize_frames_kernel(const uint8_t *frames, const FrameGeom *geom, const int *boxes, int D, float *y, int Ho, int Wo, int bgr) {
+    const size_t total = (size_t)D * Ho * Wo;
+    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        int ox = idx % Wo;
+        size_t t = idx / Wo;
+        int oy = t % Ho;
+        int d = t / Ho;
+        int x1 = boxes[d * 5], y1 = boxes[d * 5 + 1], cw = boxes[d * 5 + 2] - x1, ch = boxes[d * 5 + 3] - y1;
+        const FrameGeom g = geom[boxes[d * 5 + 4]];
+        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+        float o[3];
+        resize_px(frames + g.off + ((size_t)y1 * g.w + x1) * 3, (size_t)g.w * 3, ch, cw, Ho, Wo, oy, ox, o);
+        if (bgr) { const float t = o[0]; o[0] = o[2]; o[2] = t; }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = __fdiv_rn(__fsub_rn(__fdiv_rn(o[c], 255.f), mean[c]), stdv[c]);
+        *reinterpret_cast<float4 *>(y + idx * 4) = make_float4(o[0], o[1], o[2], 0.f);
+    }
+}
+
+void launch_crop_resize_frames(const uint8_t *frames, const FrameGeom *geom, const int *boxes_xyxy_dev, int D, const View &y, hipStream_t s,
+                               bool bgr) {
+    if (D == 0) return;
+    hipLaunchKernelGGL(crop_resize_frames_kernel, dim3(grid_for((size_t)D * y.h * y.w)), dim3(256), 0, s, frames, geom, boxes_xyxy_dev, D, y.p,
                        y.h, y.w, bgr ? 1 : 0);
     YDS_HIP(hipGetLastError());
 }

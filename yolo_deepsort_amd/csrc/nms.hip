@@ -166,7 +166,8 @@ __global__ void nms_mask_kernel(const float *sorted_all, const int *counts_all, 
 }
 
 __global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
-                                 float sx, float sy, float *kept_all, int cap) {
+                                 float sx, float sy, const float *scale, float *kept_all, int cap) {
+    if (scale) { sx = scale[blockIdx.y * 2]; sy = scale[blockIdx.y * 2 + 1]; }       // per frame (sx, sy): frames of different sizes
     const float *sorted = sorted_all + (size_t)blockIdx.y * max_cand * 6;
     const unsigned long long *mask = mask_all + (size_t)blockIdx.y * max_cand * words_ld;
     int *counts = counts_all + blockIdx.y * 4;
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256) void nms_publish_kernel(const int *counts, con
 
 // All `n_frames` images go through each stage in ONE launch (blockIdx.y = image).
 void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                          float sx, float sy, int cap, hipStream_t s, bool corner, bool merge) {
+                          float sx, float sy, int cap, hipStream_t s, bool corner, bool merge, const float *scale) {
     if (attrs < 6) fail("nms: predictions need at least one class");
     if (n_frames < 1) fail("nms: no frames");
     if (n_frames > frames) resize(max_cand, n_frames);
@@ -306,7 +307,7 @@ void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frame
     const int words_ld = max_cand / 64;
     hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
     hipLaunchKernelGGL(nms_sweep_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
-                       counts.p, max_cand, sx, sy, kept.p, cap);
+                       counts.p, max_cand, sx, sy, scale, kept.p, cap);
     if (merge) hipLaunchKernelGGL(nms_merge_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, kept.p);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
     hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));

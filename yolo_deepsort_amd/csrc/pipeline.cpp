@@ -17,7 +17,9 @@
 
 #include <limits.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <utility>
 
@@ -32,18 +34,64 @@ struct DetSlot {
     hipEvent_t e_r0, e_r1;             // around a ReID pass enqueued inside this slot's detector pass
     bool reid_in_pass = false;
     DetSlot() { for (hipEvent_t *e : {&e0, &e1, &e2, &e_nms, &e_r0, &e_r1}) YDS_HIP(hipEventCreate(e)); }
-    ~DetSlot() { for (hipEvent_t e : {e0, e1, e2, e_nms, e_r0, e_r1}) (void)hipEventDestroy(e); }
+    ~DetSlot() {
+        for (hipEvent_t e : {e0, e1, e2, e_nms, e_r0, e_r1}) (void)hipEventDestroy(e);
+        if (tab) (void)hipHostFree(tab);
+    }
+    // Frames of different sizes: the table the slot's pass reads ON THE DEVICE - the resize kernel each frame's (offset, h, w), the NMS
+    // sweep each frame's (sx, sy) - in pinned host memory the kernels read in place (like the extractor's crop list).  It lives with
+    // the slot because those kernels run long after the call that enqueued them has gone on: the look-ahead pass of the next batch
+    // is in flight while the host works on this one.  Before the table is rewritten the slot's last pass must have read it: the
+    // resize (e1) and the NMS (e_nms) - both long over in the steady state, where a slot is reused two passes later; an abandoned
+    // look-ahead pass is what the wait is for.
+    void *tab = nullptr;
+    size_t tab_frames = 0;
+    const FrameGeom *tab_geom() const { return static_cast<const FrameGeom *>(tab); }
+    const float *tab_scale() const { return reinterpret_cast<const float *>(tab_geom() + tab_frames); }
+    void write_table(const std::vector<FrameGeom> &g, int img_h, int img_w) {
+        YDS_HIP(hipEventSynchronize(e1));
+        YDS_HIP(hipEventSynchronize(e_nms));
+        if (tab_frames < g.size()) {
+            if (tab) (void)hipHostFree(tab);
+            tab = nullptr;
+            tab_frames = 0;
+            const size_t cap = std::max<size_t>(g.size(), 64);
+            YDS_HIP(hipHostMalloc(&tab, cap * (sizeof(FrameGeom) + 2 * sizeof(float)), hipHostMallocDefault));
+            tab_frames = cap;
+        }
+        memcpy(tab, g.data(), g.size() * sizeof(FrameGeom));
+        float *scale = const_cast<float *>(tab_scale());
+        for (size_t n = 0; n < g.size(); ++n) {                     // resize_boxes per frame: python-double ratio, one rounding to fp32
+            scale[n * 2] = (float)((double)g[n].w / img_w);
+            scale[n * 2 + 1] = (float)((double)g[n].h / img_h);
+        }
+    }
+};
+
+// Where the frames of a step lie.  Uniform (the plain entries): every frame h x w, frame n at byte n * h * w * 3.  Mixed: frame n
+// is frames[n].h x frames[n].w at byte frames[n].off (h and w are 0).
+struct Geometry {
+    int h = 0, w = 0;
+    std::vector<FrameGeom> frames;
+    bool mixed() const { return !frames.empty(); }
+    bool operator==(const Geometry &o) const {
+        if (h != o.h || w != o.w || frames.size() != o.frames.size()) return false;
+        for (size_t n = 0; n < frames.size(); ++n)
+            if (frames[n].off != o.frames[n].off || frames[n].h != o.frames[n].h || frames[n].w != o.frames[n].w) return false;
+        return true;
+    }
 };
 
 // One detector pass (+ NMS) over a batch, as far as it has been enqueued.
 struct Pass {
     const uint8_t *frames = nullptr;   // nullptr: no pass (slot still names the DetSlot used last)
-    int h = 0, w = 0, batch = 0;
+    Geometry geo;                      // layout of the frames the pass was enqueued with
+    int batch = 0;
     int slot = 0;                      // DetSlot
     enum { NOTHING, HEAD, WHOLE } done = NOTHING;     // NOTHING with frames set: the head is still to be (re-)enqueued
     bool split = false;                // HEAD: the first layers went with the head, the tail runs the rest
     bool open() const { return frames && done != WHOLE; }
-    bool is_whole(const uint8_t *f, int n) const { return frames == f && batch == n && done == WHOLE; }
+    bool is_whole(const uint8_t *f, int n, const Geometry &g) const { return frames == f && batch == n && geo == g && done == WHOLE; }
 };
 
 // ---- frames handed over as HOST memory (img_detect.py:70-71 starts from a host frame) ------------------------------
@@ -164,14 +212,16 @@ public:
         if (stager.find(frames_host) >= 0) return;
         stager.upload(frames_host, (size_t)batch * h * w * 3, 3, stager.cur, stager.next);      // survives this call's step and the next: consumed by the one after
     }
-    void step_host(const uint8_t *frames_host, const uint8_t *next_host, int h, int w, int batch, int32_t *out6, int cap, int32_t *counts) {
-        const size_t bytes = (size_t)batch * h * w * 3;
+    // bytes: what is uploaded of each host block - batch * h * w * 3, or the span [0, max(off + size)) of a mixed layout
+    void step_host(const uint8_t *frames_host, const uint8_t *next_host, const Geometry &geo, size_t bytes, int batch, int32_t *out6, int cap,
+                   int32_t *counts) {
+        check_step(geo, batch);                                     // (before anything is uploaded)
         // batches handed over earlier (as `next` of the previous call, or through prefetch_host) are already resident or on their way
         stager.cur = stager.find(frames_host);
         if (stager.cur < 0) stager.cur = stager.upload(frames_host, bytes, 1, stager.find(next_host));
         stager.next = next_host ? stager.find(next_host) : -1;
         if (next_host && stager.next < 0) stager.next = stager.upload(next_host, bytes, 2, stager.cur);      // survives this step: the next call's `frames`
-        step(stager.dev(stager.cur), stager.next >= 0 ? stager.dev(stager.next) : nullptr, h, w, batch, out6, cap, counts, true);
+        step(stager.dev(stager.cur), stager.next >= 0 ? stager.dev(stager.next) : nullptr, geo, batch, out6, cap, counts, true);
         stager.end_of_step(stager.cur);
     }
 
@@ -189,11 +239,16 @@ public:
         YDS_HIP(hipEventRecord(s.e0, net->stream));
         p.done = Pass::HEAD;
         p.split = false;
-        if (windows_for(p.h, p.w)) {                                // window mode: the whole pass (resize included) is the tail's
+        if (windows_for(p.geo)) {                                   // window mode: the whole pass (resize included) is the tail's
             YDS_HIP(hipEventRecord(s.e1, net->stream));
             return;
         }
-        launch_resize_u8(p.frames, p.batch, p.h, p.w, net->input_view(p.batch), net->stream, frames_bgr);
+        if (p.geo.mixed()) {
+            s.write_table(p.geo.frames, net->img_h, net->img_w);
+            launch_resize_u8_frames(p.frames, s.tab_geom(), p.batch, net->input_view(p.batch), net->stream, frames_bgr);
+        } else {
+            launch_resize_u8(p.frames, p.batch, p.geo.h, p.geo.w, net->input_view(p.batch), net->stream, frames_bgr);
+        }
         YDS_HIP(hipEventRecord(s.e1, net->stream));
         stager.mark_read(p.frames, net->stream, FrameStager::DET);
         p.split = split && net->forward_resized_part(p.batch, 0);
@@ -201,12 +256,12 @@ public:
     void launch_detector_tail(Pass &p) {
         DetSlot &s = det[p.slot];
         const size_t per_slot = (size_t)net->total_boxes * net->attrs;
-        if (const int T = windows_for(p.h, p.w)) {
+        if (const int T = windows_for(p.geo)) {
             if (win_pred.n < (size_t)p.batch * T * per_slot) {
                 YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
                 win_pred.alloc((size_t)p.batch * T * per_slot);
             }
-            net->forward_windows(p.frames, p.h, p.w, p.batch, win, win_pred.p, frames_bgr);
+            net->forward_windows(p.frames, p.geo.h, p.geo.w, p.batch, win, win_pred.p, frames_bgr);
             stager.mark_read(p.frames, net->stream, FrameStager::DET);
             YDS_HIP(hipEventRecord(s.e2, net->stream));
             s.nms->launch(win_pred.p, (size_t)T * per_slot, p.batch, T * net->total_boxes, net->attrs, conf, nms_thres, 1.f, 1.f, 300, net->stream,
@@ -215,8 +270,9 @@ public:
             if (p.split) (void)net->forward_resized_part(p.batch, 1);
             else net->forward_resized(p.batch);
             YDS_HIP(hipEventRecord(s.e2, net->stream));
-            const float sx = (float)((double)p.w / net->img_w), sy = (float)((double)p.h / net->img_h);
-            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream);
+            const float sx = (float)((double)p.geo.w / net->img_w), sy = (float)((double)p.geo.h / net->img_h);
+            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream, false, false,
+                          p.geo.mixed() ? s.tab_scale() : nullptr);    // mixed: every frame's own ratio, from the slot's table
         }
         YDS_HIP(hipEventRecord(s.e_nms, net->stream));
         p.done = Pass::WHOLE;
@@ -240,6 +296,7 @@ public:
         win_tab_h = win_tab_w = 0;
     }
     // number of windows T of an h x w frame; 0 = the plain path (window mode off, or a frame smaller than the window: img_detect.py:68)
+    int windows_for(const Geometry &g) { return g.mixed() ? 0 : windows_for(g.h, g.w); }    // (step() refuses a mixed layout in window mode)
     int windows_for(int h, int w) {
         if (win_w <= 0 || (w < win_w && h < win_h)) return 0;
         if (h == win_tab_h && w == win_tab_w) return win.T;
@@ -259,6 +316,7 @@ public:
         std::vector<float> tlwh, payload;
         std::vector<int> frame_of, first, n_det;
         const uint8_t *frames = nullptr;
+        Geometry geo;                             // layout of `frames`: the crops read it
         int batch = 0;
         bool reid_in_flight = false;
         hipStream_t reid_on = nullptr;            // stream the ReID pass of this batch was enqueued on
@@ -276,7 +334,7 @@ public:
             // Rare slow path; bench-only logit injection is not re-selected for it.
             YDS_HIP(hipStreamSynchronize(net->stream));
             s.nms->resize(s.nms->needed(batch), s.nms->frames);
-            Pass redo{p.frames, p.h, p.w, batch, p.slot};
+            Pass redo{p.frames, p.geo, batch, p.slot};
             launch_detector(redo);
             if (pending.done == Pass::HEAD) pending.done = Pass::NOTHING;      // a head enqueued for the next pass has been overwritten
             YDS_HIP(hipEventSynchronize(s.e_nms));
@@ -297,7 +355,7 @@ public:
         std::vector<float> det_rows(300 * 6);
         d.tlwh.clear(); d.payload.clear(); d.frame_of.clear();
         d.first.assign(batch + 1, 0); d.n_det.assign(batch, 0);
-        d.frames = p.frames; d.batch = batch; d.reid_in_flight = false;
+        d.frames = p.frames; d.geo = p.geo; d.batch = batch; d.reid_in_flight = false;
         for (int b = 0; b < batch; ++b) {
             d.n_det[b] = s.nms->collect(b, det_rows.data(), 300);
             for (int i = 0; i < d.n_det[b]; ++i) {
@@ -317,7 +375,7 @@ public:
     // with them from the extractor's own stream
     // inside: the pass sits between the head and the tail of that detector pass (serialized schedule) and gets an event pair of
     // its own in the pass's DetSlot (see finish_detector).
-    void launch_reid(Dets &d, int h, int w, hipStream_t on = nullptr, const Pass *inside = nullptr) {
+    void launch_reid(Dets &d, hipStream_t on = nullptr, const Pass *inside = nullptr) {
         d.reid_on = on ? on : reid->stream;
         if (!d.payload.empty()) {
             struct Swap { hipStream_t &s; hipStream_t keep; ~Swap() { s = keep; } } swap{reid->stream, reid->stream};
@@ -328,7 +386,8 @@ public:
             reid->stream = d.reid_on;
             if (reid_last_on && reid_last_on != d.reid_on) reid->sync_before_regrow = reid_last_on;
             if (inside) YDS_HIP(hipEventRecord(det[inside->slot].e_r0, d.reid_on));
-            reid->embed_multi_dev(d.frames, h, w, d.tlwh.data(), d.frame_of.data(), (int)d.payload.size(), frames_bgr);
+            reid->embed_multi_dev(d.frames, d.geo.h, d.geo.w, d.tlwh.data(), d.frame_of.data(), (int)d.payload.size(), frames_bgr,
+                                  d.geo.mixed() ? d.geo.frames.data() : nullptr, (int)d.geo.frames.size());
             reid->sync_before_regrow = nullptr;
             if (inside) { YDS_HIP(hipEventRecord(det[inside->slot].e_r1, d.reid_on)); det[inside->slot].reid_in_pass = true; }
             YDS_HIP(hipEventRecord(ev_reid_done, d.reid_on));
@@ -378,14 +437,22 @@ public:
         }
     };
 
-    void step(const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int batch, int32_t *out6, int cap, int32_t *counts,
+    // what a step refuses, before anything is uploaded or enqueued
+    void check_step(const Geometry &geo, int batch) {
+        if (batch < 1 || batch > net->batch_max) fail("pipeline: batch %d outside [1,%d]", batch, net->batch_max);
+        if (geo.mixed() && (int)geo.frames.size() != batch) fail("pipeline: a layout of %zu frames for a step of %d", geo.frames.size(), batch);
+        if (geo.mixed() && win_w > 0)
+            fail("pipeline: window mode takes frames of one size (yds_pipeline_step_multi); a mixed layout is refused while windows are set");
+    }
+    // geo: the layout of `frames_dev` AND of `next_frames_dev` (a steady camera set; pass no next frames when the layout changes)
+    void step(const uint8_t *frames_dev, const uint8_t *next_frames_dev, const Geometry &geo, int batch, int32_t *out6, int cap, int32_t *counts,
               bool uploaded = false) {
         using clk = std::chrono::steady_clock;
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<float, std::micro>(b - a).count(); };
-        if (batch < 1 || batch > net->batch_max) fail("pipeline: batch %d outside [1,%d]", batch, net->batch_max);
+        check_step(geo, batch);
         auto t_begin = clk::now();
         const int inject_set = std::exchange(next_inject_set, -1); // bench-only: applies to the pass this step enqueues for `next`
-        const bool resumed = ahead.reid_in_flight && ahead.frames == frames_dev && ahead.batch == batch;
+        const bool resumed = ahead.reid_in_flight && ahead.frames == frames_dev && ahead.batch == batch && ahead.geo == geo;
         // Serialized schedule (round 4).  The ReID pass of batch i and the detector pass of batch i+1 are both chip-filling
         // sequences of matrix-core kernels; from two streams they time-share the CUs, every launch stretched by the other
         // stream's work (1.3x on the detector's kernels at cfg2) for the same total.  With >= serial_min crops in the batch the
@@ -415,7 +482,7 @@ public:
                                : (trial.wants_serial() ? 256 : -1);
         // detector (+ NMS) of the next batch goes in flight, in the DetSlot this batch's pass does not use
         auto launch_next = [&](int this_slot, bool head_only) {
-            pending = next_frames_dev ? Pass{next_frames_dev, h, w, batch, this_slot ^ 1} : Pass{nullptr, 0, 0, 0, this_slot};
+            pending = next_frames_dev ? Pass{next_frames_dev, geo, batch, this_slot ^ 1} : Pass{nullptr, Geometry(), 0, this_slot};
             if (!next_frames_dev) return;
             if (inject_set >= 0) net->select_injection_set(inject_set);
             if (head_only) launch_detector_head(pending, true);
@@ -437,18 +504,18 @@ public:
             launch_next(pending.slot, false);
         } else {
             ahead.reid_in_flight = false;
-            Pass now = pending.is_whole(frames_dev, batch) ? pending : Pass{frames_dev, h, w, batch, pending.slot ^ 1};
+            Pass now = pending.is_whole(frames_dev, batch, geo) ? pending : Pass{frames_dev, geo, batch, pending.slot ^ 1};
             launch_detector(now);
             launch_next(now.slot, serial_min >= 0);                 // enqueued BEFORE the host waits for this batch's NMS
             finish_detector(cur, now);
             serial = serial_min >= 0 && (int)cur.payload.size() >= std::max(serial_min, 1);
             if (serial) {
-                launch_reid(cur, h, w, net->stream, pending.open() ? &pending : nullptr);
+                launch_reid(cur, net->stream, pending.open() ? &pending : nullptr);
                 copy_feats();
                 if (pending.open()) launch_detector(pending, true);
             } else {
                 if (pending.open()) launch_detector(pending, true); // (the head again first if a redone pass overwrote it)
-                launch_reid(cur, h, w);
+                launch_reid(cur);
                 copy_feats();
             }
         }
@@ -467,7 +534,7 @@ public:
         if (next_frames_dev && D_all >= deep_min * batch) {
             finish_detector(ahead, pending);
             pending.frames = nullptr;                               // consumed: its detections are in `ahead`
-            launch_reid(ahead, h, w, serial ? net->stream : nullptr);
+            launch_reid(ahead, serial ? net->stream : nullptr);
         }
         // association of the whole batch on the group's stream, one host synchronisation: frame b advances tracker stream_of[b] (a
         // single stream: all zeros), every tracker in the same launches
@@ -532,8 +599,22 @@ static void pipeline_step(yds_pipe *p, bool multi_entry, bool host, const uint8_
                           const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host) {
     if (multi_entry) p->p->set_streams(stream_of_frame, n);
     else if (p->p->multi) yds::fail("pipeline: created by yds_pipeline_create_multi: use yds_pipeline_step_multi%s", host ? "_host" : "");
-    if (host) p->p->step_host(frames, next_frames, h, w, n, out6_host, cap, counts_host);
-    else p->p->step(frames, next_frames, h, w, n, out6_host, cap, counts_host);
+    const yds::Geometry geo{h, w, {}};
+    if (host) p->p->step_host(frames, next_frames, geo, (size_t)n * h * w * 3, n, out6_host, cap, counts_host);
+    else p->p->step(frames, next_frames, geo, n, out6_host, cap, counts_host);
+}
+// the two mixed entries: every frame with its own (offset, h, w) inside a block of frames_bytes bytes
+static void pipeline_step_mixed(yds_pipe *p, bool host, const uint8_t *frames, const uint8_t *next_frames, const uint64_t *frame_off,
+                                const int32_t *frame_hw, size_t frames_bytes, int n, const int32_t *stream_of_frame, int32_t *out6_host, int cap,
+                                int32_t *counts_host) {
+    if (!frames) yds::fail("pipeline: NULL frames");
+    p->p->set_streams(stream_of_frame, n);                           // (refuses n outside [1, batch_max] and a single-stream pipeline)
+    yds::Geometry geo;
+    geo.frames = yds::checked_layout(frame_off, frame_hw, n, frames_bytes);
+    if (!host) { p->p->step(frames, next_frames, geo, n, out6_host, cap, counts_host); return; }
+    size_t span = 0;
+    for (const yds::FrameGeom &g : geo.frames) span = std::max(span, (size_t)(g.off + (uint64_t)g.h * g.w * 3));
+    p->p->step_host(frames, next_frames, geo, span, n, out6_host, cap, counts_host);
 }
 
 extern "C" {
@@ -584,6 +665,22 @@ int yds_pipeline_step_multi_host(yds_pipe *p, const uint8_t *frames_host, const 
                                  const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host) {
     YDS_API_BEGIN
     pipeline_step(p, true, true, frames_host, next_frames_host, h, w, n_frames, stream_of_frame, out6_host, cap, counts_host);
+    YDS_API_END
+}
+int yds_pipeline_step_multi_mixed(yds_pipe *p, const uint8_t *frames_dev, const uint8_t *next_frames_dev, const uint64_t *frame_off,
+                                  const int32_t *frame_hw, size_t frames_bytes, int n_frames, const int32_t *stream_of_frame, int32_t *out6_host,
+                                  int cap, int32_t *counts_host) {
+    YDS_API_BEGIN
+    pipeline_step_mixed(p, false, frames_dev, next_frames_dev, frame_off, frame_hw, frames_bytes, n_frames, stream_of_frame, out6_host, cap,
+                        counts_host);
+    YDS_API_END
+}
+int yds_pipeline_step_multi_mixed_host(yds_pipe *p, const uint8_t *frames_host, const uint8_t *next_frames_host, const uint64_t *frame_off,
+                                       const int32_t *frame_hw, size_t frames_bytes, int n_frames, const int32_t *stream_of_frame,
+                                       int32_t *out6_host, int cap, int32_t *counts_host) {
+    YDS_API_BEGIN
+    pipeline_step_mixed(p, true, frames_host, next_frames_host, frame_off, frame_hw, frames_bytes, n_frames, stream_of_frame, out6_host, cap,
+                        counts_host);
     YDS_API_END
 }
 int yds_pipeline_prefetch_host(yds_pipe *p, const uint8_t *frames_host, int h, int w, int batch) {

@@ -199,15 +199,24 @@ void ReidNet::forward(int D) {
     launch_avgpool_l2norm(cur, feat.p, stream);
 }
 
-static void crop_boxes_host(const float *tlwh, int D, int H, int W, std::vector<int> &out, const int *frame_of = nullptr) {
+// geom: the box of detection d is clamped to frame frame_of[d]'s own size (H, W are not used)
+static void crop_boxes_host(const float *tlwh, int D, int H, int W, std::vector<int> &out, const int *frame_of = nullptr,
+                            const FrameGeom *geom = nullptr, int n_geom = 0) {
     out.resize((size_t)D * 5);
     for (int d = 0; d < D; ++d) {
+        if (geom) {
+            if (!frame_of || frame_of[d] < 0 || frame_of[d] >= n_geom) fail("reid: detection %d names frame %d outside [0,%d)", d, frame_of ? frame_of[d] : -1, n_geom);
+            H = geom[frame_of[d]].h; W = geom[frame_of[d]].w;
+        }
         float x = tlwh[d * 4], y = tlwh[d * 4 + 1], w = tlwh[d * 4 + 2], h = tlwh[d * 4 + 3];
         float xe = x + w, ye = y + h;                         // fp32 sums like the reference's tensor ops
         int x1 = (int)x > 0 ? (int)x : 0;
         int y1 = (int)y > 0 ? (int)y : 0;
         int x2 = (int)xe < W - 1 ? (int)xe : W - 1;
         int y2 = (int)ye < H - 1 ? (int)ye : H - 1;
+        if ((x2 <= x1 || y2 <= y1) && geom)                       // frames of different sizes: say which one clamped the box
+            fail("reid: detection %d yields an empty crop (%d,%d,%d,%d) in frame %d (%d x %d); cv2.resize raises in the reference", d, x1, y1, x2, y2,
+                 frame_of[d], H, W);
         if (x2 <= x1 || y2 <= y1) fail("reid: detection %d yields an empty crop (%d,%d,%d,%d); cv2.resize raises in the reference", d, x1, y1, x2, y2);
         out[d * 5] = x1; out[d * 5 + 1] = y1; out[d * 5 + 2] = x2; out[d * 5 + 3] = y2; out[d * 5 + 4] = frame_of ? frame_of[d] : 0;
     }
@@ -230,13 +239,23 @@ void ReidNet::embed_dev(const uint8_t *frame_dev, int h, int w, const float *tlw
     YDS_HIP(hipStreamSynchronize(stream));
 }
 
-void ReidNet::embed_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr) {
+void ReidNet::embed_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
+                              const FrameGeom *geom, int n_geom) {
     if (D == 0) return;
     if (!ready) fail("reid: weights not loaded (yds_reid_finalize)");
+    crop_multi_dev(frames_dev, h, w, tlwh_host, frame_of, D, bgr, geom, n_geom);
+    forward(D);
+}
+
+void ReidNet::crop_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
+                             const FrameGeom *geom, int n_geom) {
     reserve(D);
-    crop_boxes_host(tlwh_host, D, h, w, boxes_host, frame_of);
+    crop_boxes_host(tlwh_host, D, h, w, boxes_host, frame_of, geom, n_geom);
+    // the list of a pass with frames of different sizes starts with their table (n_geom entries of 16 bytes), the boxes follow
+    static_assert(sizeof(FrameGeom) == 4 * sizeof(int), "the frame table is laid out in the int list");
+    const size_t head = geom ? (size_t)n_geom * 4 : 0, need = head + boxes_host.size();
     const int t = boxes_pin_turn ^= 1;
-    if (boxes_pin_cap[t] < boxes_host.size()) {
+    if (boxes_pin_cap[t] < need) {
         if (boxes_pin[t]) {
             // the previous tenants of this list may still be read by crop kernels: on this stream, and - when the pipeline moved
             // the pass to another stream since - on the one the earlier pass ran on
@@ -245,13 +264,27 @@ void ReidNet::embed_multi_dev(const uint8_t *frames_dev, int h, int w, const flo
             (void)hipHostFree(boxes_pin[t]);
             boxes_pin[t] = nullptr;
         }
-        boxes_pin_cap[t] = std::max<size_t>(boxes_host.size() * 2, 4096);
+        boxes_pin_cap[t] = std::max<size_t>(need * 2, 4096);
         YDS_HIP(hipHostMalloc((void **)&boxes_pin[t], boxes_pin_cap[t] * sizeof(int), hipHostMallocDefault));
     }
-    memcpy(boxes_pin[t], boxes_host.data(), boxes_host.size() * sizeof(int));
+    if (geom) memcpy(boxes_pin[t], geom, head * sizeof(int));
+    memcpy(boxes_pin[t] + head, boxes_host.data(), boxes_host.size() * sizeof(int));
     View x0; x0.p = in.p; x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
-    launch_crop_resize(frames_dev, h, w, boxes_pin[t], D, x0, stream, bgr);
-    forward(D);
+    if (geom) launch_crop_resize_frames(frames_dev, reinterpret_cast<const FrameGeom *>(boxes_pin[t]), boxes_pin[t] + head, D, x0, stream, bgr);
+    else launch_crop_resize(frames_dev, h, w, boxes_pin[t], D, x0, stream, bgr);
+}
+
+void ReidNet::preprocess_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom, const float *tlwh_host, const int *frame_of,
+                                    int D, float *nchw_host) {
+    if (D == 0) return;
+    reserve(D);
+    if (!in.p) in.alloc((size_t)max_crops * CROP_H * CROP_W * 4);
+    crop_multi_dev(frames_dev, 0, 0, tlwh_host, frame_of, D, false, geom.data(), (int)geom.size());
+    View x3; x3.p = in.p; x3.n = D; x3.h = CROP_H; x3.w = CROP_W; x3.c = 3; x3.ld = 4;
+    DevBuf<float> tmp((size_t)D * 3 * CROP_H * CROP_W);
+    launch_nhwc_to_nchw(x3, tmp.p, stream);
+    YDS_HIP(hipMemcpyAsync(nchw_host, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    YDS_HIP(hipStreamSynchronize(stream));
 }
 
 void ReidNet::embed_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *out_host) {
@@ -335,6 +368,13 @@ const float *yds_reid_features_dev(yds_reid *r) { return r->r->feat.p; }
 int yds_reid_preprocess(yds_reid *r, const uint8_t *frame, int h, int w, const float *tlwh, int D, float *nchw) {
     YDS_API_BEGIN
     r->r->preprocess_host(frame, h, w, tlwh, D, nchw);
+    YDS_API_END
+}
+int yds_reid_preprocess_mixed(yds_reid *r, const uint8_t *frames_dev, const uint64_t *frame_off, const int32_t *frame_hw, int n_frames,
+                              size_t frames_bytes, const float *tlwh, const int32_t *frame_of, int D, float *nchw) {
+    YDS_API_BEGIN
+    if (!frames_dev) yds::fail("reid: NULL frames");
+    r->r->preprocess_frames_dev(frames_dev, yds::checked_layout(frame_off, frame_hw, n_frames, frames_bytes), tlwh, frame_of, D, nchw);
     YDS_API_END
 }
 int yds_reid_forward_f32(yds_reid *r, const float *nchw, int D, float *out) {

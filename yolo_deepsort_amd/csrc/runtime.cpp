@@ -56,6 +56,23 @@ hipStream_t make_stream(bool latency_role) {
     return st;
 }
 
+// A wrong table must end here as a message: the front-end kernels read whatever it describes.
+std::vector<FrameGeom> checked_layout(const uint64_t *frame_off, const int32_t *frame_hw, int n, size_t frames_bytes) {
+    if (!frame_off || !frame_hw) fail("frame layout: NULL table");
+    if (n < 1) fail("frame layout: %d frames", n);
+    std::vector<FrameGeom> g((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int32_t h = frame_hw[i * 2], w = frame_hw[i * 2 + 1];
+        if (h < 1 || w < 1) fail("frame layout: frame %d is %d x %d", i, h, w);
+        const uint64_t size = (uint64_t)h * (uint64_t)w * 3;           // < 2^64 for any int32 h, w
+        if (size > frames_bytes || frame_off[i] > frames_bytes - size)
+            fail("frame layout: frame %d (%d x %d at byte %llu) ends past the %zu bytes of the frames buffer", i, h, w,
+                 (unsigned long long)frame_off[i], frames_bytes);
+        g[i] = FrameGeom{frame_off[i], h, w};
+    }
+    return g;
+}
+
 }  // namespace yds
 
 extern "C" {

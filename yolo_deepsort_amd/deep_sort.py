@@ -66,6 +66,23 @@ class Extractor:
                                                    _lib.ptr(tlwh), tlwh.shape[0], _lib.ptr(out)))
         return out
 
+    def preprocess_mixed(self, frames, tlwh, frame_of):
+        """preprocess() over several frames of different sizes resident in HBM (parity tests, yds_reid_preprocess_mixed): the crop of
+        detection d is cut from frames[frame_of[d]] and clamped to that frame's size."""
+        from .pipeline import pack_frames
+        block, off, hw = pack_frames(frames)
+        tlwh = _np(tlwh).reshape(-1, 4)
+        frame_of = np.ascontiguousarray(frame_of, dtype=np.int32).reshape(-1)
+        assert frame_of.size == tlwh.shape[0]
+        out = np.empty((tlwh.shape[0], 3, 128, 64), np.float32)
+        dev = _lib.DeviceBuffer.from_array(block)
+        try:
+            _lib.check(_lib.load().yds_reid_preprocess_mixed(self._h, dev.ptr, _lib.ptr(off), _lib.ptr(hw), len(off), block.nbytes,
+                                                             _lib.ptr(tlwh), _lib.ptr(frame_of), tlwh.shape[0], _lib.ptr(out)))
+        finally:
+            dev.free()
+        return out
+
     def forward(self, batch):
         batch = _np(batch)
         out = np.empty((batch.shape[0], 512), np.float32)

@@ -593,7 +593,7 @@ class VideoDetector:
             if real_show and cv2 is not None:
                 cv2.destroyAllWindows()
 
-    def detect_streams(self, sources, frames_per_stream=None, show_fps=True):
+    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -604,7 +604,10 @@ class VideoDetector:
         others go on.  frames_per_stream=None: 1 when any source is live (_is_live), else max(1, AUTO_BATCH // len(sources)).
         Limits: every frame of every source must have one uint8 [h, w, 3] shape, and action_id is not supported - both raise
         ValueError; the tracker must be this package's DeepSort around its Extractor, with nms_max_overlap=1.  A detector with
-        win_size runs the pipeline in window mode (MultiStreamPipeline(win_size=...))."""
+        win_size runs the pipeline in window mode (MultiStreamPipeline(win_size=...)).
+        mixed_sizes=True lifts the first limit: every stream has its own uint8 [h, w, 3] shape (1080p and 720p cameras in one step,
+        MultiStreamPipeline.step_mixed) and keeps it - a stream that changes its shape midway raises ValueError naming the stream;
+        window mode takes frames of one size, so win_size with mixed_sizes=True raises ValueError."""
         from . import _lib, pipeline as pl
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
@@ -612,10 +615,13 @@ class VideoDetector:
             raise ValueError("VideoDetector.detect_streams does not support action_id")
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
+        if mixed_sizes and self.image_detector.win_size is not None:
+            raise ValueError("VideoDetector.detect_streams: mixed_sizes=True cannot be combined with win_size (window mode cuts frames of one size)")
         sources = list(sources)
         S = len(sources)
         if S == 0:
             return
+        shapes = [None] * S                              # mixed_sizes: the shape each stream started with
         F = int(frames_per_stream) if frames_per_stream else (1 if any(self._is_live(src) for src in sources) else max(1, self.AUTO_BATCH // S))
         det = self.image_detector
         if det.model.batch_max < S * F:
@@ -636,9 +642,15 @@ class VideoDetector:
                         alive[s] = False
                         break
                     frame = np.asarray(frame)
-                    if shape is None:
+                    if mixed_sizes:
+                        if shapes[s] is None:
+                            shapes[s] = frame.shape
+                        if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+                            raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
+                                             % (s, shapes[s], frame.shape, frame.dtype))
+                    elif shape is None:
                         shape = frame.shape
-                    if frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3:
+                    if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
                         raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
                                          "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
                     proc = since[s] % self.skip_frames == 0
@@ -650,12 +662,17 @@ class VideoDetector:
             procs = [(s, f) for s, f, p in items if p]
             outs = []
             if procs:
-                h, w = shape[:2]
-                batch = np.ascontiguousarray(np.stack([f for _, f in procs], 0))
+                if mixed_sizes:
+                    batch, off, hw = pl.pack_frames([f for _, f in procs])
+                else:
+                    batch = np.ascontiguousarray(np.stack([f for _, f in procs], 0))
                 if dev is None or dev.nbytes < batch.nbytes:
                     dev = _lib.DeviceBuffer(batch.nbytes)
                 _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
-                outs = pipe.step(dev.offset(0), h, w, [s for s, _ in procs])
+                if mixed_sizes:
+                    outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
+                else:
+                    outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
             out, k = [], 0
             for s, frame, proc in items:
                 if proc:

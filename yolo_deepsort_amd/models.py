@@ -153,6 +153,21 @@ class Darknet:
         _lib.check(_lib.load().yds_darknet_forward_u8(self._h, _lib.ptr(frames), h, w, b, _lib.ptr(out)))
         return out
 
+    def forward_u8_mixed(self, frames):
+        """frames: a list of uint8 [h, w, 3] host arrays of ANY sizes -> the detector's pass over all of them in one batch (packed
+        back to back, uploaded, every frame stretched to the model size by its own rule: yds_darknet_forward_u8_mixed_dev).
+        Asynchronous like forward_u8(want_output=False): read the result through get_input / layer_output / nms."""
+        from .pipeline import pack_frames
+        block, off, hw = pack_frames(frames)
+        if len(off) > self.batch_max:
+            self.set_batch_max(len(off))
+        dev = _lib.DeviceBuffer.from_array(block)
+        try:
+            _lib.check(_lib.load().yds_darknet_forward_u8_mixed_dev(self._h, dev.ptr, _lib.ptr(off), _lib.ptr(hw), block.nbytes, len(off)))
+            _lib.check(_lib.load().yds_device_sync())              # the frames' device copy goes away with this call
+        finally:
+            dev.free()
+
     def last_frame_dev(self, frame):
         """Device pointer of `frame` if it is the single frame the last forward_u8 uploaded, else None."""
         if getattr(self, "_last_frame_src", None) is not frame:

@@ -24,6 +24,21 @@ def _check_host_frames(frames, next_frames=None):
     return frames.shape[:3]
 
 
+def pack_frames(frames):
+    """Frames of any sizes back to back in one block: (uint8 block, byte offsets uint64 [n], sizes int32 [n,2]) - the layout the
+    mixed entries take (yds_pipeline_step_multi_mixed).  Each frame must be a uint8 [h, w, 3] array."""
+    frames = [np.asarray(f) for f in frames]
+    for i, f in enumerate(frames):
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError("frame %d must be a uint8 [h, w, 3] array, got %s %s" % (i, f.dtype, f.shape))
+    sizes = np.array([f.shape[0] * f.shape[1] * 3 for f in frames], np.uint64)
+    off = np.zeros(len(frames), np.uint64)
+    off[1:] = np.cumsum(sizes)[:-1]
+    block = np.concatenate([f.reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8)
+    hw = np.array([f.shape[:2] for f in frames], np.int32).reshape(-1, 2)
+    return block, off, hw
+
+
 class Pipeline:
     def __init__(self, net, deepsort, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         self.net, self.ds, self.cap = net, deepsort, int(cap)
@@ -114,7 +129,8 @@ class MultiStreamPipeline(Pipeline):
     one DeepSort (deep_sort.py:41-44), sharing its Extractor - and one detector.  A step takes frames of any of the streams (all of
     one size): the detector, NMS and ReID run once over all of them, the association advances every stream's tracker in the same
     launches (a stream's k-th frame of the step in round k).  Per stream the results are those of that stream run alone through
-    Pipeline.  Schedule, frame order, prefetch and stage times: as Pipeline."""
+    Pipeline.  Schedule, frame order, prefetch and stage times: as Pipeline.  step_mixed / step_host_mixed take cameras of different
+    frame sizes in one step (every frame with its own offset and size); window mode takes frames of one size."""
 
     def __init__(self, net, deepsorts, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         from .deep_sort import Extractor
@@ -162,6 +178,42 @@ class MultiStreamPipeline(Pipeline):
             raise ValueError("MultiStreamPipeline: %d frames but %d stream ids" % (n, s.size))
         return self._run(n, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_host(
             self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, n, _lib.ptr(s), out, self.cap, counts))
+
+
+    def _layout(self, n, frame_off, frame_hw):
+        off = np.ascontiguousarray(frame_off, dtype=np.uint64).reshape(-1)
+        hw = np.ascontiguousarray(frame_hw, dtype=np.int32)
+        if off.size != n or hw.size != 2 * n:
+            raise ValueError("MultiStreamPipeline: %d frames need %d offsets and [%d, 2] sizes, got %d and %s" % (n, n, n, off.size, hw.shape))
+        return off, hw.reshape(n, 2)
+
+    def step_mixed(self, frames_dev, frame_off, frame_hw, stream_of_frame, frames_bytes, next_frames_dev=None, select_next=None):
+        """step() for frames of different sizes: frame i is uint8 [frame_hw[i][0], frame_hw[i][1], 3] at frames_dev + frame_off[i],
+        inside a device buffer of frames_bytes bytes (a layout that leaves it raises YdsError before anything runs).
+        next_frames_dev (optional): the next call's frames in a buffer of the SAME layout and at least frames_bytes bytes."""
+        s = self._streams(stream_of_frame)
+        off, hw = self._layout(s.size, frame_off, frame_hw)
+        return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_mixed(
+            self._h, frames_dev, next_frames_dev, _lib.ptr(off), _lib.ptr(hw), int(frames_bytes), s.size, _lib.ptr(s), out, self.cap, counts))
+
+    def step_host_mixed(self, frames, stream_of_frame, next_frames=None, select_next=None):
+        """frames: a list of uint8 [h, w, 3] HOST arrays of any sizes, frame i of stream stream_of_frame[i], or the triple
+        pack_frames() made of such a list (a caller that keeps pinned blocks packs once); they are packed back to back into one
+        block and uploaded by the pipeline.  next_frames (optional): the next call's frames, given the same way - the same sizes
+        in the same order; the next call must then pass the same triple (its block's memory) as `frames`."""
+        block, off, hw = frames if isinstance(frames, tuple) else pack_frames(frames)
+        s = self._streams(stream_of_frame)
+        off, hw = self._layout(s.size, off, hw)
+        nxt = None
+        if next_frames is not None:
+            nxt, noff, nhw = next_frames if isinstance(next_frames, tuple) else pack_frames(next_frames)
+            if not (np.array_equal(noff, off) and np.array_equal(np.asarray(nhw).reshape(-1, 2), hw)):
+                raise ValueError("MultiStreamPipeline: next_frames must have the layout of frames (the same sizes in the same order)")
+            assert nxt.dtype == np.uint8 and nxt.flags["C_CONTIGUOUS"]
+        assert block.dtype == np.uint8 and block.flags["C_CONTIGUOUS"]
+        self._keep = (block, nxt)
+        return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_mixed_host(
+            self._h, _lib.ptr(block), _lib.ptr(nxt), _lib.ptr(off), _lib.ptr(hw), block.nbytes, s.size, _lib.ptr(s), out, self.cap, counts))
 
 
 def conv_timing(net, mode=0):
