@@ -162,6 +162,16 @@ int yds_reid_preprocess(yds_reid *, const uint8_t *frame_rgb_host, int h, int w,
  * nchw_host receives the [D,3,128,64] crops */
 int yds_reid_preprocess_mixed(yds_reid *, const uint8_t *frames_rgb_dev, const uint64_t *frame_off, const int32_t *frame_hw /* [n_frames,2] */,
                               int n_frames, size_t frames_bytes, const float *tlwh_host, const int32_t *frame_of_host, int D, float *nchw_host);
+/* parity tests: the ReID pass of such a step (what the pipeline enqueues), frames and detections as in yds_reid_preprocess_mixed;
+ * bgr != 0: the frames hold B, G, R bytes.  out_host receives the [D,512] features */
+int yds_reid_embed_mixed(yds_reid *, const uint8_t *frames_dev, const uint64_t *frame_off, const int32_t *frame_hw /* [n_frames,2] */,
+                         int n_frames, size_t frames_bytes, const float *tlwh_host, const int32_t *frame_of_host, int D, int bgr,
+                         float *out_host);
+/* parity tests: 1 when the last pass began with the fused front-end kernel (crop + resize + stem + max-pool in one launch), 0 when it
+ * took the crop kernel and the separate stem; and the number of crops that fill that kernel's persistent grid exactly (one more crop
+ * sends some workgroups through a second trip), < 0 on error */
+int yds_reid_front_fused(yds_reid *);
+int yds_reid_front_grid_crops(void);
 int yds_reid_forward_f32(yds_reid *, const float *nchw_host, int D, float *out_host);  /* parity tests */
 
 /* ---- tracker: DeepSort.update minus the extractor -----------------------------------------

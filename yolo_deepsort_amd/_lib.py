@@ -143,6 +143,9 @@ SIGNATURES = {
     "yds_pipeline_set_windows": (_I, [_P, _I, _I, C.c_double]),
     "yds_darknet_forward_u8_mixed_dev": (_I, [_P, _P, _P, _P, _SZ, _I]),
     "yds_reid_preprocess_mixed": (_I, [_P, _P, _P, _P, _I, _SZ, _P, _P, _I, _P]),
+    "yds_reid_embed_mixed": (_I, [_P, _P, _P, _P, _I, _SZ, _P, _P, _I, _I, _P]),
+    "yds_reid_front_fused": (_I, [_P]),
+    "yds_reid_front_grid_crops": (_I, []),
     "yds_pipeline_step_multi_mixed": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
     "yds_pipeline_step_multi_mixed_host": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
 }

@@ -164,6 +164,18 @@ void launch_crop_resize(const uint8_t *frames, int h, int w, const int *boxes5_d
 // the same with a box's frame index selecting that frame's base, row stride and size from `geom`
 void launch_crop_resize_frames(const uint8_t *frames, const FrameGeom *geom, const int *boxes5_dev, int D, const View &y, hipStream_t s,
                                bool bgr = false);
+// Where the crops of a ReID pass come from: the frames (h x w each, or `geom` when they differ in size) and the [D,5] crop list, both
+// device-readable until the pass has run.
+struct ReidFront {
+    const uint8_t *frames = nullptr;
+    const FrameGeom *geom = nullptr;
+    const int *boxes = nullptr;
+    int h = 0, w = 0, bgr = 0;
+};
+// crop + resize + normalise + stem conv + BN + ReLU + MaxPool2d(3, 2, 1) in one kernel (reid_stem.hip); pooled: H16 [D,64,32,64]
+void launch_reid_stem(const ReidFront &f, int D, const float *w, int kpad, const float *bias, const View &pooled, hipStream_t s);
+constexpr int kReidStemUnitsPerCrop = 4;         // a workgroup of that kernel takes a quarter crop at a time ...
+int reid_stem_grid();                            // ... in a persistent grid of this many workgroups
 void launch_avgpool_l2norm(const View &x, float *out, hipStream_t s);         // [D,8,4,512] -> [D,512]
 
 }  // namespace yds

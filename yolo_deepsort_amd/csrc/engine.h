@@ -210,16 +210,21 @@ public:
     // to its own frame; the table travels in the pinned crop list of the pass
     void embed_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr = false,
                          const FrameGeom *geom = nullptr, int n_geom = 0);
-    // the front end of embed_multi_dev alone: crop list + crop kernel into `in`, asynchronous
-    void crop_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
-                        const FrameGeom *geom, int n_geom);
     void preprocess_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom, const float *tlwh_host, const int *frame_of, int D,
                                float *nchw_host);
     void embed_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *out_host);
     void preprocess_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *nchw_host);
     void forward_f32_host(const float *nchw, int D, float *out_host);
-    void forward(int D);                     // input already in `in` (NHWC4)
+    // front == nullptr: input already in `in` (NHWC4).  Otherwise the pass starts from the frames: with the fused front end
+    // (reid_stem.hip) where it applies - f16x3 arithmetic, none of YDS_POOL_VALU, YDS_REID_UNFUSED, YDS_REID_FRONT_UNFUSED set -
+    // else with the crop kernel into `in`
+    void forward(int D, const ReidFront *front = nullptr);
     void reserve(int D);                     // grows the activation buffers (and `feat`) to hold D crops
+    float *in_buf();                         // `in`, allocated on first use (the fused front end never touches it), sized by max_crops
+    void crop_into_in(const ReidFront &f, int D);            // the crop kernel of the unfused front end
+    // crop list of a batched pass into the pinned list whose turn it is; the returned record points into it
+    ReidFront stage_crops(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
+                          const FrameGeom *geom, int n_geom);
     void allocate_buffers();
     static int64_t flops_per_crop();
 
@@ -233,7 +238,7 @@ public:
     std::map<std::string, std::vector<int64_t>> raw_shape;
     bool ready = false;
     std::vector<ConvW> convs;                // in execution order
-    std::vector<DevBuf<float>> bufs;
+    std::vector<DevBuf<float>> bufs;         // [0], the full-resolution stem output of the unfused pair, is allocated on first use
     DevBuf<float> in, feat, stage_f32;
     DevBuf<uint8_t> stage_u8;
     DevBuf<int> boxes_dev;
@@ -250,6 +255,7 @@ public:
     int tuned_math = -1;
     hipStream_t stream = nullptr;
     double conv_flops_last = 0;
+    bool front_fused_last = false;              // the last forward() began with the fused front end
 };
 
 // --------------------------------------------------------------------------------------------- tracker

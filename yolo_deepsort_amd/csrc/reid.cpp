@@ -107,11 +107,12 @@ void ReidNet::finalize() {
 }
 
 // activation buffers: input, stem, pooled, then (y1, out, [shortcut]) per block - everything sized by max_crops
+// `in` (131 KB per crop) and the stem output (2 MB per crop) serve the unfused front end, the fallback stem and the parity entries only:
+// they are allocated where those run (in_buf(), forward) and, once they exist, grow there with max_crops
 void ReidNet::allocate_buffers() {
-    in.alloc((size_t)max_crops * CROP_H * CROP_W * 4);
     feat.alloc((size_t)max_crops * EMB);
     bufs.clear();
-    bufs.emplace_back((size_t)max_crops * CROP_H * CROP_W * 64);           // 0 stem
+    bufs.emplace_back();                                                   // 0 stem (on first use)
     bufs.emplace_back((size_t)max_crops * 64 * 32 * 64);                   // 1 pooled
     int h = 64, w = 32;
     for (const StageDef &s : kStages) {
@@ -129,10 +130,20 @@ void ReidNet::reserve(int D) {
     while (m < D) m *= 2;
     max_crops = m;
     if (ready) allocate_buffers();
-    else in.alloc((size_t)max_crops * CROP_H * CROP_W * 4);
 }
 
-void ReidNet::forward(int D) {
+float *ReidNet::in_buf() {
+    in.ensure((size_t)max_crops * CROP_H * CROP_W * 4);
+    return in.p;
+}
+
+void ReidNet::crop_into_in(const ReidFront &f, int D) {
+    View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
+    if (f.geom) launch_crop_resize_frames(f.frames, f.geom, f.boxes, D, x0, stream, f.bgr);
+    else launch_crop_resize(f.frames, f.h, f.w, f.boxes, D, x0, stream, f.bgr);
+}
+
+void ReidNet::forward(int D, const ReidFront *front) {
     if (!ready) fail("reid: weights not loaded (yds_reid_finalize)");
     if (D < 1) fail("reid: no crops");
     reserve(D);
@@ -161,9 +172,19 @@ void ReidNet::forward(int D) {
         (void)launch_conv(a, stream, it->second.second);
         conv_flops_last += conv_flops(a);
     };
-    View x0 = mk(in, CROP_H, CROP_W, 4);
     View cur = mk(bufs[1], 64, 32, 64);
-    {
+    // frames -> pooled tensor in one kernel: it takes the crop kernel's place as the first launch of the pass
+    const bool fused_front = front && f16 && cur.fmt == FMT_H16 && !getenv("YDS_POOL_VALU") && !getenv("YDS_REID_UNFUSED") &&
+                             !getenv("YDS_REID_FRONT_UNFUSED");
+    front_fused_last = fused_front;
+    if (fused_front) {
+        const ConvW &c = convs[0];
+        launch_reid_stem(*front, D, c.wt.p, c.kpad, c.bias.p, cur, stream);
+        conv_flops_last += 2.0 * D * CROP_H * CROP_W * 64 * 9 * 4;
+    } else {
+        if (front) crop_into_in(*front, D);
+        in_buf();
+        View x0 = mk(in, CROP_H, CROP_W, 4);
         // stem conv + BN + ReLU + MaxPool2d(3, 2, 1) (model.py:52-60) as one kernel; the unfused pair stays as fallback
         const ConvW &c = convs[0];
         ConvArgs a;
@@ -172,6 +193,7 @@ void ReidNet::forward(int D) {
         if (!getenv("YDS_REID_UNFUSED") && launch_conv_maxpool3s2(a, stream)) {
             conv_flops_last += 2.0 * D * CROP_H * CROP_W * 64 * 9 * 4;
         } else {
+            bufs[0].ensure((size_t)max_crops * CROP_H * CROP_W * 64);
             View stem = mk(bufs[0], CROP_H, CROP_W, 64);
             run(0, x0, stem, ACT_RELU, nullptr, RES_NONE);
             launch_maxpool(stem, cur, 3, 2, 1, false, stream);
@@ -230,9 +252,9 @@ void ReidNet::embed_dev(const uint8_t *frame_dev, int h, int w, const float *tlw
     crop_boxes_host(tlwh_host, D, h, w, boxes);
     boxes_dev.upload(boxes.data(), boxes.size(), stream);
     YDS_HIP(hipStreamSynchronize(stream));                      // `boxes` is a stack temporary
-    View x0; x0.p = in.p; x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
-    launch_crop_resize(frame_dev, h, w, boxes_dev.p, D, x0, stream);
-    forward(D);
+    ReidFront front;
+    front.frames = frame_dev; front.h = h; front.w = w; front.boxes = boxes_dev.p;
+    forward(D, &front);
     if (out_host) YDS_HIP(hipMemcpyAsync(out_host, feat.p, (size_t)D * EMB * sizeof(float), hipMemcpyDeviceToHost, stream));
     // always complete before returning: the caller hands `feat` to the tracker, which runs on its own non-blocking
     // stream and would otherwise read features of a pass that is still in flight
@@ -243,12 +265,12 @@ void ReidNet::embed_multi_dev(const uint8_t *frames_dev, int h, int w, const flo
                               const FrameGeom *geom, int n_geom) {
     if (D == 0) return;
     if (!ready) fail("reid: weights not loaded (yds_reid_finalize)");
-    crop_multi_dev(frames_dev, h, w, tlwh_host, frame_of, D, bgr, geom, n_geom);
-    forward(D);
+    const ReidFront front = stage_crops(frames_dev, h, w, tlwh_host, frame_of, D, bgr, geom, n_geom);
+    forward(D, &front);
 }
 
-void ReidNet::crop_multi_dev(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
-                             const FrameGeom *geom, int n_geom) {
+ReidFront ReidNet::stage_crops(const uint8_t *frames_dev, int h, int w, const float *tlwh_host, const int *frame_of, int D, bool bgr,
+                               const FrameGeom *geom, int n_geom) {
     reserve(D);
     crop_boxes_host(tlwh_host, D, h, w, boxes_host, frame_of, geom, n_geom);
     // the list of a pass with frames of different sizes starts with their table (n_geom entries of 16 bytes), the boxes follow
@@ -269,17 +291,17 @@ void ReidNet::crop_multi_dev(const uint8_t *frames_dev, int h, int w, const floa
     }
     if (geom) memcpy(boxes_pin[t], geom, head * sizeof(int));
     memcpy(boxes_pin[t] + head, boxes_host.data(), boxes_host.size() * sizeof(int));
-    View x0; x0.p = in.p; x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
-    if (geom) launch_crop_resize_frames(frames_dev, reinterpret_cast<const FrameGeom *>(boxes_pin[t]), boxes_pin[t] + head, D, x0, stream, bgr);
-    else launch_crop_resize(frames_dev, h, w, boxes_pin[t], D, x0, stream, bgr);
+    ReidFront front;
+    front.frames = frames_dev; front.h = h; front.w = w; front.bgr = bgr ? 1 : 0;
+    front.geom = geom ? reinterpret_cast<const FrameGeom *>(boxes_pin[t]) : nullptr;
+    front.boxes = boxes_pin[t] + head;
+    return front;
 }
 
 void ReidNet::preprocess_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom, const float *tlwh_host, const int *frame_of,
                                     int D, float *nchw_host) {
     if (D == 0) return;
-    reserve(D);
-    if (!in.p) in.alloc((size_t)max_crops * CROP_H * CROP_W * 4);
-    crop_multi_dev(frames_dev, 0, 0, tlwh_host, frame_of, D, false, geom.data(), (int)geom.size());
+    crop_into_in(stage_crops(frames_dev, 0, 0, tlwh_host, frame_of, D, false, geom.data(), (int)geom.size()), D);
     View x3; x3.p = in.p; x3.n = D; x3.h = CROP_H; x3.w = CROP_W; x3.c = 3; x3.ld = 4;
     DevBuf<float> tmp((size_t)D * 3 * CROP_H * CROP_W);
     launch_nhwc_to_nchw(x3, tmp.p, stream);
@@ -298,7 +320,6 @@ void ReidNet::embed_host(const uint8_t *frame_host, int h, int w, const float *t
 void ReidNet::preprocess_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *nchw_host) {
     if (D == 0) return;
     reserve(D);
-    if (!in.p) in.alloc((size_t)max_crops * CROP_H * CROP_W * 4);
     size_t n = (size_t)h * w * 3;
     stage_u8.ensure(n);
     YDS_HIP(hipMemcpyAsync(stage_u8.p, frame_host, n, hipMemcpyHostToDevice, stream));
@@ -306,7 +327,7 @@ void ReidNet::preprocess_host(const uint8_t *frame_host, int h, int w, const flo
     crop_boxes_host(tlwh_host, D, h, w, boxes);
     boxes_dev.upload(boxes.data(), boxes.size(), stream);
     YDS_HIP(hipStreamSynchronize(stream));
-    View x0; x0.p = in.p; x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
+    View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
     launch_crop_resize(stage_u8.p, h, w, boxes_dev.p, D, x0, stream);
     View x3 = x0; x3.c = 3;
     DevBuf<float> tmp((size_t)D * 3 * CROP_H * CROP_W);
@@ -322,7 +343,7 @@ void ReidNet::forward_f32_host(const float *nchw, int D, float *out_host) {
     size_t n = (size_t)D * 3 * CROP_H * CROP_W;
     stage_f32.ensure(n);
     YDS_HIP(hipMemcpyAsync(stage_f32.p, nchw, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    View x0; x0.p = in.p; x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
+    View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
     launch_nchw_to_nhwc(stage_f32.p, x0, 3, stream);
     forward(D);
     YDS_HIP(hipMemcpyAsync(out_host, feat.p, (size_t)D * EMB * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -375,6 +396,24 @@ int yds_reid_preprocess_mixed(yds_reid *r, const uint8_t *frames_dev, const uint
     YDS_API_BEGIN
     if (!frames_dev) yds::fail("reid: NULL frames");
     r->r->preprocess_frames_dev(frames_dev, yds::checked_layout(frame_off, frame_hw, n_frames, frames_bytes), tlwh, frame_of, D, nchw);
+    YDS_API_END
+}
+int yds_reid_embed_mixed(yds_reid *r, const uint8_t *frames_dev, const uint64_t *frame_off, const int32_t *frame_hw, int n_frames,
+                         size_t frames_bytes, const float *tlwh, const int32_t *frame_of, int D, int bgr, float *out) {
+    YDS_API_BEGIN
+    if (!frames_dev) yds::fail("reid: NULL frames");
+    if (D < 1) return 0;
+    const std::vector<yds::FrameGeom> geom = yds::checked_layout(frame_off, frame_hw, n_frames, frames_bytes);
+    yds::ReidNet &net = *r->r;
+    net.embed_multi_dev(frames_dev, 0, 0, tlwh, frame_of, D, bgr != 0, geom.data(), (int)geom.size());
+    YDS_HIP(hipMemcpyAsync(out, net.feat.p, (size_t)D * 512 * sizeof(float), hipMemcpyDeviceToHost, net.stream));
+    YDS_HIP(hipStreamSynchronize(net.stream));
+    YDS_API_END
+}
+int yds_reid_front_fused(yds_reid *r) { return r && r->r->front_fused_last ? 1 : 0; }
+int yds_reid_front_grid_crops(void) {
+    YDS_API_BEGIN
+    return yds::reid_stem_grid() / yds::kReidStemUnitsPerCrop;
     YDS_API_END
 }
 int yds_reid_forward_f32(yds_reid *r, const float *nchw, int D, float *out) {

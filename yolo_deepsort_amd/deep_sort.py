@@ -83,6 +83,27 @@ class Extractor:
             dev.free()
         return out
 
+    def embed_mixed(self, frames, tlwh, frame_of, bgr=False):
+        """embed() over several frames of different sizes resident in HBM (parity tests, yds_reid_embed_mixed): the ReID pass of a
+        pipeline step, detections as in preprocess_mixed; bgr: the frames hold B, G, R bytes."""
+        from .pipeline import pack_frames
+        block, off, hw = pack_frames(frames)
+        tlwh = _np(tlwh).reshape(-1, 4)
+        frame_of = np.ascontiguousarray(frame_of, dtype=np.int32).reshape(-1)
+        assert frame_of.size == tlwh.shape[0]
+        out = np.empty((tlwh.shape[0], 512), np.float32)
+        dev = _lib.DeviceBuffer.from_array(block)
+        try:
+            _lib.check(_lib.load().yds_reid_embed_mixed(self._h, dev.ptr, _lib.ptr(off), _lib.ptr(hw), len(off), block.nbytes,
+                                                        _lib.ptr(tlwh), _lib.ptr(frame_of), tlwh.shape[0], 1 if bgr else 0, _lib.ptr(out)))
+        finally:
+            dev.free()
+        return out
+
+    def front_fused(self):
+        """True when the last pass began with the fused front-end kernel (parity tests)."""
+        return bool(_lib.load().yds_reid_front_fused(self._h))
+
     def forward(self, batch):
         batch = _np(batch)
         out = np.empty((batch.shape[0], 512), np.float32)
