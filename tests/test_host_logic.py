@@ -746,3 +746,65 @@ def test_bench_dump_outputs_layout(tmp_path):
     assert r.dtype == c.dtype == np.float64
     assert c.tolist() == [[1, -1, 0], [2, -1, -1]]
     assert r.tolist() == [[0, 0, 1, 2, 3, 4, 7, 0], [1, 0, 0, 1, 2, 3, 4, 5], [1, 0, 6, 7, 8, 9, 10, 11]]
+
+
+_PACK_MAIN = r"""
+#include "conv_pack.h"
+#include <stdio.h>
+#include <stdlib.h>
+// naive triple loop over (filter, k position, padded channel): every element of every row, padding included
+static int check(int cout, int cin_file, int cin, int k, int want_kpad, bool scaled) {
+    std::vector<float> w((size_t)cout * cin_file * k * k);
+    std::vector<double> scale(cout);
+    unsigned s = 7u + cout;
+    for (auto &v : w) { s = s * 1664525u + 1013904223u; v = ((s >> 8) & 0xffff) / 32768.f - 1.f; }
+    for (int o = 0; o < cout; ++o) scale[o] = 0.5 + o / 3.0;
+    std::vector<float> rows(5, 123.f);
+    yds::pack_conv_rows(w.data(), cout, cin_file, cin, k, scaled ? scale.data() : nullptr, rows);
+    const int kpad = yds::conv_kpad(k, cin);
+    if (kpad != want_kpad || rows.size() != (size_t)cout * kpad) return 1;
+    int bad = 0;
+    for (int o = 0; o < cout; ++o)
+        for (int t = 0; t < k * k; ++t)
+            for (int c = 0; c < cin; ++c) {
+                const float src = c < cin_file ? w[(((size_t)o * cin_file + c) * k + t / k) * k + t % k] : 0.f;
+                const float want = scaled ? (float)((double)src * scale[o]) : src;
+                bad += rows[(size_t)o * kpad + t * cin + c] != want;
+            }
+    for (int o = 0; o < cout; ++o)
+        for (int j = k * k * cin; j < kpad; ++j) bad += rows[(size_t)o * kpad + j] != 0.f;
+    // weights already in k order: the rows of the unscaled pack without their padding give the same rows back
+    if (!scaled && cin == cin_file) {
+        std::vector<float> kord, again;
+        for (int o = 0; o < cout; ++o) kord.insert(kord.end(), rows.begin() + (size_t)o * kpad, rows.begin() + (size_t)o * kpad + k * k * cin);
+        yds::pack_conv_rows_korder(kord.data(), cout, cin, k, again);
+        bad += again != rows;
+    }
+    return bad;
+}
+int main() {
+    int bad = 0;
+    for (int scaled = 0; scaled < 2; ++scaled) {
+        bad += check(5, 3, 4, 3, 64, scaled);       // K = 36, the image's padded channel
+        bad += check(255, 8, 8, 1, 32, scaled);     // most of the row is padding
+        bad += check(2, 32, 32, 3, 288, scaled);    // K = 288 = kpad: no padding
+    }
+    printf("bad %d\n", bad);
+    return bad ? 1 : 0;
+}
+"""
+
+
+def test_conv_weight_packer_under_sanitizers(tmp_path):
+    """csrc/conv_pack.h (plain C++, what ConvWeights::upload runs before the copies) in a stand-alone program built with
+    AddressSanitizer and UBSan: index mapping, zero padding and the per-filter scale against a naive loop, element for element."""
+    import shutil
+    cxx = shutil.which("g++")
+    assert cxx, "g++ not found"
+    csrc = os.path.join(ROOT, "yolo_deepsort_amd", "csrc")
+    src, exe = tmp_path / "pack_main.cpp", tmp_path / "pack_main"
+    src.write_text(_PACK_MAIN)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc, str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "bad 0", (out.stdout, out.stderr)

@@ -136,6 +136,7 @@ void launch_copy(const View &x, const View &y, hipStream_t s);                 /
 void launch_add(const View &a, const View &b, const View &y, hipStream_t s);
 void launch_nchw_to_nhwc(const float *src_nchw, const View &y, int c_src, hipStream_t s);   // pads channels with 0
 void launch_nhwc_to_nchw(const View &x, float *dst_nchw, hipStream_t s);   // decodes H16 views
+void nhwc_to_host(const View &x, float *dst_nchw_host, hipStream_t s);     // launch_nhwc_to_nchw + copy to the host; returns when it is there
 void launch_pack_h16(const float *src_f32, const View &y, hipStream_t s);   // fp32 NHWC (ld = c) -> H16 view (tests / tools)
 // yolo decode: head NHWC [n,h,w,A*(5+C)] -> out[n, box_off + a*h*w + y*w + x, 5+C]
 void launch_yolo_decode(const View &head, float *out, int total_boxes, int box_off, int num_classes,

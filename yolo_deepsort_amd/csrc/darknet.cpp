@@ -49,6 +49,12 @@ std::vector<CfgBlock> parse_cfg(const std::string &text) {
     return blocks;
 }
 
+static LayerType layer_type(const std::string &section) {
+    static const char *const kSections[] = {"convolutional", "maxpool", "upsample", "route", "shortcut", "yolo"};     // in LayerType order
+    for (int t = L_CONV; t <= L_YOLO; ++t)
+        if (section == kSections[t]) return (LayerType)t;
+    fail("cfg: unsupported section [%s]", section.c_str());
+}
 static int geti(const CfgBlock &b, const char *k) {
     auto it = b.kv.find(k);
     if (it == b.kv.end()) fail("cfg: [%s] lacks '%s'", b.type.c_str(), k);
@@ -81,27 +87,22 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
     };
     // ---- pass 1: shapes, operators, references
     int pc = 4, ph = img_h, pw = img_w;   // previous layer's logical shape (input is channel-padded to 4)
-    int prev_c_logical = in_channels;
-    (void)prev_c_logical;
     for (int i = 0; i < L; ++i) {
         Layer &l = layers[i];
         const CfgBlock &b = blocks[i];
-        l.type = b.type;
+        l.type = layer_type(b.type);
         l.root = i;
-        if (b.type == "convolutional") {
+        if (l.type == L_CONV) {
             l.bn = geti(b, "batch_normalize");
-            l.ksize = geti(b, "size");
-            l.stride = geti(b, "stride");
-            l.pad = (l.ksize - 1) / 2;                       // models.py:39, cfg 'pad' ignored
-            l.cin = pc;
-            l.cin_file = i == 0 ? in_channels : pc;
+            const int k = geti(b, "size"), stride = geti(b, "stride"), pad = (k - 1) / 2;      // models.py:39, cfg 'pad' ignored
             l.c = geti(b, "filters");
-            l.h = (ph + 2 * l.pad - l.ksize) / l.stride + 1;
-            l.w = (pw + 2 * l.pad - l.ksize) / l.stride + 1;
+            l.cw.shape(l.c, i == 0 ? in_channels : pc, pc, k, stride, pad);                   // (the image is channel-padded: 3 -> 4)
+            l.h = (ph + 2 * pad - k) / stride + 1;
+            l.w = (pw + 2 * pad - k) / stride + 1;
             std::string act = b.kv.count("activation") ? b.kv.at("activation") : "linear";
             l.act = act == "leaky" ? ACT_LEAKY : act == "mish" ? ACT_MISH : ACT_LINEAR;   // models.py:53-56
             l.src = i - 1;
-        } else if (b.type == "maxpool") {
+        } else if (l.type == L_MAXPOOL) {
             l.ksize = geti(b, "size");
             l.stride = geti(b, "stride");
             l.c = pc;
@@ -116,13 +117,13 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
                 l.w = (pw + 2 * l.pad - l.ksize) / l.stride + 1;
             }
             l.src = i - 1;
-        } else if (b.type == "upsample") {
+        } else if (l.type == L_UPSAMPLE) {
             l.stride = geti(b, "stride");
             l.c = pc;
             l.h = ph * l.stride;
             l.w = pw * l.stride;
             l.src = i - 1;
-        } else if (b.type == "route") {
+        } else if (l.type == L_ROUTE) {
             for (int r : get_list(b, "layers")) l.refs.push_back(resolve(r, i));
             l.c = 0;
             for (int j : l.refs) {
@@ -137,13 +138,13 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
                 if (l.c % l.groups) fail("cfg: route %d groups do not divide channels", i);
                 l.c /= l.groups;
             }
-        } else if (b.type == "shortcut") {
+        } else if (l.type == L_SHORTCUT) {
             l.refs = {i - 1, resolve(geti(b, "from"), i)};
             l.c = layers[l.refs[1]].c;
             l.h = ph;
             l.w = pw;
             if (layers[l.refs[0]].c != l.c || layers[l.refs[1]].h != ph) fail("cfg: shortcut %d shape mismatch", i);
-        } else if (b.type == "yolo") {
+        } else {                                             // L_YOLO
             auto mask = get_list(b, "mask");
             auto an = get_list(b, "anchors");
             for (int m : mask) {
@@ -160,8 +161,6 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
             l.box_off = total_boxes;
             total_boxes += (int)mask.size() * ph * pw;
             yolo_layers.push_back(i);
-        } else {
-            fail("cfg: unsupported section [%s]", b.type.c_str());
         }
         pc = l.c; ph = l.h; pw = l.w;
     }
@@ -177,7 +176,7 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
     }
     for (int i = 1; i < L; ++i) {
         Layer &l = layers[i];
-        if (l.type == "shortcut" && layers[i - 1].type == "convolutional" && readers[i - 1] == 1 && l.refs[1] != i - 1) {
+        if (l.type == L_SHORTCUT && layers[i - 1].type == L_CONV && readers[i - 1] == 1 && l.refs[1] != i - 1) {
             layers[i - 1].fused_res = l.refs[1];
             l.fused = true;
             l.root = i - 1;          // view of the conv's (post-add) buffer
@@ -185,23 +184,22 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
         }
     }
     // the first two convolutions can run as one kernel (conv_stem2.hip) when only layer 1 reads layer 0
-    stem_fusable = L >= 2 && layers[0].type == "convolutional" && layers[1].type == "convolutional" && readers[0] == 1 &&
+    stem_fusable = L >= 2 && layers[0].type == L_CONV && layers[1].type == L_CONV && readers[0] == 1 &&
                    layers[1].src == 0 && layers[0].fused_res < 0 && layers[1].fused_res < 0;
     // ... and so can the first residual block (conv_block1.hip): conv a (read only by conv b), conv b absorbing the
     // shortcut back to conv a's input
     for (int i = 1; i + 1 < L && block1_at < 0; ++i)
-        if (layers[i].type == "convolutional" && layers[i + 1].type == "convolutional" && readers[i] == 1 && layers[i + 1].src == i &&
-            layers[i].fused_res < 0 && layers[i + 1].fused_res >= 0 && layers[i + 1].fused_res == layers[i].src && layers[i].ksize == 1 &&
-            layers[i + 1].ksize == 3)
+        if (layers[i].type == L_CONV && layers[i + 1].type == L_CONV && readers[i] == 1 && layers[i + 1].src == i &&
+            layers[i].fused_res < 0 && layers[i + 1].fused_res >= 0 && layers[i + 1].fused_res == layers[i].src && layers[i].cw.ksize == 1 &&
+            layers[i + 1].cw.ksize == 3)
             block1_at = i;
     // single-source routes are views
     for (int i = 0; i < L; ++i) {
         Layer &l = layers[i];
-        if (l.type == "route" && l.refs.size() == 1) {
+        if (l.type == L_ROUTE && l.refs.size() == 1) {
             const Layer &s = layers[l.refs[0]];
             l.root = s.root;
             l.coff = s.coff + (l.groups ? l.group_id * l.c : 0);
-            l.is_view = true;
         }
     }
     // ---- pass 3: storage.  Producers own [batch_max, h, w, ld] buffers; a multi-source route owns the
@@ -209,11 +207,11 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
     storage.resize(L);
     auto is_producer = [&](int j) {
         const Layer &s = layers[j];
-        return s.root == j && (s.type == "convolutional" || s.type == "maxpool" || s.type == "upsample" || (s.type == "shortcut" && !s.fused));
+        return s.root == j && (s.type == L_CONV || s.type == L_MAXPOOL || s.type == L_UPSAMPLE || (s.type == L_SHORTCUT && !s.fused));
     };
     for (int i = 0; i < L; ++i) {
         Layer &l = layers[i];
-        if (!(l.type == "route" && l.refs.size() > 1)) continue;
+        if (!l.concat()) continue;
         int ctot = 0;
         for (int j : l.refs) ctot += layers[j].c;
         if (ctot % 4) continue;                               // keep float4 alignment; falls back to a copy
@@ -240,7 +238,7 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
     math = conv_math();
     std::vector<char> h16_ok(L, math == MATH_F16X3 ? 1 : 0);
     for (int j = 0; j < L; ++j) {
-        if (layers[j].type == "yolo") continue;
+        if (layers[j].type == L_YOLO) continue;
         int off = 0, o = owner_of(j, off);
         if (off % 32 || layers[j].c % 32) h16_ok[o] = 0;
     }
@@ -253,7 +251,7 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
             }
     for (int i = 0; i < L; ++i) {
         Layer &l = layers[i];
-        bool owns = (is_producer(i) && !storage[i].redirected) || (l.type == "route" && l.refs.size() > 1);
+        bool owns = (is_producer(i) && !storage[i].redirected) || l.concat();
         if (!owns) continue;
         if (storage[i].ld == 0) storage[i].ld = (l.c + 3) / 4 * 4;
         storage[i].fmt = (h16_ok[i] && storage[i].ld % 32 == 0) ? FMT_H16 : FMT_F32;
@@ -266,10 +264,10 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
         Layer &a = layers[i];
         const Layer &r = layers[i + 1];
         Layer &b = layers[i + 2];
-        if (a.type != "convolutional" || b.type != "convolutional" || r.type != "route" || r.refs.size() != 1 || r.groups) continue;
+        if (a.type != L_CONV || b.type != L_CONV || r.type != L_ROUTE || r.refs.size() != 1 || r.groups) continue;
         if (a.src < 0 || r.refs[0] != a.src || b.src != i + 1) continue;
-        if (a.ksize != 1 || b.ksize != 1 || a.stride != 1 || b.stride != 1 || a.act != b.act || a.fused_res >= 0 || b.fused_res >= 0) continue;
-        if (a.merged_into >= 0 || a.merge_next >= 0 || a.cin != b.cin) continue;
+        if (a.cw.ksize != 1 || b.cw.ksize != 1 || a.cw.stride != 1 || b.cw.stride != 1 || a.act != b.act || a.fused_res >= 0 || b.fused_res >= 0) continue;
+        if (a.merged_into >= 0 || a.merge_next >= 0 || a.cw.cin != b.cw.cin) continue;
         if ((int)i == block1_at || (int)i + 2 == block1_at || i + 2 == (int)block1_at + 1) continue;      // (the fused first block keeps its own kernel)
         int oa = 0, ob = 0;
         const int sa = owner_of(i, oa), sb = owner_of(i + 2, ob);
@@ -284,7 +282,7 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
 
 int Darknet::owner_of(int j, int &off) const {
     const Layer &l = layers[j];
-    if (l.type == "route" && l.refs.size() > 1) { off = 0; return j; }
+    if (l.concat()) { off = 0; return j; }
     int r = l.root;
     if (storage[r].redirected) { off = storage[r].coff + l.coff; return storage[r].into; }
     off = l.coff;
@@ -311,7 +309,7 @@ void Darknet::plan_half_formats() {
     for (int i = 0; i < L; ++i) ok[i] = storage[i].owns && storage[i].fmt == FMT_H16 && storage[i].ld % 64 == 0;
     auto own = [&](int j) { int off = 0; return owner_of(j, off); };
     for (int j = 0; j < L; ++j) {
-        if (layers[j].type == "yolo") continue;
+        if (layers[j].type == L_YOLO) continue;
         int off = 0, o = owner_of(j, off);
         if (o >= 0 && (off % 64 || layers[j].c % 64)) ok[o] = 0;
     }
@@ -324,9 +322,9 @@ void Darknet::plan_half_formats() {
         for (int i = 0; i < L; ++i) {
             const Layer &l = layers[i];
             for (auto &cp : l.copies) tie(own(cp.first), i);
-            if (l.type == "convolutional" && l.fused_res >= 0) tie(own(i), own(l.fused_res));
-            if (l.type == "convolutional" && l.merge_next >= 0) tie(own(i), own(l.merge_next));
-            if (l.type == "upsample") tie(own(i), own(l.src));
+            if (l.type == L_CONV && l.fused_res >= 0) tie(own(i), own(l.fused_res));
+            if (l.type == L_CONV && l.merge_next >= 0) tie(own(i), own(l.merge_next));
+            if (l.type == L_UPSAMPLE) tie(own(i), own(l.src));
             if (i == block1_at && l.src >= 0) tie(own(l.src), own(i + 1));
         }
         if (!changed) break;
@@ -340,25 +338,22 @@ void Darknet::set_half(bool on) {
     YDS_HIP(hipStreamSynchronize(stream));
     half_mode = on;
     plan_half_formats();
-    stem_checked_reset();
+    ++plan_epoch;
 }
 
 // Everything whose size depends on batch_max.  set_batch_max() re-runs it inside the SAME object, so handles held by
 // others (a pipeline, the Python wrapper) stay valid when a caller later sends a larger batch.
 void Darknet::allocate_buffers() {
-    size_t total_floats = 0;
     for (size_t i = 0; i < layers.size(); ++i) {
         if (!storage[i].owns) continue;
         const Layer &l = layers[i];
         size_t n = (size_t)batch_max * l.h * l.w * storage[i].ld;
         storage[i].buf.alloc(n);
         YDS_HIP(hipMemsetAsync(storage[i].buf.p, 0, n * sizeof(float), stream));
-        total_floats += n;
     }
     input.alloc((size_t)batch_max * img_h * img_w * 4);
     out.alloc((size_t)batch_max * total_boxes * attrs);
     stage_f32.alloc((size_t)batch_max * img_h * img_w * 4);
-    activation_bytes = total_floats * sizeof(float);
     YDS_HIP(hipStreamSynchronize(stream));
     inject_rows.clear();
     inject_rows.resize(batch_max);
@@ -366,7 +361,7 @@ void Darknet::allocate_buffers() {
     inject_active = false;                                       // injection tables are laid out per batch slot
     inject_offsets.clear();
     inject_set = -1;
-    stem_checked = block1_checked = -1;
+    ++plan_epoch;                                                // (the plan's fusion checks looked at the old buffers)
     stage_n = 0;
 }
 
@@ -384,16 +379,16 @@ Darknet::~Darknet() {
     if (stream) (void)hipStreamDestroy(stream);
 }
 
-View Darknet::view(int i, int batch) const {
+View Darknet::view(int i, int batch, int first) const {
     const Layer &l = layers[i];
     int r = l.root;
     View v;
     v.n = batch; v.h = l.h; v.w = l.w; v.c = l.c;
     // (strides and channel offsets of an F16 buffer count float slots: half the channels, h16.h)
-    if (l.type == "route" && l.refs.size() > 1) {
+    if (l.concat()) {
         v.fmt = half_mode ? storage[i].fmt_half : storage[i].fmt;
         v.p = storage[i].buf.p; v.ld = fmt_slots(v.fmt, storage[i].ld);
-        v.p += (size_t)lane_img0 * l.h * l.w * v.ld;
+        v.p += (size_t)first * l.h * l.w * v.ld;
         return v;
     }
     const Storage &st = storage[r];
@@ -407,127 +402,161 @@ View Darknet::view(int i, int batch) const {
         v.p = st.buf.p + fmt_slots(v.fmt, l.coff);
         v.ld = fmt_slots(v.fmt, st.ld);
     }
-    v.p += (size_t)lane_img0 * l.h * l.w * v.ld;                // image range of the lane being enqueued (run_graph)
+    v.p += (size_t)first * l.h * l.w * v.ld;
     return v;
 }
 
-View Darknet::input_view(int batch) const {
+View Darknet::input_view(int batch, int first) const {
     View v;
-    v.p = input.p + (size_t)lane_img0 * img_h * img_w * 4; v.n = batch; v.h = img_h; v.w = img_w; v.c = 4; v.ld = 4;
+    v.p = input.p + (size_t)first * img_h * img_w * 4; v.n = batch; v.h = img_h; v.w = img_w; v.c = 4; v.ld = 4;
     return v;
 }
 
 // --------------------------------------------------------------------------------------- weights
-size_t Darknet::weight_floats() const {
-    size_t n = 0;
-    for (const Layer &l : layers)
-        if (l.type == "convolutional") n += (size_t)(l.bn ? 4 : 1) * l.c + (size_t)l.c * l.cin_file * l.ksize * l.ksize;
-    return n;
-}
-
 void Darknet::load_weights(const void *blob, size_t nbytes, int cutoff) {
     // models.py:315-366: 5 x int32 header, then per conv: [beta, gamma, mean, var] | [bias], then W[cout][cin][k][k]
     if (nbytes < 20) fail("weights: blob shorter than the 20-byte header");
     const float *w = reinterpret_cast<const float *>(static_cast<const char *>(blob) + 20);
     size_t avail = (nbytes - 20) / 4, ptr = 0;
-    memcpy(header, blob, 20);
+    ++plan_epoch;                                                // (up here: a load that fails half way leaves no plan of the old weights)
+    for (Layer &l : layers) l.cw_merged.release();
+    // a load replaces the weights of the whole net: what the file does not reach, past `cutoff`, has none afterwards
     for (int i = 0; i < (int)layers.size(); ++i) {
-        if (cutoff >= 0 && i == cutoff) break;
         Layer &l = layers[i];
-        if (l.type != "convolutional") continue;
-        const int co = l.c, ci = l.cin_file, k = l.ksize;
-        size_t need = (size_t)(l.bn ? 4 : 1) * co + (size_t)co * ci * k * k;
+        if (l.type != L_CONV) continue;
+        if (cutoff >= 0 && i >= cutoff) { l.cw.release(); continue; }
+        const int co = l.c;
+        const size_t nw = (size_t)co * l.cw.cin_file * l.cw.ksize * l.cw.ksize, need = (size_t)(l.bn ? 4 : 1) * co + nw;
         if (ptr + need > avail) fail("weights: file too short at layer %d (need %zu more floats, have %zu)", i, need, avail - ptr);
         std::vector<double> scale(co, 1.0);
         std::vector<float> bias(co);
         if (l.bn) {
             const float *beta = w + ptr, *gamma = beta + co, *mean = gamma + co, *var = mean + co;
-            ptr += 4 * (size_t)co;
             for (int o = 0; o < co; ++o) {
                 scale[o] = (double)gamma[o] / sqrt((double)var[o] + 1e-5);      // BatchNorm2d eps=1e-5, models.py:52
                 bias[o] = (float)((double)beta[o] - (double)mean[o] * scale[o]);
             }
         } else {
             for (int o = 0; o < co; ++o) bias[o] = w[ptr + o];
-            ptr += co;
         }
-        const int cin_p = l.cin;                             // channel-padded input (3 -> 4 for the image)
-        const int K = k * k * cin_p;
-        l.kpad = (K + 31) / 32 * 32;
-        std::vector<float> packed((size_t)co * l.kpad, 0.f);
-        const float *src = w + ptr;
-        for (int o = 0; o < co; ++o)
-            for (int c = 0; c < ci; ++c)
-                for (int kh = 0; kh < k; ++kh)
-                    for (int kw = 0; kw < k; ++kw)
-                        packed[(size_t)o * l.kpad + (kh * k + kw) * cin_p + c] =
-                            (float)((double)src[(((size_t)o * ci + c) * k + kh) * k + kw] * scale[o]);
-        ptr += (size_t)co * ci * k * k;
-        l.wt.upload(packed.data(), packed.size(), stream);
-        {
-            std::vector<uint16_t> split;
-            pack_weights_f16x3(packed.data(), co, l.kpad, split);
-            l.wt16.upload(split.data(), split.size(), stream);
-            YDS_HIP(hipStreamSynchronize(stream));
-        }
-        l.bias.upload(bias.data(), bias.size(), stream);
-        YDS_HIP(hipStreamSynchronize(stream));
-        l.loaded = true;
+        ptr += (size_t)(l.bn ? 4 : 1) * co;
+        l.cw.upload(w + ptr, scale.data(), bias.data(), stream);
+        ptr += nw;
     }
-    // concatenated filter sets of the CSP splits (device-to-device: [a's filters ; b's filters], same K)
-    for (int i = 0; i < (int)layers.size(); ++i) {
-        Layer &a = layers[i];
+    // concatenated filter sets of the CSP splits, while both convolutions have weights
+    for (Layer &a : layers) {
         if (a.merge_next < 0) continue;
-        Layer &b = layers[a.merge_next];
-        if (!a.loaded || !b.loaded || a.kpad != b.kpad) { a.merge_next = -1; b.merged_into = -1; continue; }
-        const size_t na = (size_t)a.c * a.kpad, nb = (size_t)b.c * b.kpad;
-        a.wt_m.alloc(na + nb); a.wt16_m.alloc(2 * (na + nb)); a.bias_m.alloc((size_t)a.c + b.c);
-        YDS_HIP(hipMemcpyAsync(a.wt_m.p, a.wt.p, na * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipMemcpyAsync(a.wt_m.p + na, b.wt.p, nb * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipMemcpyAsync(a.wt16_m.p, a.wt16.p, na * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipMemcpyAsync(a.wt16_m.p + 2 * na, b.wt16.p, nb * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipMemcpyAsync(a.bias_m.p, a.bias.p, (size_t)a.c * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipMemcpyAsync(a.bias_m.p + a.c, b.bias.p, (size_t)b.c * 4, hipMemcpyDeviceToDevice, stream));
-        YDS_HIP(hipStreamSynchronize(stream));
+        const Layer &b = layers[a.merge_next];
+        if (a.cw.loaded() && b.cw.loaded()) a.cw_merged = ConvWeights::concat(a.cw, b.cw, stream);
     }
-    weights_loaded = true;
 }
 
 // --------------------------------------------------------------------------------------- forward
-ConvArgs Darknet::conv_args(int i, int batch) const {
+ConvArgs Darknet::conv_args(int i, int batch, int first, bool merged) const {
     const Layer &l = layers[i];
     ConvArgs a;
-    a.x = l.src < 0 ? input_view(batch) : view(l.src, batch);
-    a.y = view(i, batch);
-    a.w = l.wt.p; a.bias = l.bias.p; a.w16 = l.wt16.p;
-    a.ksize = l.ksize; a.stride = l.stride; a.pad = l.pad; a.kpad = l.kpad;
+    a.x = l.src < 0 ? input_view(batch, first) : view(l.src, batch, first);
+    a.y = view(i, batch, first);
+    l.cw.fill(a);
     a.act = l.act;
-    if (l.fused_res >= 0) { a.res = view(l.fused_res, batch); a.res_mode = RES_AFTER_ACT; }
+    if (l.fused_res >= 0) { a.res = view(l.fused_res, batch, first); a.res_mode = RES_AFTER_ACT; }
     a.terms = half_mode ? 1 : 3;
+    if (merged) {                                                // both convolutions of a CSP split: the partner's filters follow
+        a.y2 = view(l.merge_next, batch, first);
+        a.n_split = a.y.c;
+        a.y.c = a.y.c + a.y2.c;                                  // (pointer, stride and format stay those of the first output)
+        l.cw_merged.fill(a);
+    }
     return a;
 }
 
-ConvArgs Darknet::merged_conv_args(int i, int batch) const {
-    const Layer &l = layers[i];
-    ConvArgs a = conv_args(i, batch);
-    const ConvArgs b = conv_args(l.merge_next, batch);
-    a.y2 = b.y;
-    a.n_split = a.y.c;
-    a.y.c = a.y.c + b.y.c;                                       // (pointer, stride and format stay those of the first output)
-    a.w = l.wt_m.p; a.w16 = l.wt16_m.p; a.bias = l.bias_m.p;
-    return a;
+// What a pass costs, launch by launch.  The static plan (constructor) says what may be fused or merged; whether it is depends on the
+// batch (the fused kernels' own applicability checks see the views), on half mode (tensor formats), on the weights that are there and
+// on the conv math - the key the list is cached on.
+const LaunchPlan &Darknet::plan(int batch) {
+    LaunchPlan &p = plan_;
+    if (p.batch == batch && p.math == conv_math() && p.epoch == plan_epoch) return p;
+    p.batch = batch; p.math = conv_math(); p.epoch = plan_epoch;
+    p.steps.clear();
+    p.produced_by.assign(layers.size(), -1);
+    static const bool no_stem = getenv("YDS_NO_STEM_FUSE") != nullptr, no_block = getenv("YDS_NO_BLOCK_FUSE") != nullptr;
+    const bool f16x3 = p.math == MATH_F16X3;
+    auto has_w = [&](int i) { return layers[i].cw.loaded(); };
+    auto kargs = [&](int i) { return make_conv_args(conv_args(i, batch)); };
+    // (half mode keeps the fused kernels: they compute the first layers in the default arithmetic, which half mode does anyway)
+    const bool stem = !no_stem && stem_fusable && f16x3 && has_w(0) && has_w(1) && view(1, batch).fmt != FMT_F32 &&
+                      conv_stem2_applicable(kargs(0), kargs(1));
+    const bool block1 = !no_block && block1_at >= 0 && f16x3 && has_w(block1_at) && has_w(block1_at + 1) &&
+                        conv_block1_applicable(kargs(block1_at), kargs(block1_at + 1));
+    int heads = 0;
+    auto add = [&](Step::Kind kind, int layer) -> Step & {
+        p.produced_by[layer] = (int)p.steps.size();
+        p.steps.push_back(Step{kind, layer});
+        return p.steps.back();
+    };
+    for (int i = 0; i < (int)layers.size(); ++i) {
+        const Layer &l = layers[i];
+        switch (l.type) {
+        case L_CONV:
+            if (l.merged_into >= 0 && layers[l.merged_into].cw_merged.loaded()) p.produced_by[i] = p.produced_by[l.merged_into];
+            else if ((i == 0 && stem) || (i == block1_at && block1)) break;       // computed inside the next layer's launch, never written
+            else if (i == 1 && stem) add(Step::CONV_STEM2, i);
+            else if (i == block1_at + 1 && block1) add(Step::CONV_BLOCK1, i);
+            else add(l.cw_merged.loaded() ? Step::CONV_MERGED : Step::CONV, i);
+            break;
+        case L_MAXPOOL: {
+            Step &st = add(Step::MAXPOOL, i);
+            st.src = l.src; st.ksize = l.ksize; st.stride = l.stride; st.pad = l.pad; st.zero_br = l.zero_br;
+            // SPP (yolov4: 5 / 9 / 13, stride 1, all on one tensor): a k x k max with -inf padding is a 5 x 5 max of the
+            // (k-4) x (k-4) max, so a pool whose input already has a (k-4)-pool of the same tensor reads THAT instead -
+            // 25 loads per value instead of 81 / 169, same maxima
+            if (l.stride != 1 || l.zero_br || l.ksize < 9 || l.pad != (l.ksize - 1) / 2) break;
+            for (int j = i - 1; j >= 0; --j) {
+                const Layer &q = layers[j];
+                if (q.type == L_MAXPOOL && q.stride == 1 && !q.zero_br && q.ksize == l.ksize - 4 && q.pad == (q.ksize - 1) / 2 && q.c == l.c &&
+                    layers[q.src].root == layers[l.src].root && layers[q.src].coff == layers[l.src].coff) {
+                    st.src = j; st.ksize = 5; st.pad = 2;
+                    break;
+                }
+            }
+            break;
+        }
+        case L_UPSAMPLE: add(Step::UPSAMPLE, i); break;
+        case L_ROUTE:
+            for (auto &cp : l.copies) {
+                Step &st = add(Step::COPY, i);
+                st.src = cp.first; st.arg = cp.second;
+            }
+            break;
+        case L_SHORTCUT:
+            if (!l.fused) add(Step::ADD, i);
+            break;
+        case L_YOLO: add(Step::YOLO, i).arg = heads++; break;
+        }
+    }
+    return p;
 }
 
 void Darknet::autotune(int batch) {
-    for (int i = 0; i < (int)layers.size(); ++i) {
+    const int mode = conv_math() + (half_mode ? 10 : 0);
+    auto tune = [&](int i, bool merged) {
         Layer &l = layers[i];
-        const int mode = conv_math() + (half_mode ? 10 : 0);
-        if (l.type != "convolutional" || !l.loaded || (l.tuned_batch == batch && l.tuned_math == mode)) continue;
-        if (l.merged_into >= 0 && layers[l.merged_into].wt_m.p) { l.tuned_batch = batch; l.tuned_math = mode; continue; }   // launched by its partner
-        l.variant = conv_autotune(l.merge_next >= 0 && l.wt_m.p ? merged_conv_args(i, batch) : conv_args(i, batch), stream, nullptr);
+        if (!l.cw.loaded() || (l.tuned_batch == batch && l.tuned_math == mode)) return;
+        l.variant = conv_autotune(conv_args(i, batch, 0, merged), stream, nullptr);
         l.tuned_batch = batch;
         l.tuned_math = mode;
+    };
+    for (const Step &st : plan(batch).steps) {
+        if (st.kind > Step::CONV_BLOCK1) continue;              // (the four conv kinds come first)
+        // (the layers of a fused launch are measured on their own too: layer_output_host launches them that way on demand)
+        if (st.kind == Step::CONV_STEM2 || st.kind == Step::CONV_BLOCK1) tune(st.layer - 1, false);
+        tune(st.layer, st.kind == Step::CONV_MERGED);
     }
+}
+
+void Darknet::check_pass(int batch) const {
+    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
+    if (math != conv_math()) fail("forward: this network was planned for conv math %d, current mode is %d (re-create it)", math, conv_math());
 }
 
 // The detector is stateless per image, so a batch is enqueued as LANES independent image ranges on their own streams:
@@ -537,8 +566,7 @@ void Darknet::autotune(int batch) {
 // desynchronised PROCESSES with half the batch each did gain 11 %), so the default is one lane and YDS_DET_LANES opts in.
 // Results are unchanged by the split (every image sees exactly the same kernels).
 void Darknet::run_graph(int batch) {
-    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
-    if (math != conv_math()) fail("forward: this network was planned for conv math %d, current mode is %d (re-create it)", math, conv_math());
+    check_pass(batch);
     int lanes = getenv("YDS_DET_LANES") ? atoi(getenv("YDS_DET_LANES")) : 1;     // opt-in: see the note above
     while (lanes > 1 && batch / lanes < 4) --lanes;             // at least four images per lane
     if (lanes < 1) lanes = 1;
@@ -573,9 +601,9 @@ void Darknet::run_graph(int batch) {
 int Darknet::head_layers() const {
     double total = 0, acc = 0;
     for (int i = 0; i < (int)layers.size(); ++i)
-        if (layers[i].type == "convolutional") total += conv_flops(conv_args(i, 1));
+        if (layers[i].type == L_CONV) total += conv_flops(conv_args(i, 1));
     for (int i = 0; i < (int)layers.size(); ++i) {
-        if (layers[i].type != "convolutional") continue;
+        if (layers[i].type != L_CONV) continue;
         acc += conv_flops(conv_args(i, 1));
         if (acc >= 0.06 * total) return i + 1;
     }
@@ -583,8 +611,7 @@ int Darknet::head_layers() const {
 }
 
 bool Darknet::forward_resized_part(int batch, int part) {
-    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
-    if (math != conv_math()) fail("forward: this network was planned for conv math %d, current mode is %d (re-create it)", math, conv_math());
+    check_pass(batch);
     if (getenv("YDS_DET_LANES") && atoi(getenv("YDS_DET_LANES")) > 1) return false;
     const int cut = head_layers();
     if (part == 0) run_lane(0, batch, stream, 0, cut);
@@ -592,90 +619,78 @@ bool Darknet::forward_resized_part(int batch, int part) {
     return true;
 }
 
+// One conv step: the launch, and - while the per-variant statistics are collected - its event pair and its record.  A fused launch is
+// booked under the variant of the kernel family it belongs to, with the flops of both layers and without the bytes of the tensor
+// that never reaches HBM.
+void Darknet::enqueue_conv(const Step &st, int first, int batch, hipStream_t stream) {
+    const int i = st.layer;
+    const Layer &l = layers[i];
+    if (!l.cw.loaded()) fail("forward: layer %d has no weights (call load_darknet_weights)", i);
+    const ConvArgs a = conv_args(i, batch, first, st.kind == Step::CONV_MERGED);
+    ConvTimeRec rec;
+    if (time_convs) { rec.e0 = timing_event(); rec.e1 = timing_event(); YDS_HIP(hipEventRecord(rec.e0, stream)); }
+    int variant;
+    double extra_flops = 0, extra_bytes = 0;
+    if (st.kind == Step::CONV_STEM2) {
+        const ConvArgs a0 = conv_args(i - 1, batch, first);
+        ConvKernelArgs k0 = make_conv_args(a0), k1 = make_conv_args(a);
+        k1.w = reinterpret_cast<const float *>(a.w16);
+        launch_conv_stem2(k0, k1, stream);
+        variant = VAR_DIRECT_RGB;                           // accounted with the direct first-layer kernel
+        extra_flops = conv_flops(a0);
+        extra_bytes = conv_bytes(a0) - conv_bytes_io(a0.y) - conv_bytes_io(a.x);     // the intermediate tensor never reaches HBM
+    } else if (st.kind == Step::CONV_BLOCK1) {
+        const ConvArgs a2 = conv_args(i - 1, batch, first);
+        ConvKernelArgs k2 = make_conv_args(a2), k3 = make_conv_args(a);
+        k2.w = reinterpret_cast<const float *>(a2.w16);
+        k3.w = reinterpret_cast<const float *>(a.w16);
+        launch_conv_block1(k2, k3, stream);
+        variant = VAR_WIN_256x128;                          // accounted with the window-resident 3x3 kernel
+        extra_flops = conv_flops(a2);
+        // the block input is read once (it is also the residual), the 32-channel intermediate never reaches HBM
+        extra_bytes = conv_bytes(a2) - conv_bytes_io(a2.y) - conv_bytes_io(a.x) - (a.res.p ? conv_bytes_io(a.res) : 0.0);
+    } else {
+        variant = launch_conv(a, stream, l.variant);
+    }
+    if (time_convs) {
+        // no host synchronisation here: the pair is resolved when the counters are read, so the pass runs exactly as it
+        // does untimed (other streams live, the stream fed a pass ahead)
+        YDS_HIP(hipEventRecord(rec.e1, stream));
+        rec.variant = variant;
+        rec.flops = conv_flops(a) + extra_flops;
+        rec.bytes = conv_bytes(a) + extra_bytes;
+        // bound of the arithmetic the launch really used: f16x3 = three fp16 MFMAs per product block; the window kernel's
+        const double peak = conv_math() == MATH_F32 ? 157.3e12 : (a.terms == 1 ? 2500e12 : 2500e12 / 3);
+        rec.attain_us = std::max(rec.flops / peak, rec.bytes / 6.29e12) * 1e6;
+        conv_pending.push_back(rec);
+    }
+}
+
 void Darknet::run_lane(int first, int batch, hipStream_t stream, int l0, int l1) {
     autotune(batch);                                            // (tuning launches use the main stream; cached per image count)
-    lane_img0 = first;
-    struct Reset { int &v; ~Reset() { v = 0; } } reset{lane_img0};
-    if (l1 < 0 || l1 > (int)layers.size()) l1 = (int)layers.size();
-    for (int i = l0; i < l1; ++i) {
-        Layer &l = layers[i];
-        if (l.type == "convolutional") {
-            if (!l.loaded) fail("forward: layer %d has no weights (call load_darknet_weights)", i);
-            if (l.merged_into >= 0 && layers[l.merged_into].wt_m.p) continue;   // computed by the first convolution of the CSP split
-            ConvArgs a = l.merge_next >= 0 && l.wt_m.p ? merged_conv_args(i, batch) : conv_args(i, batch);
-            if (i == 0 && stem_fused(batch)) continue;              // computed inside layer 1's launch
-            if (i == block1_at && block1_fused(batch)) continue;    // computed inside the next layer's launch
-            ConvTimeRec rec;
-            if (time_convs) { rec.e0 = timing_event(); rec.e1 = timing_event(); YDS_HIP(hipEventRecord(rec.e0, stream)); }
-            int variant;
-            double extra_flops = 0, extra_bytes = 0;
-            if (i == 1 && stem_fused(batch)) {
-                ConvArgs a0 = conv_args(0, batch);
-                ConvKernelArgs k0 = make_conv_args(a0), k1 = make_conv_args(a);
-                k1.w = reinterpret_cast<const float *>(a.w16);
-                launch_conv_stem2(k0, k1, stream);
-                variant = VAR_DIRECT_RGB;                           // accounted with the direct first-layer kernel
-                extra_flops = conv_flops(a0);
-                extra_bytes = conv_bytes(a0) - conv_bytes_io(a0.y) - conv_bytes_io(a.x);     // the intermediate tensor never reaches HBM
-            } else if (i == block1_at + 1 && block1_at >= 0 && block1_fused(batch)) {
-                ConvArgs a2 = conv_args(block1_at, batch);
-                ConvKernelArgs k2 = make_conv_args(a2), k3 = make_conv_args(a);
-                k2.w = reinterpret_cast<const float *>(a2.w16);
-                k3.w = reinterpret_cast<const float *>(a.w16);
-                launch_conv_block1(k2, k3, stream);
-                variant = VAR_WIN_256x128;                          // accounted with the window-resident 3x3 kernel
-                extra_flops = conv_flops(a2);
-                // the block input is read once (it is also the residual), the 32-channel intermediate never reaches HBM
-                extra_bytes = conv_bytes(a2) - conv_bytes_io(a2.y) - conv_bytes_io(a.x) - (a.res.p ? conv_bytes_io(a.res) : 0.0);
-            } else {
-                variant = launch_conv(a, stream, l.variant);
-            }
-            if (time_convs) {
-                // no host synchronisation here: the pair is resolved when the counters are read, so the pass runs exactly as it
-                // does untimed (other streams live, the stream fed a pass ahead)
-                YDS_HIP(hipEventRecord(rec.e1, stream));
-                rec.variant = variant;
-                rec.flops = conv_flops(a) + extra_flops;
-                rec.bytes = conv_bytes(a) + extra_bytes;
-                // bound of the arithmetic the launch really used: f16x3 = three fp16 MFMAs per product block; the window kernel's
-                const double peak = conv_math() == MATH_F32 ? 157.3e12 : (a.terms == 1 ? 2500e12 : 2500e12 / 3);
-                rec.attain_us = std::max(rec.flops / peak, rec.bytes / 6.29e12) * 1e6;
-                conv_pending.push_back(rec);
-            }
-        } else if (l.type == "maxpool") {
-            // SPP (yolov4: 5 / 9 / 13, stride 1, all on one tensor): a k x k max with -inf padding is a 5 x 5 max of the
-            // (k-4) x (k-4) max, so a pool whose input already has a (k-4)-pool of the same tensor reads THAT instead -
-            // 25 loads per value instead of 81 / 169, same maxima
-            int cascade = -1;
-            if (l.stride == 1 && !l.zero_br && l.ksize >= 9 && l.pad == (l.ksize - 1) / 2)
-                for (int j = i - 1; j >= 0 && cascade < 0; --j) {
-                    const Layer &q = layers[j];
-                    if (q.type == "maxpool" && q.stride == 1 && !q.zero_br && q.ksize == l.ksize - 4 && q.pad == (q.ksize - 1) / 2 && q.c == l.c &&
-                        layers[q.src].root == layers[l.src].root && layers[q.src].coff == layers[l.src].coff)
-                        cascade = j;
-                }
-            if (cascade >= 0) launch_maxpool(view(cascade, batch), view(i, batch), 5, 1, 2, false, stream);
-            else launch_maxpool(view(l.src, batch), view(i, batch), l.ksize, l.stride, l.pad, l.zero_br, stream);
-        } else if (l.type == "upsample") {
-            launch_upsample(view(l.src, batch), view(i, batch), l.stride, stream);
-        } else if (l.type == "route") {
-            if (l.refs.size() > 1) {
-                View dst = view(i, batch);
-                for (auto &cp : l.copies) {
-                    View d = dst;
-                    d.p += fmt_slots(dst.fmt, cp.second);
-                    launch_copy(view(cp.first, batch), d, stream);
-                }
-            }
-        } else if (l.type == "shortcut") {
-            if (!l.fused) launch_add(view(l.refs[0], batch), view(l.refs[1], batch), view(i, batch), stream);
-        } else if (l.type == "yolo") {
-            View head = view(l.src, batch);
-            int hidx = 0;
-            for (int y : yolo_layers) { if (y == i) break; ++hidx; }
-            // `out` is about to be overwritten: wait for whoever still reads the previous pass's predictions (pipeline NMS
-            // running on its own stream); the first decode sits ~3/4 into the pass, so this wait is free in practice
-            if (hidx == 0 && out_guard) YDS_HIP(hipStreamWaitEvent(stream, out_guard, 0));
+    if (l1 < 0) l1 = (int)layers.size();
+    auto v = [&](int layer) { return view(layer, batch, first); };
+    for (const Step &st : plan(batch).steps) {                  // (in cfg order)
+        const int i = st.layer;
+        if (i < l0) continue;
+        if (i >= l1) break;
+        const Layer &l = layers[i];
+        switch (st.kind) {
+        case Step::CONV: case Step::CONV_MERGED: case Step::CONV_STEM2: case Step::CONV_BLOCK1:
+            enqueue_conv(st, first, batch, stream);
+            break;
+        case Step::MAXPOOL: launch_maxpool(v(st.src), v(i), st.ksize, st.stride, st.pad, st.zero_br, stream); break;
+        case Step::UPSAMPLE: launch_upsample(v(l.src), v(i), l.stride, stream); break;
+        case Step::COPY: {
+            View d = v(i);
+            d.p += fmt_slots(d.fmt, st.arg);
+            launch_copy(v(st.src), d, stream);
+            break;
+        }
+        case Step::ADD: launch_add(v(l.refs[0]), v(l.refs[1]), v(i), stream); break;
+        case Step::YOLO: {
+            const View head = v(l.src);
+            const int hidx = st.arg;
             if (inject_active && inject_set >= 0) {
                 launch_inject_batch(head, batch, inject_table.p, inject_offsets_dev.p + (size_t)inject_set * batch_max + first, inject_max_rows, hidx,
                                     l.classes, inject_logit, stream);
@@ -684,6 +699,8 @@ void Darknet::run_lane(int first, int batch, hipStream_t stream, int l0, int l1)
                     launch_inject(head, b, inject_rows[first + b].p, inject_n[first + b], hidx, l.classes, inject_logit, stream);
             }
             launch_yolo_decode(head, out.p + (size_t)first * total_boxes * attrs, total_boxes, l.box_off, l.classes, l.anchors.data(), (int)l.anchors.size() / 2, img_h, img_w, stream);
+            break;
+        }
         }
     }
 }
@@ -699,7 +716,7 @@ void Darknet::forward_f32_host(const float *nchw, int batch, float *out_host) {
 
 void Darknet::forward_u8_dev(const uint8_t *frames_dev, int h, int w, int batch) {
     if (in_channels != 3) fail("forward_u8: network expects %d channels", in_channels);
-    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
+    check_pass(batch);
     launch_resize_u8(frames_dev, batch, h, w, input_view(batch), stream);
     run_graph(batch);
 }
@@ -707,7 +724,7 @@ void Darknet::forward_u8_dev(const uint8_t *frames_dev, int h, int w, int batch)
 void Darknet::forward_u8_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom) {
     const int batch = (int)geom.size();
     if (in_channels != 3) fail("forward_u8: network expects %d channels", in_channels);
-    if (batch < 1 || batch > batch_max) fail("forward: batch %d outside [1,%d]", batch, batch_max);
+    check_pass(batch);
     geom_dev.ensure(batch_max);
     YDS_HIP(hipMemcpyAsync(geom_dev.p, geom.data(), geom.size() * sizeof(FrameGeom), hipMemcpyHostToDevice, stream));
     YDS_HIP(hipStreamSynchronize(stream));                      // the caller's table may go away
@@ -769,56 +786,20 @@ void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *
     YDS_HIP(hipStreamSynchronize(stream));          // the caller's buffers may go away
 }
 
-bool Darknet::stem_fused(int batch) {
-    static const bool off = getenv("YDS_NO_STEM_FUSE") != nullptr;
-    // (half mode keeps the fused kernels: they compute the first layers in the default arithmetic, which half mode does anyway)
-    if (off || !stem_fusable || conv_math() != MATH_F16X3 || !layers[0].loaded || !layers[1].loaded) return false;
-    if (stem_checked != batch) {
-        ConvArgs a0 = conv_args(0, batch), a1 = conv_args(1, batch);
-        stem_ok = a1.w16 && a1.y.fmt != FMT_F32 && conv_stem2_applicable(make_conv_args(a0), make_conv_args(a1));
-        stem_checked = batch;
-    }
-    return stem_ok;
-}
-
-bool Darknet::block1_fused(int batch) {
-    static const bool off = getenv("YDS_NO_BLOCK_FUSE") != nullptr;
-    if (off || block1_at < 0 || conv_math() != MATH_F16X3 || !layers[block1_at].loaded || !layers[block1_at + 1].loaded) return false;
-    if (block1_checked != batch) {
-        ConvArgs a2 = conv_args(block1_at, batch), a3 = conv_args(block1_at + 1, batch);
-        block1_ok = a2.w16 && a3.w16 && conv_block1_applicable(make_conv_args(a2), make_conv_args(a3));
-        block1_checked = batch;
-    }
-    return block1_ok;
-}
-
 void Darknet::layer_output_host(int i, int batch, float *nchw) {
     if (i < 0 || i >= (int)layers.size()) fail("layer_output: no layer %d", i);
     const Layer &l = layers[i];
-    if (i == block1_at && block1_fused(batch)) {                  // never written by the fused block: produce it on demand
-        ConvArgs a2 = conv_args(i, batch);
-        (void)launch_conv(a2, stream, layers[i].variant);
-    }
-    if (i == 0 && stem_fused(batch)) {                            // the fused stem never writes layer 0: produce it on demand
-        ConvArgs a0 = conv_args(0, batch);
-        (void)launch_conv(a0, stream, layers[0].variant);
-    }
-    if (l.type == "yolo") fail("layer_output: yolo layers are read through the forward output");
+    // a convolution that a fused launch computes without writing it: produce it on demand
+    if (l.type == L_CONV && l.cw.loaded() && plan(batch).produced_by[i] < 0) (void)launch_conv(conv_args(i, batch), stream, l.variant);
+    if (l.type == L_YOLO) fail("layer_output: yolo layers are read through the forward output");
     if (l.fused_res >= 0) fail("layer_output: layer %d is fused with the following shortcut", i);
-    View v = view(i, batch);
-    DevBuf<float> tmp(v.pixels() * v.c);
-    launch_nhwc_to_nchw(v, tmp.p, stream);
-    YDS_HIP(hipMemcpyAsync(nchw, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    YDS_HIP(hipStreamSynchronize(stream));
+    nhwc_to_host(view(i, batch), nchw, stream);
 }
 
 void Darknet::get_input_host(int batch, float *nchw) {
     View v = input_view(batch);
     v.c = in_channels;
-    DevBuf<float> tmp(v.pixels() * v.c);
-    launch_nhwc_to_nchw(v, tmp.p, stream);
-    YDS_HIP(hipMemcpyAsync(nchw, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    YDS_HIP(hipStreamSynchronize(stream));
+    nhwc_to_host(v, nchw, stream);
 }
 
 void Darknet::set_injection(int image, const float *rows, int n, float logit) {
@@ -856,7 +837,7 @@ void Darknet::select_injection_set(int set) {
 int64_t Darknet::flops_per_image() const {
     int64_t f = 0;
     for (const Layer &l : layers)
-        if (l.type == "convolutional") f += 2ll * l.h * l.w * l.c * l.ksize * l.ksize * l.cin_file;
+        if (l.type == L_CONV) f += 2ll * l.h * l.w * l.c * l.cw.ksize * l.cw.ksize * l.cw.cin_file;
     return f;
 }
 
@@ -926,7 +907,7 @@ int yds_darknet_set_half(yds_net *n, int on) {
     YDS_API_END
 }
 int yds_darknet_layer_format(const yds_net *n, int layer) {
-    if (!n || layer < 0 || layer >= (int)n->d->layers.size() || n->d->layers[layer].type == "yolo") return -1;
+    if (!n || layer < 0 || layer >= (int)n->d->layers.size() || n->d->layers[layer].type == yds::L_YOLO) return -1;
     return n->d->view(layer, 1).fmt;
 }
 int yds_darknet_num_boxes(const yds_net *n) { return n->d->total_boxes; }
@@ -1009,60 +990,6 @@ const char *yds_conv_variant_name(int v) { return yds::conv_variant_name(v); }
 int yds_conv_num_variants(void) { return yds::kConvVariants; }
 int yds_set_conv_math(int mode) { yds::set_conv_math(mode); return 0; }
 int yds_get_conv_math(void) { return yds::conv_math(); }
-int yds_conv_bench(int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int with_residual, int iters, double *avg_us,
-                   int *variant) {
-    YDS_API_BEGIN
-    using namespace yds;
-    const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
-    const int kpad = (ksize * ksize * cin + 31) / 32 * 32, ldy = (cout + 3) / 4 * 4;
-    std::vector<float> hx((size_t)n * h * w * cin), hw((size_t)cout * kpad), hb(cout);
-    unsigned s = 12345u;
-    auto rnd = [&]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 32768.f - 1.f; };
-    // YDS_BENCH_DATA=zero | const: power experiment (the chip is power limited: operands that do not toggle run at a higher clock)
-    const char *dk = getenv("YDS_BENCH_DATA");
-    const int data_kind = !dk ? 0 : (!strcmp(dk, "zero") ? 1 : (!strcmp(dk, "const") ? 2 : 0));
-    for (auto &v : hx) v = data_kind == 1 ? 0.f : data_kind == 2 ? 0.5f : rnd();
-    for (auto &v : hw) v = data_kind == 1 ? 0.f : data_kind == 2 ? 0.03125f : rnd() * 0.05f;
-    for (auto &v : hb) v = rnd();
-    DevBuf<float> x, wt, b, y((size_t)n * ho * wo * ldy), r((size_t)n * ho * wo * ldy);
-    DevBuf<uint16_t> wt16;
-    x.upload(hx.data(), hx.size()); wt.upload(hw.data(), hw.size()); b.upload(hb.data(), hb.size());
-    {
-        std::vector<uint16_t> split;
-        pack_weights_f16x3(hw.data(), cout, kpad, split);
-        wt16.upload(split.data(), split.size());
-        YDS_HIP(hipDeviceSynchronize());
-    }
-    YDS_HIP(hipMemset(r.p, 0, r.n * sizeof(float)));
-    ConvArgs a;
-    const bool f16 = conv_math() == MATH_F16X3;
-    a.x = View{x.p, n, h, w, cin, cin, (f16 && cin % 32 == 0) ? FMT_H16 : FMT_F32};
-    a.y = View{y.p, n, ho, wo, cout, ldy, (f16 && cout % 32 == 0) ? FMT_H16 : FMT_F32};
-    if (a.x.fmt == FMT_H16) {
-        DevBuf<float> raw;
-        raw.upload(hx.data(), hx.size());
-        launch_pack_h16(raw.p, a.x, nullptr);
-        YDS_HIP(hipDeviceSynchronize());
-    }
-    a.w = wt.p; a.w16 = wt16.p; a.bias = b.p; a.ksize = ksize; a.stride = stride; a.pad = pad; a.kpad = kpad; a.act = act;
-    if (with_residual) { a.res = View{r.p, n, ho, wo, cout, ldy, a.y.fmt}; a.res_mode = RES_AFTER_ACT; }
-    if (const char *t = getenv("YDS_BENCH_TERMS")) a.terms = atoi(t) == 1 ? 1 : 3;      // tuning aid: the half-mode kernels on single layers
-    hipStream_t st;
-    YDS_HIP(hipStreamCreate(&st));
-    hipEvent_t e0, e1;
-    YDS_HIP(hipEventCreate(&e0)); YDS_HIP(hipEventCreate(&e1));
-    int tuned = conv_autotune(a, st, nullptr);
-    for (int i = 0; i < 3; ++i) *variant = launch_conv(a, st, tuned);
-    YDS_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) launch_conv(a, st, tuned);
-    YDS_HIP(hipEventRecord(e1, st));
-    YDS_HIP(hipEventSynchronize(e1));
-    float ms = 0;
-    YDS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1e3 / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(st);
-    YDS_API_END
-}
 int yds_conv_clock(double *ghz, double *sampled_ms, int reset) {
     YDS_API_BEGIN
     double g = 0, ms = 0;
@@ -1085,45 +1012,6 @@ int yds_conv_clock(double *ghz, double *sampled_ms, int reset) {
 #endif
     if (ghz) *ghz = g;
     if (sampled_ms) *sampled_ms = ms;
-    YDS_API_END
-}
-int yds_conv_run(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode, const float *x_nhwc,
-                 const float *w_okkc, const float *bias, const float *res_nhwc, float *y_nchw) {
-    YDS_API_BEGIN
-    using namespace yds;
-    const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
-    const int K = ksize * ksize * cin, kpad = (K + 31) / 32 * 32, ldy = (cout + 3) / 4 * 4;
-    if (cin % 4) fail("conv_run: input channels must be a multiple of 4");
-    std::vector<float> hw((size_t)cout * kpad, 0.f);
-    for (int o = 0; o < cout; ++o) memcpy(&hw[(size_t)o * kpad], w_okkc + (size_t)o * K, (size_t)K * sizeof(float));
-    const size_t npix_in = (size_t)n * h * w, npix_out = (size_t)n * ho * wo;
-    DevBuf<float> x, raw, wt, b, y(npix_out * ldy), r, rraw, out(npix_out * cout);
-    DevBuf<uint16_t> wt16;
-    wt.upload(hw.data(), hw.size()); b.upload(bias, cout);
-    std::vector<uint16_t> split;
-    pack_weights_f16x3(hw.data(), cout, kpad, split);
-    wt16.upload(split.data(), split.size());
-    YDS_HIP(hipDeviceSynchronize());
-    const bool f16 = conv_math() == MATH_F16X3;
-    ConvArgs a;
-    a.x = View{nullptr, n, h, w, cin, cin, (f16 && cin % 32 == 0) ? FMT_H16 : FMT_F32};
-    a.y = View{y.p, n, ho, wo, cout, ldy, (f16 && cout % 32 == 0) ? FMT_H16 : FMT_F32};
-    raw.upload(x_nhwc, npix_in * cin);
-    if (a.x.fmt == FMT_H16) { x.alloc(npix_in * cin); a.x.p = x.p; launch_pack_h16(raw.p, a.x, nullptr); }
-    else a.x.p = raw.p;
-    a.w = wt.p; a.w16 = wt16.p; a.bias = b.p; a.ksize = ksize; a.stride = stride; a.pad = pad; a.kpad = kpad; a.act = act;
-    if (res_mode) {
-        if (!res_nhwc) fail("conv_run: residual mode %d without a residual tensor", res_mode);
-        a.res = View{nullptr, n, ho, wo, cout, cout, a.y.fmt};
-        rraw.upload(res_nhwc, npix_out * cout);
-        if (a.res.fmt == FMT_H16) { r.alloc(npix_out * cout); a.res.p = r.p; launch_pack_h16(rraw.p, a.res, nullptr); }
-        else a.res.p = rraw.p;
-        a.res_mode = res_mode;
-    }
-    YDS_HIP(hipDeviceSynchronize());
-    launch_conv(a, nullptr, variant);
-    launch_nhwc_to_nchw(a.y, out.p, nullptr);
-    YDS_HIP(hipMemcpy(y_nchw, out.p, npix_out * cout * sizeof(float), hipMemcpyDeviceToHost));
     YDS_API_END
 }
 int yds_darknet_load_injection_sets(yds_net *n, const float *rows_host, const int32_t *offsets_host, int n_sets, float logit) {

@@ -1,6 +1,7 @@
 // Host-side engine classes of libydsort (detector, ReID, tracker, pipeline).
 #pragma once
 #include "common.h"
+#include "conv_weights.h"
 
 #include <map>
 #include <memory>
@@ -16,33 +17,55 @@ struct CfgBlock {
 };
 std::vector<CfgBlock> parse_cfg(const std::string &text);
 
+enum LayerType { L_CONV, L_MAXPOOL, L_UPSAMPLE, L_ROUTE, L_SHORTCUT, L_YOLO };     // (the cfg's section names end in the parser)
+
 struct Layer {
-    std::string type;
+    LayerType type = L_CONV;
     int c = 0, h = 0, w = 0;              // logical output shape
     int root = -1, coff = 0;              // storage owner + channel offset (views)
-    bool is_view = false;
     int src = -1;                         // single data input (conv/pool/upsample/yolo)
     std::vector<int> refs;                // route sources / shortcut operands
     std::vector<std::pair<int, int>> copies;   // (source layer, channel offset) needing a copy kernel
-    // conv
-    int bn = 0, ksize = 1, stride = 1, pad = 0, cin = 0, cin_file = 0, kpad = 0, act = ACT_LINEAR;
+    bool concat() const { return type == L_ROUTE && refs.size() > 1; }   // a route that owns the concatenated buffer
+    // conv: geometry (fixed when the net is planned) and folded weights (load_weights) in cw
+    int bn = 0, act = ACT_LINEAR;
+    ConvWeights cw;
     int fused_res = -1;                   // residual layer absorbed from the following shortcut
     int variant = -1, tuned_batch = 0, tuned_math = -1;   // measured conv tile variant, the batch and math mode it was measured at
-    bool loaded = false;
-    DevBuf<float> wt, bias;
-    DevBuf<uint16_t> wt16;                // split-fp16 copy of wt for the f16x3 kernel
     // CSP split (yolov4: conv 1x1, route -2, conv 1x1 - two convolutions of the same tensor): the first one launches both
-    // (merge_next = the second conv, which is skipped: merged_into = the first) from concatenated filters, so the shared
-    // input is read from HBM once
+    // (merge_next = the second conv, merged_into = the first) from the concatenated filters in cw_merged, so the shared input is
+    // read from HBM once.  The pairing is part of the static plan; the launch is merged while both have weights (cw_merged loaded).
     int merge_next = -1, merged_into = -1;
-    DevBuf<float> wt_m, bias_m;
-    DevBuf<uint16_t> wt16_m;
+    ConvWeights cw_merged;
+    // pool / upsample
+    int ksize = 1, stride = 1, pad = 0;
     // shortcut / route / pool
     bool fused = false, zero_br = false;
     int groups = 0, group_id = 0;
     // yolo
     std::vector<float> anchors;
     int classes = 0, box_off = 0;
+};
+
+// One launch (or launch-shaped piece of work) of a detector pass.  Indices only: views are built when the step is enqueued, because
+// they depend on the lane's first image and on buffers that set_batch_max replaces.
+struct Step {
+    enum Kind { CONV, CONV_MERGED, CONV_STEM2, CONV_BLOCK1, MAXPOOL, UPSAMPLE, COPY, ADD, YOLO };
+    Kind kind;
+    int layer;                            // cfg position the step runs at (forward_resized_part cuts by it); the layer it writes.
+                                          // CONV_MERGED also writes layers[layer].merge_next; CONV_STEM2 / CONV_BLOCK1 compute layer - 1 inside
+    int src = -1;                         // MAXPOOL: the tensor read (an earlier pool of the same tensor in an SPP cascade); COPY: source layer
+    int arg = 0;                          // COPY: channel offset in the concatenation; YOLO: head index
+    int ksize = 1, stride = 1, pad = 0;   // MAXPOOL, as launched (a cascaded pool is 5 / 1 / 2)
+    bool zero_br = false;
+};
+// The steps of one pass in cfg order, for one (batch, conv math, plan epoch).  Everything that decides what layer i costs a launch
+// is decided where this is built (Darknet::plan) and nowhere else.
+struct LaunchPlan {
+    std::vector<Step> steps;
+    std::vector<int> produced_by;         // layer -> the step that writes it (a concatenation: its last copy); -1: a view, or a layer
+                                          // that a fused launch computes without writing it
+    int batch = -1, math = -1, epoch = -1;
 };
 
 struct Storage {
@@ -96,16 +119,15 @@ public:
     void enable_conv_timing(bool on);
     void autotune(int batch);                // measure the fastest conv tile per layer at this batch size
     int64_t flops_per_image() const;
-    size_t weight_floats() const;
-    View view(int layer, int batch) const;
-    ConvArgs conv_args(int layer, int batch) const;
-    ConvArgs merged_conv_args(int layer, int batch) const;     // both convolutions of a CSP split in one launch
-    View input_view(int batch) const;
+    // `batch` images from image `first` of the buffers on (a lane of run_graph starts past 0)
+    View view(int layer, int batch, int first = 0) const;
+    View input_view(int batch, int first = 0) const;
+    // merged: both convolutions of a CSP split in one launch (layer = the first of the pair)
+    ConvArgs conv_args(int layer, int batch, int first = 0, bool merged = false) const;
 
     int img_h, img_w, batch_max, in_channels = 3;
     int math = 0;                            // conv arithmetic the plan (tensor formats) was built for
     bool half_mode = false;                  // Darknet.half(): single-term fp16 operands in the LDS-DMA / window kernels
-    void stem_checked_reset() { stem_checked = block1_checked = -1; }
     void set_half(bool on);                  // half mode on / off: re-plans the activation formats (2-byte tensors while it is on)
     void plan_half_formats();
     int owner_of(int layer, int &off) const; // layer -> the storage its view lives in and the channel offset of that view
@@ -120,9 +142,6 @@ public:
     DevBuf<float> tiled_pred;
     WindowTable tiles;
     hipStream_t stream = nullptr;
-    int32_t header[5] = {0, 0, 0, 0, 0};
-    bool weights_loaded = false;
-    size_t activation_bytes = 0;
     // bench-only logit injection
     std::vector<DevBuf<float>> inject_rows;
     std::vector<int> inject_n;
@@ -146,17 +165,17 @@ public:
 
 private:
     void allocate_buffers();
+    void check_pass(int batch) const;                         // batch within [1, batch_max], conv math the one planned for
     void run_graph(int batch);
     // layers [l0, l1) over images [first, first + batch) on one stream (l1 < 0: to the end)
     void run_lane(int first, int batch, hipStream_t st, int l0 = 0, int l1 = -1);
-    bool stem_fusable = false, stem_ok = false;               // layers 0+1 as one kernel (conv_stem2.hip)
-    int stem_checked = -1;
-    bool stem_fused(int batch);
-    int block1_at = -1, block1_checked = -1;                  // first conv of the fused residual block (conv_block1.hip), -1: none
-    bool block1_ok = false;
-    bool block1_fused(int batch);
-    hipEvent_t out_guard = nullptr;                           // optional: event the decode waits for before it overwrites `out`
-    int lane_img0 = 0;                                        // image offset applied by view() / input_view() while a lane is enqueued
+    void enqueue_conv(const Step &st, int first, int batch, hipStream_t s);
+    const LaunchPlan &plan(int batch);                        // the cached step list, rebuilt when its key moved
+    LaunchPlan plan_;
+    int plan_epoch = 0;                                       // bumped by whatever the plan reads besides batch and conv math: half mode,
+                                                              // the buffers (set_batch_max), the weights (load_weights)
+    bool stem_fusable = false;                                // layers 0+1 can run as one kernel (conv_stem2.hip)
+    int block1_at = -1;                                       // first conv of the fusable residual block (conv_block1.hip), -1: none
     std::vector<hipStream_t> lane_streams;
     std::vector<hipEvent_t> lane_done;
     hipEvent_t lane_fork = nullptr;
@@ -228,16 +247,11 @@ public:
     void allocate_buffers();
     static int64_t flops_per_crop();
 
-    struct ConvW {
-        int cin = 0, cin_file = 0, cout = 0, k = 0, stride = 1, pad = 0, kpad = 0;
-        DevBuf<float> wt, bias;
-        DevBuf<uint16_t> wt16;
-    };
     int max_crops;
     std::map<std::string, std::vector<float>> raw;
     std::map<std::string, std::vector<int64_t>> raw_shape;
     bool ready = false;
-    std::vector<ConvW> convs;                // in execution order
+    std::vector<ConvWeights> convs;                // in execution order
     std::vector<DevBuf<float>> bufs;         // [0], the full-resolution stem output of the unfused pair, is allocated on first use
     DevBuf<float> in, feat, stage_f32;
     DevBuf<uint8_t> stage_u8;

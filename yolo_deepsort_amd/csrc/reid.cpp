@@ -65,30 +65,16 @@ void ReidNet::finalize() {
         if (w.size() != (size_t)cout * cin_file * k * k) fail("reid: %s.weight has %zu elements, expected %d", conv.c_str(), w.size(), cout * cin_file * k * k);
         const auto &g = need(bn + ".weight"), &b = need(bn + ".bias"), &m = need(bn + ".running_mean"), &v = need(bn + ".running_var");
         const std::vector<float> *cb = has_bias ? &need(conv + ".bias") : nullptr;
-        ConvW c;
-        c.cin_file = cin_file;
-        c.cin = (cin_file + 3) / 4 * 4;
-        c.cout = cout; c.k = k; c.stride = stride; c.pad = k == 3 ? 1 : 0;
-        c.kpad = (k * k * c.cin + 31) / 32 * 32;
-        std::vector<float> packed((size_t)cout * c.kpad, 0.f), bias(cout);
+        ConvWeights c;
+        c.shape(cout, cin_file, (cin_file + 3) / 4 * 4, k, stride, k == 3 ? 1 : 0);
+        std::vector<double> scale(cout);
+        std::vector<float> bias(cout);
         for (int o = 0; o < cout; ++o) {
-            double scale = (double)g[o] / sqrt((double)v[o] + 1e-5);     // nn.BatchNorm2d default eps
+            scale[o] = (double)g[o] / sqrt((double)v[o] + 1e-5);         // nn.BatchNorm2d default eps
             double b0 = cb ? (double)(*cb)[o] : 0.0;
-            bias[o] = (float)((b0 - (double)m[o]) * scale + (double)b[o]);
-            for (int ci = 0; ci < cin_file; ++ci)
-                for (int kh = 0; kh < k; ++kh)
-                    for (int kw = 0; kw < k; ++kw)
-                        packed[(size_t)o * c.kpad + (kh * k + kw) * c.cin + ci] = (float)((double)w[(((size_t)o * cin_file + ci) * k + kh) * k + kw] * scale);
+            bias[o] = (float)((b0 - (double)m[o]) * scale[o] + (double)b[o]);
         }
-        c.wt.upload(packed.data(), packed.size(), stream);
-        {
-            std::vector<uint16_t> split;
-            pack_weights_f16x3(packed.data(), cout, c.kpad, split);
-            c.wt16.upload(split.data(), split.size(), stream);
-            YDS_HIP(hipStreamSynchronize(stream));
-        }
-        c.bias.upload(bias.data(), bias.size(), stream);
-        YDS_HIP(hipStreamSynchronize(stream));
+        c.upload(w.data(), scale.data(), bias.data(), stream);
         convs.push_back(std::move(c));
     };
     add_conv("conv.0", "conv.1", 3, 64, 3, 1, true);
@@ -155,10 +141,9 @@ void ReidNet::forward(int D, const ReidFront *front) {
     };
     conv_flops_last = 0;
     auto run = [&](int ci, const View &x, const View &y, int act, const View *res, int res_mode) {
-        const ConvW &c = convs[ci];
         ConvArgs a;
-        a.x = x; a.y = y; a.w = c.wt.p; a.w16 = c.wt16.p; a.bias = c.bias.p;
-        a.ksize = c.k; a.stride = c.stride; a.pad = c.pad; a.kpad = c.kpad; a.act = act;
+        a.x = x; a.y = y; a.act = act;
+        convs[ci].fill(a);
         if (res) { a.res = *res; a.res_mode = res_mode; }
         // measured tile choice per layer; the crop count varies from call to call, so a measurement is reused
         // while D stays within a factor of two of the D it was taken at
@@ -178,7 +163,7 @@ void ReidNet::forward(int D, const ReidFront *front) {
                              !getenv("YDS_REID_FRONT_UNFUSED");
     front_fused_last = fused_front;
     if (fused_front) {
-        const ConvW &c = convs[0];
+        const ConvWeights &c = convs[0];
         launch_reid_stem(*front, D, c.wt.p, c.kpad, c.bias.p, cur, stream);
         conv_flops_last += 2.0 * D * CROP_H * CROP_W * 64 * 9 * 4;
     } else {
@@ -186,10 +171,9 @@ void ReidNet::forward(int D, const ReidFront *front) {
         in_buf();
         View x0 = mk(in, CROP_H, CROP_W, 4);
         // stem conv + BN + ReLU + MaxPool2d(3, 2, 1) (model.py:52-60) as one kernel; the unfused pair stays as fallback
-        const ConvW &c = convs[0];
         ConvArgs a;
-        a.x = x0; a.y = cur; a.w = c.wt.p; a.w16 = c.wt16.p; a.bias = c.bias.p;
-        a.ksize = c.k; a.stride = c.stride; a.pad = c.pad; a.kpad = c.kpad; a.act = ACT_RELU;
+        a.x = x0; a.y = cur; a.act = ACT_RELU;
+        convs[0].fill(a);
         if (!getenv("YDS_REID_UNFUSED") && launch_conv_maxpool3s2(a, stream)) {
             conv_flops_last += 2.0 * D * CROP_H * CROP_W * 64 * 9 * 4;
         } else {
@@ -303,10 +287,7 @@ void ReidNet::preprocess_frames_dev(const uint8_t *frames_dev, const std::vector
     if (D == 0) return;
     crop_into_in(stage_crops(frames_dev, 0, 0, tlwh_host, frame_of, D, false, geom.data(), (int)geom.size()), D);
     View x3; x3.p = in.p; x3.n = D; x3.h = CROP_H; x3.w = CROP_W; x3.c = 3; x3.ld = 4;
-    DevBuf<float> tmp((size_t)D * 3 * CROP_H * CROP_W);
-    launch_nhwc_to_nchw(x3, tmp.p, stream);
-    YDS_HIP(hipMemcpyAsync(nchw_host, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    YDS_HIP(hipStreamSynchronize(stream));
+    nhwc_to_host(x3, nchw_host, stream);
 }
 
 void ReidNet::embed_host(const uint8_t *frame_host, int h, int w, const float *tlwh_host, int D, float *out_host) {
@@ -330,10 +311,7 @@ void ReidNet::preprocess_host(const uint8_t *frame_host, int h, int w, const flo
     View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
     launch_crop_resize(stage_u8.p, h, w, boxes_dev.p, D, x0, stream);
     View x3 = x0; x3.c = 3;
-    DevBuf<float> tmp((size_t)D * 3 * CROP_H * CROP_W);
-    launch_nhwc_to_nchw(x3, tmp.p, stream);
-    YDS_HIP(hipMemcpyAsync(nchw_host, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    YDS_HIP(hipStreamSynchronize(stream));
+    nhwc_to_host(x3, nchw_host, stream);
 }
 
 void ReidNet::forward_f32_host(const float *nchw, int D, float *out_host) {

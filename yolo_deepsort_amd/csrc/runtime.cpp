@@ -56,6 +56,13 @@ hipStream_t make_stream(bool latency_role) {
     return st;
 }
 
+void nhwc_to_host(const View &x, float *dst_nchw_host, hipStream_t s) {
+    DevBuf<float> tmp(x.pixels() * x.c);
+    launch_nhwc_to_nchw(x, tmp.p, s);
+    YDS_HIP(hipMemcpyAsync(dst_nchw_host, tmp.p, tmp.n * sizeof(float), hipMemcpyDeviceToHost, s));
+    YDS_HIP(hipStreamSynchronize(s));
+}
+
 // A wrong table must end here as a message: the front-end kernels read whatever it describes.
 std::vector<FrameGeom> checked_layout(const uint64_t *frame_off, const int32_t *frame_hw, int n, size_t frames_bytes) {
     if (!frame_off || !frame_hw) fail("frame layout: NULL table");
