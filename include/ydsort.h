@@ -135,6 +135,14 @@ int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float con
  *                        pred_host [n_frames, n_boxes, attrs]; out6_host [n_frames, cap, 6]; n_out[n_frames] rows per image. */
 int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
                                float *out6_host, int cap, int *n_out);
+/* yds_nms_ragged_pred     <- both functions above for frames of different row counts in ONE launch sequence: the launch of a slotted
+ *                        pipeline pass (yds_pipeline_set_stream_windows).  Frame f is rows [row0[f], row0[f] + n_rows[f]) of pred_host
+ *                        [total_rows, attrs]; corner_merge[2f] != 0: its boxes are x1,y1,x2,y2, corner_merge[2f+1] != 0: the merge branch
+ *                        runs for it; its kept boxes are multiplied by (scale[2f], scale[2f+1]).  The kernels read these descriptors on
+ *                        the device.  out6_host [n_frames, cap, 6], n_out [n_frames]. */
+int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, int n_frames, const uint64_t *row0, const int32_t *n_rows,
+                        const int32_t *corner_merge, const float *scale, float conf_thres, float iou_thres, float *out6_host, int cap,
+                        int *n_out);
 
 /* ---- ReID: crop + Extractor + Net(reid=True) --------------------------------------------
  * yds_reid_load_tensor <- Extractor.__init__ load_state_dict  feature_extractor.py:13-17
@@ -283,7 +291,8 @@ int yds_pipeline_step_multi_host(yds_pipe *, const uint8_t *frames_host, const u
  * and at least frames_bytes bytes; pass NULL when the layout changes.  A look-ahead pass is reused only when pointer, count and layout
  * all match.  Refused before anything is enqueued: h or w < 1, a frame that ends past frames_bytes, n_frames outside [1, batch_max],
  * and any mixed layout while window mode is set (yds_pipeline_set_windows cuts frames of one size).  A layout of equal sizes at
- * offsets i * h * w * 3 gives exactly the rows of yds_pipeline_step_multi. */
+ * offsets i * h * w * 3 gives exactly the rows of yds_pipeline_step_multi.  yds_pipeline_set_stream_windows is the way to window a
+ * mixed layout: every stream is cut by its own setting, whatever its frame size. */
 int yds_pipeline_step_multi_mixed(yds_pipe *, const uint8_t *frames_dev, const uint8_t *next_frames_dev, const uint64_t *frame_off,
                                   const int32_t *frame_hw /* [n_frames,2] */, size_t frames_bytes, int n_frames,
                                   const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host);
@@ -328,6 +337,21 @@ int yds_pipeline_set_frame_order(yds_pipe *, int bgr);
  * first).  Memory: the shifted predictions of a step stay resident, B * T * boxes * attrs * 4 bytes (yolov3-608: 7.73 MB per window).
  * Bench-only logit injection (yds_darknet_load_injection_sets) addresses the slots of a chunk: slot b * T + t while B * T <= batch_max. */
 int yds_pipeline_set_windows(yds_pipe *, int win_w, int win_h, double overlap);
+/* ImageDetector(win_size, overlap) per camera: stream `stream` of a multi-stream pipeline is cut into its own windows
+ * (win_w <= 0: that stream takes the plain branch).  Applies to yds_pipeline_step_multi[_host] and _multi_mixed[_host].
+ * A frame of stream s, h x w pixels, gives the rows of ImageDetector(win_size=(win_w, win_h), overlap).detect on that frame: with
+ * w < win_w and h < win_h, or without a setting, the plain branch (img_detect.py:68: whole frame, centre-form NMS, boxes scaled by the
+ * frame's own ratio); else its T windows as in yds_pipeline_set_windows, merged by one NMS with merge=True, is_p1p2=True.  A step
+ * that holds a windowed frame runs as one slotted pass: a slot per window and per plain frame, in frame order then window order,
+ * through the network in chunks of at most batch_max (chunks may straddle frames), ONE NMS launch sequence for all frames that reads
+ * every frame's row count, form and scale on the device.  A step without a windowed frame runs exactly as without any setting.
+ * The look-ahead pass of a step is planned with that step's stream_of_frame: it is reused only when pointer, count, layout AND the
+ * plan the next call's stream_of_frame gives all match, else discarded and redone.  Per stream the results are those of the stream
+ * stepped alone at its own size and setting.  Bench-only logit injection addresses the slots of a chunk, as in window mode.
+ * Refused, the pipeline left usable: a single-stream pipeline, stream outside [0, n_streams), win_w > 0 with win_h <= 0 or an overlap
+ * that is not >= 0, a look-ahead pass in flight, window mode on (yds_pipeline_set_windows); yds_pipeline_set_windows(win_w > 0) is
+ * refused in turn while any stream holds a setting. */
+int yds_pipeline_set_stream_windows(yds_pipe *, int stream, int win_w, int win_h, double overlap);
 int yds_pipeline_last_schedule(yds_pipe *);
 int yds_pipeline_schedule_trial(yds_pipe *, int uploaded, int *decided, double *serialized_s, double *two_stream_s);
 /* last step, microseconds: resize (device), detector (device: the detector pass alone - a ReID pass the serialized schedule puts
@@ -433,11 +457,14 @@ int yds_comm_barrier(yds_comm *);
  *     applied on every following forward until cleared with n = 0.
  *   yds_darknet_load_injection_sets / _select_injection_set: preload n_sets x batch_max tables (offsets: n_sets*batch_max+1 row
  *     offsets) and pick one per step.
- *   yds_pipeline_set_next_injection: the set to select before the prefetched detector pass of a pipeline step. */
+ *   yds_pipeline_set_next_injection: the set to select before the prefetched detector pass of a pipeline step.
+ *   yds_pipeline_slot_pred: the prediction block of the last slotted pass (yds_pipeline_set_stream_windows) as the NMS read it,
+ *     [*n_rows, attrs] fp32, slot-major; at most cap_rows rows are copied (pred_host may be NULL to ask for *n_rows). */
 int yds_darknet_set_injection(yds_net *, int image, const float *rows_host, int n, float logit);
 int yds_darknet_load_injection_sets(yds_net *, const float *rows_host, const int32_t *offsets_host, int n_sets, float logit);
 int yds_darknet_select_injection_set(yds_net *, int set);
 int yds_pipeline_set_next_injection(yds_pipe *, int set);
+int yds_pipeline_slot_pred(yds_pipe *, float *pred_host, size_t cap_rows, size_t *n_rows);
 
 #ifdef __cplusplus
 }

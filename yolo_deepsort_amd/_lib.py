@@ -148,6 +148,9 @@ SIGNATURES = {
     "yds_reid_front_grid_crops": (_I, []),
     "yds_pipeline_step_multi_mixed": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
     "yds_pipeline_step_multi_mixed_host": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
+    "yds_nms_ragged_pred": (_I, [_P, _SZ, _I, _I, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
+    "yds_pipeline_set_stream_windows": (_I, [_P, _I, _I, _I, C.c_double]),
+    "yds_pipeline_slot_pred": (_I, [_P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -158,6 +158,15 @@ void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_
                           bool bgr);
 void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int T, int slot0, int n,
                          float *dst, hipStream_t s);
+// Slotted pass (pipeline.cpp, a window setting per stream): the network slots of a step whose frames are cut differently - a windowed
+// frame contributes one slot per window, a plain frame one slot for the whole frame.  A slot's source region is th x tw pixels at
+// frames + off (the window origin inside the frames buffer), rows `stride` bytes apart.  window != 0: its boxes go to corner form, are
+// scaled by (sx, sy) = (tw / img_w, th / img_h) and shifted by (x0, y0) (launch_window_boxes' arithmetic); else they are copied.
+struct SlotRec { uint64_t off; int32_t stride, th, tw, window, x0, y0; float sx, sy; };
+// slots [0, n) of `slots` (device-readable for as long as the kernel may run) -> the n images of y; blockIdx.y = slot
+void launch_slot_resize(const uint8_t *frames, const SlotRec *slots, int n, const View &y, hipStream_t s, bool bgr);
+// rows [0, n * n_boxes) of pred (the network output of those n slots) -> dst, same row order
+void launch_slot_boxes(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst, hipStream_t s);
 // ReID: crop + resize to 64x128 + /255 + mean/std -> NHWC4
 // boxes: [D,5] = x1,y1,x2,y2,frame index (frames are h*w*3 bytes apart)
 void launch_crop_resize(const uint8_t *frames, int h, int w, const int *boxes5_dev, int D, const View &y,

@@ -769,6 +769,15 @@ void Darknet::forward_windows(const uint8_t *frames_dev, int h, int w, int n_fra
     }
 }
 
+void Darknet::forward_slots(const uint8_t *frames_dev, const SlotRec *slots, int n_slots, float *pred, bool bgr) {
+    for (int slot0 = 0; slot0 < n_slots; slot0 += batch_max) {
+        const int nb = std::min(batch_max, n_slots - slot0);
+        launch_slot_resize(frames_dev, slots + slot0, nb, input_view(nb), stream, bgr);
+        run_graph(nb);
+        launch_slot_boxes(out.p, total_boxes, attrs, slots + slot0, nb, pred + (size_t)slot0 * total_boxes * attrs, stream);
+    }
+}
+
 void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *tiles_xyhw, int n_tiles) {
     if (in_channels != 3) fail("forward_tiles: network expects %d channels", in_channels);
     if (n_tiles < 1) fail("forward_tiles: no windows");

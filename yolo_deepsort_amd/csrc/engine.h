@@ -111,6 +111,10 @@ public:
     // batch_max (a chunk may straddle frames): resize -> network -> boxes in corner form, resize_boxes to the window's own size,
     // shifted by the window origin, to pred [slots * total_boxes, attrs].  Asynchronous on `stream`.
     void forward_windows(const uint8_t *frames_dev, int h, int w, int n_frames, const WindowTable &tab, float *pred, bool bgr);
+    // forward_windows for slots that are described one by one (a step whose frames are cut differently, pipeline.cpp): slots
+    // [0, n_slots) of `slots` (device-readable until the pass has run) in chunks of batch_max; a window slot's boxes as above, a plain
+    // slot's rows unchanged in centre form, to pred [n_slots * total_boxes, attrs]
+    void forward_slots(const uint8_t *frames_dev, const SlotRec *slots, int n_slots, float *pred, bool bgr);
     void layer_output_host(int layer, int batch, float *nchw);
     void get_input_host(int batch, float *nchw);
     void set_injection(int image, const float *rows, int n, float logit);
@@ -183,6 +187,9 @@ private:
 
 // --------------------------------------------------------------------------------------------- NMS
 // Device multi-label NMS over decoded predictions [n_boxes, attrs] (nms.hip).
+// One frame of a ragged launch: rows [row0, row0 + n_rows) of the prediction block; corner: they hold x1,y1,x2,y2; merge: the merge
+// branch runs for it; (sx, sy): resize_boxes scale of its kept boxes (1 for a windowed frame, whose boxes are in frame pixels already).
+struct NmsFrame { uint64_t row0; int32_t n_rows, corner, merge; float sx, sy; int32_t pad; };
 class NmsWorkspace {
 public:
     explicit NmsWorkspace(int max_candidates = 16384, int frames = 1);
@@ -194,6 +201,10 @@ public:
     // scale: (sx, sy) of every frame, [n_frames, 2], read on the device when the sweep runs (frames of different sizes); NULL: sx, sy
     void launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
                 float sx, float sy, int cap, hipStream_t s, bool corner = false, bool merge = false, const float *scale = nullptr);
+    // launch() for frames that differ in row count and form, described by `fr` [n_frames] which the kernels read on the device;
+    // max_rows: the largest n_rows, total_rows: the largest row0 + n_rows (box_count is addressed like the prediction block)
+    void launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
+                       float iou_thres, int cap, hipStream_t s);
     int collect(int frame, float *out6_host, int cap);
     void resize(int max_candidates, int n_frames);       // (re)allocates; contents are lost
     int needed(int n_frames) const;                       // largest candidate count of the last launch (after the caller's sync)

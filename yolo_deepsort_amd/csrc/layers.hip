@@ -449,6 +449,59 @@ void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *t
     YDS_HIP(hipGetLastError());
 }
 
+// The two front-end kernels above in one, for a step whose frames are cut differently (pipeline.cpp, a window setting per stream):
+// slot blockIdx.y of the chunk is the th x tw region at frames + off with its own row stride - a window of a frame of any size, or a
+// whole frame - so resize_px sees exactly what window_resize_kernel / resize_u8_frames_kernel hand it.
+__global__ void slot_resize_kernel(const uint8_t *frames, const SlotRec *slots, float *y, int Ho, int Wo, int bgr) {
+    const SlotRec g = slots[blockIdx.y];
+    const int per = Ho * Wo;
+    float *dst = y + (size_t)blockIdx.y * per * 4;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < per; idx += gridDim.x * blockDim.x) {
+        const int oy = idx / Wo, ox = idx - oy * Wo;
+        float o[3];
+        resize_px(frames + g.off, (size_t)g.stride, g.th, g.tw, Ho, Wo, oy, ox, o);
+        if (bgr) { const float v = o[0]; o[0] = o[2]; o[2] = v; }
+        *reinterpret_cast<float4 *>(dst + (size_t)idx * 4) = make_float4(__fdiv_rn(o[0], 255.f), __fdiv_rn(o[1], 255.f), __fdiv_rn(o[2], 255.f), 0.f);
+    }
+}
+
+void launch_slot_resize(const uint8_t *frames, const SlotRec *slots, int n, const View &y, hipStream_t s, bool bgr) {
+    if (y.c != 4 || y.ld != 4) fail("resize: destination must be NHWC4");
+    if (n < 1 || n > 65535) fail("resize: %d slots", n);
+    const int per_slot = grid_for((size_t)y.h * y.w), gx = std::min(per_slot, std::max(1, 8192 / n));
+    hipLaunchKernelGGL(slot_resize_kernel, dim3(gx, n), dim3(256), 0, s, frames, slots, y.p, y.h, y.w, bgr ? 1 : 0);
+    YDS_HIP(hipGetLastError());
+}
+
+// window_boxes_kernel with the window read per slot: a window slot's boxes go to corner form, are scaled to the window and shifted by
+// its origin (the same operations in the same order); a plain slot's rows are copied as they are, in centre form, for the NMS to
+// convert and scale like those of an unwindowed step.
+__global__ void slot_boxes_kernel(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst) {
+    const size_t total = (size_t)n * n_boxes;
+    for (size_t row = blockIdx.x * (size_t)(blockDim.x / 32) + threadIdx.x / 32; row < total; row += (size_t)gridDim.x * (blockDim.x / 32)) {
+        const SlotRec &g = slots[row / n_boxes];
+        const int lane = threadIdx.x % 32;
+        const float *p = pred + row * attrs;
+        float *d = dst + row * attrs;
+        for (int j = 4 + lane; j < attrs; j += 32) d[j] = p[j];
+        if (lane < 4) {
+            float v = p[lane];
+            if (g.window) {
+                const float half = __fdiv_rn(p[2 + (lane & 1)], 2.f);
+                v = lane < 2 ? __fsub_rn(p[lane & 1], half) : __fadd_rn(p[lane & 1], half);
+                v = __fmul_rn(v, lane & 1 ? g.sy : g.sx);
+                v = __fadd_rn(v, (float)(lane & 1 ? g.y0 : g.x0));
+            }
+            d[lane] = v;
+        }
+    }
+}
+
+void launch_slot_boxes(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst, hipStream_t s) {
+    hipLaunchKernelGGL(slot_boxes_kernel, dim3(grid_for((size_t)n * n_boxes * 32)), dim3(256), 0, s, pred, n_boxes, attrs, slots, n, dst);
+    YDS_HIP(hipGetLastError());
+}
+
 __global__ void crop_resize_kernel(const uint8_t *frames, int H, int W, const int *boxes, int D, float *y, int Ho, int Wo, int bgr) {
     const size_t total = (size_t)D * Ho * Wo;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {

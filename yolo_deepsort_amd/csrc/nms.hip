@@ -26,9 +26,10 @@ namespace yds {
 
 constexpr int MAX_DET = 300;
 
-__global__ void nms_count_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, int *box_count_all) {
-    const float *pred = pred_all + blockIdx.y * pred_stride;
-    int *box_count = box_count_all + (size_t)blockIdx.y * n_boxes;
+// The stages up to the sweep come in two forms that share one body each: the uniform form (launch: every frame n_boxes rows,
+// pred_stride apart) and the ragged form (launch_ragged: frame blockIdx.y is rows [row0, row0 + n_rows) of one block, described by an
+// NmsFrame the kernel reads on the device; box_count is addressed by the same row prefix).
+__device__ __forceinline__ void nms_count_body(const float *pred, int n_boxes, int attrs, float thr, int *box_count) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_boxes) return;
     const float *p = pred + (size_t)i * attrs;
@@ -39,11 +40,16 @@ __global__ void nms_count_kernel(const float *pred_all, size_t pred_stride, int 
     }
     box_count[i] = cnt;
 }
+__global__ void nms_count_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, int *box_count_all) {
+    nms_count_body(pred_all + blockIdx.y * pred_stride, n_boxes, attrs, thr, box_count_all + (size_t)blockIdx.y * n_boxes);
+}
+__global__ void nms_count_ragged_kernel(const float *pred, const NmsFrame *fr, int attrs, float thr, int *box_count) {
+    const NmsFrame f = fr[blockIdx.y];
+    nms_count_body(pred + (size_t)f.row0 * attrs, f.n_rows, attrs, thr, box_count + f.row0);
+}
 
 // single-workgroup exclusive scan, in place; total -> counts[0]
-__global__ void nms_scan_kernel(int *box_count_all, int n_boxes, int *counts_all) {
-    int *box_count = box_count_all + (size_t)blockIdx.y * n_boxes;
-    int *counts = counts_all + blockIdx.y * 4;
+__device__ __forceinline__ void nms_scan_body(int *box_count, int n_boxes, int *counts) {
     __shared__ int wave_sum[16];
     __shared__ int carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -69,12 +75,16 @@ __global__ void nms_scan_kernel(int *box_count_all, int n_boxes, int *counts_all
     }
     if (tid == 0) { counts[0] = carry; counts[1] = 0; }
 }
+__global__ void nms_scan_kernel(int *box_count_all, int n_boxes, int *counts_all) {
+    nms_scan_body(box_count_all + (size_t)blockIdx.y * n_boxes, n_boxes, counts_all + blockIdx.y * 4);
+}
+__global__ void nms_scan_ragged_kernel(int *box_count, const NmsFrame *fr, int *counts_all) {
+    const NmsFrame f = fr[blockIdx.y];
+    nms_scan_body(box_count + f.row0, f.n_rows, counts_all + blockIdx.y * 4);
+}
 
-__global__ void nms_emit_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, const int *box_off_all, int max_cand,
-                                float *cand_all, int corner) {
-    const float *pred = pred_all + blockIdx.y * pred_stride;
-    const int *box_off = box_off_all + (size_t)blockIdx.y * n_boxes;
-    float *cand = cand_all + (size_t)blockIdx.y * max_cand * 6;
+__device__ __forceinline__ void nms_emit_body(const float *pred, int n_boxes, int attrs, float thr, const int *box_off, int max_cand, float *cand,
+                                              int corner) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_boxes) return;
     const float *p = pred + (size_t)i * attrs;
@@ -96,6 +106,15 @@ __global__ void nms_emit_kernel(const float *pred_all, size_t pred_stride, int n
             ++slot;
         }
     }
+}
+__global__ void nms_emit_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, const int *box_off_all, int max_cand,
+                                float *cand_all, int corner) {
+    nms_emit_body(pred_all + blockIdx.y * pred_stride, n_boxes, attrs, thr, box_off_all + (size_t)blockIdx.y * n_boxes, max_cand,
+                  cand_all + (size_t)blockIdx.y * max_cand * 6, corner);
+}
+__global__ void nms_emit_ragged_kernel(const float *pred, const NmsFrame *fr, int attrs, float thr, const int *box_off, int max_cand, float *cand_all) {
+    const NmsFrame f = fr[blockIdx.y];
+    nms_emit_body(pred + (size_t)f.row0 * attrs, f.n_rows, attrs, thr, box_off + f.row0, max_cand, cand_all + (size_t)blockIdx.y * max_cand * 6, f.corner);
 }
 
 __global__ void nms_rank_kernel(const float *cand_all, const int *counts_all, int max_cand, float *sorted_all) {
@@ -165,9 +184,8 @@ __global__ void nms_mask_kernel(const float *sorted_all, const int *counts_all, 
     }
 }
 
-__global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
-                                 float sx, float sy, const float *scale, float *kept_all, int cap) {
-    if (scale) { sx = scale[blockIdx.y * 2]; sy = scale[blockIdx.y * 2 + 1]; }       // per frame (sx, sy): frames of different sizes
+__device__ __forceinline__ void nms_sweep_body(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all,
+                                               int max_cand, float sx, float sy, float *kept_all, int cap) {
     const float *sorted = sorted_all + (size_t)blockIdx.y * max_cand * 6;
     const unsigned long long *mask = mask_all + (size_t)blockIdx.y * max_cand * words_ld;
     int *counts = counts_all + blockIdx.y * 4;
@@ -199,6 +217,16 @@ __global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long lo
     }
     __syncthreads();
     if (threadIdx.x == 0) counts[1] = n_keep;
+}
+__global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
+                                 float sx, float sy, const float *scale, float *kept_all, int cap) {
+    if (scale) { sx = scale[blockIdx.y * 2]; sy = scale[blockIdx.y * 2 + 1]; }       // per frame (sx, sy): frames of different sizes
+    nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, sx, sy, kept_all, cap);
+}
+// ragged form: a plain frame's boxes are scaled by its own ratio, a windowed frame's descriptor holds (1, 1)
+__global__ void nms_sweep_ragged_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
+                                        const NmsFrame *fr, float *kept_all, int cap) {
+    nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, fr[blockIdx.y].sx, fr[blockIdx.y].sy, kept_all, cap);
 }
 
 NmsWorkspace::NmsWorkspace(int max_candidates, int frames) : max_cand(0), frames(0) { resize(max_candidates, frames); }
@@ -242,8 +270,8 @@ NmsWorkspace::~NmsWorkspace() {
 // candidate order (fp32 weight sum, fp64 box sums, like the host loop), so that the rounding and the rows where 0/0 gives NaN are
 // the host's.  `cand` holds the candidates in emit order, `sorted` in kept (score) order; runs behind the sweep, before publish.
 constexpr int MERGE_MAX = 3000;
-__global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
-                                                        float iou_thres, float *kept_all) {
+__device__ __forceinline__ void nms_merge_body(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand, float iou_thres,
+                                               float *kept_all) {
     const float *cand = cand_all + (size_t)blockIdx.x * max_cand * 6;
     const float *sorted = sorted_all + (size_t)blockIdx.x * max_cand * 6;
     float *kept = kept_all + (size_t)blockIdx.x * MAX_DET * 6;
@@ -276,6 +304,16 @@ __global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, c
     }
     __syncthreads();
     for (int i = threadIdx.x; i < k * 4; i += blockDim.x) kept[(size_t)(i >> 2) * 6 + (i & 3)] = mean[i & 3];
+}
+__global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
+                                                        float iou_thres, float *kept_all) {
+    nms_merge_body(cand_all, sorted_all, counts_all, max_cand, iou_thres, kept_all);
+}
+// ragged form: only the frames whose descriptor asks for the merge branch (the windowed ones)
+__global__ __launch_bounds__(256) void nms_merge_ragged_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
+                                                               float iou_thres, const NmsFrame *fr, float *kept_all) {
+    if (!fr[blockIdx.x].merge) return;                           // (uniform over the workgroup)
+    nms_merge_body(cand_all, sorted_all, counts_all, max_cand, iou_thres, kept_all);
 }
 
 // Results go to the host through a KERNEL that stores into the pinned buffers (host-coherent memory the device writes in place),
@@ -310,6 +348,29 @@ void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frame
                        counts.p, max_cand, sx, sy, scale, kept.p, cap);
     if (merge) hipLaunchKernelGGL(nms_merge_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, kept.p);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
+    hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
+    YDS_HIP(hipGetLastError());
+}
+
+// The same launch sequence for frames of different row counts and forms in one block of predictions (the slotted pass of the pipeline):
+// count / scan / emit take every frame's own rows, grid.x is sized by the largest frame; rank, mask and publish work per frame on the
+// candidate counts as in launch().  fr: n_frames descriptors, device-readable until the kernels have run.
+void NmsWorkspace::launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
+                                 float iou_thres, int cap, hipStream_t s) {
+    if (attrs < 6) fail("nms: predictions need at least one class");
+    if (n_frames < 1 || max_rows < 1) fail("nms: %d frames of at most %d rows", n_frames, max_rows);
+    if (n_frames > frames) resize(max_cand, n_frames);
+    box_count.ensure(total_rows);
+    const int nb = (max_rows + 255) / 256;
+    hipLaunchKernelGGL(nms_count_ragged_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, fr, attrs, conf_thres, box_count.p);
+    hipLaunchKernelGGL(nms_scan_ragged_kernel, dim3(1, n_frames), dim3(1024), 0, s, box_count.p, fr, counts.p);
+    hipLaunchKernelGGL(nms_emit_ragged_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, fr, attrs, conf_thres, box_count.p, max_cand, cand.p);
+    hipLaunchKernelGGL(nms_rank_kernel, dim3(16, n_frames), dim3(256), 0, s, cand.p, counts.p, max_cand, sorted.p);
+    const int words_ld = max_cand / 64;
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
+    hipLaunchKernelGGL(nms_sweep_ragged_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
+                       counts.p, max_cand, fr, kept.p, cap);
+    hipLaunchKernelGGL(nms_merge_ragged_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, fr, kept.p);
     hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
     YDS_HIP(hipGetLastError());
 }
@@ -440,6 +501,35 @@ int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes
     for (int pass = 0; pass < 2; ++pass) {
         // corner-form boxes, the merge branch as a kernel behind the sweep: the launch of the window-mode pipeline
         ws->launch(pred.p, stride, n_frames, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, yds::MAX_DET, nullptr, true, true);
+        YDS_HIP(hipStreamSynchronize(nullptr));
+        if (ws->needed(n_frames) <= ws->max_cand) break;
+        ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again
+    }
+    for (int f = 0; f < n_frames; ++f) n_out[f] = ws->collect(f, out6_host + (size_t)f * cap * 6, cap);
+    YDS_API_END
+}
+
+int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, int n_frames, const uint64_t *row0, const int32_t *n_rows,
+                        const int32_t *corner_merge, const float *scale, float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out) {
+    YDS_API_BEGIN
+    if (n_frames < 1) yds::fail("nms: %d frames", n_frames);
+    std::vector<yds::NmsFrame> fr(n_frames);
+    int max_rows = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        if (n_rows[f] < 1 || row0[f] + (uint64_t)n_rows[f] > total_rows)
+            yds::fail("nms: frame %d holds rows [%llu, +%d) of %zu", f, (unsigned long long)row0[f], n_rows[f], total_rows);
+        fr[f] = yds::NmsFrame{row0[f], n_rows[f], corner_merge[f * 2] != 0, corner_merge[f * 2 + 1] != 0, scale[f * 2], scale[f * 2 + 1], 0};
+        max_rows = std::max(max_rows, n_rows[f]);
+    }
+    static thread_local std::unique_ptr<yds::NmsWorkspace> ws;           // own workspace: sized by the number of frames
+    if (!ws) ws.reset(new yds::NmsWorkspace(4096, n_frames));
+    yds::DevBuf<float> pred;
+    yds::DevBuf<yds::NmsFrame> fr_dev;
+    pred.upload(pred_host, total_rows * attrs);
+    fr_dev.upload(fr.data(), fr.size());
+    YDS_HIP(hipStreamSynchronize(nullptr));
+    for (int pass = 0; pass < 2; ++pass) {
+        ws->launch_ragged(pred.p, fr_dev.p, n_frames, max_rows, total_rows, attrs, conf_thres, iou_thres, yds::MAX_DET, nullptr);
         YDS_HIP(hipStreamSynchronize(nullptr));
         if (ws->needed(n_frames) <= ws->max_cand) break;
         ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again

@@ -25,6 +25,27 @@
 
 namespace yds {
 
+// The slot plan of a step that holds at least one windowed frame (a window setting per stream, set_stream_windows): what the detector
+// runs (one network slot per window of a windowed frame, one per plain frame; frame order, then window order) and what the NMS merges
+// (one descriptor per frame).  Built on the host from the layout, the stream of every frame and the streams' settings; empty: the
+// step has no windowed frame and takes the unslotted path.
+struct SlotPlan {
+    std::vector<SlotRec> slots;
+    std::vector<NmsFrame> frames;
+    int max_rows = 0;                  // largest n_rows of a frame
+    bool empty() const { return slots.empty(); }
+    bool operator==(const SlotPlan &o) const {
+        if (slots.size() != o.slots.size() || frames.size() != o.frames.size()) return false;
+        for (size_t n = 0; n < slots.size(); ++n) {                 // (the scales follow from th, tw)
+            const SlotRec &a = slots[n], &b = o.slots[n];
+            if (a.off != b.off || a.stride != b.stride || a.th != b.th || a.tw != b.tw || a.window != b.window || a.x0 != b.x0 || a.y0 != b.y0) return false;
+        }
+        for (size_t n = 0; n < frames.size(); ++n)
+            if (frames[n].n_rows != o.frames[n].n_rows || frames[n].corner != o.frames[n].corner) return false;
+        return true;
+    }
+};
+
 // One NMS slot: workspace + pinned results, and the events of the detector pass that uses it.  Two slots alternate, so that the
 // pass of batch i+1 can be enqueued before the host has waited for and read the results of batch i: the detector stream never
 // drains between passes.
@@ -37,6 +58,27 @@ struct DetSlot {
     ~DetSlot() {
         for (hipEvent_t e : {e0, e1, e2, e_nms, e_r0, e_r1}) (void)hipEventDestroy(e);
         if (tab) (void)hipHostFree(tab);
+        if (plan_tab) (void)hipHostFree(plan_tab);
+    }
+    // Slotted pass: the plan's two tables (per slot, per frame), pinned and read in place like `tab` below, one copy per DetSlot so that a
+    // look-ahead pass keeps its own.  Only slotted passes read it, the NMS last: e_nms of the slot's previous pass is what to wait for.
+    void *plan_tab = nullptr;
+    size_t plan_bytes = 0, plan_slots_n = 0;
+    const SlotRec *plan_slots() const { return static_cast<const SlotRec *>(plan_tab); }
+    const NmsFrame *plan_frames() const { return reinterpret_cast<const NmsFrame *>(plan_slots() + plan_slots_n); }
+    void write_plan(const SlotPlan &pl) {
+        YDS_HIP(hipEventSynchronize(e_nms));
+        const size_t need = pl.slots.size() * sizeof(SlotRec) + pl.frames.size() * sizeof(NmsFrame);
+        if (plan_bytes < need) {
+            if (plan_tab) (void)hipHostFree(plan_tab);
+            plan_tab = nullptr;
+            plan_bytes = 0;
+            YDS_HIP(hipHostMalloc(&plan_tab, std::max<size_t>(need, 4096), hipHostMallocDefault));
+            plan_bytes = std::max<size_t>(need, 4096);
+        }
+        plan_slots_n = pl.slots.size();
+        memcpy(plan_tab, pl.slots.data(), pl.slots.size() * sizeof(SlotRec));
+        memcpy(const_cast<NmsFrame *>(plan_frames()), pl.frames.data(), pl.frames.size() * sizeof(NmsFrame));
     }
     // Frames of different sizes: the table the slot's pass reads ON THE DEVICE - the resize kernel each frame's (offset, h, w), the NMS
     // sweep each frame's (sx, sy) - in pinned host memory the kernels read in place (like the extractor's crop list).  It lives with
@@ -86,12 +128,15 @@ struct Geometry {
 struct Pass {
     const uint8_t *frames = nullptr;   // nullptr: no pass (slot still names the DetSlot used last)
     Geometry geo;                      // layout of the frames the pass was enqueued with
+    SlotPlan plan;                     // not empty: a slotted pass (some frame is windowed by its stream's setting)
     int batch = 0;
     int slot = 0;                      // DetSlot
     enum { NOTHING, HEAD, WHOLE } done = NOTHING;     // NOTHING with frames set: the head is still to be (re-)enqueued
     bool split = false;                // HEAD: the first layers went with the head, the tail runs the rest
     bool open() const { return frames && done != WHOLE; }
-    bool is_whole(const uint8_t *f, int n, const Geometry &g) const { return frames == f && batch == n && geo == g && done == WHOLE; }
+    bool is_whole(const uint8_t *f, int n, const Geometry &g, const SlotPlan &pl) const {
+        return frames == f && batch == n && geo == g && plan == pl && done == WHOLE;
+    }
 };
 
 // ---- frames handed over as HOST memory (img_detect.py:70-71 starts from a host frame) ------------------------------
@@ -239,7 +284,7 @@ public:
         YDS_HIP(hipEventRecord(s.e0, net->stream));
         p.done = Pass::HEAD;
         p.split = false;
-        if (windows_for(p.geo)) {                                   // window mode: the whole pass (resize included) is the tail's
+        if (windows_for(p.geo) || !p.plan.empty()) {                // window mode, slotted pass: the whole pass (resize included) is the tail's
             YDS_HIP(hipEventRecord(s.e1, net->stream));
             return;
         }
@@ -256,7 +301,20 @@ public:
     void launch_detector_tail(Pass &p) {
         DetSlot &s = det[p.slot];
         const size_t per_slot = (size_t)net->total_boxes * net->attrs;
-        if (const int T = windows_for(p.geo)) {
+        if (!p.plan.empty()) {
+            const size_t n_slots = p.plan.slots.size();
+            if (win_pred.n < n_slots * per_slot) {
+                YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
+                win_pred.alloc(n_slots * per_slot);
+            }
+            s.write_plan(p.plan);
+            pred_rows = n_slots * net->total_boxes;
+            net->forward_slots(p.frames, s.plan_slots(), (int)n_slots, win_pred.p, frames_bgr);
+            stager.mark_read(p.frames, net->stream, FrameStager::DET);
+            YDS_HIP(hipEventRecord(s.e2, net->stream));
+            s.nms->launch_ragged(win_pred.p, s.plan_frames(), p.batch, p.plan.max_rows, n_slots * net->total_boxes, net->attrs, conf, nms_thres, 300,
+                                 net->stream);
+        } else if (const int T = windows_for(p.geo)) {
             if (win_pred.n < (size_t)p.batch * T * per_slot) {
                 YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
                 win_pred.alloc((size_t)p.batch * T * per_slot);
@@ -292,6 +350,7 @@ public:
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_windows while a look-ahead pass is in flight (consume it with a step first)");
         if (ww > 0 && wh <= 0) fail("pipeline: window %d x %d", ww, wh);
         if (ww > 0 && !(overlap >= 0)) fail("pipeline: window overlap %g", overlap);
+        if (ww > 0 && any_stream_windows()) fail("pipeline: set_windows while a stream holds a window setting of its own (set_stream_windows): one or the other");
         win_w = ww > 0 ? ww : 0; win_h = ww > 0 ? wh : 0; win_overlap = overlap;
         win_tab_h = win_tab_w = 0;
     }
@@ -311,12 +370,72 @@ public:
         return win.T;
     }
 
+    // ---- a window setting per stream (yds_pipeline_set_stream_windows; ImageDetector(win_size, overlap) per camera) ----
+    // Frame b of a step belongs to stream stream_of[b]; that stream's setting decides whether the frame is cut into windows (as above,
+    // for its own size) or takes the plain branch - no setting, or w < win_w and h < win_h (img_detect.py:68).  A step with at least one
+    // windowed frame runs as a SLOTTED pass: every window and every plain frame is one network slot (SlotPlan), the slots run in chunks
+    // of batch_max (Darknet::forward_slots) into win_pred, a windowed frame's rows in corner form in frame pixels, a plain frame's
+    // rows as the network gave them; ONE ragged NMS launch (NmsWorkspace::launch_ragged) treats each frame by its descriptor - merge
+    // branch and scale 1 for a windowed frame, centre form and the frame's own ratio for a plain one.  Like window mode the whole pass
+    // is the tail's.  A step with no windowed frame has an empty plan and runs exactly the launches it runs without any setting.
+    struct StreamWindows { int w = 0, h = 0; double overlap = 0; };
+    bool any_stream_windows() const {
+        for (const StreamWindows &sw : stream_win)
+            if (sw.w > 0) return true;
+        return false;
+    }
+    void set_stream_windows(int stream, int ww, int wh, double overlap) {
+        if (!multi) fail("pipeline: created by yds_pipeline_create: it has no streams (window mode: yds_pipeline_set_windows)");
+        if (stream < 0 || stream >= (int)trks.size()) fail("pipeline: stream %d outside [0,%zu)", stream, trks.size());
+        if (ww > 0 && wh <= 0) fail("pipeline: window %d x %d", ww, wh);
+        if (ww > 0 && !(overlap >= 0)) fail("pipeline: window overlap %g", overlap);
+        if (pending.frames || ahead.reid_in_flight)
+            fail("pipeline: set_stream_windows while a look-ahead pass is in flight (consume it with a step first)");
+        if (win_w > 0) fail("pipeline: set_stream_windows while window mode is on for all streams (yds_pipeline_set_windows): one or the other");
+        stream_win.resize(trks.size());
+        stream_win[stream] = ww > 0 ? StreamWindows{ww, wh, overlap} : StreamWindows();
+    }
+    // the plan of a step of `batch` frames laid out by `geo`, frame b of stream stream_of[b]
+    SlotPlan make_plan(const Geometry &geo, int batch) const {
+        SlotPlan pl;
+        if (!multi || !any_stream_windows()) return pl;
+        bool windowed_any = false;
+        for (int b = 0; b < batch; ++b) {
+            const int h = geo.mixed() ? geo.frames[b].h : geo.h, w = geo.mixed() ? geo.frames[b].w : geo.w;
+            const uint64_t off = geo.mixed() ? geo.frames[b].off : (uint64_t)b * h * w * 3;
+            const StreamWindows &sw = stream_win[stream_of[b]];
+            NmsFrame f{(uint64_t)pl.slots.size() * net->total_boxes, 0, 0, 0, 1.f, 1.f, 0};
+            if (sw.w > 0 && !(w < sw.w && h < sw.h)) {              // img_detect.py:101-121: x-major then y, extended by the overlap, clipped
+                const int ox = (int)(sw.w * sw.overlap), oy = (int)(sw.h * sw.overlap);
+                for (int x = 0; x < w; x += sw.w)
+                    for (int y = 0; y < h; y += sw.h) {
+                        const int th = std::min(y + sw.h + oy, h) - y, tw = std::min(x + sw.w + ox, w) - x;
+                        pl.slots.push_back(SlotRec{off + ((uint64_t)y * w + x) * 3, w * 3, th, tw, 1, x, y, (float)((double)tw / net->img_w),
+                                                   (float)((double)th / net->img_h)});
+                        f.n_rows += net->total_boxes;
+                    }
+                f.corner = f.merge = 1;
+                windowed_any = true;
+            } else {                                                // plain branch: resize_boxes by the frame's own ratio, in the sweep
+                pl.slots.push_back(SlotRec{off, w * 3, h, w, 0, 0, 0, 1.f, 1.f});
+                f.n_rows = net->total_boxes;
+                f.sx = (float)((double)w / net->img_w);
+                f.sy = (float)((double)h / net->img_h);
+            }
+            pl.max_rows = std::max(pl.max_rows, (int)f.n_rows);
+            pl.frames.push_back(f);
+        }
+        if (!windowed_any) return SlotPlan();
+        return pl;
+    }
+
     // detections of one batch after NMS + class mask + p1p2Toxywh, ready for the extractor and the tracker
     struct Dets {
         std::vector<float> tlwh, payload;
         std::vector<int> frame_of, first, n_det;
         const uint8_t *frames = nullptr;
         Geometry geo;                             // layout of `frames`: the crops read it
+        SlotPlan plan;                            // plan of the pass the detections came from
         int batch = 0;
         bool reid_in_flight = false;
         hipStream_t reid_on = nullptr;            // stream the ReID pass of this batch was enqueued on
@@ -334,7 +453,7 @@ public:
             // Rare slow path; bench-only logit injection is not re-selected for it.
             YDS_HIP(hipStreamSynchronize(net->stream));
             s.nms->resize(s.nms->needed(batch), s.nms->frames);
-            Pass redo{p.frames, p.geo, batch, p.slot};
+            Pass redo{p.frames, p.geo, p.plan, batch, p.slot};
             launch_detector(redo);
             if (pending.done == Pass::HEAD) pending.done = Pass::NOTHING;      // a head enqueued for the next pass has been overwritten
             YDS_HIP(hipEventSynchronize(s.e_nms));
@@ -355,7 +474,7 @@ public:
         std::vector<float> det_rows(300 * 6);
         d.tlwh.clear(); d.payload.clear(); d.frame_of.clear();
         d.first.assign(batch + 1, 0); d.n_det.assign(batch, 0);
-        d.frames = p.frames; d.geo = p.geo; d.batch = batch; d.reid_in_flight = false;
+        d.frames = p.frames; d.geo = p.geo; d.plan = p.plan; d.batch = batch; d.reid_in_flight = false;
         for (int b = 0; b < batch; ++b) {
             d.n_det[b] = s.nms->collect(b, det_rows.data(), 300);
             for (int i = 0; i < d.n_det[b]; ++i) {
@@ -452,7 +571,10 @@ public:
         check_step(geo, batch);
         auto t_begin = clk::now();
         const int inject_set = std::exchange(next_inject_set, -1); // bench-only: applies to the pass this step enqueues for `next`
-        const bool resumed = ahead.reid_in_flight && ahead.frames == frames_dev && ahead.batch == batch && ahead.geo == geo;
+        // The plan of this step, and of the look-ahead pass it enqueues: the next call's frames are planned with THIS step's streams; if
+        // the next call names other streams (another plan) the pass is not reused - the rule of a changed layout.
+        const SlotPlan plan = make_plan(geo, batch);
+        const bool resumed = ahead.reid_in_flight && ahead.frames == frames_dev && ahead.batch == batch && ahead.geo == geo && ahead.plan == plan;
         // Serialized schedule (round 4).  The ReID pass of batch i and the detector pass of batch i+1 are both chip-filling
         // sequences of matrix-core kernels; from two streams they time-share the CUs, every launch stretched by the other
         // stream's work (1.3x on the detector's kernels at cfg2) for the same total.  With >= serial_min crops in the batch the
@@ -482,7 +604,7 @@ public:
                                : (trial.wants_serial() ? 256 : -1);
         // detector (+ NMS) of the next batch goes in flight, in the DetSlot this batch's pass does not use
         auto launch_next = [&](int this_slot, bool head_only) {
-            pending = next_frames_dev ? Pass{next_frames_dev, geo, batch, this_slot ^ 1} : Pass{nullptr, Geometry(), 0, this_slot};
+            pending = next_frames_dev ? Pass{next_frames_dev, geo, plan, batch, this_slot ^ 1} : Pass{nullptr, Geometry(), SlotPlan(), 0, this_slot};
             if (!next_frames_dev) return;
             if (inject_set >= 0) net->select_injection_set(inject_set);
             if (head_only) launch_detector_head(pending, true);
@@ -504,7 +626,7 @@ public:
             launch_next(pending.slot, false);
         } else {
             ahead.reid_in_flight = false;
-            Pass now = pending.is_whole(frames_dev, batch, geo) ? pending : Pass{frames_dev, geo, batch, pending.slot ^ 1};
+            Pass now = pending.is_whole(frames_dev, batch, geo, plan) ? pending : Pass{frames_dev, geo, plan, batch, pending.slot ^ 1};
             launch_detector(now);
             launch_next(now.slot, serial_min >= 0);                 // enqueued BEFORE the host waits for this batch's NMS
             finish_detector(cur, now);
@@ -587,7 +709,9 @@ public:
     int win_w = 0, win_h = 0, win_tab_h = 0, win_tab_w = 0;
     double win_overlap = 0;
     WindowTable win;
-    DevBuf<float> win_pred;
+    DevBuf<float> win_pred;            // shifted predictions of a window-mode pass; the prediction block of a slotted pass
+    std::vector<StreamWindows> stream_win;        // set_stream_windows: setting of every stream (empty: none was ever set)
+    size_t pred_rows = 0;              // rows of the last slotted pass in win_pred (bench / test read-out)
 };
 
 }  // namespace yds
@@ -701,6 +825,20 @@ int yds_pipeline_set_frame_order(yds_pipe *p, int bgr) {
 int yds_pipeline_set_windows(yds_pipe *p, int win_w, int win_h, double overlap) {
     YDS_API_BEGIN
     p->p->set_windows(win_w, win_h, overlap);
+    YDS_API_END
+}
+int yds_pipeline_set_stream_windows(yds_pipe *p, int stream, int win_w, int win_h, double overlap) {
+    YDS_API_BEGIN
+    p->p->set_stream_windows(stream, win_w, win_h, overlap);
+    YDS_API_END
+}
+int yds_pipeline_slot_pred(yds_pipe *p, float *pred_host, size_t cap_rows, size_t *n_rows) {
+    YDS_API_BEGIN
+    yds::Pipeline *pp = p->p;
+    YDS_HIP(hipStreamSynchronize(pp->net->stream));
+    if (n_rows) *n_rows = pp->pred_rows;
+    const size_t rows = std::min(cap_rows, pp->pred_rows);
+    if (pred_host && rows) YDS_HIP(hipMemcpy(pred_host, pp->win_pred.p, rows * pp->net->attrs * sizeof(float), hipMemcpyDeviceToHost));
     YDS_API_END
 }
 int yds_pipeline_set_schedule(yds_pipe *p, int min_crops) {

@@ -593,7 +593,7 @@ class VideoDetector:
             if real_show and cv2 is not None:
                 cv2.destroyAllWindows()
 
-    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False):
+    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -607,8 +607,14 @@ class VideoDetector:
         win_size runs the pipeline in window mode (MultiStreamPipeline(win_size=...)).
         mixed_sizes=True lifts the first limit: every stream has its own uint8 [h, w, 3] shape (1080p and 720p cameras in one step,
         MultiStreamPipeline.step_mixed) and keeps it - a stream that changes its shape midway raises ValueError naming the stream;
-        window mode takes frames of one size, so win_size with mixed_sizes=True raises ValueError."""
+        window mode takes frames of one size, so win_size with mixed_sizes=True raises ValueError.
+        stream_win_sizes: one (w, h) or None per source - that camera's ImageDetector(win_size, overlap), with this detector's overlap
+        (MultiStreamPipeline(stream_win_sizes=...)): a wide camera is cut into windows, a door camera is not, in one step, with
+        mixed_sizes False or True.  It needs a detector whose own win_size is None (ValueError otherwise); per stream the items are
+        those of detect() with a detector of that win_size."""
         from . import _lib, pipeline as pl
+        sources = list(sources)
+        stream_win_sizes = pl.check_stream_win_sizes(len(sources), self.image_detector.win_size, stream_win_sizes, "VideoDetector.detect_streams")
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
         if self.action_id is not None:
@@ -616,8 +622,8 @@ class VideoDetector:
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
-            raise ValueError("VideoDetector.detect_streams: mixed_sizes=True cannot be combined with win_size (window mode cuts frames of one size)")
-        sources = list(sources)
+            raise ValueError("VideoDetector.detect_streams: mixed_sizes=True cannot be combined with win_size (window mode cuts frames of one "
+                             "size); give every stream its own setting with stream_win_sizes")
         S = len(sources)
         if S == 0:
             return
@@ -627,7 +633,7 @@ class VideoDetector:
         if det.model.batch_max < S * F:
             det.model.set_batch_max(S * F)
         pipe = pl.MultiStreamPipeline(det.model, [self.tracker.clone() for _ in range(S)], det.thres, det.nms_thres, class_mask=self.class_mask,
-                                      win_size=det.win_size, overlap=det.overlap)
+                                      win_size=det.win_size, overlap=det.overlap, stream_win_sizes=stream_win_sizes)
         lib = _lib.load()
         its = [iter(self._frames(src)) for src in sources]
         since, hold, alive = [0] * S, [None] * S, [True] * S

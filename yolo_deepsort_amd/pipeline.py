@@ -39,6 +39,24 @@ def pack_frames(frames):
     return block, off, hw
 
 
+def check_stream_win_sizes(n_streams, win_size, stream_win_sizes, who="MultiStreamPipeline"):
+    """stream_win_sizes of n_streams streams as a list of (w, h) or None; raises ValueError for a list of another length, an entry
+    that is no (w, h) pair, or win_size given as well (one window setting for all streams, or one per stream)."""
+    if stream_win_sizes is None:
+        return None
+    if win_size is not None:
+        raise ValueError("%s: win_size (one setting for all streams) and stream_win_sizes (one per stream) exclude each other" % who)
+    sizes = list(stream_win_sizes)
+    if len(sizes) != n_streams:
+        raise ValueError("%s: stream_win_sizes needs one entry per stream (%d), got %d" % (who, n_streams, len(sizes)))
+    out = []
+    for s, ws in enumerate(sizes):
+        if ws is not None and (len(ws) != 2 or int(ws[0]) < 1 or int(ws[1]) < 1):
+            raise ValueError("%s: stream_win_sizes[%d] must be None or a positive (w, h), got %r" % (who, s, ws))
+        out.append(None if ws is None else (int(ws[0]), int(ws[1])))
+    return out
+
+
 class Pipeline:
     def __init__(self, net, deepsort, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
         self.net, self.ds, self.cap = net, deepsort, int(cap)
@@ -130,14 +148,18 @@ class MultiStreamPipeline(Pipeline):
     one size): the detector, NMS and ReID run once over all of them, the association advances every stream's tracker in the same
     launches (a stream's k-th frame of the step in round k).  Per stream the results are those of that stream run alone through
     Pipeline.  Schedule, frame order, prefetch and stage times: as Pipeline.  step_mixed / step_host_mixed take cameras of different
-    frame sizes in one step (every frame with its own offset and size); window mode takes frames of one size."""
+    frame sizes in one step (every frame with its own offset and size); window mode (win_size) takes frames of one size.
+    stream_win_sizes: one (w, h) or None per stream - ImageDetector(win_size, overlap) per camera (set_stream_windows), in uniform
+    and mixed steps alike; exclusive with win_size."""
 
-    def __init__(self, net, deepsorts, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15):
+    def __init__(self, net, deepsorts, conf_thres=0.5, nms_thres=0.4, class_mask=None, cap=512, win_size=None, overlap=0.15,
+                 stream_win_sizes=None):
         from .deep_sort import Extractor
         self._h = None
         deepsorts = list(deepsorts)
         if not deepsorts:
             raise ValueError("MultiStreamPipeline: no streams")
+        stream_win_sizes = check_stream_win_sizes(len(deepsorts), win_size, stream_win_sizes)
         ex = deepsorts[0].extractor
         if not isinstance(ex, Extractor) or any(d.extractor is not ex for d in deepsorts):
             raise ValueError("MultiStreamPipeline: the streams' DeepSort objects must share one Extractor (DeepSort.clone())")
@@ -153,6 +175,19 @@ class MultiStreamPipeline(Pipeline):
         self._h = _lib.check_ptr(_lib.load().yds_pipeline_create_multi(net._h, ex._h, trks, self.n_streams, conf_thres, nms_thres,
                                                                        _lib.ptr(mask) if mask.size else None, int(mask.size)))
         self.set_windows(win_size, overlap)
+        self.stream_win_sizes = [None] * self.n_streams
+        for s, ws in enumerate(stream_win_sizes or []):
+            if ws is not None:
+                self.set_stream_windows(s, ws, overlap)
+
+    def set_stream_windows(self, stream, win_size=None, overlap=0.15):
+        """The window setting of ONE stream, ImageDetector(win_size=(win_w, win_h), overlap) of that camera: its frames are cut into
+        their own windows whatever their size (None: the plain branch), in step / step_host and step_mixed / step_host_mixed
+        (yds_pipeline_set_stream_windows).  Refused (YdsError) for a stream outside [0, n_streams), while a look-ahead pass is in
+        flight, and while set_windows holds a setting for all streams."""
+        ww, wh = (0, 0) if win_size is None else (int(win_size[0]), int(win_size[1]))
+        _lib.check(_lib.load().yds_pipeline_set_stream_windows(self._h, int(stream), ww, wh, float(overlap)))
+        self.stream_win_sizes[int(stream)] = None if win_size is None else (ww, wh)
 
     def _streams(self, stream_of_frame):
         s = np.ascontiguousarray(stream_of_frame, dtype=np.int32).reshape(-1)
