@@ -415,6 +415,18 @@ int yds_conv_clock(double *ghz, double *sampled_ms, int reset);
  * (res_mode 0 none, 1 after the activation, 2 before it), y NCHW [n,cout,ho,wo]. */
 int yds_conv_run(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
                  const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc, float *y_nchw);
+/* The same convolution on strided views, as the planner lays tensors out inside concatenation buffers.  view[9] = {x_ld, x_off,
+ * y_ld, y_off, r_ld, r_off, n_split, y2_ld, y2_off}: the input is channels [x_off, x_off + cin) of x_nhwc [n,h,w,x_ld], the residual
+ * channels [r_off, r_off + cout) of res_nhwc [n,ho,wo,r_ld], the output goes to channels [y_off, ..) of a y_ld-channel buffer that is
+ * pre-filled with `sentinel`.  n_split > 0 is the merged launch of two convolutions of one tensor: filters [0, n_split) go to the
+ * first view, filters [n_split, cout) to channels [y2_off, ..) of a second buffer of y2_ld channels (no residual then).  Returns the
+ * WHOLE buffers, decoded: y_nchw [n,y_ld,ho,wo], y2_nchw [n,y2_ld,ho,wo] (NULL without a split).  A tensor is H16 when the
+ * arithmetic is f16x3 and its channel count, ld and offset are multiples of 32, else fp32 (multiples of 4).  Refuses, with a
+ * message, a variant that the planner would never launch on this case: one that is neither a timing candidate of the layer nor
+ * the split-K kernel where the planner's rule selects it. */
+int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
+                      const int *view, const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc,
+                      float sentinel, float *y_nchw, float *y2_nchw);
 
 /* ---- multi-GPU exchange step ------------------------------------------------------
  * The reference is single-GPU; what shards is the video stream: every stream owns a tracker (DeepSort.clone(),

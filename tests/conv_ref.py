@@ -1,0 +1,193 @@
+"""Float64 reference of one fused convolution layer, and what the conv kernel tests derive from it (plain helpers, no fixtures).
+
+The bound.  The f16x3 kernels compute x*w as  x_hi*w_hi + x_hi*w_lo + x_lo*w_hi  on fp16 operands with fp32 accumulation
+(csrc/h16.h, csrc/conv_f16x3.hip).  A kernel that loses one of the cross terms computes the convolution of a ROUNDED operand
+instead: x_hat = float16(x / 256) * 256 (the hi half of an activation) or w_hat = float16(w).  `mutant_bound` evaluates both of
+these wrong convolutions in float64; the smaller of their errors, `mut`, is what a broken variant would show at the very least.
+The tests hold every kernel to mut / 16 and the reference arithmetic itself (CPU, test_conv_ref.py) to mut / 64, so the bound comes
+from the reference computation alone, never from what a kernel returns."""
+import functools
+
+import numpy as np
+
+F32 = np.float32
+ACT = {"linear": 0, "leaky": 1, "mish": 2, "relu": 3}
+
+CASES = [  # n, h, w, cin, cout, k, s, act, res_mode
+    (2, 19, 19, 64, 128, 3, 1, "leaky", 0),
+    (1, 38, 38, 128, 256, 3, 1, "leaky", 1),          # fused shortcut
+    (3, 20, 12, 96, 160, 3, 2, "mish", 0),            # stride 2, ragged M / Cout tiles
+    (2, 26, 26, 256, 255, 1, 1, "linear", 0),         # head: fp32 output, Cout % 4 != 0
+    (1, 16, 8, 64, 64, 3, 1, "relu", 2),              # ReID basic block (residual before the activation)
+    (5, 13, 13, 32, 512, 1, 1, "leaky", 0),
+    (1, 40, 40, 32, 64, 3, 1, "mish", 1),
+    # 3x3 stride 1 at the detector's widths: tiles cross image boundaries, ragged tails, 1 / 2 / 4 channel groups
+    (3, 19, 19, 128, 128, 3, 1, "leaky", 0),
+    (2, 76, 76, 64, 128, 3, 1, "leaky", 1),
+    (5, 13, 13, 32, 96, 3, 1, "mish", 0),
+    (7, 8, 4, 256, 256, 3, 1, "relu", 2),
+    (1, 12, 304, 32, 64, 3, 1, "leaky", 1),           # one channel group: single window buffer, wide image
+    (2, 38, 38, 64, 256, 3, 1, "mish", 1),            # two N tiles, four half groups, 2 x 1444 pixels: tiles straddle the image boundary
+    (1, 120, 127, 32, 128, 3, 1, "leaky", 0),         # widest image the two-workgroup window kernel takes (384 window rows)
+    (3, 64, 32, 64, 64, 3, 1, "relu", 0),             # ReID layer1 shape: the 128x64 tile (two workgroups per CU), tiles cross crops
+    (2, 30, 43, 96, 48, 3, 1, "leaky", 1),            # its widest image (216 window rows), three channel groups, ragged filters
+    # layer shapes of the real workloads that the cases above do not reach
+    (2, 7, 5, 64, 96, 1, 2, "relu", 0),               # 1x1 stride 2, pad 0 (ReID downsample): odd extents, ragged output rows
+    (3, 16, 8, 128, 256, 1, 2, "linear", 0),          # ... even extents
+    (1, 3, 5, 32, 64, 3, 1, "leaky", 0),              # M = 15: less than any tile
+    (1, 1, 1, 64, 64, 3, 1, "relu", 2),               # one pixel: all taps but one lie in the padding
+    (2, 2, 1, 32, 32, 3, 1, "mish", 1),               # ... all but two
+    (40, 3, 3, 64, 128, 3, 1, "leaky", 1),            # 14 images per 128-row tile: every tile straddles many image borders
+    (2, 13, 13, 64, 18, 1, 1, "linear", 0),           # one-class head: Cout < 32, Cout % 4 != 0, fp32 output
+    (1, 9, 11, 12, 40, 3, 2, "leaky", 0),             # Cin, Cout no multiples of 32: fp32 tensors through the staged kernels' on-the-fly split
+]
+
+
+def act_ref(v, act):
+    if act == 1:
+        return np.where(v > 0, v, v * 0.1)
+    if act == 2:
+        sp = np.where(v > 20, v, np.log1p(np.exp(np.minimum(v, 20))))
+        return v * np.tanh(sp)
+    if act == 3:
+        return np.maximum(v, 0)
+    return v
+
+
+def out_hw(h, wd, k, s):
+    pad = (k - 1) // 2
+    return (h + 2 * pad - k) // s + 1, (wd + 2 * pad - k) // s + 1
+
+
+def conv_pre(x, w, k, s):
+    """The bare convolution in float64: x NHWC, w [cout][k*k*cin] in (kh, kw, c) order, pad (k - 1) // 2 -> NHWC."""
+    n, h, wd, cin = x.shape
+    cout = w.shape[0]
+    pad = (k - 1) // 2
+    ho, wo = out_hw(h, wd, k, s)
+    xp = np.zeros((n, h + 2 * pad, wd + 2 * pad, cin), np.float64)
+    xp[:, pad:pad + h, pad:pad + wd] = x
+    y = np.zeros((n, ho, wo, cout), np.float64)
+    w64 = np.asarray(w, np.float64).reshape(cout, k, k, cin)
+    for kh in range(k):
+        for kw in range(k):
+            patch = xp[:, kh:kh + s * (ho - 1) + 1:s, kw:kw + s * (wo - 1) + 1:s]
+            y += patch @ w64[:, kh, kw].T
+    return y
+
+
+def epilogue(pre, bias, act, res, res_mode):
+    """bias, residual (2: before the activation, 1: after it) and activation on an NHWC pre-activation -> NCHW, float64"""
+    y = pre + np.asarray(bias, np.float64)
+    if res_mode == 2:
+        y = y + res
+    y = act_ref(y, act)
+    if res_mode == 1:
+        y = y + res
+    return y.transpose(0, 3, 1, 2)
+
+
+def conv_ref(x, w, bias, k, s, act, res, res_mode):
+    return epilogue(conv_pre(x, w, k, s), bias, act, res, res_mode)
+
+
+# ---- the split-fp16 operands, in float64 (csrc/h16.h: x / 256 = hi + lo / 2048, w = hi + lo / 2048; hi, lo fp16) -------------------
+def _f16(v):
+    return np.asarray(v, np.float64).astype(np.float16).astype(np.float64)
+
+
+def split_x(x):
+    xs = np.asarray(x, np.float64) / 256
+    hi = _f16(xs)
+    return hi * 256, _f16((xs - hi) * 2048) / 2048 * 256
+
+
+def split_w(w):
+    w = np.asarray(w, np.float64)
+    hi = _f16(w)
+    return hi, _f16((w - hi) * 2048) / 2048
+
+
+def x_hat(x):
+    return split_x(x)[0]
+
+
+def w_hat(w):
+    return split_w(w)[0]
+
+
+def mutant_bound(x, w, bias, k, s, act, res, res_mode, want):
+    """min over the two single-cross-term mutants of max|mutant - want|"""
+    no_xlo = np.abs(conv_ref(x_hat(x), w, bias, k, s, act, res, res_mode) - want).max()
+    no_wlo = np.abs(conv_ref(x, w_hat(w), bias, k, s, act, res, res_mode) - want).max()
+    return float(min(no_xlo, no_wlo))
+
+
+def emulated_f16x3(x, w, bias, k, s, act, res, res_mode):
+    """x_hi*w_hi + x_hi*w_lo + x_lo*w_hi accumulated exactly, epilogue in float64, result rounded to fp32"""
+    xh, xl = split_x(x)
+    wh, wl = split_w(w)
+    pre = conv_pre(xh, wh, k, s) + conv_pre(xh, wl, k, s) + conv_pre(xl, wh, k, s)
+    return epilogue(pre, bias, act, res, res_mode).astype(F32)
+
+
+def fp32_conv(x, w, bias, k, s, act, res, res_mode):
+    """the convolution evaluated in fp32 on the CPU (torch), epilogue in float64, result rounded to fp32"""
+    import torch
+    cout, cin = w.shape[0], x.shape[3]
+    xt = torch.from_numpy(np.ascontiguousarray(x)).permute(0, 3, 1, 2)
+    wt = torch.from_numpy(np.ascontiguousarray(w.reshape(cout, k, k, cin))).permute(0, 3, 1, 2).contiguous()
+    pre = torch.nn.functional.conv2d(xt, wt, None, stride=s, padding=(k - 1) // 2).permute(0, 2, 3, 1).numpy().astype(np.float64)
+    return epilogue(pre, bias, act, res, res_mode).astype(F32)
+
+
+def make_case(rng, n, h, wd, cin, cout, k, s, res_mode):
+    """the tests' operands: standard-normal input, bias and residual, weights scaled by 1 / sqrt(K)"""
+    x = rng.standard_normal((n, h, wd, cin)).astype(F32)
+    w = (rng.standard_normal((cout, k * k * cin)) / np.sqrt(k * k * cin)).astype(F32)
+    bias = rng.standard_normal(cout).astype(F32)
+    ho, wo = out_hw(h, wd, k, s)
+    res = rng.standard_normal((n, ho, wo, cout)).astype(F32) if res_mode else None
+    return x, w, bias, res
+
+
+class Ref:
+    """one case's operands with its float64 result `want`, the mutant bound `mut` and the fp32 CPU error `err_fp32`"""
+
+    def __init__(self, case, x, w, bias, res):
+        n, h, wd, cin, cout, k, s, act, res_mode = case
+        self.case, self.x, self.w, self.bias, self.res = case, x, w, bias, res
+        self.k, self.s, self.act, self.res_mode = k, s, ACT[act], res_mode
+        args = (bias, k, s, self.act, res, res_mode)
+        self.want = conv_ref(x, w, *args)
+        self.scale = float(np.abs(self.want).max())
+        self.mut = mutant_bound(x, w, *args, self.want)
+        self.err_fp32 = float(np.abs(fp32_conv(x, w, *args) - self.want).max())
+        for a in (self.x, self.w, self.bias, self.res, self.want):
+            if a is not None:
+                a.setflags(write=False)
+
+    def err(self, got):
+        return float(np.abs(got - self.want).max())
+
+
+@functools.lru_cache(maxsize=None)
+def case_refs():
+    """Ref of every entry of CASES (one RandomState(17) stream in list order); computed once per process, read-only"""
+    rng = np.random.RandomState(17)
+    return tuple(Ref(c, *make_case(rng, *c[:7], c[8])) for c in CASES)
+
+
+# ---- host restatement of plan_tile_map (csrc/conv_common.h): the XCD grid with the smallest per-K-step footprint ---------------------
+def plan_tile_map(M, cout, BM, BN):
+    """-> (tiles_m, tiles_n, xm, rm, rn)"""
+    tiles_m, tiles_n = (M + BM - 1) // BM, (cout + BN - 1) // BN
+    best = None
+    for xm in (1, 2, 4, 8):
+        xn = 8 // xm
+        rm, rn = (tiles_m + xm - 1) // xm, (tiles_n + xn - 1) // xn
+        waste = rm * rn * 8 - tiles_m * tiles_n
+        cost = (rm * BM + rn * BN) * 64 + waste * (BM + BN)
+        if best is None or cost < best[0]:
+            best = (cost, xm, rm, rn)
+    return (tiles_m, tiles_n) + best[1:]

@@ -1,19 +1,29 @@
 // Single convolutions through the C ABI: yds_conv_bench times one layer shape on synthetic data, yds_conv_run runs one tile variant
 // on the caller's tensors (the kernel tests).  Both build the same case - input and residual (pre-split where the kernels take them
-// that way), weights, output - and differ in what they do with the launch.
+// that way), weights, output - and differ in what they do with the launch.  yds_conv_run_view is yds_conv_run on channel slices of
+// wider buffers and on the merged launch of two convolutions.
+#include "conv_common.h"
 #include "conv_weights.h"
 #include "h16.h"
 
+#include <algorithm>
 #include <stdlib.h>
 #include <string.h>
 
 namespace yds {
 namespace {
 
+// Where a case's tensors sit inside wider buffers (yds_conv_run_view): channel offsets and row lengths of the input, output and
+// residual views, and the second output of a merged launch.  Without one the tensors are dense.
+struct CaseViews {
+    int x_ld, x_off, y_ld, y_off, r_ld, r_off, n_split, y2_ld, y2_off;
+};
+
 struct ConvCase {
     ConvArgs a;
     ConvWeights cw;
-    DevBuf<float> x, y, res, raw[2];
+    DevBuf<float> x, y, y2, res, raw[4];
+    View y_whole, y2_whole;                  // the buffers a.y / a.y2 are slices of
 
     // host fp32 NHWC (ld = c) -> the device tensor v.p in v's format
     static void put(View &v, const float *host, DevBuf<float> &raw, DevBuf<float> &packed) {
@@ -24,22 +34,50 @@ struct ConvCase {
         v.p = packed.p;
         launch_pack_h16(raw.p, v, nullptr);
     }
-    // x_nhwc [n, h, w, cin], w_okkc [cout][ksize * ksize * cin], bias [cout], res_nhwc [n, ho, wo, cout] (read when res_mode): host
+    // channels [off, off + c) of the ld-channel tensor `whole`
+    static View slice(const View &whole, int off, int c) {
+        View v = whole;
+        v.p = whole.p + off;
+        v.c = c;
+        return v;
+    }
+    static bool h16_ok(int c, int ld, int off) { return c % 32 == 0 && ld % 32 == 0 && off % 32 == 0; }
+    // x_nhwc [n, h, w, x_ld], w_okkc [cout][ksize * ksize * cin], bias [cout], res_nhwc [n, ho, wo, r_ld] (read when res_mode): host;
+    // vw == nullptr: dense tensors (x_ld = cin, r_ld = cout), the output row padded to a multiple of 4.  With views the output
+    // buffers start out filled with `sentinel`.
     ConvCase(int n, int h, int w, int cin, int cout, int ksize, int stride, int act, const float *x_nhwc, const float *w_okkc, const float *bias,
-             const float *res_nhwc, int res_mode) {
-        const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1, ldy = (cout + 3) / 4 * 4;
+             const float *res_nhwc, int res_mode, const CaseViews *vw = nullptr, float sentinel = 0.f) {
+        const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
+        const CaseViews d = vw ? *vw : CaseViews{cin, 0, (cout + 3) / 4 * 4, 0, cout, 0, 0, 0, 0};
         const bool f16 = conv_math() == MATH_F16X3;
+        const int c1 = d.n_split > 0 ? d.n_split : cout, c2 = cout - c1;      // filters of the first / second output
         cw.shape(cout, cin, cin, ksize, stride, pad);
         cw.upload_korder(w_okkc, bias, nullptr);
         cw.fill(a);
         a.act = act;
-        y.alloc((size_t)n * ho * wo * ldy);
-        a.x = View{nullptr, n, h, w, cin, cin, (f16 && cin % 32 == 0) ? FMT_H16 : FMT_F32};
-        a.y = View{y.p, n, ho, wo, cout, ldy, (f16 && cout % 32 == 0) ? FMT_H16 : FMT_F32};
-        put(a.x, x_nhwc, raw[0], x);
+        View x_whole{nullptr, n, h, w, d.x_ld, d.x_ld, (f16 && h16_ok(cin, d.x_ld, d.x_off)) ? FMT_H16 : FMT_F32};
+        const int yfmt = (f16 && h16_ok(c1, d.y_ld, d.y_off) && h16_ok(c2, d.y2_ld, d.y2_off)) ? FMT_H16 : FMT_F32;
+        y_whole = View{nullptr, n, ho, wo, d.y_ld, d.y_ld, yfmt};
+        put(x_whole, x_nhwc, raw[0], x);
+        a.x = slice(x_whole, d.x_off, cin);
+        if (vw) {
+            const std::vector<float> fill(y_whole.pixels() * (size_t)std::max(d.y_ld, d.y2_ld), sentinel);
+            put(y_whole, fill.data(), raw[2], y);
+            if (c2 > 0) {
+                y2_whole = View{nullptr, n, ho, wo, d.y2_ld, d.y2_ld, yfmt};
+                put(y2_whole, fill.data(), raw[3], y2);
+                a.y2 = slice(y2_whole, d.y2_off, c2);
+                a.n_split = c1;
+            }
+        } else {
+            y.alloc(y_whole.pixels() * d.y_ld);
+            y_whole.p = y.p;
+        }
+        a.y = slice(y_whole, d.y_off, cout);                     // (merged: both filter counts, the first output's pointer and stride)
         if (res_mode) {
-            a.res = View{nullptr, n, ho, wo, cout, cout, a.y.fmt};
-            put(a.res, res_nhwc, raw[1], res);
+            View r_whole{nullptr, n, ho, wo, d.r_ld, d.r_ld, yfmt};
+            put(r_whole, res_nhwc, raw[1], res);
+            a.res = slice(r_whole, d.r_off, cout);
             a.res_mode = res_mode;
         }
         YDS_HIP(hipDeviceSynchronize());
@@ -94,6 +132,39 @@ int yds_conv_run(int variant, int n, int h, int w, int cin, int cout, int ksize,
     ConvCase c(n, h, w, cin, cout, ksize, stride, act, x_nhwc, w_okkc, bias, res_nhwc, res_mode);
     launch_conv(c.a, nullptr, variant);
     nhwc_to_host(c.a.y, y_nchw, nullptr);
+    YDS_API_END
+}
+
+int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode, const int *view,
+                      const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc, float sentinel, float *y_nchw,
+                      float *y2_nchw) {
+    YDS_API_BEGIN
+    using namespace yds;
+    const CaseViews v{view[0], view[1], view[2], view[3], view[4], view[5], view[6], view[7], view[8]};
+    const bool merged = v.n_split > 0;
+    const int c1 = merged ? v.n_split : cout;
+    if (n < 1 || h < 1 || w < 1 || cin < 4 || cout < 1 || cin % 4) fail("conv_run_view: bad shape (input channels must be a multiple of 4)");
+    if (res_mode && !res_nhwc) fail("conv_run_view: residual mode %d without a residual tensor", res_mode);
+    if (merged && (v.n_split >= cout || res_mode || !y2_nchw)) fail("conv_run_view: a merged launch needs 0 < n_split < cout, a second output and no residual");
+    auto inside = [](int off, int c, int ld) { return off >= 0 && c > 0 && off % 4 == 0 && ld % 4 == 0 && off + c <= ld; };
+    if (!inside(v.x_off, cin, v.x_ld)) fail("conv_run_view: input slice [%d, %d) does not fit %d channels (multiples of 4)", v.x_off, v.x_off + cin, v.x_ld);
+    if (!inside(v.y_off, c1, v.y_ld)) fail("conv_run_view: output slice [%d, %d) does not fit %d channels (multiples of 4)", v.y_off, v.y_off + c1, v.y_ld);
+    if (merged && !inside(v.y2_off, cout - c1, v.y2_ld)) fail("conv_run_view: second output slice [%d, %d) does not fit %d channels (multiples of 4)", v.y2_off, v.y2_off + cout - c1, v.y2_ld);
+    if (res_mode && !inside(v.r_off, cout, v.r_ld)) fail("conv_run_view: residual slice [%d, %d) does not fit %d channels (multiples of 4)", v.r_off, v.r_off + cout, v.r_ld);
+    ConvCase c(n, h, w, cin, cout, ksize, stride, act, x_nhwc, w_okkc, bias, res_nhwc, res_mode, &v, sentinel);
+    // only what the planner launches on such a layer: a timing candidate, or split-K where its rule applies
+    const int id = variant & kVariantMask;
+    if (variant < 0 || id >= kConvVariants) fail("conv_run_view: no such variant %d", variant);
+    const std::vector<int> cand = conv_candidates(c.a);
+    bool planned = std::find(cand.begin(), cand.end(), id) != cand.end();
+    if (id == VAR_SPLITK_64x128 && conv_math() == MATH_F16X3 && !merged && conv_presplit_input(c.a)) {
+        const ConvKernelArgs k = make_conv_args(c.a);
+        planned = conv_splitk_applicable(k, 0) && conv_splitk_preferred(k);
+    }
+    if (!planned) fail("conv_run_view: the planner never launches %s on this layer%s", conv_variant_name(id), merged ? " (merged launch)" : "");
+    launch_conv(c.a, nullptr, variant);
+    nhwc_to_host(c.y_whole, y_nchw, nullptr);
+    if (merged) nhwc_to_host(c.y2_whole, y2_nchw, nullptr);
     YDS_API_END
 }
 
