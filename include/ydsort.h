@@ -129,14 +129,15 @@ int yds_detect_tiled(yds_net *, const uint8_t *rgb_hwc_host, int h, int w, const
 int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres,
                        float *out6_host, int cap, int *n_out);
 /* yds_nms_merge_pred_batched <- the same function for n_frames images in ONE launch sequence, entirely on the device: the launch the
- *                        window-mode pipeline uses (yds_pipeline_set_windows) - corner-form candidates, blockIdx.y = image, the merge
+ *                        window-mode pipeline uses (yds_pipeline_set_windows; yds_nms_ragged_pred with one corner-form, merging
+ *                        descriptor of n_boxes rows per image) - corner-form candidates, blockIdx.y = image, the merge
  *                        branch as a kernel (one workgroup per image, sums in candidate order like the host loop of
  *                        yds_nms_merge_pred, so NaN rows agree) before the results are published; no candidate copy to the host.
  *                        pred_host [n_frames, n_boxes, attrs]; out6_host [n_frames, cap, 6]; n_out[n_frames] rows per image. */
 int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
                                float *out6_host, int cap, int *n_out);
-/* yds_nms_ragged_pred     <- both functions above for frames of different row counts in ONE launch sequence: the launch of a slotted
- *                        pipeline pass (yds_pipeline_set_stream_windows).  Frame f is rows [row0[f], row0[f] + n_rows[f]) of pred_host
+/* yds_nms_ragged_pred     <- both functions above for frames of different row counts in ONE launch sequence: the launch of a pipeline
+ *                        pass with a slot plan (window mode, a window setting per stream, a mixed layout).  Frame f is rows [row0[f], row0[f] + n_rows[f]) of pred_host
  *                        [total_rows, attrs]; corner_merge[2f] != 0: its boxes are x1,y1,x2,y2, corner_merge[2f+1] != 0: the merge branch
  *                        runs for it; its kept boxes are multiplied by (scale[2f], scale[2f+1]).  The kernels read these descriptors on
  *                        the device.  out6_host [n_frames, cap, 6], n_out [n_frames]. */
@@ -329,7 +330,8 @@ int yds_pipeline_set_frame_order(yds_pipe *, int bgr);
  * size straight from the frames in HBM (frame order honoured) and run through the network in chunks of at most batch_max; behind every
  * chunk the boxes go to corner form, are scaled to the window (resize_boxes) and shifted by its origin into per-frame storage in the
  * order of the concatenation at :142; ONE NMS launch per step does soft_non_max_suppression(merge=True, is_p1p2=True) for all frames
- * (yds_nms_merge_pred_batched), the merge branch included, on the device.  ReID, association, look-ahead, host-frame entries,
+ * (yds_nms_merge_pred_batched), the merge branch included, on the device - the slotted pass of yds_pipeline_set_stream_windows with
+ * the same setting for every stream.  ReID, association, look-ahead, host-frame entries,
  * prefetch, multi-stream and stage times work as without windows (stage_us[0] is 0: the resize is part of the detector's figure;
  * the serialized schedule applies, with the whole detector pass behind the ReID pass instead of split around it).  A frame with
  * w < win_w and h < win_h takes the plain path (:68).  win_w <= 0: window mode off (the default).  Valid for single- and multi-stream
@@ -470,7 +472,7 @@ int yds_comm_barrier(yds_comm *);
  *   yds_darknet_load_injection_sets / _select_injection_set: preload n_sets x batch_max tables (offsets: n_sets*batch_max+1 row
  *     offsets) and pick one per step.
  *   yds_pipeline_set_next_injection: the set to select before the prefetched detector pass of a pipeline step.
- *   yds_pipeline_slot_pred: the prediction block of the last slotted pass (yds_pipeline_set_stream_windows) as the NMS read it,
+ *   yds_pipeline_slot_pred: the prediction block of the last slotted pass (yds_pipeline_set_windows, yds_pipeline_set_stream_windows) as the NMS read it,
  *     [*n_rows, attrs] fp32, slot-major; at most cap_rows rows are copied (pred_host may be NULL to ask for *n_rows). */
 int yds_darknet_set_injection(yds_net *, int image, const float *rows_host, int n, float logit);
 int yds_darknet_load_injection_sets(yds_net *, const float *rows_host, const int32_t *offsets_host, int n_sets, float logit);

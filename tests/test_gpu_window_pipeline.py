@@ -1,6 +1,6 @@
 """Sliding-window detection in the batched pipelines (csrc/pipeline.cpp window mode, yds_pipeline_set_windows): the windows of all
 frames of a step are cut on the device, run through the detector in chunks of batch_max and merged per frame by one NMS launch
-(merge branch included, csrc/nms.hip nms_merge_kernel).  The yardstick is the frame-by-frame path - VideoDetector.process with an
+(merge branch included, csrc/nms.hip launch_ragged).  The yardstick is the frame-by-frame path - VideoDetector.process with an
 ImageDetector(win_size=...) (yds_detect_tiled, host merge branch) + DeepSort.update - which tests/test_gpu_assoc.py pins to the
 reference's golden vectors.  Row criterion as tests/test_gpu_pipeline.py: track ids and classes bit exact, boxes within one pixel,
 None frames agree.  yolov3-tiny at 416, win_size = (416, 416), overlap 0.15 throughout."""
@@ -182,6 +182,61 @@ def test_scripted_scene_one_forward_with_lookahead():
     assert got[7] is None and want[7] is None
     assert rows >= 20, rows
     assert pipe.stage_us()["detector_dev"] > 0
+
+
+# ------------------------------------------------------------------------------------------------ 1b. front end, bit exact
+def _slot_pred(pipe, attrs):
+    from yolo_deepsort_amd import _lib as L
+    n = C.c_size_t(0)
+    L.check(L.load().yds_pipeline_slot_pred(pipe._h, None, 0, C.byref(n)))
+    out = np.zeros((n.value, attrs), F32)
+    L.check(L.load().yds_pipeline_slot_pred(pipe._h, L.ptr(out), n.value, C.byref(n)))
+    return out
+
+
+def test_window_mode_front_end_bit_exact(monkeypatch):
+    """Window mode itself, one step of two random 480 x 640 frames = 8 slots (slot = frame * 4 + window).  batch_max = 8, one chunk:
+    every network-input slot equals the oracle's cv2-exact resize of its window; every row of the prediction block equals
+    img_detect.py:132-138 restated in fp32 on the network's raw rows - corner form, resize_boxes to the window, shift by its origin.
+    batch_max = 5 (chunks of 5 + 3 straddle the frames), and the same frames handed over in BGR order: the same block bit for bit.
+    The detector's built-in tile choice is pinned (YDS_NO_AUTOTUNE): a measured choice is made per batch size, and two conv tiles may
+    round a sum differently (seen between the chunks of 5 / 3 and of 8: 1e-7 relative), which is the detector's and not the route's."""
+    monkeypatch.setenv("YDS_NO_AUTOTUNE", "1")
+    from oracle.resize import resize_bilinear_u8
+    from yolo_deepsort_amd import _lib, pipeline as pl
+    blob = synth.darknet_weights_blob(_cfg(), 0, -1.3)
+    frames = np.random.RandomState(12).randint(0, 256, (2, 480, 640, 3)).astype(np.uint8)
+    slots = [(f, win) for f in range(2) for win in WINDOWS_480x640]
+
+    def block(batch_max, bgr):
+        net = _net(blob, batch_max)
+        pipe = pl.Pipeline(net, _deepsort(), 0.5, 0.4, win_size=WIN, overlap=OVERLAP)
+        pipe.set_frame_order(bgr)
+        dev = _lib.DeviceBuffer.from_array(np.ascontiguousarray(frames[..., ::-1]) if bgr else frames)
+        assert len(pipe.step(dev.ptr, 480, 640, 2)) == 2
+        return net, _slot_pred(pipe, net.num_attrs)
+
+    net, got = block(8, False)
+    boxes = net.num_boxes
+    got = got.reshape(8, boxes, net.num_attrs)
+    want_in = np.stack([resize_bilinear_u8(frames[f][y0:y0 + th, x0:x0 + tw], (SIZE, SIZE)).astype(F32).transpose(2, 0, 1) / F32(255.)
+                        for f, (x0, y0, th, tw) in slots], 0)
+    got_in = net.get_input(8)
+    for n, slot in enumerate(slots):
+        assert np.array_equal(got_in[n], want_in[n]), (n, slot)
+    raw = net.forward(want_in)                                             # the same 8 images through the same detector
+    assert raw.shape == got.shape
+    for n, (f, (x0, y0, th, tw)) in enumerate(slots):
+        half = raw[n][:, 2:4] / F32(2)
+        corner = np.concatenate([raw[n][:, :2] - half, raw[n][:, :2] + half], 1)
+        scale = np.array([F32(tw / SIZE), F32(th / SIZE)] * 2, F32)        # resize_boxes: python-double ratio, fp32 multiply
+        want = raw[n].copy()
+        want[:, :4] = corner * scale + np.array([x0, y0, x0, y0], F32)
+        assert want.dtype == F32 and np.array_equal(got[n], want), (n, f)
+    for batch_max, bgr in ((5, False), (8, True), (5, True)):
+        other = block(batch_max, bgr)[1]
+        print("batch_max", batch_max, "bgr", bgr, "rows", other.shape[0], "elements that differ", int((other.reshape(got.shape) != got).sum()))
+        assert other.shape == (8 * boxes, net.num_attrs) and np.array_equal(other.reshape(got.shape), got), (batch_max, bgr)
 
 
 # ------------------------------------------------------------------------------------------------ 2. chunks straddling frames

@@ -808,3 +808,117 @@ def test_conv_weight_packer_under_sanitizers(tmp_path):
                    check=True, capture_output=True, text=True, timeout=300)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == "bad 0", (out.stdout, out.stderr)
+
+
+_PLAN_MAIN = r"""
+#include "slot_plan.h"
+#include <stdio.h>
+using namespace yds;
+static int bad = 0;
+#define CHECK(c) do { if (!(c)) { ++bad; printf("line %d: %s\n", __LINE__, #c); } } while (0)
+static const int NET = 416, BOXES = 2535;
+struct Win { int x, y, th, tw; };
+static void check_slot(const SlotRec &s, uint64_t frame_off, int w, const Win *win, int h) {
+    if (win) {
+        CHECK(s.off == frame_off + ((uint64_t)win->y * w + win->x) * 3 && s.stride == w * 3);
+        CHECK(s.window == 1 && s.x0 == win->x && s.y0 == win->y && s.th == win->th && s.tw == win->tw);
+        CHECK(s.sx == (float)((double)win->tw / NET) && s.sy == (float)((double)win->th / NET));
+    } else {
+        CHECK(s.off == frame_off && s.stride == w * 3 && s.window == 0 && s.x0 == 0 && s.y0 == 0 && s.th == h && s.tw == w);
+        CHECK(s.sx == 1.f && s.sy == 1.f);
+    }
+}
+static void check_frame(const NmsFrame &f, size_t slot0, int n_slots, bool windowed, int h, int w) {
+    CHECK(f.row0 == (uint64_t)slot0 * BOXES && f.n_rows == n_slots * BOXES && f.pad == 0);
+    if (windowed) CHECK(f.corner == 1 && f.merge == 1 && f.sx == 1.f && f.sy == 1.f);
+    else CHECK(f.corner == 0 && f.merge == 0 && f.sx == (float)((double)w / NET) && f.sy == (float)((double)h / NET));
+}
+int main() {
+    // the camera set of tests/test_gpu_stream_windows.py: A, a 333 x 501 frame, B, C, D, E
+    const Win A[4] = {{0, 0, 478, 478}, {0, 416, 64, 478}, {416, 0, 478, 224}, {416, 416, 64, 224}};
+    const Win B[2] = {{0, 0, 360, 478}, {416, 0, 360, 64}};
+    const Win E[4] = {{0, 0, 276, 368}, {0, 240, 240, 368}, {320, 0, 276, 320}, {320, 240, 240, 320}};
+    const int hw[6][2] = {{480, 640}, {333, 501}, {360, 480}, {300, 400}, {480, 640}, {480, 640}};
+    const Win *wins[6] = {A, nullptr, B, nullptr, nullptr, E};
+    const int n_win[6] = {4, 0, 2, 0, 0, 4};
+    const WindowSetting W{416, 416, 0.15}, WE{320, 240, 0.15}, none;
+    const std::vector<WindowSetting> per_frame = {W, none, W, W, none, WE};
+    std::vector<FrameGeom> geom;
+    uint64_t off = 0;
+    for (int b = 0; b < 6; ++b) { geom.push_back(FrameGeom{off, hw[b][0], hw[b][1]}); off += (uint64_t)hw[b][0] * hw[b][1] * 3; }
+    CHECK(geom[2].off % 2 == 1);
+    {
+        const SlotPlan pl = build_slot_plan(6, 0, 0, geom.data(), per_frame, NET, NET, BOXES);
+        CHECK(pl.slots.size() == 13 && pl.frames.size() == 6 && pl.windowed && !pl.direct() && !pl.empty() && pl.max_rows == 4 * BOXES);
+        size_t n = 0;
+        for (int b = 0; b < 6 && pl.slots.size() == 13 && pl.frames.size() == 6; ++b) {
+            check_frame(pl.frames[b], n, n_win[b] ? n_win[b] : 1, n_win[b] > 0, hw[b][0], hw[b][1]);
+            if (!n_win[b]) check_slot(pl.slots[n++], geom[b].off, hw[b][1], nullptr, hw[b][0]);
+            for (int t = 0; t < n_win[b]; ++t) check_slot(pl.slots[n++], geom[b].off, hw[b][1], &wins[b][t], hw[b][0]);
+        }
+        CHECK(n == 13);
+        CHECK(pl == pl && !(pl == SlotPlan()));
+    }
+    {   // the same layout, no setting: a direct plan, slot b = frame b
+        for (const std::vector<WindowSetting> &win : {std::vector<WindowSetting>(), std::vector<WindowSetting>(6)}) {
+            const SlotPlan pl = build_slot_plan(6, 0, 0, geom.data(), win, NET, NET, BOXES);
+            CHECK(pl.slots.size() == 6 && pl.frames.size() == 6 && !pl.windowed && pl.direct() && pl.max_rows == BOXES);
+            for (int b = 0; b < 6 && pl.slots.size() == 6 && pl.frames.size() == 6; ++b) {
+                check_slot(pl.slots[b], geom[b].off, hw[b][1], nullptr, hw[b][0]);
+                check_frame(pl.frames[b], b, 1, false, hw[b][0], hw[b][1]);
+            }
+        }
+    }
+    {   // a uniform layout: no setting, a setting per frame that is none, a window larger than the frame - no plan
+        CHECK(build_slot_plan(3, 480, 640, nullptr, {}, NET, NET, BOXES).empty());
+        CHECK(build_slot_plan(3, 480, 640, nullptr, {none, none, none}, NET, NET, BOXES).empty());
+        CHECK(build_slot_plan(3, 300, 400, nullptr, {W}, NET, NET, BOXES).empty());
+        CHECK(!build_slot_plan(3, 300, 400, nullptr, {W}, NET, NET, BOXES).direct());
+    }
+    {   // the setting of all streams on two 480 x 640 frames: slot b * 4 + t
+        const SlotPlan pl = build_slot_plan(2, 480, 640, nullptr, {W}, NET, NET, BOXES);
+        CHECK(pl.slots.size() == 8 && pl.frames.size() == 2 && pl.windowed && pl.max_rows == 4 * BOXES);
+        for (int b = 0; b < 2 && pl.slots.size() == 8 && pl.frames.size() == 2; ++b) {
+            check_frame(pl.frames[b], b * 4, 4, true, 480, 640);
+            for (int t = 0; t < 4; ++t) check_slot(pl.slots[b * 4 + t], (uint64_t)b * 480 * 640 * 3, 640, &A[t], 480);
+        }
+        CHECK(pl == build_slot_plan(2, 480, 640, nullptr, {W, W}, NET, NET, BOXES));
+        CHECK(!(pl == build_slot_plan(2, 480, 640, nullptr, {W, none}, NET, NET, BOXES)));
+    }
+    {   // a 1 x 1 frame (plain: both sides under the window) and a frame of exactly the window size (one window, itself)
+        const std::vector<FrameGeom> g = {FrameGeom{0, 1, 1}, FrameGeom{3, 416, 416}};
+        const SlotPlan pl = build_slot_plan(2, 0, 0, g.data(), {W}, NET, NET, BOXES);
+        const Win whole{0, 0, 416, 416};
+        CHECK(pl.slots.size() == 2 && pl.frames.size() == 2 && pl.windowed && pl.max_rows == BOXES);
+        if (pl.slots.size() == 2 && pl.frames.size() == 2) {
+            check_slot(pl.slots[0], 0, 1, nullptr, 1);
+            check_frame(pl.frames[0], 0, 1, false, 1, 1);
+            check_slot(pl.slots[1], 3, 416, &whole, 416);
+            check_frame(pl.frames[1], 1, 1, true, 416, 416);
+        }
+        const SlotPlan one = build_slot_plan(1, 1, 1, nullptr, {WindowSetting{1, 1, 0.0}}, NET, NET, BOXES);     // a 1 x 1 window
+        const Win px{0, 0, 1, 1};
+        CHECK(one.slots.size() == 1 && one.windowed);
+        if (one.slots.size() == 1) check_slot(one.slots[0], 0, 1, &px, 1);
+    }
+    printf("bad %d\n", bad);
+    return bad ? 1 : 0;
+}
+"""
+
+
+def test_slot_plan_under_sanitizers(tmp_path):
+    """csrc/slot_plan.h (plain C++, the one place the window grid and the slot / frame records of a detector pass are built) in a
+    stand-alone program built with AddressSanitizer and UBSan, on the camera set of tests/test_gpu_stream_windows.py (whose window
+    lists that module pins to oracle.tiled.windows): the 13 slots and 6 frame descriptors element for element, then the empty, the
+    direct and the all-streams plan, a 1 x 1 frame and a frame of exactly the window size."""
+    import shutil
+    cxx = shutil.which("g++")
+    assert cxx, "g++ not found"
+    csrc = os.path.join(ROOT, "yolo_deepsort_amd", "csrc")
+    src, exe = tmp_path / "plan_main.cpp", tmp_path / "plan_main"
+    src.write_text(_PLAN_MAIN)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc, str(src), "-o", str(exe)],
+                   check=True, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "bad 0", (out.stdout, out.stderr)

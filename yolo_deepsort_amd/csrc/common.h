@@ -7,6 +7,8 @@
 #include <vector>
 #include <stdexcept>
 
+#include "slot_plan.h"
+
 namespace yds {
 
 // ---- error plumbing ---------------------------------------------------------------------
@@ -147,25 +149,13 @@ void launch_inject_batch(const View &head, int batch, const float *table_dev, co
                          int num_classes, float logit, hipStream_t s);
 // stretch-resize uint8 HWC frames to NHWC4 fp32 in [0,1] (4th channel 0)
 void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y, hipStream_t s, bool bgr = false);   // bgr: frames in a decoder's B, G, R byte order
-// One frame of a step whose frames differ in size (the "mixed" entries): h x w pixels at frames + off, rows w * 3 bytes apart.
-struct FrameGeom { uint64_t off; int32_t h, w; };
 // (off[n], h[n], w[n]) from the C ABI's two arrays; refuses h or w < 1 and a frame that ends past `frames_bytes`
 std::vector<FrameGeom> checked_layout(const uint64_t *frame_off, const int32_t *frame_hw, int n, size_t frames_bytes);
-// launch_resize_u8 with the geometry of every frame read from `geom` (n entries, device-readable for as long as the kernel may run)
-void launch_resize_u8_frames(const uint8_t *frames, const FrameGeom *geom, int n, const View &y, hipStream_t s, bool bgr = false);
-// sliding windows: slots [slot0, slot0 + n) of B frames x T windows (slot = b * T + t; one host frame: B = 1), layers.hip
-void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_dev, int T, int slot0, int n, const View &y, hipStream_t s,
-                          bool bgr);
-void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int T, int slot0, int n,
-                         float *dst, hipStream_t s);
-// Slotted pass (pipeline.cpp, a window setting per stream): the network slots of a step whose frames are cut differently - a windowed
-// frame contributes one slot per window, a plain frame one slot for the whole frame.  A slot's source region is th x tw pixels at
-// frames + off (the window origin inside the frames buffer), rows `stride` bytes apart.  window != 0: its boxes go to corner form, are
-// scaled by (sx, sy) = (tw / img_w, th / img_h) and shifted by (x0, y0) (launch_window_boxes' arithmetic); else they are copied.
-struct SlotRec { uint64_t off; int32_t stride, th, tw, window, x0, y0; float sx, sy; };
-// slots [0, n) of `slots` (device-readable for as long as the kernel may run) -> the n images of y; blockIdx.y = slot
+// The front end of a pass with a slot plan (slot_plan.h): slots [0, n) of `slots` (device-readable for as long as the kernel may
+// run) -> the n images of y; blockIdx.y = slot
 void launch_slot_resize(const uint8_t *frames, const SlotRec *slots, int n, const View &y, hipStream_t s, bool bgr);
-// rows [0, n * n_boxes) of pred (the network output of those n slots) -> dst, same row order
+// rows [0, n * n_boxes) of pred (the network output of those n slots) -> dst, same row order: a window slot's boxes in corner form,
+// scaled and shifted (SlotRec), a plain slot's rows copied
 void launch_slot_boxes(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst, hipStream_t s);
 // ReID: crop + resize to 64x128 + /255 + mean/std -> NHWC4
 // boxes: [D,5] = x1,y1,x2,y2,frame index (frames are h*w*3 bytes apart)

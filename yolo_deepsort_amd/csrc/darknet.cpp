@@ -725,10 +725,11 @@ void Darknet::forward_u8_frames_dev(const uint8_t *frames_dev, const std::vector
     const int batch = (int)geom.size();
     if (in_channels != 3) fail("forward_u8: network expects %d channels", in_channels);
     check_pass(batch);
-    geom_dev.ensure(batch_max);
-    YDS_HIP(hipMemcpyAsync(geom_dev.p, geom.data(), geom.size() * sizeof(FrameGeom), hipMemcpyHostToDevice, stream));
-    YDS_HIP(hipStreamSynchronize(stream));                      // the caller's table may go away
-    launch_resize_u8_frames(frames_dev, geom_dev.p, batch, input_view(batch), stream);
+    std::vector<SlotRec> slots;
+    for (const FrameGeom &g : geom) slots.push_back(plain_slot(g.off, g.h, g.w));
+    slot_tab.upload(slots.data(), slots.size(), stream);
+    YDS_HIP(hipStreamSynchronize(stream));                      // `slots` goes away
+    launch_slot_resize(frames_dev, slot_tab.p, batch, input_view(batch), stream, false);
     run_graph(batch);
 }
 
@@ -740,33 +741,6 @@ void Darknet::forward_u8_host(const uint8_t *frames, int h, int w, int batch, fl
     forward_u8_dev(stage_u8.p, h, w, batch);
     if (out_host) YDS_HIP(hipMemcpyAsync(out_host, out.p, (size_t)batch * total_boxes * attrs * sizeof(float), hipMemcpyDeviceToHost, stream));
     YDS_HIP(hipStreamSynchronize(stream));
-}
-
-void WindowTable::build(const int *rects_xyhw, int n, int img_h, int img_w, hipStream_t s) {
-    scale_host.resize((size_t)n * 2);
-    for (int t = 0; t < n; ++t) {
-        const int th = rects_xyhw[t * 4 + 2], tw = rects_xyhw[t * 4 + 3];
-        scale_host[t * 2] = (float)((double)tw / img_w);       // resize_boxes: python-double ratio, fp32 multiply
-        scale_host[t * 2 + 1] = (float)((double)th / img_h);
-    }
-    rects.ensure((size_t)n * 4);
-    scale.ensure((size_t)n * 2);
-    // s: enqueued on s; nullptr: synchronous
-    YDS_HIP(s ? hipMemcpyAsync(rects.p, rects_xyhw, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, s)
-              : hipMemcpy(rects.p, rects_xyhw, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice));
-    YDS_HIP(s ? hipMemcpyAsync(scale.p, scale_host.data(), scale_host.size() * sizeof(float), hipMemcpyHostToDevice, s)
-              : hipMemcpy(scale.p, scale_host.data(), scale_host.size() * sizeof(float), hipMemcpyHostToDevice));
-    T = n;
-}
-
-void Darknet::forward_windows(const uint8_t *frames_dev, int h, int w, int n_frames, const WindowTable &tab, float *pred, bool bgr) {
-    const int slots = n_frames * tab.T;
-    for (int slot0 = 0; slot0 < slots; slot0 += batch_max) {
-        const int nb = std::min(batch_max, slots - slot0);
-        launch_window_resize(frames_dev, h, w, tab.rects.p, tab.T, slot0, nb, input_view(nb), stream, bgr);
-        run_graph(nb);
-        launch_window_boxes(out.p, total_boxes, attrs, tab.rects.p, tab.scale.p, tab.T, slot0, nb, pred, stream);
-    }
 }
 
 void Darknet::forward_slots(const uint8_t *frames_dev, const SlotRec *slots, int n_slots, float *pred, bool bgr) {
@@ -790,9 +764,12 @@ void Darknet::forward_tiles_host(const uint8_t *frame, int h, int w, const int *
     tiled_pred.ensure((size_t)n_tiles * total_boxes * attrs);
     YDS_HIP(hipMemcpyAsync(stage_u8.p, frame, nbytes, hipMemcpyHostToDevice, stream));
     stage_h = h; stage_w = w; stage_n = 1;                      // stage_u8 now holds exactly this frame
-    tiles.build(tiles_xyhw, n_tiles, img_h, img_w, stream);
-    forward_windows(stage_u8.p, h, w, 1, tiles, tiled_pred.p, false);
-    YDS_HIP(hipStreamSynchronize(stream));          // the caller's buffers may go away
+    std::vector<SlotRec> slots;
+    for (int t = 0; t < n_tiles; ++t)
+        slots.push_back(window_slot(0, w, tiles_xyhw[t * 4], tiles_xyhw[t * 4 + 1], tiles_xyhw[t * 4 + 2], tiles_xyhw[t * 4 + 3], img_h, img_w));
+    slot_tab.upload(slots.data(), slots.size(), stream);
+    forward_slots(stage_u8.p, slot_tab.p, n_tiles, tiled_pred.p, false);
+    YDS_HIP(hipStreamSynchronize(stream));          // the caller's buffers and `slots` may go away
 }
 
 void Darknet::layer_output_host(int i, int batch, float *nchw) {

@@ -78,16 +78,6 @@ struct Storage {
     int into = -1, coff = 0;
 };
 
-// Rectangles (x, y, th, tw) of T windows of a frame and each window's resize_boxes scale (tw / img_w, th / img_h), on the device.
-struct WindowTable {
-    DevBuf<int> rects;
-    DevBuf<float> scale;
-    int T = 0;
-    // s: the two copies are enqueued on s (the caller synchronises s before rects_xyhw goes away); nullptr: synchronous copies
-    void build(const int *rects_xyhw, int n, int img_h, int img_w, hipStream_t s);
-    std::vector<float> scale_host;                          // source of the enqueued copy
-};
-
 class Darknet {
 public:
     Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_max);
@@ -97,7 +87,7 @@ public:
     void forward_f32_host(const float *nchw, int batch, float *out_host);
     void forward_u8_host(const uint8_t *frames, int h, int w, int batch, float *out_host);
     void forward_u8_dev(const uint8_t *frames_dev, int h, int w, int batch);
-    // frames of different sizes: frame n at frames_dev + geom[n].off (the table is copied before the call returns)
+    // frames of different sizes: frame n at frames_dev + geom[n].off, one plain slot each (the table is copied before the call returns)
     void forward_u8_frames_dev(const uint8_t *frames_dev, const std::vector<FrameGeom> &geom);
     void forward_resized(int batch) { run_graph(batch); }      // input buffer already filled
     // the same pass enqueued in two pieces (layers [0, head_layers()) and the rest): the pipeline puts another stream-ordered
@@ -107,13 +97,10 @@ public:
     // sliding-window front end (img_detect.py:97-139): windows (x, y, th, tw) of one host frame -> corner-form, window-
     // shifted predictions [n_tiles * total_boxes, attrs] in tiled_pred (windows run in chunks of batch_max)
     void forward_tiles_host(const uint8_t *frame, int h, int w, const int *tiles_xyhw, int n_tiles);
-    // window slots [0, n_frames * tab.T) of n_frames frames in HBM (slot = frame * T + window) through the network in chunks of
-    // batch_max (a chunk may straddle frames): resize -> network -> boxes in corner form, resize_boxes to the window's own size,
-    // shifted by the window origin, to pred [slots * total_boxes, attrs].  Asynchronous on `stream`.
-    void forward_windows(const uint8_t *frames_dev, int h, int w, int n_frames, const WindowTable &tab, float *pred, bool bgr);
-    // forward_windows for slots that are described one by one (a step whose frames are cut differently, pipeline.cpp): slots
-    // [0, n_slots) of `slots` (device-readable until the pass has run) in chunks of batch_max; a window slot's boxes as above, a plain
-    // slot's rows unchanged in centre form, to pred [n_slots * total_boxes, attrs]
+    // slots [0, n_slots) of `slots` (slot_plan.h; device-readable until the pass has run) through the network in chunks of batch_max (a
+    // chunk may straddle frames): resize -> network -> a window slot's boxes in corner form, resize_boxes to the window's own size,
+    // shifted by the window origin, a plain slot's rows unchanged in centre form, to pred [n_slots * total_boxes, attrs].
+    // Asynchronous on `stream`.
     void forward_slots(const uint8_t *frames_dev, const SlotRec *slots, int n_slots, float *pred, bool bgr);
     void layer_output_host(int layer, int batch, float *nchw);
     void get_input_host(int batch, float *nchw);
@@ -141,10 +128,9 @@ public:
     std::vector<int> yolo_layers;
     DevBuf<float> input, out, stage_f32;
     DevBuf<uint8_t> stage_u8;
-    DevBuf<FrameGeom> geom_dev;                              // table of the last forward_u8_frames_dev
+    DevBuf<SlotRec> slot_tab;                                // slots of the last forward_u8_frames_dev / forward_tiles_host
     int stage_h = 0, stage_w = 0, stage_n = 0;               // frames last uploaded by forward_u8_host (device copy in stage_u8)
     DevBuf<float> tiled_pred;
-    WindowTable tiles;
     hipStream_t stream = nullptr;
     // bench-only logit injection
     std::vector<DevBuf<float>> inject_rows;
@@ -187,21 +173,17 @@ private:
 
 // --------------------------------------------------------------------------------------------- NMS
 // Device multi-label NMS over decoded predictions [n_boxes, attrs] (nms.hip).
-// One frame of a ragged launch: rows [row0, row0 + n_rows) of the prediction block; corner: they hold x1,y1,x2,y2; merge: the merge
-// branch runs for it; (sx, sy): resize_boxes scale of its kept boxes (1 for a windowed frame, whose boxes are in frame pixels already).
-struct NmsFrame { uint64_t row0; int32_t n_rows, corner, merge; float sx, sy; int32_t pad; };
 class NmsWorkspace {
 public:
     explicit NmsWorkspace(int max_candidates = 16384, int frames = 1);
     ~NmsWorkspace();
     NmsWorkspace(const NmsWorkspace &) = delete;
     // asynchronous form: launch() enqueues the kernels and the copies into pinned host memory, collect() reads
-    // them after the caller synchronised the stream.  corner: the predictions already hold x1,y1,x2,y2 (is_p1p2=True);
-    // merge: the reference's merge branch as a kernel behind the sweep (nms_merge_kernel) - both per launch, no state
-    // scale: (sx, sy) of every frame, [n_frames, 2], read on the device when the sweep runs (frames of different sizes); NULL: sx, sy
+    // them after the caller synchronised the stream.  corner: the predictions already hold x1,y1,x2,y2 (is_p1p2=True)
     void launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                float sx, float sy, int cap, hipStream_t s, bool corner = false, bool merge = false, const float *scale = nullptr);
-    // launch() for frames that differ in row count and form, described by `fr` [n_frames] which the kernels read on the device;
+                float sx, float sy, int cap, hipStream_t s, bool corner = false);
+    // launch() for frames that differ in row count and form, described by `fr` [n_frames] (slot_plan.h) which the kernels read on the
+    // device - per frame corner form or not, the reference's merge branch as a kernel behind the sweep or not, its own (sx, sy);
     // max_rows: the largest n_rows, total_rows: the largest row0 + n_rows (box_count is addressed like the prediction block)
     void launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
                        float iou_thres, int cap, hipStream_t s);

@@ -369,89 +369,10 @@ void launch_resize_u8(const uint8_t *frames, int n, int h, int w, const View &y,
     YDS_HIP(hipGetLastError());
 }
 
-// The same front end for a step whose frames differ in size (pipeline.cpp, the mixed entries): frame n = blockIdx.y lies at
-// frames + geom[n].off and is geom[n].h x geom[n].w, so the mode (copy, exact 2x, linear) is that frame's own; arithmetic: resize_px.
-__global__ void resize_u8_frames_kernel(const uint8_t *frames, const FrameGeom *geom, float *y, int Ho, int Wo, int bgr) {
-    const FrameGeom g = geom[blockIdx.y];
-    const int per = Ho * Wo;
-    float *dst = y + (size_t)blockIdx.y * per * 4;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < per; idx += gridDim.x * blockDim.x) {
-        const int oy = idx / Wo, ox = idx - oy * Wo;
-        float o[3];
-        resize_px(frames + g.off, (size_t)g.w * 3, g.h, g.w, Ho, Wo, oy, ox, o);
-        if (bgr) { const float v = o[0]; o[0] = o[2]; o[2] = v; }
-        *reinterpret_cast<float4 *>(dst + (size_t)idx * 4) = make_float4(__fdiv_rn(o[0], 255.f), __fdiv_rn(o[1], 255.f), __fdiv_rn(o[2], 255.f), 0.f);
-    }
-}
-
-void launch_resize_u8_frames(const uint8_t *frames, const FrameGeom *geom, int n, const View &y, hipStream_t s, bool bgr) {
-    if (y.c != 4 || y.ld != 4) fail("resize: destination must be NHWC4");
-    if (n < 1 || n > 65535) fail("resize: %d frames", n);
-    const int per_frame = grid_for((size_t)y.h * y.w), gx = std::min(per_frame, std::max(1, 8192 / n));
-    hipLaunchKernelGGL(resize_u8_frames_kernel, dim3(gx, n), dim3(256), 0, s, frames, geom, y.p, y.h, y.w, bgr ? 1 : 0);
-    YDS_HIP(hipGetLastError());
-}
-
-// Sliding-window front end (img_detect.py:103-111): every window (x, y, th, tw) is stretched to the model size into its batch slot,
-// same bilinear arithmetic as resize_u8_kernel.  A step of the batched pipeline (pipeline.cpp window mode) holds B frames of T
-// windows each, window t of frame b is slot b * T + t; `tiles` is the table of ONE frame's T windows - every frame of a step is cut
-// alike.  A launch covers the slots [slot0, slot0 + n) of one network chunk (which may straddle frames) and reads the frames where
-// they lie in HBM; bgr as resize_u8_kernel.  One host frame (Darknet::forward_tiles_host) is the case B = 1.
-__global__ void window_resize_kernel(const uint8_t *frames, int H, int W, const int *tiles, int T, int slot0, int n, float *y, int Ho, int Wo,
-                                     int bgr) {
-    const size_t total = (size_t)n * Ho * Wo;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        int ox = idx % Wo;
-        size_t r = idx / Wo;
-        int oy = r % Ho;
-        const int slot = slot0 + (int)(r / Ho), b = slot / T, t = slot - b * T;
-        const int x0 = tiles[t * 4 + 0], y0 = tiles[t * 4 + 1], th = tiles[t * 4 + 2], tw = tiles[t * 4 + 3];
-        float o[3];
-        resize_px(frames + ((size_t)b * H * W + (size_t)y0 * W + x0) * 3, (size_t)W * 3, th, tw, Ho, Wo, oy, ox, o);
-        if (bgr) { const float v = o[0]; o[0] = o[2]; o[2] = v; }
-        *reinterpret_cast<float4 *>(y + idx * 4) = make_float4(__fdiv_rn(o[0], 255.f), __fdiv_rn(o[1], 255.f), __fdiv_rn(o[2], 255.f), 0.f);
-    }
-}
-
-void launch_window_resize(const uint8_t *frames, int h, int w, const int *tiles_dev, int T, int slot0, int n, const View &y, hipStream_t s,
-                          bool bgr) {
-    if (y.c != 4 || y.ld != 4) fail("resize: destination must be NHWC4");
-    hipLaunchKernelGGL(window_resize_kernel, dim3(grid_for((size_t)n * y.h * y.w)), dim3(256), 0, s, frames, h, w, tiles_dev, T, slot0, n, y.p,
-                       y.h, y.w, bgr ? 1 : 0);
-    YDS_HIP(hipGetLastError());
-}
-
-// img_detect.py:131-139 for the predictions of one chunk: centre form -> corner form (x -+ w/2), resize_boxes to the window's own
-// size (python-double ratio rounded to fp32, passed in `scale`), shift by the window origin; the other attributes are copied.  Row r
-// of `pred` is a box of slot slot0 + r / n_boxes, whose window is slot % T; `dst` is the step's whole [B * T * n_boxes, attrs] block,
-// so a frame's rows lie window-major, then in box order - the concatenation of img_detect.py:142.
-__global__ void window_boxes_kernel(const float *pred, int n_boxes, int attrs, const int *tiles, const float *scale, int T, int slot0, int n,
-                                    float *dst) {
-    const size_t total = (size_t)n * n_boxes;
-    for (size_t row = blockIdx.x * (size_t)(blockDim.x / 32) + threadIdx.x / 32; row < total; row += (size_t)gridDim.x * (blockDim.x / 32)) {
-        const int t = (slot0 + (int)(row / n_boxes)) % T, lane = threadIdx.x % 32;
-        const float *p = pred + row * attrs;
-        float *d = dst + ((size_t)slot0 * n_boxes + row) * attrs;
-        for (int j = 4 + lane; j < attrs; j += 32) d[j] = p[j];
-        if (lane < 4) {
-            const float half = __fdiv_rn(p[2 + (lane & 1)], 2.f);
-            float v = lane < 2 ? __fsub_rn(p[lane & 1], half) : __fadd_rn(p[lane & 1], half);
-            v = __fmul_rn(v, scale[t * 2 + (lane & 1)]);
-            d[lane] = __fadd_rn(v, (float)tiles[t * 4 + (lane & 1)]);
-        }
-    }
-}
-
-void launch_window_boxes(const float *pred, int n_boxes, int attrs, const int *tiles_dev, const float *scale_dev, int T, int slot0, int n,
-                         float *dst, hipStream_t s) {
-    hipLaunchKernelGGL(window_boxes_kernel, dim3(grid_for((size_t)n * n_boxes * 32)), dim3(256), 0, s, pred, n_boxes, attrs, tiles_dev, scale_dev,
-                       T, slot0, n, dst);
-    YDS_HIP(hipGetLastError());
-}
-
-// The two front-end kernels above in one, for a step whose frames are cut differently (pipeline.cpp, a window setting per stream):
-// slot blockIdx.y of the chunk is the th x tw region at frames + off with its own row stride - a window of a frame of any size, or a
-// whole frame - so resize_px sees exactly what window_resize_kernel / resize_u8_frames_kernel hand it.
+// The front end of a pass with a slot plan (slot_plan.h; pipeline.cpp: a mixed layout, window mode, a window setting per stream): slot
+// blockIdx.y of the chunk is the th x tw region at frames + off with its own row stride - a window of a frame of any size
+// (img_detect.py:103-111), or a whole frame - so the mode (copy, exact 2x, linear) is that region's own; arithmetic: resize_px, bgr as
+// resize_u8_kernel.  A launch covers the slots of one network chunk (which may straddle frames) and reads the frames where they lie.
 __global__ void slot_resize_kernel(const uint8_t *frames, const SlotRec *slots, float *y, int Ho, int Wo, int bgr) {
     const SlotRec g = slots[blockIdx.y];
     const int per = Ho * Wo;
@@ -473,9 +394,11 @@ void launch_slot_resize(const uint8_t *frames, const SlotRec *slots, int n, cons
     YDS_HIP(hipGetLastError());
 }
 
-// window_boxes_kernel with the window read per slot: a window slot's boxes go to corner form, are scaled to the window and shifted by
-// its origin (the same operations in the same order); a plain slot's rows are copied as they are, in centre form, for the NMS to
-// convert and scale like those of an unwindowed step.
+// img_detect.py:131-139 for the predictions of one chunk.  A window slot's boxes: centre form -> corner form (x -+ w/2), resize_boxes to
+// the window's own size (python-double ratio rounded to fp32: SlotRec sx, sy), shift by the window origin; the other attributes are
+// copied.  A plain slot's rows are copied as they are, in centre form, for the NMS to convert and scale like those of an unwindowed
+// step.  Row r is a box of slot r / n_boxes, so a frame's rows lie window-major, then in box order - the concatenation of
+// img_detect.py:142, which the stable ranking and the merge branch depend on.
 __global__ void slot_boxes_kernel(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst) {
     const size_t total = (size_t)n * n_boxes;
     for (size_t row = blockIdx.x * (size_t)(blockDim.x / 32) + threadIdx.x / 32; row < total; row += (size_t)gridDim.x * (blockDim.x / 32)) {

@@ -219,8 +219,7 @@ __device__ __forceinline__ void nms_sweep_body(const float *sorted_all, const un
     if (threadIdx.x == 0) counts[1] = n_keep;
 }
 __global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
-                                 float sx, float sy, const float *scale, float *kept_all, int cap) {
-    if (scale) { sx = scale[blockIdx.y * 2]; sy = scale[blockIdx.y * 2 + 1]; }       // per frame (sx, sy): frames of different sizes
+                                 float sx, float sy, float *kept_all, int cap) {
     nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, sx, sy, kept_all, cap);
 }
 // ragged form: a plain frame's boxes are scaled by its own ratio, a windowed frame's descriptor holds (1, 1)
@@ -263,7 +262,7 @@ NmsWorkspace::~NmsWorkspace() {
 }
 
 // The merge branch of soft_non_max_suppression(merge=True, is_p1p2=True) on the device, one workgroup per image: what the host loop
-// of run_merge() does (model_build.py:122-131; see the comment there), for the batched launch of the window-mode pipeline.  It fires
+// of run_merge() does (model_build.py:122-131; see the comment there), for the windowed frames of a ragged launch.  It fires
 // when 1 < n < 3000 and the kept count k is n or 1: every kept row's box becomes the weighted mean of ALL candidates whose +1-pixel
 // IoU (model_build.py:354-381, on class-offset boxes) with the paired kept box - kept row j when k == n, kept row 0 when k == 1 -
 // exceeds the threshold, weights = the candidates' scores.  The IoUs are computed by all threads; the sums are taken by ONE thread in
@@ -305,11 +304,7 @@ __device__ __forceinline__ void nms_merge_body(const float *cand_all, const floa
     __syncthreads();
     for (int i = threadIdx.x; i < k * 4; i += blockDim.x) kept[(size_t)(i >> 2) * 6 + (i & 3)] = mean[i & 3];
 }
-__global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
-                                                        float iou_thres, float *kept_all) {
-    nms_merge_body(cand_all, sorted_all, counts_all, max_cand, iou_thres, kept_all);
-}
-// ragged form: only the frames whose descriptor asks for the merge branch (the windowed ones)
+// only the frames whose descriptor asks for the merge branch (the windowed ones)
 __global__ __launch_bounds__(256) void nms_merge_ragged_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
                                                                float iou_thres, const NmsFrame *fr, float *kept_all) {
     if (!fr[blockIdx.x].merge) return;                           // (uniform over the workgroup)
@@ -331,7 +326,7 @@ __global__ __launch_bounds__(256) void nms_publish_kernel(const int *counts, con
 
 // All `n_frames` images go through each stage in ONE launch (blockIdx.y = image).
 void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                          float sx, float sy, int cap, hipStream_t s, bool corner, bool merge, const float *scale) {
+                          float sx, float sy, int cap, hipStream_t s, bool corner) {
     if (attrs < 6) fail("nms: predictions need at least one class");
     if (n_frames < 1) fail("nms: no frames");
     if (n_frames > frames) resize(max_cand, n_frames);
@@ -345,14 +340,13 @@ void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frame
     const int words_ld = max_cand / 64;
     hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
     hipLaunchKernelGGL(nms_sweep_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
-                       counts.p, max_cand, sx, sy, scale, kept.p, cap);
-    if (merge) hipLaunchKernelGGL(nms_merge_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, kept.p);
+                       counts.p, max_cand, sx, sy, kept.p, cap);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
     hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
     YDS_HIP(hipGetLastError());
 }
 
-// The same launch sequence for frames of different row counts and forms in one block of predictions (the slotted pass of the pipeline):
+// The same launch sequence for frames of different row counts and forms in one block of predictions (a pipeline pass with a slot plan):
 // count / scan / emit take every frame's own rows, grid.x is sized by the largest frame; rank, mask and publish work per frame on the
 // candidate counts as in launch().  fr: n_frames descriptors, device-readable until the kernels have run.
 void NmsWorkspace::launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
@@ -488,27 +482,6 @@ int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float con
     YDS_API_END
 }
 
-int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host,
-                               int cap, int *n_out) {
-    YDS_API_BEGIN
-    if (n_frames < 1 || n_boxes < 1) yds::fail("nms: %d frames of %d boxes", n_frames, n_boxes);
-    static thread_local std::unique_ptr<yds::NmsWorkspace> ws;           // own workspace: sized by the number of frames
-    if (!ws) ws.reset(new yds::NmsWorkspace(4096, n_frames));
-    yds::DevBuf<float> pred;
-    const size_t stride = (size_t)n_boxes * attrs;
-    pred.upload(pred_host, (size_t)n_frames * stride);
-    YDS_HIP(hipStreamSynchronize(nullptr));
-    for (int pass = 0; pass < 2; ++pass) {
-        // corner-form boxes, the merge branch as a kernel behind the sweep: the launch of the window-mode pipeline
-        ws->launch(pred.p, stride, n_frames, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, yds::MAX_DET, nullptr, true, true);
-        YDS_HIP(hipStreamSynchronize(nullptr));
-        if (ws->needed(n_frames) <= ws->max_cand) break;
-        ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again
-    }
-    for (int f = 0; f < n_frames; ++f) n_out[f] = ws->collect(f, out6_host + (size_t)f * cap * 6, cap);
-    YDS_API_END
-}
-
 int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, int n_frames, const uint64_t *row0, const int32_t *n_rows,
                         const int32_t *corner_merge, const float *scale, float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
@@ -535,6 +508,20 @@ int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, in
         ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again
     }
     for (int f = 0; f < n_frames; ++f) n_out[f] = ws->collect(f, out6_host + (size_t)f * cap * 6, cap);
+    YDS_API_END
+}
+
+int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host,
+                               int cap, int *n_out) {
+    YDS_API_BEGIN
+    if (n_frames < 1 || n_boxes < 1) yds::fail("nms: %d frames of %d boxes", n_frames, n_boxes);
+    // corner-form boxes, the merge branch as a kernel behind the sweep: one descriptor per frame, the launch of a windowed pipeline pass
+    std::vector<uint64_t> row0(n_frames);
+    std::vector<int32_t> n_rows(n_frames, n_boxes), corner_merge((size_t)n_frames * 2, 1);
+    std::vector<float> scale((size_t)n_frames * 2, 1.f);
+    for (int f = 0; f < n_frames; ++f) row0[f] = (uint64_t)f * n_boxes;
+    return yds_nms_ragged_pred(pred_host, (size_t)n_frames * n_boxes, attrs, n_frames, row0.data(), n_rows.data(), corner_merge.data(), scale.data(),
+                               conf_thres, iou_thres, out6_host, cap, n_out);
     YDS_API_END
 }
 

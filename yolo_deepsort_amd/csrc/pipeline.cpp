@@ -25,27 +25,6 @@
 
 namespace yds {
 
-// The slot plan of a step that holds at least one windowed frame (a window setting per stream, set_stream_windows): what the detector
-// runs (one network slot per window of a windowed frame, one per plain frame; frame order, then window order) and what the NMS merges
-// (one descriptor per frame).  Built on the host from the layout, the stream of every frame and the streams' settings; empty: the
-// step has no windowed frame and takes the unslotted path.
-struct SlotPlan {
-    std::vector<SlotRec> slots;
-    std::vector<NmsFrame> frames;
-    int max_rows = 0;                  // largest n_rows of a frame
-    bool empty() const { return slots.empty(); }
-    bool operator==(const SlotPlan &o) const {
-        if (slots.size() != o.slots.size() || frames.size() != o.frames.size()) return false;
-        for (size_t n = 0; n < slots.size(); ++n) {                 // (the scales follow from th, tw)
-            const SlotRec &a = slots[n], &b = o.slots[n];
-            if (a.off != b.off || a.stride != b.stride || a.th != b.th || a.tw != b.tw || a.window != b.window || a.x0 != b.x0 || a.y0 != b.y0) return false;
-        }
-        for (size_t n = 0; n < frames.size(); ++n)
-            if (frames[n].n_rows != o.frames[n].n_rows || frames[n].corner != o.frames[n].corner) return false;
-        return true;
-    }
-};
-
 // One NMS slot: workspace + pinned results, and the events of the detector pass that uses it.  Two slots alternate, so that the
 // pass of batch i+1 can be enqueued before the host has waited for and read the results of batch i: the detector stream never
 // drains between passes.
@@ -57,16 +36,20 @@ struct DetSlot {
     DetSlot() { for (hipEvent_t *e : {&e0, &e1, &e2, &e_nms, &e_r0, &e_r1}) YDS_HIP(hipEventCreate(e)); }
     ~DetSlot() {
         for (hipEvent_t e : {e0, e1, e2, e_nms, e_r0, e_r1}) (void)hipEventDestroy(e);
-        if (tab) (void)hipHostFree(tab);
         if (plan_tab) (void)hipHostFree(plan_tab);
     }
-    // Slotted pass: the plan's two tables (per slot, per frame), pinned and read in place like `tab` below, one copy per DetSlot so that a
-    // look-ahead pass keeps its own.  Only slotted passes read it, the NMS last: e_nms of the slot's previous pass is what to wait for.
+    // The plan's two tables (per slot, per frame) as the pass reads them ON THE DEVICE - the resize and box kernels each slot's record, the
+    // NMS each frame's descriptor - in pinned host memory the kernels read in place (like the extractor's crop list).  It lives with
+    // the DetSlot because those kernels run long after the call that enqueued them has gone on: the look-ahead pass of the next batch
+    // is in flight while the host works on this one, and keeps its own copy.  Before the table is rewritten the slot's last pass must
+    // have read it: the head's resize (e1) and the NMS (e_nms) - both long over in the steady state, where a slot is reused two passes
+    // later; an abandoned look-ahead pass that only got its head is what the wait on e1 is for.
     void *plan_tab = nullptr;
     size_t plan_bytes = 0, plan_slots_n = 0;
     const SlotRec *plan_slots() const { return static_cast<const SlotRec *>(plan_tab); }
     const NmsFrame *plan_frames() const { return reinterpret_cast<const NmsFrame *>(plan_slots() + plan_slots_n); }
     void write_plan(const SlotPlan &pl) {
+        YDS_HIP(hipEventSynchronize(e1));
         YDS_HIP(hipEventSynchronize(e_nms));
         const size_t need = pl.slots.size() * sizeof(SlotRec) + pl.frames.size() * sizeof(NmsFrame);
         if (plan_bytes < need) {
@@ -79,34 +62,6 @@ struct DetSlot {
         plan_slots_n = pl.slots.size();
         memcpy(plan_tab, pl.slots.data(), pl.slots.size() * sizeof(SlotRec));
         memcpy(const_cast<NmsFrame *>(plan_frames()), pl.frames.data(), pl.frames.size() * sizeof(NmsFrame));
-    }
-    // Frames of different sizes: the table the slot's pass reads ON THE DEVICE - the resize kernel each frame's (offset, h, w), the NMS
-    // sweep each frame's (sx, sy) - in pinned host memory the kernels read in place (like the extractor's crop list).  It lives with
-    // the slot because those kernels run long after the call that enqueued them has gone on: the look-ahead pass of the next batch
-    // is in flight while the host works on this one.  Before the table is rewritten the slot's last pass must have read it: the
-    // resize (e1) and the NMS (e_nms) - both long over in the steady state, where a slot is reused two passes later; an abandoned
-    // look-ahead pass is what the wait is for.
-    void *tab = nullptr;
-    size_t tab_frames = 0;
-    const FrameGeom *tab_geom() const { return static_cast<const FrameGeom *>(tab); }
-    const float *tab_scale() const { return reinterpret_cast<const float *>(tab_geom() + tab_frames); }
-    void write_table(const std::vector<FrameGeom> &g, int img_h, int img_w) {
-        YDS_HIP(hipEventSynchronize(e1));
-        YDS_HIP(hipEventSynchronize(e_nms));
-        if (tab_frames < g.size()) {
-            if (tab) (void)hipHostFree(tab);
-            tab = nullptr;
-            tab_frames = 0;
-            const size_t cap = std::max<size_t>(g.size(), 64);
-            YDS_HIP(hipHostMalloc(&tab, cap * (sizeof(FrameGeom) + 2 * sizeof(float)), hipHostMallocDefault));
-            tab_frames = cap;
-        }
-        memcpy(tab, g.data(), g.size() * sizeof(FrameGeom));
-        float *scale = const_cast<float *>(tab_scale());
-        for (size_t n = 0; n < g.size(); ++n) {                     // resize_boxes per frame: python-double ratio, one rounding to fp32
-            scale[n * 2] = (float)((double)g[n].w / img_w);
-            scale[n * 2 + 1] = (float)((double)g[n].h / img_h);
-        }
     }
 };
 
@@ -128,7 +83,7 @@ struct Geometry {
 struct Pass {
     const uint8_t *frames = nullptr;   // nullptr: no pass (slot still names the DetSlot used last)
     Geometry geo;                      // layout of the frames the pass was enqueued with
-    SlotPlan plan;                     // not empty: a slotted pass (some frame is windowed by its stream's setting)
+    SlotPlan plan;                     // empty: the plain uniform pass; direct: a mixed layout; else slotted (some frame is windowed)
     int batch = 0;
     int slot = 0;                      // DetSlot
     enum { NOTHING, HEAD, WHOLE } done = NOTHING;     // NOTHING with frames set: the head is still to be (re-)enqueued
@@ -273,6 +228,11 @@ public:
     // One detector pass over a batch AND its NMS, all asynchronous on the detector stream, in two pieces (serialized schedule, see
     // step()): head = upload wait + resize + the first layers (Darknet::head_layers), tail = the remaining layers + NMS.  split =
     // false (or a network that cannot be split) puts the whole network into the tail.  launch_detector enqueues what is missing.
+    // Two pass forms.  No plan: the plain uniform pass - one stack of frames of one size, geometry and scale as kernel arguments.  A
+    // slot plan (slot_plan.h), written into the DetSlot's table by the head: DIRECT (a mixed layout, no windowed frame) keeps that
+    // shape, the head's resize reads one plain slot per frame and the ragged NMS reads the network's output in place, frame b = rows
+    // [b * total_boxes, +total_boxes) in centre form with its own (sx, sy); SLOTTED (some frame is windowed) runs the whole pass in
+    // the tail, see window mode below.
     void launch_detector(Pass &p, bool split = false) {
         if (p.done == Pass::NOTHING) launch_detector_head(p, split);
         if (p.done == Pass::HEAD) launch_detector_tail(p);
@@ -284,67 +244,55 @@ public:
         YDS_HIP(hipEventRecord(s.e0, net->stream));
         p.done = Pass::HEAD;
         p.split = false;
-        if (windows_for(p.geo) || !p.plan.empty()) {                // window mode, slotted pass: the whole pass (resize included) is the tail's
+        if (!p.plan.empty()) s.write_plan(p.plan);
+        if (p.plan.windowed) {                                      // slotted pass: the whole pass (resize included) is the tail's
             YDS_HIP(hipEventRecord(s.e1, net->stream));
             return;
         }
-        if (p.geo.mixed()) {
-            s.write_table(p.geo.frames, net->img_h, net->img_w);
-            launch_resize_u8_frames(p.frames, s.tab_geom(), p.batch, net->input_view(p.batch), net->stream, frames_bgr);
-        } else {
-            launch_resize_u8(p.frames, p.batch, p.geo.h, p.geo.w, net->input_view(p.batch), net->stream, frames_bgr);
-        }
+        if (p.plan.direct()) launch_slot_resize(p.frames, s.plan_slots(), p.batch, net->input_view(p.batch), net->stream, frames_bgr);
+        else launch_resize_u8(p.frames, p.batch, p.geo.h, p.geo.w, net->input_view(p.batch), net->stream, frames_bgr);
         YDS_HIP(hipEventRecord(s.e1, net->stream));
         stager.mark_read(p.frames, net->stream, FrameStager::DET);
         p.split = split && net->forward_resized_part(p.batch, 0);
     }
     void launch_detector_tail(Pass &p) {
         DetSlot &s = det[p.slot];
-        const size_t per_slot = (size_t)net->total_boxes * net->attrs;
-        if (!p.plan.empty()) {
-            const size_t n_slots = p.plan.slots.size();
+        const size_t per_slot = (size_t)net->total_boxes * net->attrs, n_slots = p.plan.slots.size();
+        if (p.plan.windowed) {
             if (win_pred.n < n_slots * per_slot) {
                 YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
                 win_pred.alloc(n_slots * per_slot);
             }
-            s.write_plan(p.plan);
             pred_rows = n_slots * net->total_boxes;
             net->forward_slots(p.frames, s.plan_slots(), (int)n_slots, win_pred.p, frames_bgr);
             stager.mark_read(p.frames, net->stream, FrameStager::DET);
-            YDS_HIP(hipEventRecord(s.e2, net->stream));
-            s.nms->launch_ragged(win_pred.p, s.plan_frames(), p.batch, p.plan.max_rows, n_slots * net->total_boxes, net->attrs, conf, nms_thres, 300,
-                                 net->stream);
-        } else if (const int T = windows_for(p.geo)) {
-            if (win_pred.n < (size_t)p.batch * T * per_slot) {
-                YDS_HIP(hipStreamSynchronize(net->stream));         // (an NMS of the previous pass may still read the old buffer)
-                win_pred.alloc((size_t)p.batch * T * per_slot);
-            }
-            net->forward_windows(p.frames, p.geo.h, p.geo.w, p.batch, win, win_pred.p, frames_bgr);
-            stager.mark_read(p.frames, net->stream, FrameStager::DET);
-            YDS_HIP(hipEventRecord(s.e2, net->stream));
-            s.nms->launch(win_pred.p, (size_t)T * per_slot, p.batch, T * net->total_boxes, net->attrs, conf, nms_thres, 1.f, 1.f, 300, net->stream,
-                          true, true);
+        } else if (p.split) {
+            (void)net->forward_resized_part(p.batch, 1);
         } else {
-            if (p.split) (void)net->forward_resized_part(p.batch, 1);
-            else net->forward_resized(p.batch);
-            YDS_HIP(hipEventRecord(s.e2, net->stream));
-            const float sx = (float)((double)p.geo.w / net->img_w), sy = (float)((double)p.geo.h / net->img_h);
-            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream, false, false,
-                          p.geo.mixed() ? s.tab_scale() : nullptr);    // mixed: every frame's own ratio, from the slot's table
+            net->forward_resized(p.batch);
+        }
+        YDS_HIP(hipEventRecord(s.e2, net->stream));
+        if (p.plan.empty()) {
+            const float sx = box_scale(p.geo.w, net->img_w), sy = box_scale(p.geo.h, net->img_h);
+            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream);
+        } else {
+            s.nms->launch_ragged(p.plan.windowed ? win_pred.p : net->out.p, s.plan_frames(), p.batch, p.plan.max_rows, n_slots * net->total_boxes,
+                                 net->attrs, conf, nms_thres, 300, net->stream);
         }
         YDS_HIP(hipEventRecord(s.e_nms, net->stream));
         p.done = Pass::WHOLE;
     }
 
     // ---- window mode (yds_pipeline_set_windows; ImageDetector(win_size, overlap), img_detect.py:97-151, for a batch of frames) ----
-    // Every frame of a step is cut into the same T windows (the reference's grid: x-major, then y; each window extended by the
-    // overlap and clipped to the frame); window t of frame b is slot b * T + t.  The slots run through the network in chunks of at
-    // most batch_max (Darknet::forward_windows) into win_pred [batch * T * total_boxes, attrs], a frame's rows window-major then in
-    // box order: the concatenation of img_detect.py:142, which the stable ranking and the merge branch depend on.  ONE NMS launch per step over n_boxes = T * total_boxes per frame, merge branch as a kernel (nms.hip); no
-    // copy of candidates to the host and no synchronisation inside the pass.  win_pred holds the FULL shifted predictions (no
-    // compaction per chunk): batch * T * total_boxes * attrs * 4 bytes - yolov3-608 (22743 boxes x 85): 7.73 MB per window, 8 frames of
-    // 1080p (T = 8) 495 MB.  One buffer serves both NMS slots: the NMS of a pass and the box kernels of the next are ordered by the
-    // detector's stream.  The window table (T rectangles + scales) is rebuilt when the frame size or the window setting changes.
+    // Every frame of a step is cut into the same T windows (build_slot_plan: the reference's grid); window t of frame b is slot
+    // b * T + t.  The pass is SLOTTED: the slots run through the network in chunks of at most batch_max (Darknet::forward_slots) into
+    // win_pred [batch * T * total_boxes, attrs], a frame's rows window-major then in box order - the concatenation of
+    // img_detect.py:142, which the stable ranking and the merge branch depend on.  ONE ragged NMS launch per step, n_rows =
+    // T * total_boxes per frame, merge branch as a kernel (nms.hip); no copy of candidates to the host and no synchronisation inside
+    // the pass.  win_pred holds the FULL shifted predictions (no compaction per chunk): batch * T * total_boxes * attrs * 4 bytes -
+    // yolov3-608 (22743 boxes x 85): 7.73 MB per window, 8 frames of 1080p (T = 8) 495 MB.  One buffer serves both NMS slots: the NMS
+    // of a pass and the box kernels of the next are ordered by the detector's stream.  A frame smaller than the window (w < win_w and
+    // h < win_h, img_detect.py:68) is not cut: the plan is empty and the plain uniform pass runs.
     // Bench-only logit injection addresses the slots of a CHUNK (tables [0, batch_max) of the selected set serve every chunk).
     void set_windows(int ww, int wh, double overlap) {
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_windows while a look-ahead pass is in flight (consume it with a step first)");
@@ -352,35 +300,16 @@ public:
         if (ww > 0 && !(overlap >= 0)) fail("pipeline: window overlap %g", overlap);
         if (ww > 0 && any_stream_windows()) fail("pipeline: set_windows while a stream holds a window setting of its own (set_stream_windows): one or the other");
         win_w = ww > 0 ? ww : 0; win_h = ww > 0 ? wh : 0; win_overlap = overlap;
-        win_tab_h = win_tab_w = 0;
     }
-    // number of windows T of an h x w frame; 0 = the plain path (window mode off, or a frame smaller than the window: img_detect.py:68)
-    int windows_for(const Geometry &g) { return g.mixed() ? 0 : windows_for(g.h, g.w); }    // (step() refuses a mixed layout in window mode)
-    int windows_for(int h, int w) {
-        if (win_w <= 0 || (w < win_w && h < win_h)) return 0;
-        if (h == win_tab_h && w == win_tab_w) return win.T;
-        const int ox = (int)(win_w * win_overlap), oy = (int)(win_h * win_overlap);
-        std::vector<int> rects;
-        for (int x = 0; x < w; x += win_w)
-            for (int y = 0; y < h; y += win_h)
-                rects.insert(rects.end(), {x, y, std::min(y + win_h + oy, h) - y, std::min(x + win_w + ox, w) - x});
-        YDS_HIP(hipStreamSynchronize(net->stream));                 // a pass that reads the previous table may still run
-        win.build(rects.data(), (int)rects.size() / 4, net->img_h, net->img_w, nullptr);
-        win_tab_h = h; win_tab_w = w;
-        return win.T;
-    }
-
     // ---- a window setting per stream (yds_pipeline_set_stream_windows; ImageDetector(win_size, overlap) per camera) ----
     // Frame b of a step belongs to stream stream_of[b]; that stream's setting decides whether the frame is cut into windows (as above,
-    // for its own size) or takes the plain branch - no setting, or w < win_w and h < win_h (img_detect.py:68).  A step with at least one
-    // windowed frame runs as a SLOTTED pass: every window and every plain frame is one network slot (SlotPlan), the slots run in chunks
-    // of batch_max (Darknet::forward_slots) into win_pred, a windowed frame's rows in corner form in frame pixels, a plain frame's
-    // rows as the network gave them; ONE ragged NMS launch (NmsWorkspace::launch_ragged) treats each frame by its descriptor - merge
-    // branch and scale 1 for a windowed frame, centre form and the frame's own ratio for a plain one.  Like window mode the whole pass
-    // is the tail's.  A step with no windowed frame has an empty plan and runs exactly the launches it runs without any setting.
-    struct StreamWindows { int w = 0, h = 0; double overlap = 0; };
+    // for its own size) or takes the plain branch - no setting, or w < win_w and h < win_h.  A step with at least one windowed frame
+    // is slotted like window mode, with frames that differ: every window and every plain frame is one network slot, a windowed frame's
+    // rows in corner form in frame pixels, a plain frame's rows as the network gave them; the ragged NMS treats each frame by its
+    // descriptor - merge branch and scale 1 for a windowed frame, centre form and the frame's own ratio for a plain one.  A step with
+    // no windowed frame runs exactly the launches it runs without any setting.
     bool any_stream_windows() const {
-        for (const StreamWindows &sw : stream_win)
+        for (const WindowSetting &sw : stream_win)
             if (sw.w > 0) return true;
         return false;
     }
@@ -393,40 +322,16 @@ public:
             fail("pipeline: set_stream_windows while a look-ahead pass is in flight (consume it with a step first)");
         if (win_w > 0) fail("pipeline: set_stream_windows while window mode is on for all streams (yds_pipeline_set_windows): one or the other");
         stream_win.resize(trks.size());
-        stream_win[stream] = ww > 0 ? StreamWindows{ww, wh, overlap} : StreamWindows();
+        stream_win[stream] = ww > 0 ? WindowSetting{ww, wh, overlap} : WindowSetting();
     }
-    // the plan of a step of `batch` frames laid out by `geo`, frame b of stream stream_of[b]
+    // the plan of a step of `batch` frames laid out by `geo`, frame b of stream stream_of[b]: the setting of all streams, or each
+    // frame's stream's own (the two exclude each other)
     SlotPlan make_plan(const Geometry &geo, int batch) const {
-        SlotPlan pl;
-        if (!multi || !any_stream_windows()) return pl;
-        bool windowed_any = false;
-        for (int b = 0; b < batch; ++b) {
-            const int h = geo.mixed() ? geo.frames[b].h : geo.h, w = geo.mixed() ? geo.frames[b].w : geo.w;
-            const uint64_t off = geo.mixed() ? geo.frames[b].off : (uint64_t)b * h * w * 3;
-            const StreamWindows &sw = stream_win[stream_of[b]];
-            NmsFrame f{(uint64_t)pl.slots.size() * net->total_boxes, 0, 0, 0, 1.f, 1.f, 0};
-            if (sw.w > 0 && !(w < sw.w && h < sw.h)) {              // img_detect.py:101-121: x-major then y, extended by the overlap, clipped
-                const int ox = (int)(sw.w * sw.overlap), oy = (int)(sw.h * sw.overlap);
-                for (int x = 0; x < w; x += sw.w)
-                    for (int y = 0; y < h; y += sw.h) {
-                        const int th = std::min(y + sw.h + oy, h) - y, tw = std::min(x + sw.w + ox, w) - x;
-                        pl.slots.push_back(SlotRec{off + ((uint64_t)y * w + x) * 3, w * 3, th, tw, 1, x, y, (float)((double)tw / net->img_w),
-                                                   (float)((double)th / net->img_h)});
-                        f.n_rows += net->total_boxes;
-                    }
-                f.corner = f.merge = 1;
-                windowed_any = true;
-            } else {                                                // plain branch: resize_boxes by the frame's own ratio, in the sweep
-                pl.slots.push_back(SlotRec{off, w * 3, h, w, 0, 0, 0, 1.f, 1.f});
-                f.n_rows = net->total_boxes;
-                f.sx = (float)((double)w / net->img_w);
-                f.sy = (float)((double)h / net->img_h);
-            }
-            pl.max_rows = std::max(pl.max_rows, (int)f.n_rows);
-            pl.frames.push_back(f);
-        }
-        if (!windowed_any) return SlotPlan();
-        return pl;
+        std::vector<WindowSetting> win;
+        if (win_w > 0) win.push_back(WindowSetting{win_w, win_h, win_overlap});
+        else if (multi && any_stream_windows())
+            for (int b = 0; b < batch; ++b) win.push_back(stream_win[stream_of[b]]);
+        return build_slot_plan(batch, geo.h, geo.w, geo.mixed() ? geo.frames.data() : nullptr, win, net->img_h, net->img_w, net->total_boxes);
     }
 
     // detections of one batch after NMS + class mask + p1p2Toxywh, ready for the extractor and the tracker
@@ -705,12 +610,10 @@ public:
     bool last_serial = false;          // schedule of the last step
     bool frames_bgr = false;           // yds_pipeline_set_frame_order: the frames handed over hold B, G, R bytes (a decoder's order)
     float stage_us[5] = {0, 0, 0, 0, 0};
-    // window mode (set_windows): setting, the table on the device and the frame size it was built for, the shifted predictions
-    int win_w = 0, win_h = 0, win_tab_h = 0, win_tab_w = 0;
+    int win_w = 0, win_h = 0;          // window mode (set_windows): the setting of all streams
     double win_overlap = 0;
-    WindowTable win;
-    DevBuf<float> win_pred;            // shifted predictions of a window-mode pass; the prediction block of a slotted pass
-    std::vector<StreamWindows> stream_win;        // set_stream_windows: setting of every stream (empty: none was ever set)
+    DevBuf<float> win_pred;            // the prediction block of a slotted pass: shifted corner-form rows of window slots, raw rows of plain ones
+    std::vector<WindowSetting> stream_win;        // set_stream_windows: setting of every stream (empty: none was ever set)
     size_t pred_rows = 0;              // rows of the last slotted pass in win_pred (bench / test read-out)
 };
 
