@@ -129,10 +129,9 @@ int yds_detect_tiled(yds_net *, const uint8_t *rgb_hwc_host, int h, int w, const
 int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres,
                        float *out6_host, int cap, int *n_out);
 /* yds_nms_merge_pred_batched <- the same function for n_frames images in ONE launch sequence, entirely on the device: the launch the
- *                        window-mode pipeline uses (yds_pipeline_set_windows; yds_nms_ragged_pred with one corner-form, merging
- *                        descriptor of n_boxes rows per image) - corner-form candidates, blockIdx.y = image, the merge
- *                        branch as a kernel (one workgroup per image, sums in candidate order like the host loop of
- *                        yds_nms_merge_pred, so NaN rows agree) before the results are published; no candidate copy to the host.
+ *                        window-mode pipeline uses (yds_pipeline_set_windows) with the frames described uniformly - n_boxes
+ *                        corner-form rows per image, blockIdx.y = image, the merge branch as a kernel (one workgroup per image,
+ *                        the kernel yds_nms_merge_pred runs for its one image) before the results are published.
  *                        pred_host [n_frames, n_boxes, attrs]; out6_host [n_frames, cap, 6]; n_out[n_frames] rows per image. */
 int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
                                float *out6_host, int cap, int *n_out);

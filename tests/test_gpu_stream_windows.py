@@ -1,7 +1,7 @@
 """A window setting per stream in one multi-stream step (csrc/pipeline.cpp yds_pipeline_set_stream_windows): every camera is cut by
 its own ImageDetector(win_size, overlap), a step that holds a windowed frame runs as one slotted pass - a network slot per window and
 per plain frame (csrc/layers.hip slot_resize_kernel / slot_boxes_kernel), one ragged NMS launch over all frames (csrc/nms.hip
-launch_ragged).  The yardstick per stream is the stream run alone at its own size and setting: the frame-by-frame path
+launch with a frame table).  The yardstick per stream is the stream run alone at its own size and setting: the frame-by-frame path
 (VideoDetector.process with an ImageDetector(win_size=...)), or the single-stream Pipeline where the same device arithmetic is
 compared exactly.  Row criterion as tests/test_gpu_window_pipeline.py: track ids and classes bit exact, None frames agree, boxes
 within one pixel.  yolov3-tiny at 416, overlap 0.15 throughout.
@@ -352,7 +352,7 @@ def test_ragged_nms_equals_each_frame_alone(attrs):
 
 def test_ragged_nms_golden_merge_cases():
     """The four cases of tests/golden/tiled_detect.npz (all kept, one kept, plain, single) as merge frames of one ragged launch,
-    centre-form frames between them: the reference's golden outputs, and bit for bit the host merge of yds_nms_merge_pred."""
+    centre-form frames between them: the reference's golden outputs, and bit for bit the uniform form of yds_nms_merge_pred."""
     from yolo_deepsort_amd import _lib
     _lib.init(0)
     g = golden("tiled_detect")
@@ -370,6 +370,105 @@ def test_ragged_nms_golden_merge_cases():
         np.testing.assert_allclose(got[2 * k][:, :4], want[:, :4], rtol=1e-6, atol=1e-4, equal_nan=True, err_msg=nme)
         _same_rows(got[2 * k], _nms_merge(frames[2 * k][0], 0.5, 0.4), nme)
         _same_rows(got[2 * k + 1], _nms_plain(frames[2 * k + 1][0], 0.5, 0.4, (1.25, 0.75)), (nme, "plain"))
+
+
+def _nms_merge_batched(preds, ct, it):
+    """preds: list of [n_boxes, attrs] of one length -> kept rows per frame from ONE uniform launch with the merge branch"""
+    from yolo_deepsort_amd import _lib as L
+    stack = np.ascontiguousarray(np.stack(preds, 0), dtype=F32)
+    out = np.zeros((len(preds), 300, 6), F32)
+    n = np.zeros(len(preds), np.int32)
+    L.check(L.load().yds_nms_merge_pred_batched(L.ptr(stack), len(preds), stack.shape[1], stack.shape[2], ct, it, L.ptr(out), 300, L.ptr(n)))
+    return [out[f, :n[f]].copy() for f in range(len(preds))]
+
+
+def test_uniform_multi_frame_nms_equals_the_table_form():
+    """The two descriptions of a launch's frames, several frames each: four corner-form frames of 507 rows (spread boxes, one tight
+    cluster, no candidate, two boxes far apart) with the merge branch through yds_nms_merge_pred_batched (uniform record in the
+    kernel arguments) and through yds_nms_ragged_pred (table read on the device), bit for bit."""
+    from yolo_deepsort_amd import _lib
+    _lib.init(0)
+    rng = np.random.RandomState(11)
+    preds = [_synthetic_frame(rng, 507, 7, 12, True), _synthetic_frame(rng, 507, 7, 5, True, cluster=True),
+             _synthetic_frame(rng, 507, 7, 0, True), _synthetic_frame(rng, 507, 7, 2, True)]
+    uniform = _nms_merge_batched(preds, 0.5, 0.4)
+    table = _nms_ragged([(p, 1, (1.0, 1.0)) for p in preds], 0.5, 0.4)
+    for f, (u, t) in enumerate(zip(uniform, table)):
+        _same_rows(u, t, f)
+    kept = [len(u) for u in uniform]
+    assert kept[0] > 1 and kept[1:] == [1, 0, 2], kept
+
+
+def _tight_cluster(n):
+    """n candidates of class 0, attrs = 7: corners 300 + U(-3, 3) to + 120 + U(-3, 3), objectness U(0.6, 1), class score U(0.9, 1).
+    Returned in centre form and in corner form; the corners are the centre form's x -+ w/2 in fp32, as the emit stage computes them,
+    so that both forms hold the same candidates bit for bit (they differ from the drawn corners by an fp32 rounding)."""
+    rng = np.random.RandomState(n)
+    p1 = 300 + rng.uniform(-3, 3, (n, 2))
+    p2 = p1 + 120 + rng.uniform(-3, 3, (n, 2))
+    centre = np.zeros((n, 7), F32)
+    centre[:, :2] = (p1 + p2) / 2
+    centre[:, 2:4] = p2 - p1
+    centre[:, 4] = rng.uniform(0.6, 1, n)
+    centre[:, 5] = rng.uniform(0.9, 1, n)
+    corner = centre.copy()
+    half = centre[:, 2:4] / F32(2)
+    corner[:, :2] = centre[:, :2] - half
+    corner[:, 2:4] = centre[:, :2] + half
+    assert corner.dtype == F32
+    return centre, corner
+
+
+def test_merge_limit_is_3000_candidates():
+    """The merge branch fires for 1 < n < 3000 candidates (model_build.py:122): a tight cluster of n = 2999 and of n = 3000 through
+    yds_nms_merge_pred.  Both keep one row.  At 3000 it is the best candidate unmerged: bit for bit the row of yds_nms_pred on the
+    same candidates in centre form.  At 2999 its box is the score-weighted mean of ALL candidates: within rtol (n + 2) * 2**-24 of
+    that mean in float64 - the branch's only fp32 accumulation is the sequential sum of the n weights (error <= (n - 1) * 2**-24
+    relative, all terms positive), the product sums are float64, one rounding of the sum to fp32 and one division follow - and more
+    than half a pixel away from the best candidate's own box."""
+    from yolo_deepsort_amd import _lib
+    _lib.init(0)
+    for n in (2999, 3000):
+        centre, corner = _tight_cluster(n)
+        score = centre[:, 5] * centre[:, 4]                                   # fp32 product, as the emit stage
+        assert score.dtype == F32 and (score > 0.5).all()
+        best = int(np.argmax(score))                                          # (first of equals: the stable ranking)
+        got = _nms_merge(corner, 0.5, 0.4)
+        print("merge limit: n", n, "rows", len(got), "box", got[0, :4] if len(got) else None)
+        assert got.shape == (1, 6), n
+        assert got[0, 4] == score[best] and got[0, 5] == 0, n
+        if n == 3000:
+            _same_rows(got, _nms_plain(centre, 0.5, 0.4, (1.0, 1.0)), n)
+            assert np.array_equal(got[0, :4], corner[best, :4])
+        else:
+            w = score.astype(np.float64)
+            mean = (w[:, None] * corner[:, :4].astype(np.float64)).sum(0) / w.sum()
+            print("merge limit: relative distance from the float64 mean", np.abs(got[0, :4] - mean) / np.abs(mean), "bound", (n + 2) * 2.0 ** -24)
+            np.testing.assert_allclose(got[0, :4].astype(np.float64), mean, rtol=(n + 2) * 2.0 ** -24, atol=0)
+            assert np.abs(got[0, :4] - corner[best, :4]).max() > 0.5
+
+
+def test_ragged_nms_grows_its_workspace_and_reuses_it():
+    """The grow-and-retry step from the table side: two centre-form frames, 2050 rows of which every row passes with both classes -
+    4100 candidates against the 4096 of yds_nms_ragged_pred's own workspace - and 61 rows, each with a scale of its own.  Every
+    frame's rows equal, bit for bit, the frame alone through yds_nms_pred (whose workspace of 16384 does not grow), scaled on the
+    host as the sweep does; a second call runs in the grown workspace and returns the same."""
+    from yolo_deepsort_amd import _lib
+    _lib.init(0)
+    rng = np.random.RandomState(5)
+    big = np.zeros((2050, 7), F32)
+    wh = rng.uniform(5, 60, (2050, 2))
+    big[:, :2] = rng.uniform(0, 1500, (2050, 2)) + wh / 2
+    big[:, 2:4] = wh
+    big[:, 4] = rng.uniform(0.8, 1, 2050)
+    big[:, 5:] = rng.uniform(0.7, 1, (2050, 2))
+    assert int(((big[:, 5:] * big[:, 4:5] > 0.5) & (big[:, 4:5] > 0.5)).sum()) == 4100
+    frames = [(big, 0, (1.5384616, 1.1538461)), (_synthetic_frame(rng, 61, 7, 4, False), 0, (1.25, 0.75))]
+    want = [_nms_plain(p, 0.5, 0.4, scale) for p, _, scale in frames]
+    assert len(want[0]) > 1 and len(want[1]) > 1
+    for call in range(2):
+        for f, (g, w) in enumerate(zip(_nms_ragged(frames, 0.5, 0.4), want)):
+            _same_rows(g, w, (call, f))
 
 
 # ------------------------------------------------------------------------------------------------ 3. scripted scene

@@ -1,6 +1,6 @@
 """Sliding-window detection in the batched pipelines (csrc/pipeline.cpp window mode, yds_pipeline_set_windows): the windows of all
 frames of a step are cut on the device, run through the detector in chunks of batch_max and merged per frame by one NMS launch
-(merge branch included, csrc/nms.hip launch_ragged).  The yardstick is the frame-by-frame path - VideoDetector.process with an
+(merge branch included, csrc/nms.hip launch with a frame table).  The yardstick is the frame-by-frame path - VideoDetector.process with an
 ImageDetector(win_size=...) (yds_detect_tiled, host merge branch) + DeepSort.update - which tests/test_gpu_assoc.py pins to the
 reference's golden vectors.  Row criterion as tests/test_gpu_pipeline.py: track ids and classes bit exact, boxes within one pixel,
 None frames agree.  yolov3-tiny at 416, win_size = (416, 416), overlap 0.15 throughout."""
@@ -296,8 +296,8 @@ def test_nms_workspace_overflow_redoes_the_window_pass():
     assert _compare(got, want) > 0
 
 
-# ------------------------------------------------------------------------------------------------ 3. device merge against the host merge
-def _merge_host(pred, ct, it):
+# ------------------------------------------------------------------------------------------------ 3. merge branch: a frame in a batch against the frame alone
+def _merge_alone(pred, ct, it):
     from yolo_deepsort_amd import _lib as L
     pred = np.ascontiguousarray(pred, dtype=F32)
     out = np.zeros((300, 6), F32)
@@ -319,17 +319,24 @@ def _merge_batched(preds, ct, it):
     return [out[f, :n[f]].copy() for f in range(len(preds))]
 
 
-def _same_detections(got, want, tag):
+def _same_detections(got, want, tag, atol=1e-4):
     assert got.shape == want.shape, tag
     assert np.array_equal(got[:, 4:], want[:, 4:]), tag                       # scores and classes: bit exact
     assert np.array_equal(np.isnan(got), np.isnan(want)), tag
-    np.testing.assert_allclose(got[:, :4], want[:, :4], rtol=1e-6, atol=1e-4, equal_nan=True, err_msg=str(tag))
+    np.testing.assert_allclose(got[:, :4], want[:, :4], rtol=1e-6, atol=atol, equal_nan=True, err_msg=str(tag))
 
 
-def test_device_merge_equals_host_merge():
-    """yds_nms_merge_pred_batched (merge branch as a kernel, all frames in one launch) against yds_nms_merge_pred (host loop) and the
-    reference's golden outputs: the four cases of tiled_detect.npz as four frames, then the 40 random trials of
-    test_gpu_assoc.py::test_nms_merge_branch_golden_and_oracle in groups of ten."""
+def _same_rows(got, want, tag):
+    assert got.shape == want.shape, tag
+    assert np.array_equal(got, want, equal_nan=True), (tag, got, want)        # bit for bit; 0 / 0 rows agree as NaN
+
+
+def test_merge_frame_in_a_uniform_batch_equals_the_frame_alone():
+    """yds_nms_merge_pred_batched (several frames in one uniform launch, the merge branch for each) against yds_nms_merge_pred (the
+    same launch with one frame): a frame inside a multi-frame launch equals the frame alone, bit for bit.  Both against the
+    reference's golden outputs: the four cases of tiled_detect.npz as four frames.  Then the 40 random trials of
+    test_gpu_assoc.py::test_nms_merge_branch_golden_and_oracle in groups of ten, each also against the oracle
+    (soft_non_max_suppression_merge) at that test's tolerances: scores, classes and NaN pattern bit-exact, boxes rtol 1e-6, atol 1e-3."""
     from yolo_deepsort_amd import _lib
     from oracle import nms as onms
     _lib.init(0)
@@ -339,7 +346,7 @@ def test_device_merge_equals_host_merge():
     preds[1] = np.concatenate([preds[1], np.zeros((7, preds[1].shape[1]), F32)], 0)      # (frames of different length: padding inside the call too)
     for nme, p, got in zip(names, preds, _merge_batched(preds, 0.5, 0.4)):
         _same_detections(got, g[nme + "_out"], nme)
-        _same_detections(got, _merge_host(p, 0.5, 0.4), nme)
+        _same_rows(got, _merge_alone(p, 0.5, 0.4), nme)
     rng = np.random.RandomState(8)
     trials = []
     for trial in range(40):
@@ -358,10 +365,12 @@ def test_device_merge_equals_host_merge():
     for g0 in range(0, 40, 10):
         group = trials[g0:g0 + 10]
         for i, (p, got) in enumerate(zip(group, _merge_batched([p[0] for p in group], 0.5, 0.4))):
-            host = _merge_host(p[0], 0.5, 0.4)
-            _same_detections(got, host, g0 + i)
-            if not got.shape[0]:
+            _same_rows(got, _merge_alone(p[0], 0.5, 0.4), g0 + i)
+            want = onms.soft_non_max_suppression_merge(p, 0.5, 0.4)[0]         # independent of the code under test
+            if want is None:
+                assert got.shape[0] == 0, g0 + i
                 continue
+            _same_detections(got, want, g0 + i, atol=1e-3)
             b = p[..., :4].astype(np.float64)
             centre = np.stack([(b[..., 0] + b[..., 2]) / 2, (b[..., 1] + b[..., 3]) / 2, b[..., 2] - b[..., 0], b[..., 3] - b[..., 1]], -1)
             plain = onms.soft_non_max_suppression(np.concatenate([centre.astype(F32), p[..., 4:]], -1), 0.5, 0.4)[0]

@@ -157,21 +157,16 @@ void launch_slot_resize(const uint8_t *frames, const SlotRec *slots, int n, cons
 // rows [0, n * n_boxes) of pred (the network output of those n slots) -> dst, same row order: a window slot's boxes in corner form,
 // scaled and shifted (SlotRec), a plain slot's rows copied
 void launch_slot_boxes(const float *pred, int n_boxes, int attrs, const SlotRec *slots, int n, float *dst, hipStream_t s);
-// ReID: crop + resize to 64x128 + /255 + mean/std -> NHWC4
-// boxes: [D,5] = x1,y1,x2,y2,frame index (frames are h*w*3 bytes apart)
-void launch_crop_resize(const uint8_t *frames, int h, int w, const int *boxes5_dev, int D, const View &y,
-                        hipStream_t s, bool bgr = false);
-// the same with a box's frame index selecting that frame's base, row stride and size from `geom`
-void launch_crop_resize_frames(const uint8_t *frames, const FrameGeom *geom, const int *boxes5_dev, int D, const View &y, hipStream_t s,
-                               bool bgr = false);
-// Where the crops of a ReID pass come from: the frames (h x w each, or `geom` when they differ in size) and the [D,5] crop list, both
-// device-readable until the pass has run.
+// Where the crops of a ReID pass come from: the frames (h x w each, h*w*3 bytes apart, or `geom` when they differ in size) and the
+// [D,5] crop list x1,y1,x2,y2,frame index (into the stack, or into `geom`), both device-readable until the pass has run.
 struct ReidFront {
     const uint8_t *frames = nullptr;
     const FrameGeom *geom = nullptr;
     const int *boxes = nullptr;
     int h = 0, w = 0, bgr = 0;
 };
+// ReID: crop + resize to 64x128 + /255 + mean/std -> NHWC4
+void launch_crop_resize(const ReidFront &f, int D, const View &y, hipStream_t s);
 // crop + resize + normalise + stem conv + BN + ReLU + MaxPool2d(3, 2, 1) in one kernel (reid_stem.hip); pooled: H16 [D,64,32,64]
 void launch_reid_stem(const ReidFront &f, int D, const float *w, int kpad, const float *bias, const View &pooled, hipStream_t s);
 constexpr int kReidStemUnitsPerCrop = 4;         // a workgroup of that kernel takes a quarter crop at a time ...

@@ -173,20 +173,23 @@ private:
 
 // --------------------------------------------------------------------------------------------- NMS
 // Device multi-label NMS over decoded predictions [n_boxes, attrs] (nms.hip).
+// The uniform description of a launch's frames, carried in the kernel arguments: frame f is rows [f * n_boxes, (f + 1) * n_boxes), every
+// frame in the same form (corner: x1,y1,x2,y2 as with is_p1p2=True; merge: the reference's merge branch runs) with the same scale.
+struct NmsUniform { int32_t n_boxes, corner, merge; float sx, sy; };
 class NmsWorkspace {
 public:
     explicit NmsWorkspace(int max_candidates = 16384, int frames = 1);
     ~NmsWorkspace();
     NmsWorkspace(const NmsWorkspace &) = delete;
-    // asynchronous form: launch() enqueues the kernels and the copies into pinned host memory, collect() reads
-    // them after the caller synchronised the stream.  corner: the predictions already hold x1,y1,x2,y2 (is_p1p2=True)
-    void launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                float sx, float sy, int cap, hipStream_t s, bool corner = false);
-    // launch() for frames that differ in row count and form, described by `fr` [n_frames] (slot_plan.h) which the kernels read on the
-    // device - per frame corner form or not, the reference's merge branch as a kernel behind the sweep or not, its own (sx, sy);
-    // max_rows: the largest n_rows, total_rows: the largest row0 + n_rows (box_count is addressed like the prediction block)
-    void launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
-                       float iou_thres, int cap, hipStream_t s);
+    // asynchronous form: launch() enqueues the kernels, the last of which stores the results into pinned host memory; collect() reads
+    // them after the caller synchronised the stream.  One kernel set and one launch sequence, the frames described in one of two ways:
+    // uniformly (the plain pipeline pass: no table, no merge kernel unless u.merge) ...
+    void launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, float iou_thres, int cap, hipStream_t s);
+    // ... or by a table `fr` [n_frames] (slot_plan.h) which the kernels read on the device, for frames that differ in row count and
+    // form - per frame corner form or not, the merge branch or not, its own (sx, sy); max_rows: the largest n_rows, total_rows: the
+    // largest row0 + n_rows (box_count is addressed like the prediction block)
+    void launch(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
+                float iou_thres, int cap, hipStream_t s);
     int collect(int frame, float *out6_host, int cap);
     void resize(int max_candidates, int n_frames);       // (re)allocates; contents are lost
     int needed(int n_frames) const;                       // largest candidate count of the last launch (after the caller's sync)
@@ -195,7 +198,8 @@ public:
     // scaled by (sx, sy) when scale is requested (resize_boxes).
     int run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float sx, float sy,
             float *out6_host, int cap, hipStream_t s);
-    // merge=True / is_p1p2=True form used by the sliding-window detector: corner-form boxes, the reference's merge branch
+    // merge=True / is_p1p2=True form used by the sliding-window detector: corner-form boxes, the reference's merge branch (the same
+    // kernel behind the sweep that a windowed pipeline pass runs)
     int run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap, hipStream_t s);
     int max_cand, frames;
     DevBuf<float> cand;          // [max_cand, 6]   x1,y1,x2,y2,score,cls in candidate order
@@ -204,7 +208,6 @@ public:
     DevBuf<int> box_count;       // per box candidate count / offsets
     DevBuf<unsigned long long> mask;   // [max_cand, max_cand/64] suppression bits
     DevBuf<float> kept;          // [300, 6]
-    DevBuf<int> order;
     int *h_counts = nullptr;     // pinned
     float *h_kept = nullptr;     // pinned [300,6]
 };

@@ -425,57 +425,33 @@ void launch_slot_boxes(const float *pred, int n_boxes, int attrs, const SlotRec 
     YDS_HIP(hipGetLastError());
 }
 
-__global__ void crop_resize_kernel(const uint8_t *frames, int H, int W, const int *boxes, int D, float *y, int Ho, int Wo, int bgr) {
+// boxes[d * 5 + 4] is the crop's frame: frame number fi of a stack of h x w frames, or - frames of different sizes - an index into
+// f.geom (the box was clamped to that frame on the host); resolved as reid_stem.hip's load_src does
+__global__ void crop_resize_kernel(ReidFront f, int D, float *y, int Ho, int Wo) {
     const size_t total = (size_t)D * Ho * Wo;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         int ox = idx % Wo;
         size_t t = idx / Wo;
         int oy = t % Ho;
         int d = t / Ho;
-        int x1 = boxes[d * 5], y1 = boxes[d * 5 + 1], cw = boxes[d * 5 + 2] - x1, ch = boxes[d * 5 + 3] - y1;
-        const uint8_t *frame = frames + (size_t)boxes[d * 5 + 4] * H * W * 3;
+        const int *b = f.boxes + (size_t)d * 5;
+        int x1 = b[0], y1 = b[1], cw = b[2] - x1, ch = b[3] - y1, fi = b[4];
+        size_t off = (size_t)fi * f.h * f.w * 3;
+        int W = f.w;
+        if (f.geom) { const FrameGeom g = f.geom[fi]; off = g.off; W = g.w; }
         const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
         float o[3];
-        resize_px(frame + ((size_t)y1 * W + x1) * 3, (size_t)W * 3, ch, cw, Ho, Wo, oy, ox, o);
-        if (bgr) { const float t = o[0]; o[0] = o[2]; o[2] = t; }       // (BGR frames: see resize_u8_kernel)
+        resize_px(f.frames + off + ((size_t)y1 * W + x1) * 3, (size_t)W * 3, ch, cw, Ho, Wo, oy, ox, o);
+        if (f.bgr) { const float t = o[0]; o[0] = o[2]; o[2] = t; }     // (BGR frames: see resize_u8_kernel)
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = __fdiv_rn(__fsub_rn(__fdiv_rn(o[c], 255.f), mean[c]), stdv[c]);
         *reinterpret_cast<float4 *>(y + idx * 4) = make_float4(o[0], o[1], o[2], 0.f);
     }
 }
 
-void launch_crop_resize(const uint8_t *frame, int h, int w, const int *boxes_xyxy_dev, int D, const View &y, hipStream_t s, bool bgr) {   // boxes: [D,5]
+void launch_crop_resize(const ReidFront &f, int D, const View &y, hipStream_t s) {   // f.boxes: [D,5]
     if (D == 0) return;
-    hipLaunchKernelGGL(crop_resize_kernel, dim3(grid_for((size_t)D * y.h * y.w)), dim3(256), 0, s, frame, h, w, boxes_xyxy_dev, D, y.p,
-                       y.h, y.w, bgr ? 1 : 0);
-    YDS_HIP(hipGetLastError());
-}
-
-// crop_resize_kernel for frames of different sizes: boxes[d * 5 + 4] indexes `geom` (the box was clamped to that frame on the host)
-__global__ void crop_resize_frames_kernel(const uint8_t *frames, const FrameGeom *geom, const int *boxes, int D, float *y, int Ho, int Wo, int bgr) {
-    const size_t total = (size_t)D * Ho * Wo;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        int ox = idx % Wo;
-        size_t t = idx / Wo;
-        int oy = t % Ho;
-        int d = t / Ho;
-        int x1 = boxes[d * 5], y1 = boxes[d * 5 + 1], cw = boxes[d * 5 + 2] - x1, ch = boxes[d * 5 + 3] - y1;
-        const FrameGeom g = geom[boxes[d * 5 + 4]];
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-        float o[3];
-        resize_px(frames + g.off + ((size_t)y1 * g.w + x1) * 3, (size_t)g.w * 3, ch, cw, Ho, Wo, oy, ox, o);
-        if (bgr) { const float t = o[0]; o[0] = o[2]; o[2] = t; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = __fdiv_rn(__fsub_rn(__fdiv_rn(o[c], 255.f), mean[c]), stdv[c]);
-        *reinterpret_cast<float4 *>(y + idx * 4) = make_float4(o[0], o[1], o[2], 0.f);
-    }
-}
-
-void launch_crop_resize_frames(const uint8_t *frames, const FrameGeom *geom, const int *boxes_xyxy_dev, int D, const View &y, hipStream_t s,
-                               bool bgr) {
-    if (D == 0) return;
-    hipLaunchKernelGGL(crop_resize_frames_kernel, dim3(grid_for((size_t)D * y.h * y.w)), dim3(256), 0, s, frames, geom, boxes_xyxy_dev, D, y.p,
-                       y.h, y.w, bgr ? 1 : 0);
+    hipLaunchKernelGGL(crop_resize_kernel, dim3(grid_for((size_t)D * y.h * y.w)), dim3(256), 0, s, f, D, y.p, y.h, y.w);
     YDS_HIP(hipGetLastError());
 }
 

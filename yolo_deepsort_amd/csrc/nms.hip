@@ -19,16 +19,20 @@
 
 #include <string.h>
 
-#include <algorithm>
 #include <vector>
 
 namespace yds {
 
 constexpr int MAX_DET = 300;
 
-// The stages up to the sweep come in two forms that share one body each: the uniform form (launch: every frame n_boxes rows,
-// pred_stride apart) and the ragged form (launch_ragged: frame blockIdx.y is rows [row0, row0 + n_rows) of one block, described by an
-// NmsFrame the kernel reads on the device; box_count is addressed by the same row prefix).
+// Every stage is ONE kernel.  Frame blockIdx.y is rows [row0, row0 + n_rows) of one block of predictions (box_count is addressed by
+// the same row prefix); its NmsFrame comes from the kernel's `frames` argument, either of the two launch() forms: an NmsUniform held
+// in the kernel arguments (every frame n_boxes rows, one form and scale) or a table of NmsFrame the kernel reads on the device.
+__device__ __forceinline__ NmsFrame frame_at(const NmsUniform &u, int f) {
+    return NmsFrame{(uint64_t)f * u.n_boxes, u.n_boxes, u.corner, u.merge, u.sx, u.sy, 0};
+}
+__device__ __forceinline__ NmsFrame frame_at(const NmsFrame *fr, int f) { return fr[f]; }
+
 __device__ __forceinline__ void nms_count_body(const float *pred, int n_boxes, int attrs, float thr, int *box_count) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_boxes) return;
@@ -40,11 +44,8 @@ __device__ __forceinline__ void nms_count_body(const float *pred, int n_boxes, i
     }
     box_count[i] = cnt;
 }
-__global__ void nms_count_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, int *box_count_all) {
-    nms_count_body(pred_all + blockIdx.y * pred_stride, n_boxes, attrs, thr, box_count_all + (size_t)blockIdx.y * n_boxes);
-}
-__global__ void nms_count_ragged_kernel(const float *pred, const NmsFrame *fr, int attrs, float thr, int *box_count) {
-    const NmsFrame f = fr[blockIdx.y];
+template <class Frames> __global__ void nms_count_kernel(const float *pred, Frames frames, int attrs, float thr, int *box_count) {
+    const NmsFrame f = frame_at(frames, blockIdx.y);
     nms_count_body(pred + (size_t)f.row0 * attrs, f.n_rows, attrs, thr, box_count + f.row0);
 }
 
@@ -75,11 +76,8 @@ __device__ __forceinline__ void nms_scan_body(int *box_count, int n_boxes, int *
     }
     if (tid == 0) { counts[0] = carry; counts[1] = 0; }
 }
-__global__ void nms_scan_kernel(int *box_count_all, int n_boxes, int *counts_all) {
-    nms_scan_body(box_count_all + (size_t)blockIdx.y * n_boxes, n_boxes, counts_all + blockIdx.y * 4);
-}
-__global__ void nms_scan_ragged_kernel(int *box_count, const NmsFrame *fr, int *counts_all) {
-    const NmsFrame f = fr[blockIdx.y];
+template <class Frames> __global__ void nms_scan_kernel(int *box_count, Frames frames, int *counts_all) {
+    const NmsFrame f = frame_at(frames, blockIdx.y);
     nms_scan_body(box_count + f.row0, f.n_rows, counts_all + blockIdx.y * 4);
 }
 
@@ -107,13 +105,9 @@ __device__ __forceinline__ void nms_emit_body(const float *pred, int n_boxes, in
         }
     }
 }
-__global__ void nms_emit_kernel(const float *pred_all, size_t pred_stride, int n_boxes, int attrs, float thr, const int *box_off_all, int max_cand,
-                                float *cand_all, int corner) {
-    nms_emit_body(pred_all + blockIdx.y * pred_stride, n_boxes, attrs, thr, box_off_all + (size_t)blockIdx.y * n_boxes, max_cand,
-                  cand_all + (size_t)blockIdx.y * max_cand * 6, corner);
-}
-__global__ void nms_emit_ragged_kernel(const float *pred, const NmsFrame *fr, int attrs, float thr, const int *box_off, int max_cand, float *cand_all) {
-    const NmsFrame f = fr[blockIdx.y];
+template <class Frames>
+__global__ void nms_emit_kernel(const float *pred, Frames frames, int attrs, float thr, const int *box_off, int max_cand, float *cand_all) {
+    const NmsFrame f = frame_at(frames, blockIdx.y);
     nms_emit_body(pred + (size_t)f.row0 * attrs, f.n_rows, attrs, thr, box_off + f.row0, max_cand, cand_all + (size_t)blockIdx.y * max_cand * 6, f.corner);
 }
 
@@ -218,14 +212,12 @@ __device__ __forceinline__ void nms_sweep_body(const float *sorted_all, const un
     __syncthreads();
     if (threadIdx.x == 0) counts[1] = n_keep;
 }
+// a plain frame's boxes are scaled by its own ratio, a windowed frame's descriptor holds (1, 1)
+template <class Frames>
 __global__ void nms_sweep_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
-                                 float sx, float sy, float *kept_all, int cap) {
-    nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, sx, sy, kept_all, cap);
-}
-// ragged form: a plain frame's boxes are scaled by its own ratio, a windowed frame's descriptor holds (1, 1)
-__global__ void nms_sweep_ragged_kernel(const float *sorted_all, const unsigned long long *mask_all, int words_ld, int *counts_all, int max_cand,
-                                        const NmsFrame *fr, float *kept_all, int cap) {
-    nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, fr[blockIdx.y].sx, fr[blockIdx.y].sy, kept_all, cap);
+                                 Frames frames, float *kept_all, int cap) {
+    const NmsFrame f = frame_at(frames, blockIdx.y);
+    nms_sweep_body(sorted_all, mask_all, words_ld, counts_all, max_cand, f.sx, f.sy, kept_all, cap);
 }
 
 NmsWorkspace::NmsWorkspace(int max_candidates, int frames) : max_cand(0), frames(0) { resize(max_candidates, frames); }
@@ -261,13 +253,15 @@ NmsWorkspace::~NmsWorkspace() {
     if (h_kept) (void)hipHostFree(h_kept);
 }
 
-// The merge branch of soft_non_max_suppression(merge=True, is_p1p2=True) on the device, one workgroup per image: what the host loop
-// of run_merge() does (model_build.py:122-131; see the comment there), for the windowed frames of a ragged launch.  It fires
-// when 1 < n < 3000 and the kept count k is n or 1: every kept row's box becomes the weighted mean of ALL candidates whose +1-pixel
-// IoU (model_build.py:354-381, on class-offset boxes) with the paired kept box - kept row j when k == n, kept row 0 when k == 1 -
-// exceeds the threshold, weights = the candidates' scores.  The IoUs are computed by all threads; the sums are taken by ONE thread in
-// candidate order (fp32 weight sum, fp64 box sums, like the host loop), so that the rounding and the rows where 0/0 gives NaN are
-// the host's.  `cand` holds the candidates in emit order, `sorted` in kept (score) order; runs behind the sweep, before publish.
+// The merge branch of soft_non_max_suppression(merge=True, is_p1p2=True) as the reference behaves (model_build.py:122-131, see
+// oracle/nms.py soft_non_max_suppression_merge), one workgroup per image, for the frames whose description asks for it.
+// `bbox_iou(boxes[i], boxes)` is elementwise, so it only broadcasts when the number of kept boxes k is 1 or equals the number of
+// candidates n; in those two cases every kept box is replaced by one weighted-mean box before the following line raises into the bare
+// except, otherwise the plain result stands.  So it fires when 1 < n < MERGE_MAX and k is n or 1: every kept row's box becomes the
+// weighted mean of ALL candidates whose +1-pixel IoU (model_build.py:354-381, on class-offset boxes) with the paired kept box - kept
+// row j when k == n, kept row 0 when k == 1 - exceeds the threshold, weights = the candidates' scores.  The IoUs are computed by all
+// threads; the sums are taken by ONE thread in candidate order (fp32 weight sum, fp64 box sums) and 0/0 gives NaN rows as in the
+// reference.  `cand` holds the candidates in emit order, `sorted` in kept (score) order; runs behind the sweep, before publish.
 constexpr int MERGE_MAX = 3000;
 __device__ __forceinline__ void nms_merge_body(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand, float iou_thres,
                                                float *kept_all) {
@@ -304,10 +298,11 @@ __device__ __forceinline__ void nms_merge_body(const float *cand_all, const floa
     __syncthreads();
     for (int i = threadIdx.x; i < k * 4; i += blockDim.x) kept[(size_t)(i >> 2) * 6 + (i & 3)] = mean[i & 3];
 }
-// only the frames whose descriptor asks for the merge branch (the windowed ones)
-__global__ __launch_bounds__(256) void nms_merge_ragged_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
-                                                               float iou_thres, const NmsFrame *fr, float *kept_all) {
-    if (!fr[blockIdx.x].merge) return;                           // (uniform over the workgroup)
+// only the frames whose description asks for the merge branch (the windowed ones)
+template <class Frames>
+__global__ __launch_bounds__(256) void nms_merge_kernel(const float *cand_all, const float *sorted_all, const int *counts_all, int max_cand,
+                                                        float iou_thres, Frames frames, float *kept_all) {
+    if (!frame_at(frames, blockIdx.x).merge) return;             // (uniform over the workgroup)
     nms_merge_body(cand_all, sorted_all, counts_all, max_cand, iou_thres, kept_all);
 }
 
@@ -324,49 +319,52 @@ __global__ __launch_bounds__(256) void nms_publish_kernel(const int *counts, con
     for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
 }
 
-// All `n_frames` images go through each stage in ONE launch (blockIdx.y = image).
-void NmsWorkspace::launch(const float *pred_dev, size_t pred_stride, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
-                          float sx, float sy, int cap, hipStream_t s, bool corner) {
+// All `n_frames` images go through each stage in ONE launch (blockIdx.y = image): count / scan / emit take every frame's own rows,
+// grid.x is sized by the largest frame (max_rows); rank, mask, sweep and publish work per frame on the candidate counts.
+// total_rows: the largest row0 + n_rows; merge: some frame may ask for the merge branch.
+template <class Frames>
+static void launch_stages(NmsWorkspace &w, const float *pred_dev, Frames frames, int n_frames, int max_rows, size_t total_rows, bool merge, int attrs,
+                          float conf_thres, float iou_thres, int cap, hipStream_t s) {
     if (attrs < 6) fail("nms: predictions need at least one class");
-    if (n_frames < 1) fail("nms: no frames");
-    if (n_frames > frames) resize(max_cand, n_frames);
-    box_count.ensure((size_t)frames * n_boxes);
-    const int nb = (n_boxes + 255) / 256;
-    hipLaunchKernelGGL(nms_count_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, pred_stride, n_boxes, attrs, conf_thres, box_count.p);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(1, n_frames), dim3(1024), 0, s, box_count.p, n_boxes, counts.p);
-    hipLaunchKernelGGL(nms_emit_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, pred_stride, n_boxes, attrs, conf_thres, box_count.p,
-                       max_cand, cand.p, corner ? 1 : 0);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3(16, n_frames), dim3(256), 0, s, cand.p, counts.p, max_cand, sorted.p);
-    const int words_ld = max_cand / 64;
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
-    hipLaunchKernelGGL(nms_sweep_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
-                       counts.p, max_cand, sx, sy, kept.p, cap);
+    if (n_frames < 1 || max_rows < 1) fail("nms: %d frames of at most %d rows", n_frames, max_rows);
+    if (n_frames > w.frames) w.resize(w.max_cand, n_frames);
+    w.box_count.ensure(total_rows);
+    const int nb = (max_rows + 255) / 256, max_cand = w.max_cand, words_ld = max_cand / 64;
+    hipLaunchKernelGGL(nms_count_kernel<Frames>, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, frames, attrs, conf_thres, w.box_count.p);
+    hipLaunchKernelGGL(nms_scan_kernel<Frames>, dim3(1, n_frames), dim3(1024), 0, s, w.box_count.p, frames, w.counts.p);
+    hipLaunchKernelGGL(nms_emit_kernel<Frames>, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, frames, attrs, conf_thres, w.box_count.p, max_cand,
+                       w.cand.p);
+    hipLaunchKernelGGL(nms_rank_kernel, dim3(16, n_frames), dim3(256), 0, s, w.cand.p, w.counts.p, max_cand, w.sorted.p);
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, w.sorted.p, w.counts.p, max_cand, (double)iou_thres, w.mask.p, words_ld);
+    hipLaunchKernelGGL(nms_sweep_kernel<Frames>, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, w.sorted.p, w.mask.p, words_ld,
+                       w.counts.p, max_cand, frames, w.kept.p, cap);
+    if (merge)
+        hipLaunchKernelGGL(nms_merge_kernel<Frames>, dim3(n_frames), dim3(256), 0, s, w.cand.p, w.sorted.p, w.counts.p, max_cand, iou_thres, frames,
+                           w.kept.p);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
-    hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
+    hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, w.counts.p, w.kept.p, w.h_counts, w.h_kept, std::min(cap, (int)MAX_DET));
     YDS_HIP(hipGetLastError());
 }
 
-// The same launch sequence for frames of different row counts and forms in one block of predictions (a pipeline pass with a slot plan):
-// count / scan / emit take every frame's own rows, grid.x is sized by the largest frame; rank, mask and publish work per frame on the
-// candidate counts as in launch().  fr: n_frames descriptors, device-readable until the kernels have run.
-void NmsWorkspace::launch_ragged(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
-                                 float iou_thres, int cap, hipStream_t s) {
-    if (attrs < 6) fail("nms: predictions need at least one class");
-    if (n_frames < 1 || max_rows < 1) fail("nms: %d frames of at most %d rows", n_frames, max_rows);
-    if (n_frames > frames) resize(max_cand, n_frames);
-    box_count.ensure(total_rows);
-    const int nb = (max_rows + 255) / 256;
-    hipLaunchKernelGGL(nms_count_ragged_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, fr, attrs, conf_thres, box_count.p);
-    hipLaunchKernelGGL(nms_scan_ragged_kernel, dim3(1, n_frames), dim3(1024), 0, s, box_count.p, fr, counts.p);
-    hipLaunchKernelGGL(nms_emit_ragged_kernel, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, fr, attrs, conf_thres, box_count.p, max_cand, cand.p);
-    hipLaunchKernelGGL(nms_rank_kernel, dim3(16, n_frames), dim3(256), 0, s, cand.p, counts.p, max_cand, sorted.p);
-    const int words_ld = max_cand / 64;
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, sorted.p, counts.p, max_cand, (double)iou_thres, mask.p, words_ld);
-    hipLaunchKernelGGL(nms_sweep_ragged_kernel, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, sorted.p, mask.p, words_ld,
-                       counts.p, max_cand, fr, kept.p, cap);
-    hipLaunchKernelGGL(nms_merge_ragged_kernel, dim3(n_frames), dim3(256), 0, s, cand.p, sorted.p, counts.p, max_cand, iou_thres, fr, kept.p);
-    hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, counts.p, kept.p, h_counts, h_kept, std::min(cap, (int)MAX_DET));
-    YDS_HIP(hipGetLastError());
+void NmsWorkspace::launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, float iou_thres, int cap,
+                          hipStream_t s) {
+    launch_stages(*this, pred_dev, u, n_frames, u.n_boxes, (size_t)std::max(frames, n_frames) * u.n_boxes, u.merge != 0, attrs, conf_thres,
+                  iou_thres, cap, s);
+}
+
+void NmsWorkspace::launch(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
+                          float iou_thres, int cap, hipStream_t s) {
+    launch_stages(*this, pred_dev, fr, n_frames, max_rows, total_rows, true, attrs, conf_thres, iou_thres, cap, s);
+}
+
+// launch, wait, and once more when the launch met more candidates than the workspace holds: grow, run again
+template <class Launch> static void launch_grown(NmsWorkspace &w, int n_frames, hipStream_t s, Launch launch) {
+    launch();
+    YDS_HIP(hipStreamSynchronize(s));
+    if (w.needed(n_frames) <= w.max_cand) return;
+    w.resize(w.needed(n_frames), w.frames);
+    launch();
+    YDS_HIP(hipStreamSynchronize(s));
 }
 
 int NmsWorkspace::collect(int frame, float *out6_host, int cap) {
@@ -379,63 +377,16 @@ int NmsWorkspace::collect(int frame, float *out6_host, int cap) {
 
 int NmsWorkspace::run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float sx, float sy,
                       float *out6_host, int cap, hipStream_t s) {
-    launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, sx, sy, cap, s);
-    YDS_HIP(hipStreamSynchronize(s));
-    if (needed(1) > max_cand) {                                  // more candidates than the workspace holds: grow, run again
-        resize(needed(1), frames);
-        launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, sx, sy, cap, s);
-        YDS_HIP(hipStreamSynchronize(s));
-    }
+    launch_grown(*this, 1, s, [&] { launch(pred_dev, NmsUniform{n_boxes, 0, 0, sx, sy}, 1, attrs, conf_thres, iou_thres, cap, s); });
     return collect(0, out6_host, cap);
 }
 
-// soft_non_max_suppression(merge=True, is_p1p2=True) as the reference behaves (model_build.py:122-131, see
-// oracle/nms.py soft_non_max_suppression_merge): `bbox_iou(boxes[i], boxes)` is elementwise, so it only broadcasts when
-// the number of kept boxes k is 1 or equals the number of candidates n.  In those two cases every kept box is replaced
-// by one weighted-mean box before the following line raises into the bare except; otherwise the plain result stands.
+// soft_non_max_suppression(merge=True, is_p1p2=True): corner-form boxes, the merge branch (nms_merge_body) behind a sweep that keeps
+// MAX_DET rows whatever `cap` is - the branch depends on the kept count
 int NmsWorkspace::run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap,
                             hipStream_t s) {
-    launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s, true);
-    YDS_HIP(hipStreamSynchronize(s));
-    if (needed(1) > max_cand) {
-        resize(needed(1), frames);
-        launch(pred_dev, 0, 1, n_boxes, attrs, conf_thres, iou_thres, 1.f, 1.f, MAX_DET, s, true);
-        YDS_HIP(hipStreamSynchronize(s));
-    }
-    const int n = h_counts[0], k = h_counts[1];
-    if (n > 1 && n < 3000 && (k == n || k == 1)) {
-        std::vector<float> c((size_t)n * 6);
-        YDS_HIP(hipMemcpy(c.data(), cand.p, c.size() * sizeof(float), hipMemcpyDeviceToHost));
-        // kept order = stable descending score order over the candidates (all of them, or just the first)
-        std::vector<int> order(n);
-        for (int i = 0; i < n; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return c[(size_t)a * 6 + 4] > c[(size_t)b * 6 + 4]; });
-        auto off = [&](int i, float b[4]) {
-            const float o = c[(size_t)i * 6 + 5] * 4096.f;
-            for (int d = 0; d < 4; ++d) b[d] = c[(size_t)i * 6 + d] + o;
-        };
-        double acc[4] = {0, 0, 0, 0};
-        float wsum = 0.f;
-        for (int j = 0; j < n; ++j) {
-            float a[4], b[4];
-            off(order[k == 1 ? 0 : j], a);
-            off(j, b);
-            // bbox_iou, +1 pixel convention (model_build.py:354-381), fp32
-            float iw = fminf(a[2], b[2]) - fmaxf(a[0], b[0]) + 1.f, ih = fminf(a[3], b[3]) - fmaxf(a[1], b[1]) + 1.f;
-            iw = iw > 0.f ? iw : 0.f; ih = ih > 0.f ? ih : 0.f;
-            const float inter = iw * ih;
-            const float a1 = (a[2] - a[0] + 1.f) * (a[3] - a[1] + 1.f), a2 = (b[2] - b[0] + 1.f) * (b[3] - b[1] + 1.f);
-            const float iou = inter / ((a1 + a2) - inter + 1e-16f);
-            const float wgt = iou > iou_thres ? c[(size_t)j * 6 + 4] : 0.f;
-            wsum += wgt;
-            for (int d = 0; d < 4; ++d) acc[d] += (double)wgt * c[(size_t)j * 6 + d];
-        }
-        for (int r = 0; r < k; ++r)
-            for (int d = 0; d < 4; ++d) h_kept[(size_t)r * 6 + d] = (float)acc[d] / wsum;      // 0/0 -> NaN like the reference
-    }
-    const int rows = k < cap ? k : cap;
-    if (rows > 0) memcpy(out6_host, h_kept, (size_t)rows * 6 * sizeof(float));
-    return rows;
+    launch_grown(*this, 1, s, [&] { launch(pred_dev, NmsUniform{n_boxes, 1, 1, 1.f, 1.f}, 1, attrs, conf_thres, iou_thres, MAX_DET, s); });
+    return collect(0, out6_host, cap);
 }
 
 }  // namespace yds
@@ -446,6 +397,12 @@ namespace {
 yds::NmsWorkspace &workspace() {
     static thread_local std::unique_ptr<yds::NmsWorkspace> ws;
     if (!ws) ws.reset(new yds::NmsWorkspace());
+    return *ws;
+}
+// the entries that take several frames: a workspace of their own, small per frame, that grows with the number of frames
+yds::NmsWorkspace &frames_workspace(int n_frames) {
+    static thread_local std::unique_ptr<yds::NmsWorkspace> ws;
+    if (!ws) ws.reset(new yds::NmsWorkspace(4096, n_frames));
     return *ws;
 }
 }  // namespace
@@ -494,20 +451,15 @@ int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, in
         fr[f] = yds::NmsFrame{row0[f], n_rows[f], corner_merge[f * 2] != 0, corner_merge[f * 2 + 1] != 0, scale[f * 2], scale[f * 2 + 1], 0};
         max_rows = std::max(max_rows, n_rows[f]);
     }
-    static thread_local std::unique_ptr<yds::NmsWorkspace> ws;           // own workspace: sized by the number of frames
-    if (!ws) ws.reset(new yds::NmsWorkspace(4096, n_frames));
+    yds::NmsWorkspace &ws = frames_workspace(n_frames);
     yds::DevBuf<float> pred;
     yds::DevBuf<yds::NmsFrame> fr_dev;
     pred.upload(pred_host, total_rows * attrs);
     fr_dev.upload(fr.data(), fr.size());
     YDS_HIP(hipStreamSynchronize(nullptr));
-    for (int pass = 0; pass < 2; ++pass) {
-        ws->launch_ragged(pred.p, fr_dev.p, n_frames, max_rows, total_rows, attrs, conf_thres, iou_thres, yds::MAX_DET, nullptr);
-        YDS_HIP(hipStreamSynchronize(nullptr));
-        if (ws->needed(n_frames) <= ws->max_cand) break;
-        ws->resize(ws->needed(n_frames), ws->frames);                    // more candidates than the workspace holds: grow, run again
-    }
-    for (int f = 0; f < n_frames; ++f) n_out[f] = ws->collect(f, out6_host + (size_t)f * cap * 6, cap);
+    yds::launch_grown(ws, n_frames, nullptr,
+                      [&] { ws.launch(pred.p, fr_dev.p, n_frames, max_rows, total_rows, attrs, conf_thres, iou_thres, yds::MAX_DET, nullptr); });
+    for (int f = 0; f < n_frames; ++f) n_out[f] = ws.collect(f, out6_host + (size_t)f * cap * 6, cap);
     YDS_API_END
 }
 
@@ -515,13 +467,15 @@ int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes
                                int cap, int *n_out) {
     YDS_API_BEGIN
     if (n_frames < 1 || n_boxes < 1) yds::fail("nms: %d frames of %d boxes", n_frames, n_boxes);
-    // corner-form boxes, the merge branch as a kernel behind the sweep: one descriptor per frame, the launch of a windowed pipeline pass
-    std::vector<uint64_t> row0(n_frames);
-    std::vector<int32_t> n_rows(n_frames, n_boxes), corner_merge((size_t)n_frames * 2, 1);
-    std::vector<float> scale((size_t)n_frames * 2, 1.f);
-    for (int f = 0; f < n_frames; ++f) row0[f] = (uint64_t)f * n_boxes;
-    return yds_nms_ragged_pred(pred_host, (size_t)n_frames * n_boxes, attrs, n_frames, row0.data(), n_rows.data(), corner_merge.data(), scale.data(),
-                               conf_thres, iou_thres, out6_host, cap, n_out);
+    // corner-form boxes and the merge branch for every frame: the uniform description with several frames
+    yds::NmsWorkspace &ws = frames_workspace(n_frames);
+    yds::DevBuf<float> pred;
+    pred.upload(pred_host, (size_t)n_frames * n_boxes * attrs);
+    YDS_HIP(hipStreamSynchronize(nullptr));
+    yds::launch_grown(ws, n_frames, nullptr, [&] {
+        ws.launch(pred.p, yds::NmsUniform{n_boxes, 1, 1, 1.f, 1.f}, n_frames, attrs, conf_thres, iou_thres, yds::MAX_DET, nullptr);
+    });
+    for (int f = 0; f < n_frames; ++f) n_out[f] = ws.collect(f, out6_host + (size_t)f * cap * 6, cap);
     YDS_API_END
 }
 

@@ -274,10 +274,10 @@ public:
         YDS_HIP(hipEventRecord(s.e2, net->stream));
         if (p.plan.empty()) {
             const float sx = box_scale(p.geo.w, net->img_w), sy = box_scale(p.geo.h, net->img_h);
-            s.nms->launch(net->out.p, per_slot, p.batch, net->total_boxes, net->attrs, conf, nms_thres, sx, sy, 300, net->stream);
+            s.nms->launch(net->out.p, NmsUniform{net->total_boxes, 0, 0, sx, sy}, p.batch, net->attrs, conf, nms_thres, 300, net->stream);
         } else {
-            s.nms->launch_ragged(p.plan.windowed ? win_pred.p : net->out.p, s.plan_frames(), p.batch, p.plan.max_rows, n_slots * net->total_boxes,
-                                 net->attrs, conf, nms_thres, 300, net->stream);
+            s.nms->launch(p.plan.windowed ? win_pred.p : net->out.p, s.plan_frames(), p.batch, p.plan.max_rows, n_slots * net->total_boxes,
+                          net->attrs, conf, nms_thres, 300, net->stream);
         }
         YDS_HIP(hipEventRecord(s.e_nms, net->stream));
         p.done = Pass::WHOLE;

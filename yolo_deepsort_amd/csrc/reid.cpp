@@ -125,8 +125,7 @@ float *ReidNet::in_buf() {
 
 void ReidNet::crop_into_in(const ReidFront &f, int D) {
     View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
-    if (f.geom) launch_crop_resize_frames(f.frames, f.geom, f.boxes, D, x0, stream, f.bgr);
-    else launch_crop_resize(f.frames, f.h, f.w, f.boxes, D, x0, stream, f.bgr);
+    launch_crop_resize(f, D, x0, stream);
 }
 
 void ReidNet::forward(int D, const ReidFront *front) {
@@ -308,9 +307,10 @@ void ReidNet::preprocess_host(const uint8_t *frame_host, int h, int w, const flo
     crop_boxes_host(tlwh_host, D, h, w, boxes);
     boxes_dev.upload(boxes.data(), boxes.size(), stream);
     YDS_HIP(hipStreamSynchronize(stream));
-    View x0; x0.p = in_buf(); x0.n = D; x0.h = CROP_H; x0.w = CROP_W; x0.c = 4; x0.ld = 4;
-    launch_crop_resize(stage_u8.p, h, w, boxes_dev.p, D, x0, stream);
-    View x3 = x0; x3.c = 3;
+    ReidFront front;
+    front.frames = stage_u8.p; front.h = h; front.w = w; front.boxes = boxes_dev.p;
+    crop_into_in(front, D);
+    View x3; x3.p = in.p; x3.n = D; x3.h = CROP_H; x3.w = CROP_W; x3.c = 3; x3.ld = 4;
     nhwc_to_host(x3, nchw_host, stream);
 }
 
