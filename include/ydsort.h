@@ -245,6 +245,41 @@ int yds_cosine_min_cost(const float *gallery_host, const int32_t *seg_offsets_ho
 int yds_euclidean_min_cost(const float *gallery_host, const int32_t *seg_offsets_host, int T,
                            const float *feats_host, int D, int dim, float *out_TxD_host);   /* nn_matching.py:4-27,56-74 per track */
 
+/* ---- cross-camera search: queries against the appearance galleries of many trackers ------------------------
+ * No reference call does this: the reference asks a tracker's NearestNeighborDistanceMetric only for the cost of that tracker's own
+ * detections (deep_sort/sort/nn_matching.py:158-187).  The arithmetic is _nn_cosine_distance (:77-100) over the rows the trackers hold
+ * in HBM: dist[q][g] = min over the stored rows r of track g of 1 - <r, query_q / |query_q|>; g runs over the live tracks of trks[0],
+ * then trks[1], ... each in track-list order (a tracker without tracks contributes nothing; budgets may differ, nn_budget=None
+ * included).  A query whose norm is 0 or not finite has distance +inf to everything and so matches nothing.
+ * WHEN: between steps.  A tracker's step (alone or inside a pipeline step) returns after its own synchronisation, and a look-ahead
+ * detector pass in flight does not touch tracker state, so a search may follow any step call that has returned; it must not run
+ * concurrently with one.  The search reads tracker state and writes none of it.  One host synchronisation and one device-to-host copy
+ * per call; no tracker table is copied to the host (the link entry reads the caller's OWN tracker's table once, to resolve track_id).
+ * queries: fp32 [Q,512], host memory or (queries_on_device != 0) device memory whose producer has returned (what
+ * the feature-buffer getter of a ReID handle points to after an embed call) - "search by picture" without a round trip.
+ * state_mask: bit 0 = Tentative tracks, bit 1 = Confirmed tracks may be returned.
+ *   yds_gallery_search        per query the top_k smallest distances <= max_dist among tracks the mask admits, ordered by (distance, stream,
+ *                             track-list index): n_hits[q] hits at hit_*[q * top_k + k].
+ *   yds_gallery_search_dense  the whole matrix: dist_out[q * *n_tracks + g], and per g its stream, track id and state.  cap: tracks the
+ *                             g arrays hold (dist_out: Q * cap); when it is too small the call fails and *n_tracks holds the needed size.
+ *   yds_gallery_link          hand-over: the queries are the stored rows of live track track_id of trks[stream]; the distance to track g is
+ *                             the minimum over the rows of both tracks (symmetric by construction).  The track itself is never returned,
+ *                             nor any track of stream exclude_stream (-1: none).  Outputs as for one query.
+ *   yds_tracker_get_gallery   the rows track track_index (track-list order) holds, as stored (normalised for the cosine metric), in ring
+ *                             storage order; cap rows of 512; *n_rows = rows held (also when cap is too small, which fails).
+ * Refused before anything is launched, with a message: a tracker of the euclidean metric (its rows are not normalised), a tracker given
+ * twice, Q outside [1, 4096], top_k < 1, a track_id that is not live, cap too small. */
+int yds_gallery_search(yds_trk *const *trks, int n_streams, const float *queries, int queries_on_device, int Q, int state_mask, float max_dist,
+                       int top_k, int32_t *n_hits, int32_t *hit_stream, int32_t *hit_id, float *hit_dist);
+int yds_gallery_search_dense(yds_trk *const *trks, int n_streams, const float *queries, int queries_on_device, int Q, float *dist_out,
+                             int32_t *stream_of, int32_t *track_id, int32_t *state, int cap, int *n_tracks);
+int yds_gallery_link(yds_trk *const *trks, int n_streams, int stream, int track_id, int exclude_stream /* -1: none */, int state_mask,
+                     float max_dist, int top_k, int32_t *n_hits, int32_t *hit_stream, int32_t *hit_id, float *hit_dist);
+int yds_tracker_get_gallery(yds_trk *, int track_index, float *rows_out, int cap, int *n_rows);
+/* parity tests: the storage slot of every live track, track-list order.  A slot freed by a deleted track is handed to a later one
+ * with the old rows still behind the new track's row count; the search must never read them. */
+int yds_tracker_get_slots(yds_trk *, int32_t *slots, int cap);
+
 /* ---- pipeline: VideoDetector.detect hot glue (video_detect.py:134-157) ----------------------
  * One stream of frames: detector over `batch` consecutive frames, NMS of every frame, class mask,
  * p1p2Toxywh, ONE ReID pass over the crops of the whole batch, then the tracker frame by frame, in order.
@@ -478,6 +513,10 @@ int yds_darknet_load_injection_sets(yds_net *, const float *rows_host, const int
 int yds_darknet_select_injection_set(yds_net *, int set);
 int yds_pipeline_set_next_injection(yds_pipe *, int set);
 int yds_pipeline_slot_pred(yds_pipe *, float *pred_host, size_t cap_rows, size_t *n_rows);
+/* measurement aid (tools/gallery_search_bench.py): the device launch sequence of yds_gallery_search, `iters` times back to back on
+ * device-resident queries with a HIP event between every two repetitions; us_out[iters] = device time of each repetition. */
+int yds_gallery_search_bench(yds_trk *const *trks, int n_streams, const float *queries_dev, int Q, int state_mask, float max_dist, int top_k,
+                             int iters, float *us_out);
 
 #ifdef __cplusplus
 }

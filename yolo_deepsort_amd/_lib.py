@@ -152,6 +152,12 @@ SIGNATURES = {
     "yds_nms_ragged_pred": (_I, [_P, _SZ, _I, _I, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
     "yds_pipeline_set_stream_windows": (_I, [_P, _I, _I, _I, C.c_double]),
     "yds_pipeline_slot_pred": (_I, [_P, _P, _SZ, _P]),
+    "yds_gallery_search": (_I, [_P, _I, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "yds_gallery_search_dense": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "yds_gallery_link": (_I, [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "yds_tracker_get_gallery": (_I, [_P, _I, _P, _I, _P]),
+    "yds_tracker_get_slots": (_I, [_P, _P, _I]),
+    "yds_gallery_search_bench": (_I, [_P, _I, _P, _I, _I, _F, _I, _I, _P]),
 }
 
 _lib = None

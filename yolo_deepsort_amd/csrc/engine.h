@@ -270,8 +270,18 @@ public:
 
 // --------------------------------------------------------------------------------------------- tracker
 // Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
+// What a reader of a tracker's appearance galleries needs (gallery_search.hip): device pointers into the tracker's own state, valid
+// until its next step (a step may reallocate them), and what the host knows without touching the device.  Track t of the list
+// (t < n_tracks) holds n_feat[t] rows at gallery + (slot[t] * budget + r) * 512, r in [0, n_feat[t]).
+struct GalleryView {
+    const float *gallery;
+    const int *slot, *id, *state, *n_feat;
+    int budget, n_tracks, metric;
+    double max_dist;
+};
 struct TrackerIface {
     virtual ~TrackerIface() {}
+    virtual GalleryView gallery_view() const = 0;
     // stand-alone call, one frame through a driver of the tracker's own.  feats: [D,512] on device when feats_on_device, else host.
     // Returns rows written to out6 (int32 [m,6]).
     virtual int step(const float *tlwh_host, const float *feats, bool feats_on_device, const float *payload_host, int D,

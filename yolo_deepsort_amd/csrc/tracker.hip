@@ -19,8 +19,6 @@
 namespace yds {
 
 // ============================================================================================ device-resident tracker
-enum { TENTATIVE = 1, CONFIRMED = 2, DELETED = 3 };
-enum { METRIC_COSINE = 0, METRIC_EUCLIDEAN = 1 };
 
 // Integer lifecycle table, one entry per track in track-list order (deep_sort/sort/track.py:63-79), in device memory.
 struct TrackTable {
@@ -64,28 +62,6 @@ struct TrkDev {
     int *res;
     int res_out6, res_matches, res_um_t, res_um_d;   // int offsets inside res
 };
-
-// ordered compaction over [0, n) by a 256-thread workgroup: emit(i, rank) for every i with pred(i), ranks ascending
-// with i; returns the number of hits (to every thread).  s_cnt: LDS int[4].
-template <class Pred, class Emit> __device__ __forceinline__ int compact_ordered(int n, int *s_cnt, Pred pred, Emit emit) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int total = 0;
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + tid;
-        const bool p = i < n && pred(i);
-        const unsigned long long b = __ballot(p);
-        const int lane_rank = __popcll(b & ((1ull << lane) - 1ull)), wave_cnt = __popcll(b);
-        if (lane == 0) s_cnt[wave] = wave_cnt;
-        __syncthreads();
-        int woff = 0, chunk = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int c = s_cnt[w]; if (w < wave) woff += c; chunk += c; }
-        if (p) emit(i, total + woff + lane_rank);
-        __syncthreads();
-        total += chunk;
-    }
-    return total;
-}
 
 // -------------------------------------------------------------------------------------------- one frame = three launches
 // (round 4; rounds 1-3 ran ~14 launches per frame - begin, predict, cost, two LSAP forms, lists, IOU cost, two LSAP forms, lists,
@@ -375,6 +351,10 @@ public:
         grow(256);
     }
     int num_tracks() const override { return T_host; }
+    GalleryView gallery_view() const override {
+        const TrackTable t = table_at(table.p, capacity);
+        return GalleryView{gallery.p, t.slot, t.id, t.state, t.n_feat, budget, T_host, metric, max_dist};
+    }
 
     static TrackTable table_at(int *base, int cap) {
         TrackTable t;

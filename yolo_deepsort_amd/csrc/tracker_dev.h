@@ -14,6 +14,32 @@ constexpr int EMB = 512;
 constexpr float INFTY_COST = 1e5f;
 constexpr float CHI2_2DOF = 5.9915f;
 
+// Track.state (deep_sort/sort/track.py:4-14) and the NearestNeighborDistanceMetric options (nn_matching.py:128-134)
+enum { TENTATIVE = 1, CONFIRMED = 2, DELETED = 3 };
+enum { METRIC_COSINE = 0, METRIC_EUCLIDEAN = 1 };
+
+// ordered compaction over [0, n) by a 256-thread workgroup: emit(i, rank) for every i with pred(i), ranks ascending
+// with i; returns the number of hits (to every thread).  s_cnt: LDS int[4].
+template <class Pred, class Emit> __device__ __forceinline__ int compact_ordered(int n, int *s_cnt, Pred pred, Emit emit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int total = 0;
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + tid;
+        const bool p = i < n && pred(i);
+        const unsigned long long b = __ballot(p);
+        const int lane_rank = __popcll(b & ((1ull << lane) - 1ull)), wave_cnt = __popcll(b);
+        if (lane == 0) s_cnt[wave] = wave_cnt;
+        __syncthreads();
+        int woff = 0, chunk = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int c = s_cnt[w]; if (w < wave) woff += c; chunk += c; }
+        if (p) emit(i, total + woff + lane_rank);
+        __syncthreads();
+        total += chunk;
+    }
+    return total;
+}
+
 // std weights are fp32 roundings of 1/20 and 1/160 like the reference's tensors (kalman_filter.py:39-52)
 constexpr float kStdPos = 1.f / 20, kStdVel = 1.f / 160;
 

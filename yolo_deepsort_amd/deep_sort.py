@@ -168,6 +168,18 @@ class _TrackerHandle:
             float(max_dist), float(max_iou_distance), int(max_age), int(n_init), 0 if nn_budget is None else int(nn_budget),
             1 if metric == "euclidean" else 0))
         self.device = "cuda"
+        self.max_dist, self.metric = float(max_dist), metric           # what a gallery search asks a tracker (search.py)
+
+    def gallery(self, track_index):
+        """The appearance rows track ``track_index`` (track-list order, as in state()) holds, float32 [n,512], as stored - normalised
+        for the cosine metric - in ring storage order (yds_tracker_get_gallery): what a gallery search compares against, and what a
+        watch-list persists."""
+        lib = _lib.load()
+        cap = max(lib.yds_tracker_gallery_rows(self._h), 1)
+        rows = np.zeros((cap, 512), np.float32)
+        n = C.c_int(0)
+        _lib.check(lib.yds_tracker_get_gallery(self._h, int(track_index), _lib.ptr(rows), cap, C.byref(n)))
+        return rows[:n.value].copy()
 
     @property
     def tracks(self):

@@ -638,56 +638,77 @@ class VideoDetector:
         its = [iter(self._frames(src)) for src in sources]
         since, hold, alive = [0] * S, [None] * S, [True] * S
         shape, dev = None, None
-        while any(alive):
-            items = []                                   # (stream, frame, processed) in yield order
-            for s in range(S):
-                n_proc = 0
-                while alive[s] and n_proc < F:          # the groups of _processed_batches, per stream
-                    frame = next(its[s], None)
-                    if frame is None:
-                        alive[s] = False
-                        break
-                    frame = np.asarray(frame)
+        self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
+        try:
+            while any(alive):
+                items = []                                   # (stream, frame, processed) in yield order
+                for s in range(S):
+                    n_proc = 0
+                    while alive[s] and n_proc < F:          # the groups of _processed_batches, per stream
+                        frame = next(its[s], None)
+                        if frame is None:
+                            alive[s] = False
+                            break
+                        frame = np.asarray(frame)
+                        if mixed_sizes:
+                            if shapes[s] is None:
+                                shapes[s] = frame.shape
+                            if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+                                raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
+                                                 % (s, shapes[s], frame.shape, frame.dtype))
+                        elif shape is None:
+                            shape = frame.shape
+                        if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
+                            raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
+                                             "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
+                        proc = since[s] % self.skip_frames == 0
+                        if proc:
+                            since[s] = 0
+                        since[s] += 1
+                        n_proc += proc
+                        items.append((s, frame, proc))
+                procs = [(s, f) for s, f, p in items if p]
+                outs = []
+                if procs:
                     if mixed_sizes:
-                        if shapes[s] is None:
-                            shapes[s] = frame.shape
-                        if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-                            raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
-                                             % (s, shapes[s], frame.shape, frame.dtype))
-                    elif shape is None:
-                        shape = frame.shape
-                    if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
-                        raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
-                                         "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
-                    proc = since[s] % self.skip_frames == 0
+                        batch, off, hw = pl.pack_frames([f for _, f in procs])
+                    else:
+                        batch = np.ascontiguousarray(np.stack([f for _, f in procs], 0))
+                    if dev is None or dev.nbytes < batch.nbytes:
+                        dev = _lib.DeviceBuffer(batch.nbytes)
+                    _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
+                    if mixed_sizes:
+                        outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
+                    else:
+                        outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
+                out, k = [], 0
+                for s, frame, proc in items:
                     if proc:
-                        since[s] = 0
-                    since[s] += 1
-                    n_proc += proc
-                    items.append((s, frame, proc))
-            procs = [(s, f) for s, f, p in items if p]
-            outs = []
-            if procs:
-                if mixed_sizes:
-                    batch, off, hw = pl.pack_frames([f for _, f in procs])
-                else:
-                    batch = np.ascontiguousarray(np.stack([f for _, f in procs], 0))
-                if dev is None or dev.nbytes < batch.nbytes:
-                    dev = _lib.DeviceBuffer(batch.nbytes)
-                _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
-                if mixed_sizes:
-                    outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
-                else:
-                    outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
-            out, k = [], 0
-            for s, frame, proc in items:
-                if proc:
-                    o = outs[k]
-                    k += 1
-                    hold[s] = None if o is None else (o if len(o) else [])
-                out.append((s, self._render(frame, hold[s], show_fps), hold[s], []))
-            if out:
-                yield out
+                        o = outs[k]
+                        k += 1
+                        hold[s] = None if o is None else (o if len(o) else [])
+                    out.append((s, self._render(frame, hold[s], show_fps), hold[s], []))
+                if out:
+                    yield out
+        finally:
+            self._streams_pipe = None                    # the generator ended, was closed or raised
+
+    def _live_streams_pipe(self, who):
+        pipe = getattr(self, "_streams_pipe", None)
+        if pipe is None:
+            raise ValueError("VideoDetector.%s is valid between the yields of a running detect_streams generator only" % who)
+        return pipe
+
+    def search_streams(self, queries, top_k=5, max_dist=None, confirmed_only=True):
+        """Watch-list query against the live tracks of every stream of the running detect_streams generator, between two of its
+        yields (ValueError outside): per query a list of (stream_index, track_id, dist), MultiStreamPipeline.search."""
+        return self._live_streams_pipe("search_streams").search(queries, top_k=top_k, max_dist=max_dist, confirmed_only=confirmed_only)
+
+    def link_stream_track(self, stream, track_id, exclude_stream=None, top_k=5, max_dist=None, confirmed_only=True):
+        """Hand-over between the streams of the running detect_streams generator, between two of its yields (ValueError outside):
+        the tracks nearest to live track track_id of stream `stream`, MultiStreamPipeline.link."""
+        return self._live_streams_pipe("link_stream_track").link(stream, track_id, exclude_stream=exclude_stream, top_k=top_k,
+                                                                 max_dist=max_dist, confirmed_only=confirmed_only)
 
     @staticmethod
     def _source_len(video_path):

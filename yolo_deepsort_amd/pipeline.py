@@ -102,6 +102,21 @@ class Pipeline:
         return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step_host(
             self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, batch, out, self.cap, counts))
 
+    def _search_trackers(self):
+        return getattr(self, "deepsorts", None) or [self.ds]
+
+    def search(self, queries, top_k=5, max_dist=None, confirmed_only=True):
+        """search.gallery_search over this pipeline's trackers (stream = the stream index of the pipeline; 0 for a single-stream one):
+        per query a list of (stream, track_id, dist).  Between steps only; queries: float32 [Q,512] or (device_pointer, Q)."""
+        from . import search
+        return search.gallery_search(self._search_trackers(), queries, top_k=top_k, max_dist=max_dist, confirmed_only=confirmed_only)
+
+    def link(self, stream, track_id, exclude_stream=None, top_k=5, max_dist=None, confirmed_only=True):
+        """search.link_track over this pipeline's trackers: the tracks nearest to live track track_id of stream `stream`."""
+        from . import search
+        return search.link_track(self._search_trackers(), stream, track_id, exclude_stream=exclude_stream, top_k=top_k, max_dist=max_dist,
+                                 confirmed_only=confirmed_only)
+
     def set_frame_order(self, bgr):
         """bgr=True: the frames handed to step / step_host are B, G, R as a decoder delivers them (read in place, no reversed copy)."""
         _lib.check(_lib.load().yds_pipeline_set_frame_order(self._h, 1 if bgr else 0))
