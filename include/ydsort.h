@@ -31,6 +31,7 @@ typedef struct yds_net yds_net;     /* Darknet detector      (yolo3/models/model
 typedef struct yds_reid yds_reid;   /* ReID extractor        (deep_sort/deep/feature_extractor.py) */
 typedef struct yds_trk yds_trk;     /* DeepSORT tracker      (deep_sort/sort/tracker.py:8-176)      */
 typedef struct yds_pipe yds_pipe;   /* detect+ReID+associate (yolo3/detect/video_detect.py:134-157) */
+typedef struct yds_act yds_act;     /* per-stream orbit caches + action predicates (action/action_Identify.py:4-47) */
 typedef struct yds_comm yds_comm;   /* RCCL communicator of the stream-sharded multi-GPU run (no reference counterpart) */
 
 /* ---- runtime -------------------------------------------------------------------------- */
@@ -463,6 +464,57 @@ int yds_conv_run(int variant, int n, int h, int w, int cin, int cout, int ksize,
 int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
                       const int *view, const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc,
                       float sentinel, float *y_nchw, float *y2_nchw);
+
+/* ---- action identification on the device ----------------------------------------------------------------------
+ * yds_actions_create  <- ActionIdentify(actions, max_age, max_size) (action/action_Identify.py:4-13), one orbit cache (:8, a dict
+ *                        in insertion order) per stream, all in HBM.  Action a is kind[a] with class_id[a] and param[a][2] (double):
+ *                        YDS_ACT_TAKEOFF / _LANDING / _GLIDE: delta = (dx, dy) (action/actions.py:24-50, 52-78, 80-105),
+ *                        YDS_ACT_FAST_CROSSING: speed in param[a][0] (actions.py:107-134), YDS_ACT_BREAK_INTO: timeout in
+ *                        param[a][0] (actions.py:136-150).  An entry holds what Orbit holds (action/orbit.py:5-25): track id, class id
+ *                        (last column of the row that registered it), age, and a ring of max_size foot points
+ *                        (x1 + (x2 - x1) / 2, y2) (orbit.py:16-20) with their times.  1 <= max_size <= YDS_ACT_MAX_SIZE, at most
+ *                        YDS_ACT_MAX_ACTIONS actions.
+ * yds_actions_reset   <- a fresh cache (ActionIdentify.clone(), action_Identify.py:12-13) for one stream, or all of them (-1).
+ * yds_actions_update  <- ActionIdentify.update (action_Identify.py:15-47) for n_frames frames in ONE launch and one
+ *                        synchronisation.  Frame f belongs to stream stream_of[f] and holds rows [first[f], first[f + 1]) of
+ *                        rows6_host (x1, y1, x2, y2, track id, class: DeepSort.update's rows); row_time[r] replaces the
+ *                        time.time() of Orbit.update (orbit.py:22-25) for row r.  One workgroup per stream that has frames walks
+ *                        them in the order given (a stream's frames are in time order); a stream without frames is untouched.
+ *                        Per frame: a row whose id is cached appends its foot point and time and sets age 0 (:19-22), an unknown
+ *                        id is registered in row order with no point (:23-25), every other entry ages and is dropped at
+ *                        age >= max_age, the rest keeping their order (:27-34); then every entry with age 0, in cache order, is
+ *                        tested by every action in list order (:36-46).  out4_host rows = frame, track id, class id, action index;
+ *                        frames in the order given.  All arithmetic is double in the reference's operation order, so the rows EQUAL
+ *                        the host module's; the one difference: two sightings with the same time make FastCrossing divide by
+ *                        zero, which raises in Python and follows IEEE here (x / 0 = inf passes, 0 / 0 fails).  An id twice in
+ *                        one frame is refused; more than cap rows is an error naming the count (the caches have advanced).
+ * yds_actions_get_orbits <- the cache of one stream in insertion order: ids, ages, len(orbit.deque) (tests, debugging).
+ * yds_actions_set_timing / _last_us: measurement aid - HIP events around the launch; device time of the last one in us. */
+enum { YDS_ACT_TAKEOFF = 0, YDS_ACT_LANDING = 1, YDS_ACT_GLIDE = 2, YDS_ACT_FAST_CROSSING = 3, YDS_ACT_BREAK_INTO = 4 };
+#define YDS_ACT_MAX_SIZE 16
+#define YDS_ACT_MAX_ACTIONS 32
+yds_act *yds_actions_create(int n_streams, const int32_t *kind, const int32_t *class_id, const double *param, int n_actions, int max_age,
+                            int max_size);
+void yds_actions_destroy(yds_act *);
+int yds_actions_reset(yds_act *, int stream);
+int yds_actions_update(yds_act *, const int32_t *rows6_host, const int32_t *first, const int32_t *stream_of, const double *row_time,
+                       int n_frames, int32_t *out4_host, int cap, int *n_out);
+int yds_actions_get_orbits(yds_act *, int stream, int32_t *ids, int32_t *ages, int32_t *lens, int cap, int *n);
+int yds_actions_set_timing(yds_act *, int on);
+int yds_actions_last_us(yds_act *, float *us);
+/* The action stage inside a pipeline step (video_detect.py:151-152: action_id.update(detections) on the tracker's rows).
+ * yds_pipeline_set_actions: with a handle of at least as many streams as the pipeline, every step adds ONE launch behind the last
+ *   association round, ahead of the step's one synchronisation; it reads each frame's row count and rows from the tracker's result
+ *   block where the association kernels stored them.  A frame the tracker was not called for (counts = -1, video_detect.py:137) is
+ *   not seen: nothing ages, nothing is emitted; a frame with zero rows ages every orbit of its stream.  NULL switches the stage off;
+ *   without it a step runs the launches it always ran.  Refused while a look-ahead pass is in flight.
+ * yds_pipeline_set_frame_times: times of the frames of the NEXT step (n = its frame count), every row of a frame carrying its
+ *   frame's time; without it frame k (from 0) of a stream since the pipeline was made carries k / 25.0.
+ * yds_pipeline_last_actions: the action rows of the last step (frame of the step, track id, class id, action index), already on
+ *   the host: no device work. */
+int yds_pipeline_set_actions(yds_pipe *, yds_act *);
+int yds_pipeline_set_frame_times(yds_pipe *, const double *t_host, int n);
+int yds_pipeline_last_actions(yds_pipe *, int32_t *out4_host, int cap, int *n_out);
 
 /* ---- multi-GPU exchange step ------------------------------------------------------
  * The reference is single-GPU; what shards is the video stream: every stream owns a tracker (DeepSort.clone(),

@@ -157,6 +157,16 @@ SIGNATURES = {
     "yds_gallery_link": (_I, [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
     "yds_tracker_get_gallery": (_I, [_P, _I, _P, _I, _P]),
     "yds_tracker_get_slots": (_I, [_P, _P, _I]),
+    "yds_actions_create": (_P, [_I, _P, _P, _P, _I, _I, _I]),
+    "yds_actions_destroy": (None, [_P]),
+    "yds_actions_reset": (_I, [_P, _I]),
+    "yds_actions_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "yds_actions_get_orbits": (_I, [_P, _I, _P, _P, _P, _I, _P]),
+    "yds_actions_set_timing": (_I, [_P, _I]),
+    "yds_actions_last_us": (_I, [_P, _P]),
+    "yds_pipeline_set_actions": (_I, [_P, _P]),
+    "yds_pipeline_set_frame_times": (_I, [_P, _P, _I]),
+    "yds_pipeline_last_actions": (_I, [_P, _P, _I, _P]),
     "yds_gallery_search_bench": (_I, [_P, _I, _P, _I, _I, _F, _I, _I, _P]),
 }
 

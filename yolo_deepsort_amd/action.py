@@ -2,7 +2,9 @@
 
 Host-side consumer of the hot path's output (reference action/action_Identify.py:4-47,
 action/orbit.py:5-25, action/actions.py:24-150).  Pure Python, stateful and
-wall-clock dependent like the reference; kept so that ``video_deepsort.py`` imports and runs.
+wall-clock dependent like the reference; kept so that ``video_deepsort.py`` imports and runs.  Explicit timestamps
+(``update(..., timestamps)``) replace the clock where the caller knows the frames' times, and ``DeviceActionIdentify`` runs the
+same stage for many streams with the orbit caches in HBM (csrc/actions.hip), equal to this module fed the same rows and times.
 
 Every motion action below answers one question about a track's recent foot points: did EVERY
 consecutive step satisfy a predicate (the reference's flag loop reduces to exactly that: the
@@ -28,10 +30,11 @@ class Orbit:
     def _center_point(bbox):
         return bbox[0] + (bbox[2] - bbox[0]) / 2, bbox[3]
 
-    def update(self, detection):
+    def update(self, detection, timestamp=None):
+        """``timestamp=None`` reads the wall clock like the reference; a number is the sighting's time instead."""
         self.age = 0
         self.deque.append(self._center_point(detection[:4]))
-        self.timestamps.append(time.time())
+        self.timestamps.append(time.time() if timestamp is None else timestamp)
 
 
 class Action:
@@ -112,15 +115,22 @@ class ActionIdentify:
     def clone(self):
         return ActionIdentify(self.actions, self.max_age, self.max_size)
 
-    def update(self, detections):
+    def to_device(self, n_streams=1):
+        """The same actions and settings with the orbit caches of ``n_streams`` streams in HBM (``DeviceActionIdentify``)."""
+        return DeviceActionIdentify(self.actions, self.max_age, self.max_size, n_streams)
+
+    def update(self, detections, timestamps=None):
+        """``timestamps``: None (the wall clock at every ``Orbit.update``, like the reference), one number for the frame, or a
+        sequence with one number per row; used for rows whose id is already cached (a first sighting stores no time)."""
         if detections is None:
             return None
+        per_row = timestamps is not None and hasattr(timestamps, "__len__")
         seen = set()
-        for det in detections:
+        for k, det in enumerate(detections):
             tid = det[4]
             seen.add(tid)
             if tid in self.cache:
-                self.cache[tid].update(det)
+                self.cache[tid].update(det, timestamps[k] if per_row else timestamps)
             else:                                   # first sighting only registers the track
                 self.cache[tid] = Orbit(self.max_size, tid, det[-1])
         for tid in [t for t in self.cache if t not in seen]:
@@ -129,3 +139,153 @@ class ActionIdentify:
                 del self.cache[tid]
         return [(tid, o.class_id, a.name) for tid, o in self.cache.items() if o.age == 0
                 for a in self.actions if a.confirm(o)]
+
+
+# ---- the same stage with the orbit caches in HBM (csrc/actions.hip) ---------------------------------------------------------------
+_KINDS = ((TakeOff, 0), (Landing, 1), (Glide, 2), (FastCrossing, 3), (BreakInto, 4))     # YDS_ACT_* of include/ydsort.h
+MAX_SIZE_DEVICE = 16            # YDS_ACT_MAX_SIZE
+MAX_ACTIONS_DEVICE = 32         # YDS_ACT_MAX_ACTIONS
+
+
+def pack_actions(actions, max_age=30, max_size=4):
+    """(kind int32 [A], class_id int32 [A], param float64 [A, 2], names) of a list of built-in actions as yds_actions_create takes
+    them.  Raises ValueError naming ``action_id`` for anything the device cannot run: an action that is not exactly one of the five
+    built-in classes (a subclass may override ``confirm``), a class id that is no integer, max_size outside [1, 16]."""
+    import numpy as np
+    try:
+        actions = list(actions)
+    except TypeError:
+        raise ValueError(f"action_id: actions must be a list of built-in actions, got {type(actions).__name__}") from None
+    if int(max_size) != max_size or not 1 <= max_size <= MAX_SIZE_DEVICE:
+        raise ValueError(f"action_id: max_size {max_size!r} outside [1, {MAX_SIZE_DEVICE}] (the device's orbit ring)")
+    if int(max_age) != max_age:
+        raise ValueError(f"action_id: max_age {max_age!r} is not an integer")
+    if len(actions) > MAX_ACTIONS_DEVICE:
+        raise ValueError(f"action_id: {len(actions)} actions, the device runs at most {MAX_ACTIONS_DEVICE}")
+    kind = np.zeros(len(actions), np.int32)
+    cls = np.zeros(len(actions), np.int32)
+    param = np.zeros((len(actions), 2), np.float64)
+    names = []
+    for k, a in enumerate(actions):
+        code = dict(_KINDS).get(type(a))
+        if code is None:
+            raise ValueError(f"action_id: action {k} ({type(a).__name__}) is not one of the built-in actions "
+                             "TakeOff, Landing, Glide, FastCrossing, BreakInto; the device runs only those")
+        try:
+            integral = int(a.class_id) == a.class_id and abs(int(a.class_id)) < 2 ** 31
+        except (TypeError, ValueError):
+            integral = False
+        if not integral:
+            raise ValueError(f"action_id: action {k} ({a.name}) has class_id {a.class_id!r}, not an integer")
+        kind[k], cls[k] = code, int(a.class_id)
+        try:
+            if code <= 2:
+                param[k] = float(a.delta[0]), float(a.delta[1])
+            else:
+                param[k, 0] = float(a.speed if code == 3 else a.timeout)
+        except (TypeError, ValueError, IndexError):
+            raise ValueError(f"action_id: action {k} ({a.name}) has parameters the device cannot take") from None
+        names.append(a.name)
+    return kind, cls, param, names
+
+
+class DeviceActionIdentify:
+    """``ActionIdentify`` for ``n_streams`` video streams with every orbit cache in HBM: one launch advances the caches of all
+    streams over the frames of a call, and the rows equal the host module's fed the same rows and times (double arithmetic in the
+    same operation order).  One difference: two sightings with the same time make FastCrossing divide by zero - Python raises,
+    the device follows IEEE (x / 0 = inf passes, 0 / 0 fails)."""
+
+    def __init__(self, actions, max_age=30, max_size=4, n_streams=1):
+        self.kind, self.class_ids, self.param, self.names = pack_actions(actions, max_age, max_size)
+        self.actions = list(actions)
+        self.max_age, self.max_size, self.n_streams = int(max_age), int(max_size), int(n_streams)
+        self._h = None
+
+    def clone(self, n_streams=None):
+        return DeviceActionIdentify(self.actions, self.max_age, self.max_size, self.n_streams if n_streams is None else n_streams)
+
+    @property
+    def handle(self):
+        """The yds_act handle, created on first use (the descriptor itself needs no GPU)."""
+        if self._h is None:
+            from . import _lib
+            _lib.init()
+            self._h = _lib.check_ptr(_lib.load().yds_actions_create(
+                self.n_streams, _lib.ptr(self.kind), _lib.ptr(self.class_ids), _lib.ptr(self.param), len(self.names), self.max_age,
+                self.max_size))
+        return self._h
+
+    def name_rows(self, rows4):
+        return [(int(r[1]), int(r[2]), self.names[int(r[3])]) for r in rows4]
+
+    def update_batch(self, frames_rows, stream_of, times):
+        """Frames in the order given (a stream's frames in time order), frame f of stream ``stream_of[f]``; ``times[f]`` is a number
+        for the frame or a sequence with one number per row.  Returns one ``[(track_id, class_id, name), ...]`` per frame."""
+        import ctypes as C
+        import numpy as np
+        from . import _lib
+        n = len(frames_rows)
+        rows = [np.asarray(r, dtype=np.int64).reshape(-1, 6) if len(r) else np.zeros((0, 6), np.int64) for r in frames_rows]
+        first = np.zeros(n + 1, np.int32)
+        first[1:] = np.cumsum([len(r) for r in rows])
+        rows6 = np.ascontiguousarray(np.concatenate(rows) if n else np.zeros((0, 6)), dtype=np.int32)
+        row_time = np.zeros(int(first[-1]), np.float64)
+        for f in range(n):
+            row_time[first[f]:first[f + 1]] = np.asarray(times[f], np.float64)
+        sof = np.ascontiguousarray(stream_of, dtype=np.int32)
+        cap = max(int(first[-1]) * len(self.names), 1)
+        out = np.zeros((cap, 4), np.int32)
+        m = C.c_int(0)
+        _lib.check(_lib.load().yds_actions_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(row_time), n,
+                                                  _lib.ptr(out), cap, C.byref(m)))
+        per = [[] for _ in range(n)]
+        for r in out[:m.value]:
+            per[int(r[0])].append((int(r[1]), int(r[2]), self.names[int(r[3])]))
+        return per
+
+    def update(self, stream, rows, timestamp):
+        """One frame of one stream: ``ActionIdentify.update(rows, timestamp)`` (None in, None out, nothing touched)."""
+        if rows is None:
+            return None
+        return self.update_batch([rows], [stream], [timestamp])[0]
+
+    def orbits(self, stream=0):
+        """[(track_id, age, points held), ...] of one stream's cache in insertion order."""
+        import ctypes as C
+        import numpy as np
+        from . import _lib
+        n = C.c_int(0)
+        lib = _lib.load()
+        _lib.check(lib.yds_actions_get_orbits(self.handle, int(stream), None, None, None, 1 << 30, C.byref(n)))
+        ids, ages, lens = (np.zeros(max(n.value, 1), np.int32) for _ in range(3))
+        _lib.check(lib.yds_actions_get_orbits(self.handle, int(stream), _lib.ptr(ids), _lib.ptr(ages), _lib.ptr(lens), len(ids), C.byref(n)))
+        return [(int(ids[k]), int(ages[k]), int(lens[k])) for k in range(n.value)]
+
+    def reset(self, stream=None):
+        from . import _lib
+        if self._h is not None:
+            _lib.check(_lib.load().yds_actions_reset(self._h, -1 if stream is None else int(stream)))
+
+    def close(self):
+        if self._h is not None:
+            from . import _lib
+            _lib.load().yds_actions_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def as_device_actions(action_id, n_streams):
+    """``action_id`` (an ActionIdentify or a DeviceActionIdentify) as a DeviceActionIdentify of at least ``n_streams`` streams;
+    ValueError naming ``action_id`` for anything else."""
+    if isinstance(action_id, DeviceActionIdentify):
+        if action_id.n_streams < n_streams:
+            raise ValueError(f"action_id: a DeviceActionIdentify of {action_id.n_streams} streams for {n_streams} streams")
+        return action_id
+    if isinstance(action_id, ActionIdentify):
+        return action_id.to_device(n_streams)
+    raise ValueError(f"action_id must be an ActionIdentify or a DeviceActionIdentify, got {type(action_id).__name__}")

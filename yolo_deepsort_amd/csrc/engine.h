@@ -268,6 +268,30 @@ public:
     bool front_fused_last = false;              // the last forward() began with the fused front end
 };
 
+// --------------------------------------------------------------------------------------------- actions
+// Implemented in actions.hip: the orbit caches of ActionIdentify (action/action_Identify.py:4-47) for S streams in HBM, advanced over
+// the frames of a call by ONE launch (a workgroup per stream walks that stream's frames in order).
+// One frame as the kernel reads it: rows6 [n][6] int32 = x1, y1, x2, y2, track id, class - device-readable (HBM, or pinned host
+// memory such as a tracker result block).  n_rows_p: where the kernel finds the row count (a result header written earlier on the
+// same stream), nullptr = n_rows is the count; with n_rows_p, n_rows is the host's upper bound.  Every row carries time t unless
+// row_time (device-readable [n]) names one per row.  tag: what the frame's action rows carry in column 0.
+struct ActFrame {
+    const int32_t *rows6;
+    const int32_t *n_rows_p;
+    int n_rows, stream, tag;
+    double t;
+    const double *row_time;
+};
+struct ActionsIface {
+    virtual ~ActionsIface() {}
+    virtual int streams() const = 0;
+    // asynchronous on s: grows the tables, one launch; the action rows land in pinned host memory
+    virtual void enqueue(const ActFrame *fr, int n, hipStream_t s) = 0;
+    // after the caller synchronised s: the rows of that call, frame k = rows [first[k], first[k + 1]) of rows4 (tag, id, class, action)
+    virtual void collect() = 0;
+    std::vector<int32_t> rows4, first;
+};
+
 // --------------------------------------------------------------------------------------------- tracker
 // Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
 // What a reader of a tracker's appearance galleries needs (gallery_search.hip): device pointers into the tracker's own state, valid
@@ -294,6 +318,9 @@ struct TrackerIface {
 // its tracker is not called for that frame (counts[b] = -1).
 struct TrackerGroupIface {
     virtual ~TrackerGroupIface() {}
+    // the action stage of the NEXT step_batch (nullptr: none): one more launch behind the last round, before the step's one
+    // synchronisation; frame_times[b] = time of frame b of that step.  Cleared by the step.
+    virtual void set_actions(ActionsIface *act, const double *frame_times) = 0;
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
     // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)
@@ -307,3 +334,4 @@ TrackerGroupIface *make_tracker_group();
 struct yds_net { yds::Darknet *d; };
 struct yds_reid { yds::ReidNet *r; };
 struct yds_trk { yds::TrackerIface *t; };
+struct yds_act { yds::ActionsIface *a; };

@@ -568,8 +568,24 @@ public:
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
         if (!multi) stream_of.assign(batch, 0);
+        // the action stage (set_actions): frame b carries the caller's time for it, else its stream's frame count / 25
+        std::vector<double> times;
+        if ((int)frames_seen.size() < (int)trks.size()) frames_seen.resize(trks.size(), 0);
+        const std::vector<double> given = std::move(next_times);      // (they name this step's frames, whatever becomes of it)
+        next_times.clear();
+        if (actions) {
+            if (!given.empty() && (int)given.size() != batch)
+                fail("pipeline: %zu frame times for a step of %d frames (yds_pipeline_set_frame_times)", given.size(), batch);
+            times.resize(batch);
+            std::vector<int64_t> seen(frames_seen);
+            for (int b = 0; b < batch; ++b) times[b] = given.empty() ? (double)seen[stream_of[b]]++ / 25.0 : given[b];
+            group->set_actions(actions, times.data());
+        }
+        for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
+        last_actions.clear();
         group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
                           cur.payload.data(), skip.data(), out6, cap, counts);
+        if (actions) last_actions = actions->rows4;
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
@@ -586,6 +602,18 @@ public:
                 fail("pipeline: frame %d belongs to stream %d outside [0,%zu)", b, stream_of_frame[b], trks.size());
         stream_of.assign(stream_of_frame, stream_of_frame + n);
     }
+
+    // ---- the action stage (yds_pipeline_set_actions; video_detect.py:151-152 for every stream of a step) ----
+    void set_actions(ActionsIface *a) {
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_actions while a look-ahead pass is in flight (consume it with a step first)");
+        if (a && a->streams() < (int)trks.size()) fail("pipeline: an action handle of %d streams for a pipeline of %zu", a->streams(), trks.size());
+        actions = a;
+        last_actions.clear();
+    }
+    ActionsIface *actions = nullptr;
+    std::vector<double> next_times;               // set_frame_times: times of the next step's frames (empty: count / 25)
+    std::vector<int64_t> frames_seen;             // frames every stream was handed since the pipeline was made
+    std::vector<int32_t> last_actions;            // action rows of the last step [m][4]: frame of the step, id, class, action
 
     Darknet *net;
     ReidNet *reid;
@@ -733,6 +761,26 @@ int yds_pipeline_set_windows(yds_pipe *p, int win_w, int win_h, double overlap) 
 int yds_pipeline_set_stream_windows(yds_pipe *p, int stream, int win_w, int win_h, double overlap) {
     YDS_API_BEGIN
     p->p->set_stream_windows(stream, win_w, win_h, overlap);
+    YDS_API_END
+}
+int yds_pipeline_set_actions(yds_pipe *p, yds_act *a) {
+    YDS_API_BEGIN
+    p->p->set_actions(a ? a->a : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_set_frame_times(yds_pipe *p, const double *t_host, int n) {
+    YDS_API_BEGIN
+    if (n < 0 || (n && !t_host)) yds::fail("pipeline: %d frame times", n);
+    p->p->next_times.assign(t_host, t_host + n);
+    YDS_API_END
+}
+int yds_pipeline_last_actions(yds_pipe *p, int32_t *out4_host, int cap, int *n_out) {
+    YDS_API_BEGIN
+    const std::vector<int32_t> &r = p->p->last_actions;
+    const int m = (int)(r.size() / 4);
+    if (n_out) *n_out = m;
+    if (m > cap) yds::fail("pipeline: %d action rows exceed the caller's capacity %d", m, cap);
+    if (m) memcpy(out4_host, r.data(), r.size() * sizeof(int32_t));
     YDS_API_END
 }
 int yds_pipeline_slot_pred(yds_pipe *p, float *pred_host, size_t cap_rows, size_t *n_rows) {

@@ -507,6 +507,7 @@ public:
         if (stream) (void)hipStreamDestroy(stream);
     }
     void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
+    void set_actions(ActionsIface *a, const double *frame_times) override { act = a; act_times_in = frame_times; }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
                     const float *payload, const char *skip, int32_t *out6, int cap, int32_t *counts) override {
@@ -515,6 +516,7 @@ public:
         std::vector<Tracker::FrameIn> fr;
         std::vector<int32_t *> outs;
         std::vector<int> caps, cnt, which, st;
+        struct ClearActions { TrackerGroup &g; ~ClearActions() { g.act = nullptr; g.act_times_in = nullptr; g.act_tag.clear(); g.act_time.clear(); } } clear_actions{*this};
         for (int b = 0; b < n; ++b) {
             if (stream_of[b] < 0 || stream_of[b] >= S) fail("tracker group: frame %d names stream %d outside [0,%d)", b, stream_of[b], S);
             if (skip && skip[b]) { counts[b] = -1; continue; }       // detector returned None: that tracker is not called for this frame
@@ -524,8 +526,10 @@ public:
             caps.push_back(cap);
             which.push_back(b);
             st.push_back(stream_of[b]);
+            if (act) { act_tag.push_back(b); act_time.push_back(act_times_in ? act_times_in[b] : 0.0); }
         }
         cnt.assign(fr.size(), 0);
+        if (act && fr.empty()) { act->enqueue(nullptr, 0, stream); act->collect(); }      // (no frame ran: the stage reports no rows)
         if (!fr.empty()) step_group(t.data(), S, fr.data(), st.data(), (int)fr.size(), outs.data(), caps.data(), cnt.data());
         for (size_t k = 0; k < which.size(); ++k) counts[which[k]] = cnt[k];
     }
@@ -667,8 +671,20 @@ public:
             if (maxD) hipLaunchKernelGGL(trk_back_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
         }
         YDS_HIP(hipGetLastError());
+        // ---- the action stage (set_actions): one launch over the step's frames, reading each frame's row count and rows where the
+        //      association kernels stored them (the pinned result blocks), its own rows behind the same synchronisation
+        const bool with_actions = act && (int)act_tag.size() == n;
+        if (with_actions) {
+            std::vector<ActFrame> af(n);
+            for (int i = 0; i < n; ++i) {
+                const int *r = res_host + res_off[i];
+                af[i] = ActFrame{r + M_COUNT, r + M_NOUT, T_ub[i] + frames[i].D, stream_of[i], act_tag[i], act_time[i], nullptr};
+            }
+            act->enqueue(af.data(), n, stream);
+        }
         // (the result blocks are in host memory already: a device-to-host copy command would queue behind frame uploads)
         YDS_HIP(hipStreamSynchronize(stream));
+        if (with_actions) act->collect();
         for (int i = 0; i < n; ++i) {
             const int *r = res_host + res_off[i];
             const int m = r[M_NOUT];
@@ -681,6 +697,10 @@ public:
     }
 
     hipStream_t stream = nullptr;
+    ActionsIface *act = nullptr;                  // the action stage of the step being run (set_actions; step_batch clears it)
+    const double *act_times_in = nullptr;
+    std::vector<int> act_tag;                     // per frame that runs: its index in the step, its time
+    std::vector<double> act_time;
     DevBuf<int> in_dev;
     DevBuf<float> feats_n, feats_stage;
     int *res_host = nullptr, *in_host = nullptr;

@@ -602,9 +602,17 @@ class VideoDetector:
         to frames_per_stream processed frames from every stream that is still running and runs them through ONE MultiStreamPipeline
         step: one detector pass, one ReID pass, all trackers advanced in the same launches.  A stream that ends drops out, the
         others go on.  frames_per_stream=None: 1 when any source is live (_is_live), else max(1, AUTO_BATCH // len(sources)).
-        Limits: every frame of every source must have one uint8 [h, w, 3] shape, and action_id is not supported - both raise
-        ValueError; the tracker must be this package's DeepSort around its Extractor, with nms_max_overlap=1.  A detector with
-        win_size runs the pipeline in window mode (MultiStreamPipeline(win_size=...)).
+        Limits: every frame of every source must have one uint8 [h, w, 3] shape (ValueError otherwise); the tracker must be this
+        package's DeepSort around its Extractor, with nms_max_overlap=1.  A detector with win_size runs the pipeline in window mode
+        (MultiStreamPipeline(win_size=...)).
+        action_id (an action.ActionIdentify of the five built-in actions, or an action.DeviceActionIdentify) runs ON THE DEVICE
+        inside the step (MultiStreamPipeline.set_actions): every stream gets a fresh orbit cache - the device form of
+        action_id.clone() per stream - and the fourth item carries that stream's actions with the semantics of
+        video_detect.py:134-159: [] on a skipped frame, the previous value on a frame whose detector returned None, else the
+        frame's list.  Frame times are explicit, not the wall clock at the update: time.time() at read for a live source
+        (_is_live), else the stream's frame index (skipped frames counted) over the source's frame rate (25 where it has none).
+        An action_id the device cannot run (a custom Action subclass, a non-integral class id, max_size > 16) raises ValueError
+        naming action_id.  detect() keeps calling the host module with the wall clock, as the reference does.
         mixed_sizes=True lifts the first limit: every stream has its own uint8 [h, w, 3] shape (1080p and 720p cameras in one step,
         MultiStreamPipeline.step_mixed) and keeps it - a stream that changes its shape midway raises ValueError naming the stream;
         window mode takes frames of one size, so win_size with mixed_sizes=True raises ValueError.
@@ -617,8 +625,14 @@ class VideoDetector:
         stream_win_sizes = pl.check_stream_win_sizes(len(sources), self.image_detector.win_size, stream_win_sizes, "VideoDetector.detect_streams")
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
-        if self.action_id is not None:
-            raise ValueError("VideoDetector.detect_streams does not support action_id")
+        actions_dev = None
+        if self.action_id is not None:                   # (ValueError naming action_id for what the device cannot run)
+            from .action import DeviceActionIdentify, as_device_actions
+            actions_dev = as_device_actions(self.action_id, 0)
+            if isinstance(self.action_id, DeviceActionIdentify):     # fresh caches, one per stream: never the caller's own
+                actions_dev = actions_dev.clone(max(len(sources), 1))
+            else:
+                actions_dev = self.action_id.to_device(max(len(sources), 1))
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -638,6 +652,10 @@ class VideoDetector:
         its = [iter(self._frames(src)) for src in sources]
         since, hold, alive = [0] * S, [None] * S, [True] * S
         shape, dev = None, None
+        if actions_dev is not None:
+            pipe.set_actions(actions_dev)
+        live = [self._is_live(src) for src in sources]
+        n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
         try:
             while any(alive):
@@ -649,6 +667,10 @@ class VideoDetector:
                         if frame is None:
                             alive[s] = False
                             break
+                        if rate[s] is None:                 # (_frames has just opened the source)
+                            rate[s] = float(getattr(self, "_source_fps", None) or 25.0)
+                        t_frame = time.time() if live[s] else n_read[s] / rate[s]
+                        n_read[s] += 1
                         frame = np.asarray(frame)
                         if mixed_sizes:
                             if shapes[s] is None:
@@ -666,8 +688,8 @@ class VideoDetector:
                             since[s] = 0
                         since[s] += 1
                         n_proc += proc
-                        items.append((s, frame, proc))
-                procs = [(s, f) for s, f, p in items if p]
+                        items.append((s, frame, proc, t_frame))
+                procs = [(s, f) for s, f, p, _ in items if p]
                 outs = []
                 if procs:
                     if mixed_sizes:
@@ -677,17 +699,24 @@ class VideoDetector:
                     if dev is None or dev.nbytes < batch.nbytes:
                         dev = _lib.DeviceBuffer(batch.nbytes)
                     _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
+                    if actions_dev is not None:
+                        pipe.set_frame_times([t for _, _, p, t in items if p])
                     if mixed_sizes:
                         outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
                     else:
                         outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
+                step_acts = pipe.last_actions() if actions_dev is not None and procs else None
                 out, k = [], 0
-                for s, frame, proc in items:
+                for s, frame, proc, _ in items:
                     if proc:
                         o = outs[k]
+                        if step_acts is not None and step_acts[k] is not None:   # a detector-None frame leaves the previous value
+                            acts[s] = step_acts[k]
                         k += 1
                         hold[s] = None if o is None else (o if len(o) else [])
-                    out.append((s, self._render(frame, hold[s], show_fps), hold[s], []))
+                    else:
+                        acts[s] = []                        # video_detect.py:158-159
+                    out.append((s, self._render(frame, hold[s], show_fps), hold[s], acts[s]))
                 if out:
                     yield out
         finally:

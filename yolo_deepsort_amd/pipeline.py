@@ -92,6 +92,7 @@ class Pipeline:
         if select_next is not None:
             _lib.check(_lib.load().yds_pipeline_set_next_injection(self._h, int(select_next)))
         _lib.check(call(_lib.ptr(out), _lib.ptr(counts)))
+        self._last_counts = counts
         return [None if counts[b] < 0 else out[b, :counts[b]].copy() for b in range(n)]
 
     def step_host(self, frames, next_frames=None, select_next=None):
@@ -101,6 +102,40 @@ class Pipeline:
         batch, h, w = _check_host_frames(frames, next_frames)
         return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step_host(
             self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, batch, out, self.cap, counts))
+
+    def set_actions(self, action_id=None):
+        """The action stage of every following step (video_detect.py:151-152 on the device): ``action_id`` is an
+        action.ActionIdentify (its actions and settings go to the device, fresh orbit caches, one per stream) or an
+        action.DeviceActionIdentify of at least as many streams as the pipeline (its caches are used as they are); None switches
+        the stage off.  A step then adds one launch behind the association and ``last_actions()`` holds its rows; the step's own
+        return value does not change.  ValueError naming action_id for anything the device cannot run; refused (YdsError) while
+        a look-ahead pass is in flight."""
+        from .action import as_device_actions
+        dev = None if action_id is None else as_device_actions(action_id, getattr(self, "n_streams", 1))
+        _lib.check(_lib.load().yds_pipeline_set_actions(self._h, None if dev is None else dev.handle))
+        self.actions = dev                                  # (keeps the handle alive while the pipeline names it)
+
+    def set_frame_times(self, times):
+        """Times (seconds) of the frames of the NEXT step, one per frame: every row of a frame carries its frame's time in the
+        action stage.  Without it a stream's k-th frame since the pipeline was made carries k / 25."""
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        _lib.check(_lib.load().yds_pipeline_set_frame_times(self._h, _lib.ptr(t), int(t.size)))
+
+    def last_actions(self):
+        """Per frame of the last step: ``[(track_id, class_id, name), ...]`` as ActionIdentify.update returns it, ``[]`` where
+        nothing fired, None where the frame's rows were None (the stage did not see that frame).  Already on the host."""
+        dev, counts = getattr(self, "actions", None), getattr(self, "_last_counts", None)
+        if dev is None or counts is None:
+            return None
+        n = C.c_int(0)
+        lib = _lib.load()
+        lib.yds_pipeline_last_actions(self._h, None, 0, C.byref(n))      # (asks for the count; refuses to copy when it is not 0)
+        rows = np.zeros((max(n.value, 1), 4), np.int32)
+        _lib.check(lib.yds_pipeline_last_actions(self._h, _lib.ptr(rows), len(rows), C.byref(n)))
+        per = [None if counts[b] < 0 else [] for b in range(len(counts))]
+        for r in rows[:n.value]:
+            per[int(r[0])].append((int(r[1]), int(r[2]), dev.names[int(r[3])]))
+        return per
 
     def _search_trackers(self):
         return getattr(self, "deepsorts", None) or [self.ds]
