@@ -464,6 +464,15 @@ int yds_conv_run(int variant, int n, int h, int w, int cin, int cout, int ksize,
 int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
                       const int *view, const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc,
                       float sentinel, float *y_nchw, float *y2_nchw);
+/* yds_conv_run_view in HALF MODE (yds_darknet_set_half): single-term fp16 operands (the hi halves only), conv math f16x3 required.
+ * fmt_x / fmt_y: 0 = the format yds_conv_run_view picks (H16 where channels, ld and offset are multiples of 32, else fp32), 2 = F16,
+ * the 2-byte activations fp16(x * 2^-8) (round to nearest even, saturating).  The residual and the second output of a merged launch
+ * take the output's format.  view (NULL: dense tensors, y_nchw [n,cout,ho,wo]) and every returned buffer are in CHANNELS as above;
+ * an F16 slice needs channels, ld and offset to be multiples of 64.  Refuses, with a message, a variant that is no timing candidate
+ * of the layer with these single-term arguments ("the planner never launches") and slices that do not fit. */
+int yds_conv_run_half(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
+                      const int *view, int fmt_x, int fmt_y, const float *x_nhwc, const float *w_okkc, const float *bias,
+                      const float *res_nhwc, float sentinel, float *y_nchw, float *y2_nchw);
 
 /* ---- action identification on the device ----------------------------------------------------------------------
  * yds_actions_create  <- ActionIdentify(actions, max_age, max_size) (action/action_Identify.py:4-13), one orbit cache (:8, a dict

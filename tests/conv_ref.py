@@ -5,7 +5,11 @@ The bound.  The f16x3 kernels compute x*w as  x_hi*w_hi + x_hi*w_lo + x_lo*w_hi 
 instead: x_hat = float16(x / 256) * 256 (the hi half of an activation) or w_hat = float16(w).  `mutant_bound` evaluates both of
 these wrong convolutions in float64; the smaller of their errors, `mut`, is what a broken variant would show at the very least.
 The tests hold every kernel to mut / 16 and the reference arithmetic itself (CPU, test_conv_ref.py) to mut / 64, so the bound comes
-from the reference computation alone, never from what a kernel returns."""
+from the reference computation alone, never from what a kernel returns.
+
+Half mode (Darknet.half(): ConvArgs::terms == 1, optionally 2-byte F16 tensors) is held by `HalfRef`: there the kernels see the hi
+halves ONLY, so the float64 result of the rounded operands is the truth and the two mutants are the kernels that read an operand's lo
+half as well.  An F16 output adds one rounding to nearest: half a spacing of that format (`ulp16`) on top of mut / 16."""
 import functools
 
 import numpy as np
@@ -131,14 +135,18 @@ def emulated_f16x3(x, w, bias, k, s, act, res, res_mode):
     return epilogue(pre, bias, act, res, res_mode).astype(F32)
 
 
-def fp32_conv(x, w, bias, k, s, act, res, res_mode):
-    """the convolution evaluated in fp32 on the CPU (torch), epilogue in float64, result rounded to fp32"""
+def fp32_pre(x, w, k, s):
+    """the bare convolution evaluated in fp32 on the CPU (torch) -> NHWC float64"""
     import torch
     cout, cin = w.shape[0], x.shape[3]
-    xt = torch.from_numpy(np.ascontiguousarray(x)).permute(0, 3, 1, 2)
-    wt = torch.from_numpy(np.ascontiguousarray(w.reshape(cout, k, k, cin))).permute(0, 3, 1, 2).contiguous()
-    pre = torch.nn.functional.conv2d(xt, wt, None, stride=s, padding=(k - 1) // 2).permute(0, 2, 3, 1).numpy().astype(np.float64)
-    return epilogue(pre, bias, act, res, res_mode).astype(F32)
+    xt = torch.from_numpy(np.array(x, F32, order="C")).permute(0, 3, 1, 2)           # (a copy: the operands are read-only)
+    wt = torch.from_numpy(np.array(w, F32, order="C").reshape(cout, k, k, cin)).permute(0, 3, 1, 2).contiguous()
+    return torch.nn.functional.conv2d(xt, wt, None, stride=s, padding=(k - 1) // 2).permute(0, 2, 3, 1).numpy().astype(np.float64)
+
+
+def fp32_conv(x, w, bias, k, s, act, res, res_mode):
+    """the convolution evaluated in fp32 on the CPU (torch), epilogue in float64, result rounded to fp32"""
+    return epilogue(fp32_pre(x, w, k, s), bias, act, res, res_mode).astype(F32)
 
 
 def make_case(rng, n, h, wd, cin, cout, k, s, res_mode):
@@ -176,6 +184,105 @@ def case_refs():
     """Ref of every entry of CASES (one RandomState(17) stream in list order); computed once per process, read-only"""
     rng = np.random.RandomState(17)
     return tuple(Ref(c, *make_case(rng, *c[:7], c[8])) for c in CASES)
+
+
+# ---- half mode ----------------------------------------------------------------------------------------------------------------------
+FMT_AUTO, FMT_F16 = 0, 2      # yds_conv_run_half's fmt_x / fmt_y: the planner's format (H16 where it fits, else fp32) / 2-byte activations
+HALF_CASES = [  # n, h, w, cin, cout, k, s, act, res_mode: edges of the 64-channel K steps that CASES does not reach
+    (4, 5, 5, 64, 64, 1, 1, "linear", 0),             # one 64-channel K step: prologue equals epilogue
+    (2, 13, 13, 192, 64, 1, 1, "leaky", 0),           # an odd number of K steps against the double buffer
+    (1, 19, 19, 192, 128, 3, 1, "mish", 1),           # an odd number of K steps, 3x3 with a fused shortcut
+    (2, 9, 7, 128, 192, 3, 1, "relu", 2),             # two K steps per tap, three filter tiles of 64, residual before the activation
+    (3, 11, 6, 96, 128, 1, 1, "leaky", 1),            # 32-channel K steps (Cin % 64 != 0) with an F16 output and residual
+]
+
+
+def ulp16(v):
+    """spacing of the F16 activation format at v: that of fp16 at |v| / 256 (subnormals included), times 256"""
+    a = np.abs(np.asarray(v, np.float64)) / 256
+    e = np.floor(np.log2(np.maximum(a, 2.0 ** -14)))
+    return 2.0 ** (np.maximum(e, -14) - 10) * 256
+
+
+def trunc16(v):
+    """v rounded TOWARD ZERO to the F16 format (the store a test must catch), float64"""
+    v = np.asarray(v, np.float64)
+    h = (v / 256).astype(np.float16)
+    over = np.abs(h.astype(np.float64)) > np.abs(v / 256)
+    h = np.where(over, np.nextafter(h, np.float16(0)), h)
+    return h.astype(np.float64) * 256
+
+
+class _Arith:
+    """what _Worst.hold reads: one arithmetic's float64 result, its scale, the mutant bound and the fp32 CPU error"""
+
+    def __init__(self, case, want, mutants, fp32):
+        self.case, self.want = case, want
+        self.scale = float(np.abs(want).max())
+        self.mut = float(min(np.abs(m - want).max() for m in mutants))
+        self.fp32 = fp32
+        self.err_fp32 = float(np.abs(fp32 - want).max())
+        self._half_ulp = None
+        want.setflags(write=False)
+
+    def err(self, got):
+        return float(np.abs(got - self.want).max())
+
+    def err_f16(self, got):
+        """an F16 output's error beyond the format's own rounding: max(|got - want| - ulp16(want) / 2), never below 0"""
+        if self._half_ulp is None:
+            self._half_ulp = ulp16(self.want) / 2
+        return float(np.maximum(np.abs(got - self.want) - self._half_ulp, 0).max())
+
+
+class HalfRef:
+    """One case in half mode.  The kernels see x_hat(x), w_hat(w), the fp32 bias, and x_hat(res) where the output (hence the
+    residual) is F16, else res.  Per output format fy (FMT_AUTO / FMT_F16), `half(fy)` is the single-term arithmetic: `want` =
+    conv_ref on those operands in float64, `mut` = the smaller error against it of the two kernels that are wrong in the half-mode
+    sense, conv_ref(x, w_hat(w)) and conv_ref(x_hat(x), w).  `full(fy)` is the default three-term arithmetic on the same tensors
+    (Ref's want and mutants, residual as above) for the kernels that ignore `terms`.  The four bare convolutions are computed once."""
+
+    def __init__(self, case, x, w, bias, res):
+        n, h, wd, cin, cout, k, s, act, res_mode = case
+        self.case, self.x, self.w, self.bias, self.res = case, x, w, bias, res
+        self.k, self.s, self.act, self.res_mode = k, s, ACT[act], res_mode
+        xh, wh = x_hat(x), w_hat(w)
+        self._pre = {"hh": conv_pre(xh, wh, k, s), "xh": conv_pre(x, wh, k, s), "hw": conv_pre(xh, w, k, s), "xw": conv_pre(x, w, k, s),
+                     "hh32": fp32_pre(xh, wh, k, s), "xw32": fp32_pre(x, w, k, s)}
+        self._arith = {}
+        for a in (x, w, bias, res):
+            if a is not None:
+                a.setflags(write=False)
+
+    def _get(self, kind, fy):
+        fy = fy if self.res_mode else FMT_AUTO                 # without a residual the output format changes no operand
+        if (kind, fy) not in self._arith:
+            res = x_hat(self.res) if (self.res_mode and fy == FMT_F16) else self.res
+            epi = lambda key: epilogue(self._pre[key], self.bias, self.act, res, self.res_mode)
+            if kind == "half":
+                self._arith[kind, fy] = _Arith(self.case, epi("hh"), (epi("xh"), epi("hw")), epi("hh32").astype(F32).astype(np.float64))
+            else:
+                self._arith[kind, fy] = _Arith(self.case, epi("xw"), (epi("xh"), epi("hw")), epi("xw32").astype(F32).astype(np.float64))
+        return self._arith[kind, fy]
+
+    def half(self, fy=FMT_AUTO):
+        return self._get("half", fy)
+
+    def full(self, fy=FMT_AUTO):
+        return self._get("full", fy)
+
+
+def half_formats(case):
+    """the (fmt_x, fmt_y) pairs a case runs in: F16 needs 64-channel granularity on that side"""
+    cin, cout = case[3], case[4]
+    return [(fx, fy) for fx in (FMT_AUTO, FMT_F16) for fy in (FMT_AUTO, FMT_F16) if (fx == FMT_AUTO or cin % 64 == 0) and (fy == FMT_AUTO or cout % 64 == 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def half_refs():
+    """HalfRef of every entry of CASES (on case_refs()' operands) and of HALF_CASES (RandomState(53)); once per process, read-only"""
+    rng = np.random.RandomState(53)
+    return tuple(HalfRef(r.case, r.x, r.w, r.bias, r.res) for r in case_refs()) + tuple(HalfRef(c, *make_case(rng, *c[:7], c[8])) for c in HALF_CASES)
 
 
 # ---- host restatement of plan_tile_map (csrc/conv_common.h): the XCD grid with the smallest per-K-step footprint ---------------------

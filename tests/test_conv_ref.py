@@ -42,3 +42,53 @@ def test_plan_tile_map_restatement():
         assert R.plan_tile_map(2 * 40 * 40, 608, BM, BN)[3:] == (rm, rn), (BM, BN)
     assert R.plan_tile_map(2 * 28 * 28, 1248, 128, 128)[3:] == (4, 5)
     assert R.plan_tile_map(2 * 28 * 28, 1248, 128, 256)[4] == 3
+
+
+# ---- half mode ------------------------------------------------------------------------------------------------------------------------
+_HALF = list(R.CASES) + list(R.HALF_CASES)
+
+
+@pytest.mark.parametrize("i", range(len(_HALF)), ids=lambda i: "x".join(str(v) for v in _HALF[i]))
+def test_half_reference_arithmetic_separates_from_the_mutants(i):
+    """Half mode (conv_ref.HalfRef), both output formats: a plain fp32 CPU convolution of the ROUNDED operands sits at or below
+    mut / 64 of the float64 result, and rounded to nearest into the F16 format it exceeds half a spacing by no more than mut / 64 -
+    a factor 4 inside the mut / 16 of tests/test_gpu_conv_half.py.  The bound bites: the same fp32 result rounded TOWARD ZERO breaks
+    the F16 bound on every case whose |want| reaches 1 (a truncating store is one fp16 ulp, which no network test sees)."""
+    hr = R.half_refs()[i]
+    assert hr.case == _HALF[i]
+    cout = hr.case[4]
+    for fy in (R.FMT_AUTO, R.FMT_F16) if cout % 64 == 0 else (R.FMT_AUTO,):
+        r = hr.half(fy)
+        assert r.mut > 0 and np.isfinite(r.mut)
+        assert r.mut < 1e-3 * r.scale
+        stored = R.x_hat(r.fp32)                                  # the F16 store: fp16(v / 256) * 256, to nearest even
+        over = r.err_f16(stored)
+        print(f"{hr.case} fmt_y {fy}: scale {r.scale:.2f} mut {r.mut:.2e} | fp32 conv mut/{r.mut / max(r.err_fp32, 1e-30):.0f}, "
+              f"as F16 beyond half an ulp mut/{r.mut / max(over, 1e-30):.0f}")
+        assert r.err_fp32 <= r.mut / 64, (hr.case, fy, r.err_fp32, r.mut)
+        assert over <= r.mut / 64, (hr.case, fy, over, r.mut)
+        assert np.array_equal(R.x_hat(stored), stored)
+        if fy == R.FMT_F16 and r.scale >= 1:
+            cut = R.trunc16(r.fp32)
+            assert np.array_equal(R.x_hat(cut), cut) and (np.abs(cut) <= np.abs(r.fp32)).all()
+            assert r.err_f16(cut) > r.mut / 16, (hr.case, "a truncating store passes the bound", r.err_f16(cut), r.mut)
+        # the three-term arithmetic on the same tensors (the kernels that ignore `terms`): Ref's quantities, residual as stored
+        f = hr.full(fy)
+        assert 0 < f.mut < 1e-3 * f.scale and f.err_fp32 <= f.mut / 64, (hr.case, fy, f.err_fp32, f.mut)
+
+
+def test_half_operands_and_ulp16():
+    """ulp16 is the spacing of fp16(v / 256) * 256 (subnormals included), trunc16 rounds toward zero onto that grid, and the half
+    reference of a case without a residual does not depend on the output format."""
+    v = np.array([0.0, 1e-9, 2.0 ** -6, 2.0 ** -6 * 1.5, 0.999, 1.0, 1.5, 255.9, 256.0, 3e3, -7.3, 60000.0 * 256])
+    h = (np.abs(v) / 256).astype(np.float16)
+    assert np.array_equal(R.ulp16(v), np.spacing(h).astype(np.float64) * 256)
+    rng = np.random.RandomState(7)
+    x = rng.standard_normal(4096) * 5
+    t, n = R.trunc16(x), R.x_hat(x)
+    assert (np.abs(t) <= np.abs(x)).all() and (np.abs(x - t) < R.ulp16(x)).all() and np.array_equal(R.x_hat(t), t)
+    assert (np.abs(x - n) <= R.ulp16(x) / 2).all() and (t != n).mean() > 0.3
+    hr = R.half_refs()[0]
+    assert hr.res_mode == 0 and hr.half(R.FMT_F16) is hr.half(R.FMT_AUTO)
+    assert R.half_formats((1, 1, 1, 64, 64, 3, 1, "relu", 2)) == [(0, 0), (0, 2), (2, 0), (2, 2)]
+    assert R.half_formats((1, 1, 1, 96, 160, 3, 2, "mish", 0)) == [(0, 0)] and R.half_formats((1, 1, 1, 32, 64, 3, 1, "mish", 0)) == [(0, 0), (0, 2)]

@@ -426,7 +426,9 @@ def test_half_mode_single_term_fp16():
     not apply.  What it meets against the fp32 oracle through all 75 layers of yolov3 at 608x608 (random weights, so the
     box sizes exp(t) * anchor span many decades and are compared relatively): objectness / class probabilities within
     1.5e-2 absolute, box centres within 0.5 px, box sizes within 5 % (median error two orders below these bounds; the maxima
-    over 1.9 M values move between 6.6e-3 and 8.1e-3 with the summation order, i.e. with the tile shapes the planner picks)."""
+    over 1.9 M values move between 6.6e-3 and 8.1e-3 with the summation order, i.e. with the tile shapes the planner picks).
+    These are network bars; the bound of each single-term kernel on its own, against a float64 convolution of the rounded operands,
+    is in tests/test_gpu_conv_half.py."""
     cfg = cfgs.cfg_text("yolov3", 608, 608)
     net, ref = _nets(cfg, (608, 608), 0, -2.0, batch_max=2)
     x = np.random.RandomState(7).uniform(0, 1, (2, 3, 608, 608)).astype(F32)
@@ -471,7 +473,9 @@ def test_half_mode_yolov4_two_byte_activations():
     launches (two F16 outputs of one kernel), route copies / concatenations of F16 slices, the SPP max-pools on F16 tensors, the Mish
     single-term stem and first block.  Held against the default arithmetic of the same network (itself held to the reference's
     goldens above) with the fp16-class bounds of the yolov3 test; every intermediate tensor that is fp16 in HBM is read back and
-    compared with the default mode's tensor at fp16 resolution of the layer's scale."""
+    compared with the default mode's tensor at fp16 resolution of the layer's scale.  Kernel by kernel - every conv variant on F16
+    views and merged launches within mut / 16 of a float64 reference, the pools, routes and upsamples on F16 tensors bit for bit -
+    this arithmetic is held by tests/test_gpu_conv_half.py."""
     from yolo_deepsort_amd.models import Darknet
     cfg = cfgs.cfg_text("yolov4", 416, 416)
     blob = synth.darknet_weights_blob(cfg, 5, -2.0)
@@ -519,7 +523,8 @@ def test_half_mode_yolov4_two_byte_activations():
 def test_half_mode_tiny_nets_mixed_formats(name):
     """Darknet.half() on the tiny networks: narrow first layers (16 / 32 channels: they keep the 4-byte record), max-pool chains
     incl. the zero-padded k2 s1 pool, grouped routes (yolov4-tiny: 32-channel halves of a 64-channel tensor - not 64-channel granular,
-    so those buffers stay H16 next to fp16 neighbours).  Same bounds as the big networks, against the default arithmetic."""
+    so those buffers stay H16 next to fp16 neighbours).  Same bounds as the big networks, against the default arithmetic; the
+    per-kernel bounds, and these networks' pools and grouped routes on F16 tensors bit for bit, are in tests/test_gpu_conv_half.py."""
     from yolo_deepsort_amd.models import Darknet
     cfg = cfgs.cfg_text(name, 416, 416)
     net = Darknet(None, img_size=(416, 416), batch_max=2, cfg_text=cfg)

@@ -1,17 +1,29 @@
 // Single convolutions through the C ABI: yds_conv_bench times one layer shape on synthetic data, yds_conv_run runs one tile variant
 // on the caller's tensors (the kernel tests).  Both build the same case - input and residual (pre-split where the kernels take them
 // that way), weights, output - and differ in what they do with the launch.  yds_conv_run_view is yds_conv_run on channel slices of
-// wider buffers and on the merged launch of two convolutions.
+// wider buffers and on the merged launch of two convolutions; yds_conv_run_half is that entry in half mode (single-term fp16 operands,
+// optionally 2-byte F16 tensors).
 #include "conv_common.h"
 #include "conv_weights.h"
 #include "h16.h"
 
 #include <algorithm>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 namespace yds {
 namespace {
+
+// fp16(x * 2^-8) as f16_store4 encodes it: round to nearest even, an overflow saturates at +-65504 (infinities and NaNs pass)
+uint16_t f16_bits_saturating(float x) {
+    const float xs = x * H16_A_SCALE;
+    _Float16 h = (_Float16)xs;                                     // round to nearest even
+    if (isfinite(xs) && !isfinite((float)h)) h = (_Float16)(xs > 0.f ? 65504.f : -65504.f);
+    uint16_t b;
+    memcpy(&b, &h, 2);
+    return b;
+}
 
 // Where a case's tensors sit inside wider buffers (yds_conv_run_view): channel offsets and row lengths of the input, output and
 // residual views, and the second output of a merged launch.  Without one the tensors are dense.
@@ -25,8 +37,19 @@ struct ConvCase {
     DevBuf<float> x, y, y2, res, raw[4];
     View y_whole, y2_whole;                  // the buffers a.y / a.y2 are slices of
 
-    // host fp32 NHWC (ld = c) -> the device tensor v.p in v's format
+    // host fp32 NHWC (ld = c) -> the device tensor v.p in v's format.  An F16 tensor is packed on the host: 2 bytes per channel, so its
+    // row is v.c / 2 float slots (v.ld is set to that); hipMalloc aligns the pointer far beyond the 128 bytes the kernels ask for.
     static void put(View &v, const float *host, DevBuf<float> &raw, DevBuf<float> &packed) {
+        if (v.fmt == FMT_F16) {
+            const size_t count = v.pixels() * v.c;
+            std::vector<uint16_t> h(count);
+            for (size_t i = 0; i < count; ++i) h[i] = f16_bits_saturating(host[i]);
+            v.ld = fmt_slots(FMT_F16, v.c);
+            packed.upload(reinterpret_cast<const float *>(h.data()), count / 2);
+            YDS_HIP(hipDeviceSynchronize());                           // (the host vector dies with this call)
+            v.p = packed.p;
+            return;
+        }
         raw.upload(host, v.pixels() * v.c);
         v.p = raw.p;
         if (v.fmt != FMT_H16) return;
@@ -34,19 +57,20 @@ struct ConvCase {
         v.p = packed.p;
         launch_pack_h16(raw.p, v, nullptr);
     }
-    // channels [off, off + c) of the ld-channel tensor `whole`
+    // channels [off, off + c) of the tensor `whole` (F16: the offset in float slots is half the channel offset)
     static View slice(const View &whole, int off, int c) {
         View v = whole;
-        v.p = whole.p + off;
+        v.p = whole.p + fmt_slots(whole.fmt, off);
         v.c = c;
         return v;
     }
     static bool h16_ok(int c, int ld, int off) { return c % 32 == 0 && ld % 32 == 0 && off % 32 == 0; }
     // x_nhwc [n, h, w, x_ld], w_okkc [cout][ksize * ksize * cin], bias [cout], res_nhwc [n, ho, wo, r_ld] (read when res_mode): host;
     // vw == nullptr: dense tensors (x_ld = cin, r_ld = cout), the output row padded to a multiple of 4.  With views the output
-    // buffers start out filled with `sentinel`.
+    // buffers start out filled with `sentinel`.  fmt_x / fmt_y (yds_conv_run_half): 0 = the format picked here (H16 where h16_ok, else
+    // fp32), FMT_F16 = 2-byte activations; the residual and the second output of a merged launch follow fmt_y.
     ConvCase(int n, int h, int w, int cin, int cout, int ksize, int stride, int act, const float *x_nhwc, const float *w_okkc, const float *bias,
-             const float *res_nhwc, int res_mode, const CaseViews *vw = nullptr, float sentinel = 0.f) {
+             const float *res_nhwc, int res_mode, const CaseViews *vw = nullptr, float sentinel = 0.f, int fmt_x = 0, int fmt_y = 0) {
         const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
         const CaseViews d = vw ? *vw : CaseViews{cin, 0, (cout + 3) / 4 * 4, 0, cout, 0, 0, 0, 0};
         const bool f16 = conv_math() == MATH_F16X3;
@@ -55,8 +79,8 @@ struct ConvCase {
         cw.upload_korder(w_okkc, bias, nullptr);
         cw.fill(a);
         a.act = act;
-        View x_whole{nullptr, n, h, w, d.x_ld, d.x_ld, (f16 && h16_ok(cin, d.x_ld, d.x_off)) ? FMT_H16 : FMT_F32};
-        const int yfmt = (f16 && h16_ok(c1, d.y_ld, d.y_off) && h16_ok(c2, d.y2_ld, d.y2_off)) ? FMT_H16 : FMT_F32;
+        View x_whole{nullptr, n, h, w, d.x_ld, d.x_ld, fmt_x == FMT_F16 ? FMT_F16 : (f16 && h16_ok(cin, d.x_ld, d.x_off)) ? FMT_H16 : FMT_F32};
+        const int yfmt = fmt_y == FMT_F16 ? FMT_F16 : (f16 && h16_ok(c1, d.y_ld, d.y_off) && h16_ok(c2, d.y2_ld, d.y2_off)) ? FMT_H16 : FMT_F32;
         y_whole = View{nullptr, n, ho, wo, d.y_ld, d.y_ld, yfmt};
         put(x_whole, x_nhwc, raw[0], x);
         a.x = slice(x_whole, d.x_off, cin);
@@ -70,7 +94,8 @@ struct ConvCase {
                 a.n_split = c1;
             }
         } else {
-            y.alloc(y_whole.pixels() * d.y_ld);
+            y_whole.ld = fmt_slots(yfmt, d.y_ld);
+            y.alloc(y_whole.pixels() * y_whole.ld);
             y_whole.p = y.p;
         }
         a.y = slice(y_whole, d.y_off, cout);                     // (merged: both filter counts, the first output's pointer and stride)
@@ -164,6 +189,43 @@ int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int k
     if (!planned) fail("conv_run_view: the planner never launches %s on this layer%s", conv_variant_name(id), merged ? " (merged launch)" : "");
     launch_conv(c.a, nullptr, variant);
     nhwc_to_host(c.y_whole, y_nchw, nullptr);
+    if (merged) nhwc_to_host(c.y2_whole, y2_nchw, nullptr);
+    YDS_API_END
+}
+
+int yds_conv_run_half(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode, const int *view,
+                      int fmt_x, int fmt_y, const float *x_nhwc, const float *w_okkc, const float *bias, const float *res_nhwc, float sentinel,
+                      float *y_nchw, float *y2_nchw) {
+    YDS_API_BEGIN
+    using namespace yds;
+    if (conv_math() != MATH_F16X3) fail("conv_run_half: half mode needs conv math f16x3");
+    if ((fmt_x != 0 && fmt_x != FMT_F16) || (fmt_y != 0 && fmt_y != FMT_F16)) fail("conv_run_half: fmt_x / fmt_y are 0 (the planner's format) or %d (F16)", (int)FMT_F16);
+    if (n < 1 || h < 1 || w < 1 || cin < 4 || cout < 1 || cin % 4) fail("conv_run_half: bad shape (input channels must be a multiple of 4)");
+    if (res_mode && !res_nhwc) fail("conv_run_half: residual mode %d without a residual tensor", res_mode);
+    const CaseViews v = view ? CaseViews{view[0], view[1], view[2], view[3], view[4], view[5], view[6], view[7], view[8]}
+                             : CaseViews{cin, 0, (cout + 3) / 4 * 4, 0, cout, 0, 0, 0, 0};
+    const bool merged = v.n_split > 0;
+    const int c1 = merged ? v.n_split : cout;
+    if (merged && (v.n_split >= cout || res_mode || !y2_nchw)) fail("conv_run_half: a merged launch needs 0 < n_split < cout, a second output and no residual");
+    // slices in CHANNELS: multiples of 4, of 64 in an F16 tensor (whose rows and offsets the kernels see in float slots, half of these)
+    auto inside = [](int off, int c, int ld, int g) { return off >= 0 && c > 0 && off % g == 0 && ld % g == 0 && c % g == 0 && off + c <= ld; };
+    const int gx = fmt_x == FMT_F16 ? 64 : 4, gy = fmt_y == FMT_F16 ? 64 : 4;
+    if (!inside(v.x_off, cin, v.x_ld, gx)) fail("conv_run_half: input slice [%d, %d) does not fit %d channels (multiples of %d)", v.x_off, v.x_off + cin, v.x_ld, gx);
+    if (view || fmt_y == FMT_F16) {
+        if (!inside(v.y_off, c1, v.y_ld, gy)) fail("conv_run_half: output slice [%d, %d) does not fit %d channels (multiples of %d)", v.y_off, v.y_off + c1, v.y_ld, gy);
+        if (merged && !inside(v.y2_off, cout - c1, v.y2_ld, gy)) fail("conv_run_half: second output slice [%d, %d) does not fit %d channels (multiples of %d)", v.y2_off, v.y2_off + cout - c1, v.y2_ld, gy);
+        if (res_mode && !inside(v.r_off, cout, v.r_ld, gy)) fail("conv_run_half: residual slice [%d, %d) does not fit %d channels (multiples of %d)", v.r_off, v.r_off + cout, v.r_ld, gy);
+    }
+    ConvCase c(n, h, w, cin, cout, ksize, stride, act, x_nhwc, w_okkc, bias, res_nhwc, res_mode, view ? &v : nullptr, sentinel, fmt_x, fmt_y);
+    c.a.terms = 1;
+    // only what the planner launches on such a half-mode layer: a timing candidate (split-K is never one, and its rule excludes half mode)
+    const int id = variant & kVariantMask;
+    if (variant < 0 || id >= kConvVariants) fail("conv_run_half: no such variant %d", variant);
+    const std::vector<int> cand = conv_candidates(c.a);
+    if (std::find(cand.begin(), cand.end(), id) == cand.end())
+        fail("conv_run_half: the planner never launches %s on this layer in half mode%s", conv_variant_name(id), merged ? " (merged launch)" : "");
+    launch_conv(c.a, nullptr, variant);
+    nhwc_to_host(view ? c.y_whole : c.a.y, y_nchw, nullptr);
     if (merged) nhwc_to_host(c.y2_whole, y2_nchw, nullptr);
     YDS_API_END
 }

@@ -111,7 +111,8 @@ class Darknet:
 
     def half(self):
         """img_detect.py:49-50 ``model.half()``: the convolutions switch to single-term fp16 operands (fp32 accumulation);
-        fp16-class accuracy, see tests/test_gpu_detector.py::test_half_mode for the measured tolerance."""
+        fp16-class accuracy, see tests/test_gpu_detector.py::test_half_mode for the measured tolerance and
+        tests/test_gpu_conv_half.py for the bound of every single-term kernel on its own."""
         _lib.check(_lib.load().yds_darknet_set_half(self._h, 1))
         self._half = True
         return self
