@@ -32,7 +32,8 @@ typedef struct yds_reid yds_reid;   /* ReID extractor        (deep_sort/deep/fea
 typedef struct yds_trk yds_trk;     /* DeepSORT tracker      (deep_sort/sort/tracker.py:8-176)      */
 typedef struct yds_pipe yds_pipe;   /* detect+ReID+associate (yolo3/detect/video_detect.py:134-157) */
 typedef struct yds_act yds_act;     /* per-stream orbit caches + action predicates (action/action_Identify.py:4-47) */
-typedef struct yds_comm yds_comm;   /* RCCL communicator of the stream-sharded multi-GPU run (no reference counterpart) */
+typedef struct yds_ident yds_ident; /* cross-camera identity map over S trackers (no reference counterpart)                  */
+typedef struct yds_comm yds_comm;  /* RCCL communicator of the stream-sharded multi-GPU run (no reference counterpart) */
 
 /* ---- runtime -------------------------------------------------------------------------- */
 /* Binds the PROCESS to one GPU (hipSetDevice + gfx950 check).  Multi-GPU runs are one process per GPU (bench.py /
@@ -524,6 +525,65 @@ int yds_actions_last_us(yds_act *, float *us);
 int yds_pipeline_set_actions(yds_pipe *, yds_act *);
 int yds_pipeline_set_frame_times(yds_pipe *, const double *t_host, int n);
 int yds_pipeline_last_actions(yds_pipe *, int32_t *out4_host, int cap, int *n_out);
+
+/* ---- cross-camera identities: one global id per person, kept on the device ---------------------------------------------------------
+ * No reference counterpart (the reference tracks one camera); tests/identity_ref.py restates the rules below in numpy / scipy.
+ * An identity map is bound to an ordered list of S trackers (stream = index), all with the cosine metric and a finite nn_budget.  It
+ * keeps, in HBM, a pair (owner track id, global id) per stream and gallery slot.  A live track HOLDS global id g iff its slot's pair
+ * names the track's own id and g > 0: a slot reused by a later track never inherits an identity, and no call here writes tracker
+ * state.  Global ids come from ONE counter over all streams, start at 1 and are never reused; an id stays with its track for the
+ * track's life.  Only live holders are matched against: when the last holder of an id has died (its max_age coasting frames
+ * included) the id is never offered again - galleries of departed identities are not kept.
+ * yds_identity_create   <- trks[n_streams]; max_dist < 0 = the first tracker's matching threshold; max_rows = the most gallery rows
+ *                          one update admits (4096 = the search's query limit), at least the largest nn_budget so that one track
+ *                          always fits.  Refused with a message, before any launch: no / NULL trackers, a tracker given twice, a
+ *                          euclidean tracker, nn_budget=None, max_rows below the largest budget.
+ * yds_identity_reset    <- forgets every pair and the host copy; the counter keeps counting.
+ * yds_identity_update   <- stand-alone form; WHEN: between steps, as for yds_gallery_search (a tracker's step has returned, none is
+ *                          running).  Over the trackers' state as it stands:
+ *                          1. NEW tracks = the Confirmed live tracks that hold no id, in (stream, track-list) order; CANDIDATES =
+ *                             the Confirmed live tracks that hold one; Tentative tracks take no part.
+ *                          2. ADMISSION: new tracks are admitted as a prefix of that order while their gallery rows sum to at most
+ *                             max_rows; the first that does not fit ends admission, nothing is skipped past it.  The rest are
+ *                             DEFERRED: they hold no id, are no candidates, and the next update takes them up.
+ *                          3. d(n, g) = min over the stored rows q of n and r of g of 1 - <r, q>: yds_gallery_link's arithmetic and
+ *                             bits (rows are stored normalised; each value an exact-fp32 512-term chain).
+ *                          4. Streams are resolved in turn, s = 0 .. S-1, for the admitted new tracks of s in track-list order:
+ *                             columns = the global ids held by a live track of another stream (ids handed out earlier in this
+ *                             same update included) and by no live track of s, ascending; cost[n][i] = min of d(n, g) over the
+ *                             holders g of i; then min_cost_matching (deep_sort/sort/linear_assignment.py:51-72): entries >
+ *                             max_dist become max_dist + 1e-5, scipy's assignment and tie-break, a pair whose cost is > max_dist
+ *                             is dropped.  A matched track takes the column's id (LINKED); every other admitted track of s takes
+ *                             the next fresh id, in track-list order.  So no id is held twice inside one camera, and a person
+ *                             confirmed in several cameras in the same step gets a fresh id in the lowest stream and is linked
+ *                             in the others.
+ *                          One small launch collects lists and counts and one synchronisation reads them; only when a track was
+ *                          admitted do gather, distance, reduce and resolve launches run at their exact sizes, with one more
+ *                          synchronisation.  *n_linked / *n_fresh / *n_deferred (each may be NULL): what this update did.
+ * yds_identity_get      <- the live Confirmed tracks of `stream` in track-list order with their global ids, 0 = deferred; served
+ *                          from the host copy of the last update: no device work.  *n = the count; more than cap is an error
+ *                          naming it.
+ * yds_identity_last_links  <- the tracks the last update linked, in (stream, track-list) order, with the fp32 cost of each link.
+ * yds_identity_last_counts <- linked / fresh / deferred of the last update (the in-step form has no other way to report them).
+ * yds_identity_set_timing / _last_us: measurement aid - HIP events around the resolve sequence (gather .. resolve); device time of
+ *                          the last one in us, -1 when the last update launched none (nothing was admitted) or timing is off.
+ * yds_pipeline_set_identities: the stage inside a step, behind the last association round and the action stage: the collect launch
+ *   goes ahead of the step's one synchronisation, so a step in which no track needs an identity adds that one small launch and no
+ *   synchronisation; a step that admits a track runs the resolve sequence behind it and synchronises once more.  The map must have
+ *   been created over the pipeline's own trackers in stream order (else refused); NULL switches the stage off.  Refused while a
+ *   look-ahead pass is in flight.  The map must outlive its use by the pipeline.
+ * yds_pipeline_last_identities: yds_identity_get on the pipeline's map: the state after the last step, from the host copy. */
+yds_ident *yds_identity_create(yds_trk *const *trks, int n_streams, float max_dist, int max_rows);
+void yds_identity_destroy(yds_ident *);
+int yds_identity_reset(yds_ident *);
+int yds_identity_update(yds_ident *, int *n_linked, int *n_fresh, int *n_deferred);
+int yds_identity_get(yds_ident *, int stream, int32_t *track_id, int32_t *global_id, int cap, int *n);
+int yds_identity_last_links(yds_ident *, int32_t *stream, int32_t *track_id, int32_t *global_id, float *cost, int cap, int *n);
+int yds_identity_last_counts(yds_ident *, int *n_linked, int *n_fresh, int *n_deferred);
+int yds_identity_set_timing(yds_ident *, int on);
+int yds_identity_last_us(yds_ident *, float *us);
+int yds_pipeline_set_identities(yds_pipe *, yds_ident *);
+int yds_pipeline_last_identities(yds_pipe *, int stream, int32_t *track_id, int32_t *global_id, int cap, int *n);
 
 /* ---- multi-GPU exchange step ------------------------------------------------------
  * The reference is single-GPU; what shards is the video stream: every stream owns a tracker (DeepSort.clone(),

@@ -169,6 +169,17 @@ SIGNATURES = {
     "yds_pipeline_set_frame_times": (_I, [_P, _P, _I]),
     "yds_pipeline_last_actions": (_I, [_P, _P, _I, _P]),
     "yds_gallery_search_bench": (_I, [_P, _I, _P, _I, _I, _F, _I, _I, _P]),
+    "yds_identity_create": (_P, [_P, _I, _F, _I]),
+    "yds_identity_destroy": (None, [_P]),
+    "yds_identity_reset": (_I, [_P]),
+    "yds_identity_update": (_I, [_P, _P, _P, _P]),
+    "yds_identity_get": (_I, [_P, _I, _P, _P, _I, _P]),
+    "yds_identity_last_links": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "yds_identity_last_counts": (_I, [_P, _P, _P, _P]),
+    "yds_identity_set_timing": (_I, [_P, _I]),
+    "yds_identity_last_us": (_I, [_P, _P]),
+    "yds_pipeline_set_identities": (_I, [_P, _P]),
+    "yds_pipeline_last_identities": (_I, [_P, _I, _P, _P, _I, _P]),
 }
 
 _lib = None

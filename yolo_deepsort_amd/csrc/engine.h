@@ -302,6 +302,10 @@ struct GalleryView {
     const int *slot, *id, *state, *n_feat;
     int budget, n_tracks, metric;
     double max_dist;
+    // for a reader that runs inside a step, before its synchronisation (identity.hip): the live track count where the association
+    // kernels keep it, the number of slots (the most tracks the step can leave) and whether nn_budget is None
+    const int *n_tracks_dev;
+    int capacity, unbounded;
 };
 struct TrackerIface {
     virtual ~TrackerIface() {}
@@ -312,12 +316,29 @@ struct TrackerIface {
                      int32_t *out6_host, int cap) = 0;
     virtual int num_tracks() const = 0;
 };
+// The cross-camera identity map (identity.hip) as the association driver and the pipeline see it.
+struct IdentityIface {
+    virtual ~IdentityIface() {}
+    // the map was made over exactly these trackers, in this order
+    virtual bool bound_to(TrackerIface *const *trk, int S) const = 0;
+    // asynchronous on s: ONE small launch over the trackers' state as the work queued on s leaves it; counts land in pinned host memory
+    virtual void enqueue_collect(hipStream_t s) = 0;
+    // after the caller synchronised s: takes the counts; only when a new track was admitted it launches the resolve sequence on s
+    // and synchronises once more
+    virtual void finish(hipStream_t s) = 0;
+    // the map of the last update, from the host copy: live Confirmed tracks of a stream in track-list order (0 = deferred)
+    virtual void get(int stream, int32_t *track_id, int32_t *global_id, int cap, int *n) const = 0;
+};
+
 // The association driver (tracker.hip TrackerGroup): S trackers (one per video stream; the pipeline of a single stream has S = 1)
 // advanced together through the frames of one batch with ONE host synchronisation.  Frame b belongs to tracker stream_of[b], each
 // tracker's frames in time order; detections of frame b are rows [first[b], first[b+1]) of tlwh / feats_dev / payload; skip[b] != 0:
 // its tracker is not called for that frame (counts[b] = -1).
 struct TrackerGroupIface {
     virtual ~TrackerGroupIface() {}
+    // the identity stage of the NEXT step_batch (nullptr: none): one small launch behind the action stage, ahead of the step's one
+    // synchronisation, and the resolve sequence behind it in the steps that admit a new track.  Cleared by the step.
+    virtual void set_identities(IdentityIface *ident) = 0;
     // the action stage of the NEXT step_batch (nullptr: none): one more launch behind the last round, before the step's one
     // synchronisation; frame_times[b] = time of frame b of that step.  Cleared by the step.
     virtual void set_actions(ActionsIface *act, const double *frame_times) = 0;
@@ -335,3 +356,4 @@ struct yds_net { yds::Darknet *d; };
 struct yds_reid { yds::ReidNet *r; };
 struct yds_trk { yds::TrackerIface *t; };
 struct yds_act { yds::ActionsIface *a; };
+struct yds_ident { yds::IdentityIface *i; };

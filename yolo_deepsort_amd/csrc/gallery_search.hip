@@ -9,19 +9,11 @@
 //   gallery_select_kernel     per query the top_k smallest distances that pass the threshold and the state mask
 // A call reads tracker state and writes none of it.  It runs on a stream of its own, between steps: a tracker's step returns after
 // its own synchronisation, so nothing that writes a gallery is in flight.  One host synchronisation, one device-to-host copy.
-#include "tracker_dev.h"
+#include "gallery_dev.h"
 
 #include <limits.h>
 
 namespace yds {
-
-// One tracker as the kernels see it, in an array like TrkGroupDev: tracks [g0, g0 + n) of the call are its track list.
-struct alignas(16) GalleryDesc {
-    const float *gallery;                         // [slot][budget][EMB], rows normalised
-    const int *slot, *id, *state, *n_feat;        // the tracker's table columns (track-list order)
-    int budget, g0, n, stream;
-};
-static_assert(sizeof(GalleryDesc) % 16 == 0, "the host packs GalleryDesc arrays at a stride of sizeof(GalleryDesc)");
 
 // the tracker that holds track g (n_desc is small: one entry per tracker with tracks); -1 never happens for g < total
 __device__ __forceinline__ int desc_of(const GalleryDesc *desc, int n_desc, int g) {
@@ -30,7 +22,7 @@ __device__ __forceinline__ int desc_of(const GalleryDesc *desc, int n_desc, int 
     return s;
 }
 
-constexpr int SLAB = 32;                          // queries per workgroup = one MFMA tile edge
+constexpr int SLAB = GALLERY_SLAB;                // queries per workgroup = one MFMA tile edge
 constexpr int PF = 16;                            // float4 chunks of a gallery row per register batch (EMB / 8 = 64 chunks per lane)
 constexpr int LDQ = EMB + 4;                      // LDS row stride of the query slab: float4 reads of 32 rows spread over all banks
 
@@ -137,12 +129,6 @@ __global__ void gallery_link_kernel(const float *dist, int n_q, int T, const int
     link[g] = (g == self_g || meta[g] == exclude_stream) ? INFINITY : m;
 }
 
-// fp32 -> unsigned with the same order (negative values included: 1 - dot may come out a few ulps below 0)
-__device__ __forceinline__ unsigned ordered_bits(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // Workgroup q: the candidates of query q - finite distance <= max_dist, state bit set in state_mask (bit 0 Tentative, bit 1
 // Confirmed) - compacted in g order, then min(top_k, candidates) rounds that each take the smallest (distance, g) key above the
 // previous one: ties fall in (stream, track-list) order because g does.  res: n_hits [Q] | stream [Q][k_ld] | id [Q][k_ld] | dist [Q][k_ld].
@@ -192,18 +178,6 @@ __global__ __launch_bounds__(256) void gallery_select_kernel(const float *dist, 
 
 // ============================================================================================ host
 namespace {
-
-template <class T> struct PinBuf {                 // pinned host memory that only grows
-    T *p = nullptr;
-    size_t n = 0;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    void ensure(size_t count) {
-        if (count <= n) return;
-        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-        YDS_HIP(hipHostMalloc((void **)&p, count * sizeof(T)));
-        n = count;
-    }
-};
 
 constexpr int kMaxQueries = 4096;
 

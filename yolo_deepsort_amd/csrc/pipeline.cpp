@@ -583,6 +583,7 @@ public:
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
         last_actions.clear();
+        if (identities) group->set_identities(identities);
         group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
                           cur.payload.data(), skip.data(), out6, cap, counts);
         if (actions) last_actions = actions->rows4;
@@ -610,6 +611,14 @@ public:
         actions = a;
         last_actions.clear();
     }
+    // ---- the identity stage (yds_pipeline_set_identities): global ids over the streams' trackers, updated behind every step ----
+    void set_identities(IdentityIface *i) {
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_identities while a look-ahead pass is in flight (consume it with a step first)");
+        if (i && !i->bound_to(trks.data(), (int)trks.size()))
+            fail("pipeline: the identity map was not created over this pipeline's %zu trackers in stream order", trks.size());
+        identities = i;
+    }
+    IdentityIface *identities = nullptr;
     ActionsIface *actions = nullptr;
     std::vector<double> next_times;               // set_frame_times: times of the next step's frames (empty: count / 25)
     std::vector<int64_t> frames_seen;             // frames every stream was handed since the pipeline was made
@@ -781,6 +790,17 @@ int yds_pipeline_last_actions(yds_pipe *p, int32_t *out4_host, int cap, int *n_o
     if (n_out) *n_out = m;
     if (m > cap) yds::fail("pipeline: %d action rows exceed the caller's capacity %d", m, cap);
     if (m) memcpy(out4_host, r.data(), r.size() * sizeof(int32_t));
+    YDS_API_END
+}
+int yds_pipeline_set_identities(yds_pipe *p, yds_ident *i) {
+    YDS_API_BEGIN
+    p->p->set_identities(i ? i->i : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_last_identities(yds_pipe *p, int stream, int32_t *track_id, int32_t *global_id, int cap, int *n) {
+    YDS_API_BEGIN
+    if (!p->p->identities) yds::fail("pipeline: no identity map is set (yds_pipeline_set_identities)");
+    p->p->identities->get(stream, track_id, global_id, cap, n);
     YDS_API_END
 }
 int yds_pipeline_slot_pred(yds_pipe *p, float *pred_host, size_t cap_rows, size_t *n_rows) {

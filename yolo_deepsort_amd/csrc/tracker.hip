@@ -353,7 +353,7 @@ public:
     int num_tracks() const override { return T_host; }
     GalleryView gallery_view() const override {
         const TrackTable t = table_at(table.p, capacity);
-        return GalleryView{gallery.p, t.slot, t.id, t.state, t.n_feat, budget, T_host, metric, max_dist};
+        return GalleryView{gallery.p, t.slot, t.id, t.state, t.n_feat, budget, T_host, metric, max_dist, meta.p + M_T, capacity, unbounded ? 1 : 0};
     }
 
     static TrackTable table_at(int *base, int cap) {
@@ -508,6 +508,7 @@ public:
     }
     void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
     void set_actions(ActionsIface *a, const double *frame_times) override { act = a; act_times_in = frame_times; }
+    void set_identities(IdentityIface *i) override { ident = i; }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
                     const float *payload, const char *skip, int32_t *out6, int cap, int32_t *counts) override {
@@ -517,6 +518,8 @@ public:
         std::vector<int32_t *> outs;
         std::vector<int> caps, cnt, which, st;
         struct ClearActions { TrackerGroup &g; ~ClearActions() { g.act = nullptr; g.act_times_in = nullptr; g.act_tag.clear(); g.act_time.clear(); } } clear_actions{*this};
+        struct ClearIdentities { TrackerGroup &g; ~ClearIdentities() { g.ident = nullptr; } } clear_identities{*this};
+        if (ident && !ident->bound_to(trk, S)) fail("tracker group: the identity map was not made over this step's trackers in this order");
         for (int b = 0; b < n; ++b) {
             if (stream_of[b] < 0 || stream_of[b] >= S) fail("tracker group: frame %d names stream %d outside [0,%d)", b, stream_of[b], S);
             if (skip && skip[b]) { counts[b] = -1; continue; }       // detector returned None: that tracker is not called for this frame
@@ -530,6 +533,11 @@ public:
         }
         cnt.assign(fr.size(), 0);
         if (act && fr.empty()) { act->enqueue(nullptr, 0, stream); act->collect(); }      // (no frame ran: the stage reports no rows)
+        if (ident && fr.empty()) {                                  // (no frame ran: deferred tracks are still taken up)
+            ident->enqueue_collect(stream);
+            YDS_HIP(hipStreamSynchronize(stream));
+            ident->finish(stream);
+        }
         if (!fr.empty()) step_group(t.data(), S, fr.data(), st.data(), (int)fr.size(), outs.data(), caps.data(), cnt.data());
         for (size_t k = 0; k < which.size(); ++k) counts[which[k]] = cnt[k];
     }
@@ -682,6 +690,9 @@ public:
             }
             act->enqueue(af.data(), n, stream);
         }
+        // ---- the identity stage (set_identities): its collect launch reads the tables as the last round leaves them; what it counts
+        //      comes back with the same synchronisation
+        if (ident) ident->enqueue_collect(stream);
         // (the result blocks are in host memory already: a device-to-host copy command would queue behind frame uploads)
         YDS_HIP(hipStreamSynchronize(stream));
         if (with_actions) act->collect();
@@ -694,10 +705,12 @@ public:
         }
         for (int s = 0; s < S; ++s)
             if (last[s] >= 0) trk[s]->absorb_last(res_host + res_off[last[s]], T_ub[last[s]] + frames[last[s]].D);
+        if (ident) ident->finish(stream);
     }
 
     hipStream_t stream = nullptr;
     ActionsIface *act = nullptr;                  // the action stage of the step being run (set_actions; step_batch clears it)
+    IdentityIface *ident = nullptr;               // the identity stage of the step being run (set_identities; step_batch clears it)
     const double *act_times_in = nullptr;
     std::vector<int> act_tag;                     // per frame that runs: its index in the step, its time
     std::vector<double> act_time;

@@ -169,6 +169,7 @@ class _TrackerHandle:
             1 if metric == "euclidean" else 0))
         self.device = "cuda"
         self.max_dist, self.metric = float(max_dist), metric           # what a gallery search asks a tracker (search.py)
+        self.nn_budget = None if nn_budget is None else int(nn_budget)  # ... and an identity map (identity.py)
 
     def gallery(self, track_index):
         """The appearance rows track ``track_index`` (track-list order, as in state()) holds, float32 [n,512], as stored - normalised

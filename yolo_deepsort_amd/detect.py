@@ -593,7 +593,7 @@ class VideoDetector:
             if real_show and cv2 is not None:
                 cv2.destroyAllWindows()
 
-    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None):
+    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -619,7 +619,11 @@ class VideoDetector:
         stream_win_sizes: one (w, h) or None per source - that camera's ImageDetector(win_size, overlap), with this detector's overlap
         (MultiStreamPipeline(stream_win_sizes=...)): a wide camera is cut into windows, a door camera is not, in one step, with
         mixed_sizes False or True.  It needs a detector whose own win_size is None (ValueError otherwise); per stream the items are
-        those of detect() with a detector of that win_size."""
+        those of detect() with a detector of that win_size.
+        global_ids=True keeps one identity per person ACROSS the streams (MultiStreamPipeline.set_identities with the tracker's
+        own matching threshold): read it with stream_identities() between the yields.  The yielded items are the same either way:
+        track ids stay per stream.  Limits (identity.py): the tracker needs the cosine metric and a finite nn_budget (ValueError
+        otherwise); only live tracks hold an identity."""
         from . import _lib, pipeline as pl
         sources = list(sources)
         stream_win_sizes = pl.check_stream_win_sizes(len(sources), self.image_detector.win_size, stream_win_sizes, "VideoDetector.detect_streams")
@@ -654,6 +658,8 @@ class VideoDetector:
         shape, dev = None, None
         if actions_dev is not None:
             pipe.set_actions(actions_dev)
+        if global_ids:
+            pipe.set_identities(True)
         live = [self._is_live(src) for src in sources]
         n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
@@ -738,6 +744,15 @@ class VideoDetector:
         the tracks nearest to live track track_id of stream `stream`, MultiStreamPipeline.link."""
         return self._live_streams_pipe("link_stream_track").link(stream, track_id, exclude_stream=exclude_stream, top_k=top_k,
                                                                  max_dist=max_dist, confirmed_only=confirmed_only)
+
+    def stream_identities(self, stream=None):
+        """The global ids of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,
+        and for a generator started without global_ids): dict track_id -> global_id of the live Confirmed tracks of ``stream``
+        (0 = deferred to the next step), or a list of such dicts, one per stream; MultiStreamPipeline.last_identities."""
+        pipe = self._live_streams_pipe("stream_identities")
+        if getattr(pipe, "identities", None) is None:
+            raise ValueError("VideoDetector.stream_identities needs detect_streams(..., global_ids=True)")
+        return pipe.last_identities(stream)
 
     @staticmethod
     def _source_len(video_path):

@@ -239,6 +239,41 @@ class MultiStreamPipeline(Pipeline):
         _lib.check(_lib.load().yds_pipeline_set_stream_windows(self._h, int(stream), ww, wh, float(overlap)))
         self.stream_win_sizes[int(stream)] = None if win_size is None else (ww, wh)
 
+    def set_identities(self, on=True, max_dist=None, max_rows=4096):
+        """Global ids across the streams (identity.IdentityMap over this pipeline's trackers), updated behind every following step:
+        one small launch ahead of the step's synchronisation, and the resolve sequence with one more synchronisation only in the
+        steps that admit a new track.  ``on`` may also be an IdentityMap made over exactly these trackers in stream order (its
+        identities are kept); False / None switches the stage off.  max_dist=None: the first tracker's matching threshold.  The
+        step's own return value does not change: read ``last_identities()``.  Refused (YdsError) while a look-ahead pass is in
+        flight and for a map over other trackers."""
+        from .identity import IdentityMap
+        ident = None
+        if isinstance(on, IdentityMap):
+            ident = on
+        elif on:
+            ident = IdentityMap(self.deepsorts, max_dist=max_dist, max_rows=max_rows)
+        _lib.check(_lib.load().yds_pipeline_set_identities(self._h, None if ident is None else ident.handle))
+        self.identities = ident                             # (keeps the handle alive while the pipeline names it)
+        return ident
+
+    def last_identities(self, stream=None):
+        """The identity map after the last step, from the host copy: dict track_id -> global_id (0 = deferred) of the live
+        Confirmed tracks of ``stream``, or a list of such dicts for all streams; None when the stage is off."""
+        ident = getattr(self, "identities", None)
+        if ident is None:
+            return None
+        from .identity import _read_ids
+        lib = _lib.load()
+
+        def one(s):
+            return _read_ids(lambda t, g, cap, n: lib.yds_pipeline_last_identities(self._h, s, t, g, cap, n))
+        if stream is None:
+            return [one(s) for s in range(self.n_streams)]
+        stream = int(stream)
+        if stream < 0 or stream >= self.n_streams:
+            raise ValueError("MultiStreamPipeline: stream %d outside [0, %d)" % (stream, self.n_streams))
+        return one(stream)
+
     def _streams(self, stream_of_frame):
         s = np.ascontiguousarray(stream_of_frame, dtype=np.int32).reshape(-1)
         if s.size < 1 or s.size > self.net.batch_max:
