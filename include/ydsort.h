@@ -532,8 +532,8 @@ int yds_pipeline_last_actions(yds_pipe *, int32_t *out4_host, int cap, int *n_ou
  * keeps, in HBM, a pair (owner track id, global id) per stream and gallery slot.  A live track HOLDS global id g iff its slot's pair
  * names the track's own id and g > 0: a slot reused by a later track never inherits an identity, and no call here writes tracker
  * state.  Global ids come from ONE counter over all streams, start at 1 and are never reused; an id stays with its track for the
- * track's life.  Only live holders are matched against: when the last holder of an id has died (its max_age coasting frames
- * included) the id is never offered again - galleries of departed identities are not kept.
+ * track's life.  Without a memory (below) only live holders are matched against: when the last holder of an id has died (its
+ * max_age coasting frames included) the id is never offered again.
  * yds_identity_create   <- trks[n_streams]; max_dist < 0 = the first tracker's matching threshold; max_rows = the most gallery rows
  *                          one update admits (4096 = the search's query limit), at least the largest nn_budget so that one track
  *                          always fits.  Refused with a message, before any launch: no / NULL trackers, a tracker given twice, a
@@ -572,7 +572,53 @@ int yds_pipeline_last_actions(yds_pipe *, int32_t *out4_host, int cap, int *n_ou
  *   synchronisation; a step that admits a track runs the resolve sequence behind it and synchronises once more.  The map must have
  *   been created over the pipeline's own trackers in stream order (else refused); NULL switches the stage off.  Refused while a
  *   look-ahead pass is in flight.  The map must outlive its use by the pipeline.
- * yds_pipeline_last_identities: yds_identity_get on the pipeline's map: the state after the last step, from the host copy. */
+ * yds_pipeline_last_identities: yds_identity_get on the pipeline's map: the state after the last step, from the host copy.
+ *
+ * THE MEMORY (off by default; tests/identity_memory_ref.py restates it).  Without one, only live holders are matched against, as said
+ * above.  With one the map keeps, in HBM, a bank of max_ids entries, each a ring of rows_per_id rows of 512 fp32 values, normalised,
+ * copied from the tracker galleries bit for bit, so that a person who left every camera takes their old id when they come back.
+ * Each entry carries global_id, n_rows, the ring head and last_held = the last update at which a live track held the id; the map
+ * counts its updates u = 1, 2, ... from its creation (reset does not restart the count).  Each slot's pair gains a third value,
+ * `remembered` = the holder's hits at its last remembered row, void when the slot changes hands exactly as the pair is.
+ * yds_identity_set_memory <- (re)creates an EMPTY bank; max_ids = 0 frees it and switches the memory off; ttl is counted in updates,
+ *                          ttl < 0 = never expire.  Refused with a message, nothing launched: rows_per_id outside {1, 2, 4, 8, 16, 32}
+ *                          (whole entries tile a 32-row matrix tile), max_ids outside [0, 65536], a failed allocation (the memory is
+ *                          then off), and - for a map that a pipeline runs - while a look-ahead pass of that pipeline is in flight.
+ *                          An update with a memory, all orders being (stream, track-list) order:
+ *                          1. COLLECT as above.
+ *                          2. TOUCH: every entry whose id has a live Confirmed holder gets last_held = u (coasting frames count).
+ *                          3. EXPIRE: every entry without a live holder and with u - last_held > ttl is dropped.
+ *                          4. REMEMBER: every live Confirmed holder whose hits differs from its slot's `remembered` appends its
+ *                             NEWEST gallery row (ring position (hits - 1) mod nn_budget of its slot) to its id's ring and sets
+ *                             remembered = hits: one row per holder and update, however many frames lie between two updates, none
+ *                             when no tracker stepped.  An id without an entry takes a free one; if none is free, the DEPARTED
+ *                             entry (no live holder) with the smallest (last_held, global_id) is evicted for it; if there is none,
+ *                             the holder counts as UNREMEMBERED, its `remembered` stays, and the next update tries again.  Holders
+ *                             of one id in several cameras append in order; of more appenders than rows the last rows_per_id survive.
+ *                          5. RESOLVE as step 4 above with more columns: for every stream, besides the ids held live elsewhere,
+ *                             every DEPARTED id - an entry with at least one row and no live holder in any camera at that moment,
+ *                             holders created earlier in this resolve counting as live.  cost(track, departed id) = min over the
+ *                             track's rows and the entry's rows of 1 - <row, row>, the same exact-fp32 chains; clamp, assignment
+ *                             and gate unchanged.  A track matched to a departed id takes it (RELINKED), is its holder from then on
+ *                             (last_held = u), and later streams see the id as live-held.  Resolve reads the bank as steps 2-4 left
+ *                             it; an identity handed out in update u enters the bank at update u + 1.
+ *                          The two launches of steps 2-4 go behind the collect launch, ahead of the same one synchronisation; the
+ *                          resolve sequence gains one launch, the bank distance kernel.  yds_identity_reset also empties the bank.
+ * yds_identity_enrol    <- the watch-list use: n_arrays arrays of n_rows[a] rows each, concatenated in `rows` (host, any scale,
+ *                          normalised on the device; a row of zero or non-finite norm is refused).  One departed entry per array under
+ *                          the next fresh ids (global_id_out[a]), last_held = the current update, the last rows_per_id rows of each
+ *                          array kept.  Entries are had by step 4's rule (holders as of the last update); all or nothing: refused
+ *                          with a message when they do not suffice.  WHEN: between steps.
+ * yds_identity_get_memory <- per used entry, ascending by id: global id, row count, last_held.  *n = the count.
+ * yds_identity_get_memory_rows <- the rows of one id in chronological order, oldest first.
+ * yds_identity_memory_distances <- the bank distance kernel on its own, like yds_gallery_search_dense: dist_out [Q][*n_entries] over the
+ *                          used entries ascending by id (global_id_out), queries raw on the host or the device, Q in [1, 4096]; a
+ *                          query of zero or non-finite norm gives +inf everywhere.
+ * yds_identity_memory_bench <- measurement aid (tools/identity_memory_bench.py): that kernel alone `iters` times on device queries at
+ *                          strip_len bank tiles per workgroup (0: the built-in choice), HIP events around each; us_out[iters].
+ * yds_identity_last_relinked <- yds_identity_last_links' shape, the subset matched to a departed id (last_links keeps returning all).
+ * yds_identity_last_memory_counts <- counts7: entries, departed (both after the update), relinked, remembered rows, expired, evicted,
+ *                          unremembered of the last update; zeros without a memory. */
 yds_ident *yds_identity_create(yds_trk *const *trks, int n_streams, float max_dist, int max_rows);
 void yds_identity_destroy(yds_ident *);
 int yds_identity_reset(yds_ident *);
@@ -582,6 +628,15 @@ int yds_identity_last_links(yds_ident *, int32_t *stream, int32_t *track_id, int
 int yds_identity_last_counts(yds_ident *, int *n_linked, int *n_fresh, int *n_deferred);
 int yds_identity_set_timing(yds_ident *, int on);
 int yds_identity_last_us(yds_ident *, float *us);
+int yds_identity_set_memory(yds_ident *, int max_ids, int rows_per_id, int ttl);
+int yds_identity_enrol(yds_ident *, const float *rows, const int32_t *n_rows, int n_arrays, int32_t *global_id_out);
+int yds_identity_get_memory(yds_ident *, int32_t *global_id, int32_t *n_rows, int32_t *last_held, int cap, int *n);
+int yds_identity_get_memory_rows(yds_ident *, int global_id, float *rows_out, int cap, int *n_rows);
+int yds_identity_memory_distances(yds_ident *, const float *queries, int queries_on_device, int Q, float *dist_out, int32_t *global_id_out,
+                                  int cap, int *n_entries);
+int yds_identity_memory_bench(yds_ident *, const float *queries_dev, int Q, int strip_len, int iters, float *us_out);
+int yds_identity_last_relinked(yds_ident *, int32_t *stream, int32_t *track_id, int32_t *global_id, float *cost, int cap, int *n);
+int yds_identity_last_memory_counts(yds_ident *, int32_t *counts7);
 int yds_pipeline_set_identities(yds_pipe *, yds_ident *);
 int yds_pipeline_last_identities(yds_pipe *, int stream, int32_t *track_id, int32_t *global_id, int cap, int *n);
 

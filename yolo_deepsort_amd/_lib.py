@@ -178,6 +178,14 @@ SIGNATURES = {
     "yds_identity_last_counts": (_I, [_P, _P, _P, _P]),
     "yds_identity_set_timing": (_I, [_P, _I]),
     "yds_identity_last_us": (_I, [_P, _P]),
+    "yds_identity_set_memory": (_I, [_P, _I, _I, _I]),
+    "yds_identity_enrol": (_I, [_P, _P, _P, _I, _P]),
+    "yds_identity_get_memory": (_I, [_P, _P, _P, _P, _I, _P]),
+    "yds_identity_get_memory_rows": (_I, [_P, _I, _P, _I, _P]),
+    "yds_identity_memory_distances": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
+    "yds_identity_memory_bench": (_I, [_P, _P, _I, _I, _I, _P]),
+    "yds_identity_last_relinked": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "yds_identity_last_memory_counts": (_I, [_P, _P]),
     "yds_pipeline_set_identities": (_I, [_P, _P]),
     "yds_pipeline_last_identities": (_I, [_P, _I, _P, _P, _I, _P]),
 }

@@ -306,6 +306,8 @@ struct GalleryView {
     // kernels keep it, the number of slots (the most tracks the step can leave) and whether nn_budget is None
     const int *n_tracks_dev;
     int capacity, unbounded;
+    // for the identity memory: hits[t], so that a track's NEWEST row is ring position (hits[t] - 1) mod budget of its slot
+    const int *hits;
 };
 struct TrackerIface {
     virtual ~TrackerIface() {}
@@ -328,6 +330,10 @@ struct IdentityIface {
     virtual void finish(hipStream_t s) = 0;
     // the map of the last update, from the host copy: live Confirmed tracks of a stream in track-list order (0 = deferred)
     virtual void get(int stream, int32_t *track_id, int32_t *global_id, int cap, int *n) const = 0;
+    // the pipeline that runs the map as a stage (*user is null once that pipeline is gone) and its answer to "is a look-ahead pass
+    // in flight": the map refuses to rebuild its memory then, as the pipeline refuses set_identities
+    std::shared_ptr<void *> user;
+    bool (*user_busy)(void *) = nullptr;
 };
 
 // The association driver (tracker.hip TrackerGroup): S trackers (one per video stream; the pipeline of a single stream has S = 1)

@@ -15,35 +15,15 @@
 //                          min over the holders, min_cost_matching's clamp, the device LSAP (tracker_lsap_dev.h), gate, pairs, counter
 // A step in which no track needs an identity costs the collect launch alone and no synchronisation of its own; the other four run
 // at their exact sizes behind it, with one more synchronisation, only when a track was admitted.
-#include "gallery_dev.h"
+// With a memory (identity_memory_dev.h, off by default) two launches follow the collect ahead of that same synchronisation - the
+// book kernel and the row copies - and the resolve sequence gains the bank distance kernel and E = max_ids more columns: D2 is
+// [N][T + E], a departed entry (used, no live holder) is a column of every stream, its cost read straight from D2.
+#include "identity_memory_dev.h"
 #include "tracker_lsap_dev.h"
 
 #include <limits.h>
 
 namespace yds {
-
-// One tracker as the collect and resolve kernels read it (pinned host memory, rewritten ahead of every collect: a step may move
-// the tracker's buffers).  pair: [cap][2] ints of this map, indexed by the tracker's slot.
-struct alignas(16) IdentSrc {
-    const float *gallery;
-    const int *slot, *id, *state, *n_feat, *n_tracks;
-    int *pair;
-    int budget, cap;
-};
-static_assert(sizeof(IdentSrc) % 16 == 0, "IdentSrc arrays are indexed at a stride of sizeof(IdentSrc)");
-
-// counts of an update, in pinned host memory
-enum IdentCount { IC_T = 0, IC_NCONF, IC_NNEW, IC_NADM, IC_Q, IC_NLINK, IC_NFRESH, IC_NEXT, IC_COUNT };
-
-// Device arrays of the map, sized by the sum of the trackers' slot counts (no step can leave more tracks).  g = index of a track in
-// (stream, track-list) order over all trackers; n = index of a new track in the same order.
-struct IdentDev {
-    int *g_stream, *g_gid, *g_conf, *g_hpos, *g_uk;     // stream, held id (0: none), Confirmed, place in the host list, index into U
-    int *new_g, *new_rows, *new_q0;                     // new track n: its g, gallery rows, first row of its queries
-    int *U, *flag_s, *flag_o, *colk, *colof;            // U: held ids ascending; per id: held in / outside the stream; columns
-    int *link_col, *fresh_rank, *rows, *cols, *misc;    // per new track of the stream; LSAP pairs; misc[0] = LSAP pair count
-    int *next_id;                                       // the one counter of all streams (next id to hand out)
-};
 
 // the inverse of ordered_bits (gallery_dev.h)
 __device__ __forceinline__ float ident_from_ordered(unsigned b) {
@@ -131,30 +111,16 @@ __global__ __launch_bounds__(256) void ident_reduce_kernel(const float *dist, Id
     D2[(size_t)n * T + g] = m;
 }
 
-// ascending bitonic sort of P (a power of two) ints by the workgroup; a: LDS or global
-__device__ __forceinline__ void ident_sort(int *a, int P) {
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const int x = a[i], y = a[l];
-                    if (((i & k) == 0) == (x > y)) { a[i] = y; a[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-// One workgroup; N admitted new tracks, T tracks.  sort_global: where the held ids are sorted when their padded count P exceeds the
+// One workgroup; N admitted new tracks, T tracks, D2 rows of ldd = T + m.max_ids values.  sort_global: where the held ids are sorted when their padded count P exceeds the
 // dynamic LDS (else the LDS, which the LSAP takes over afterwards).  cost: [max new tracks of a stream][columns] scratch, first as
 // ordered bits, then as floats.  lk: stream | track id | global id | cost bits, [cap_total] each, of the linked tracks.
 __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src, const GalleryDesc *gdesc, int S, int N, int T, int P, IdentDev d,
-                                                            const float *D2, float max_dist, float flood, float *cost, int *sort_global,
+                                                            IdentMem m, const float *D2, float max_dist, float flood, float *cost, int *sort_global,
                                                             char *lsap_state, int smem_bytes, int cap_total, int *counts, int *hl, int *lk) {
     extern __shared__ __attribute__((aligned(16))) char lsap_smem[];
     __shared__ int s_cnt[4];
     const int tid = threadIdx.x;
+    const int E = m.max_ids, ldd = T + E;
     int *hl_gid = hl + S + 1 + cap_total;
     unsigned *cost_bits = reinterpret_cast<unsigned *>(cost);
     // ---- U: the ids held by a live track, ascending (fresh ids are appended as they are handed out: they only grow)
@@ -177,7 +143,7 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
         d.g_uk[g] = k;
     }
     __syncthreads();
-    int next = *d.next_id, n0 = 0, n_link = 0, n_fresh = 0;
+    int next = *d.next_id, n0 = 0, n_link = 0, n_fresh = 0, n_relinked = 0;
     for (int s = 0; s < S && n0 < N; ++s) {
         // the admitted new tracks of stream s: [n0, n0 + ns) (the list is in stream order)
         int ns = 0;
@@ -196,21 +162,25 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
             if (k >= 0) { if (d.g_stream[g] == s) d.flag_s[k] = 1; else d.flag_o[k] = 1; }
         }
         __syncthreads();
-        const int nc = compact_ordered(nU, s_cnt, [&](int k) { return d.flag_o[k] && !d.flag_s[k]; }, [&](int k, int c) { d.colk[c] = k; d.colof[k] = c; });
+        const int nch = compact_ordered(nU, s_cnt, [&](int k) { return d.flag_o[k] && !d.flag_s[k]; }, [&](int k, int c) { d.colk[c] = k; d.colof[k] = c; });
+        // ---- behind them the departed ids: used entries without a live holder (one relinked earlier in this resolve is live)
+        const int nd = E ? compact_ordered(E, s_cnt, [&](int e) { return m.gid[e] > 0 && m.n[e] > 0 && !m.live[e]; }, [&](int e, int c) { m.dcol[c] = e; }) : 0;
+        const int nc = nch + nd;
         __syncthreads();
         // ---- cost[n][c] = min over the holders g of column c of D2[n][g] (every holder of a column sits outside s)
         for (int i = tid; i < ns * nc; i += 256) cost_bits[i] = 0xffffffffu;
         __syncthreads();
-        if (nc > 0)
+        if (nch > 0)
             for (size_t i = tid; i < (size_t)ns * T; i += 256) {
                 const int n = (int)(i / T), g = (int)(i - (size_t)n * T);
                 const int k = d.g_uk[g];
                 const int c = k >= 0 ? d.colof[k] : -1;
-                if (c >= 0) atomicMin(&cost_bits[(size_t)n * nc + c], ordered_bits(D2[(size_t)(n0 + n) * T + g]));
+                if (c >= 0) atomicMin(&cost_bits[(size_t)n * nc + c], ordered_bits(D2[(size_t)(n0 + n) * ldd + g]));
             }
         __syncthreads();
         for (int i = tid; i < ns * nc; i += 256) {
-            const float v = ident_from_ordered(cost_bits[i]);
+            const int n = i / nc, c = i - n * nc;
+            const float v = c < nch ? ident_from_ordered(cost_bits[i]) : D2[(size_t)(n0 + n) * ldd + T + m.dcol[c - nch]];
             cost[i] = v > max_dist ? flood : v;                               // linear_assignment.py:52
         }
         __syncthreads();
@@ -226,8 +196,10 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
         __syncthreads();
         const int nl = compact_ordered(ns, s_cnt, [&](int n) { return d.link_col[n] >= 0; }, [&](int n, int r) { d.fresh_rank[n] = -1 - (n_link + r); });
         const int nf = compact_ordered(ns, s_cnt, [&](int n) { return d.link_col[n] < 0; }, [&](int n, int r) { d.fresh_rank[n] = r; });
+        const int nr = nd ? compact_ordered(ns, s_cnt, [&](int n) { return d.link_col[n] >= nch; }, [&](int n, int r) { m.g_rank[n] = r; }) : 0;
         __syncthreads();
-        // ---- hand the ids out: a matched track takes the column's id, every other one the next fresh id in track-list order
+        // ---- hand the ids out: a matched track takes the column's id, every other one the next fresh id in track-list order; an id
+        //      taken from the bank has a live holder from here on and joins U behind the fresh ones (m.g_rank: its rank, scratch)
         const IdentSrc e = src[s];
         const GalleryDesc ge = gdesc[s];
         for (int n = tid; n < ns; n += 256) {
@@ -235,7 +207,14 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
             int gid, k;
             if (fr < 0) {
                 const int c = d.link_col[n], at = -1 - fr;
-                k = d.colk[c]; gid = d.U[k];
+                if (c < nch) { k = d.colk[c]; gid = d.U[k]; }
+                else {
+                    const int en = m.dcol[c - nch];
+                    gid = m.gid[en]; k = nU + nf + m.g_rank[n];
+                    d.U[k] = gid;
+                    m.live[en] = 1; m.last[en] = m.u;
+                }
+                lk[4 * cap_total + at] = c >= nch ? 1 : 0;
                 lk[at] = s; lk[cap_total + at] = e.id[t]; lk[2 * cap_total + at] = gid;
                 lk[3 * cap_total + at] = __float_as_int(cost[(size_t)n * nc + c]);
             } else {
@@ -244,16 +223,20 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
             }
             d.g_uk[g] = k; d.g_gid[g] = gid;
             const int slot = e.slot[t];
-            if (slot >= 0 && slot < e.cap) { e.pair[2 * slot] = e.id[t]; e.pair[2 * slot + 1] = gid; }
+            if (slot >= 0 && slot < e.cap) {
+                e.pair[2 * slot] = e.id[t]; e.pair[2 * slot + 1] = gid;
+                if (e.rem) e.rem[slot] = 0;                                   // (hits >= 1: the next update remembers its newest row)
+            }
             const int hp = d.g_hpos[g];
             if (hp >= 0) hl_gid[hp] = gid;
         }
-        nU += nf; next += nf; n_link += nl; n_fresh += nf; n0 += ns;
+        nU += nf + nr; next += nf; n_link += nl; n_fresh += nf; n_relinked += nr; n0 += ns;
         __syncthreads();
     }
     if (tid == 0) {
         *d.next_id = next;
         counts[IC_NLINK] = n_link; counts[IC_NFRESH] = n_fresh; counts[IC_NEXT] = next;
+        if (E) { counts[IC_M_RELINKED] = n_relinked; counts[IC_M_DEPARTED] -= n_relinked; }
     }
 }
 
@@ -261,12 +244,29 @@ __global__ __launch_bounds__(256) void ident_resolve_kernel(const IdentSrc *src,
 namespace {
 
 constexpr int kDevArrays = 18;                     // the int arrays of IdentDev, cap_total entries each
+constexpr int kMemArrays = 5;                      // the per-track / per-id int arrays of IdentMem, cap_total entries each
+constexpr int kMemEntryArrays = 8;                 // its per-entry int arrays, max_ids entries each
+constexpr int kMaxMemoryIds = 65536;
+constexpr int kBankStrip = 8;                      // bank tiles per workgroup of ident_bank_dist_kernel (profiles/identity_memory_bench.txt)
+
+template <class... A> void launch_bank_dist(int R, dim3 grid, hipStream_t s, A... a) {
+    switch (R) {
+    case 1: hipLaunchKernelGGL(ident_bank_dist_kernel<1>, grid, dim3(256), 0, s, a...); break;
+    case 2: hipLaunchKernelGGL(ident_bank_dist_kernel<2>, grid, dim3(256), 0, s, a...); break;
+    case 4: hipLaunchKernelGGL(ident_bank_dist_kernel<4>, grid, dim3(256), 0, s, a...); break;
+    case 8: hipLaunchKernelGGL(ident_bank_dist_kernel<8>, grid, dim3(256), 0, s, a...); break;
+    case 16: hipLaunchKernelGGL(ident_bank_dist_kernel<16>, grid, dim3(256), 0, s, a...); break;
+    case 32: hipLaunchKernelGGL(ident_bank_dist_kernel<32>, grid, dim3(256), 0, s, a...); break;
+    default: fail("identity memory: rows_per_id = %d", R);
+    }
+}
 
 }  // namespace
 
 class Identity : public IdentityIface {
 public:
-    struct Link { int stream, track_id, global_id; float cost; };
+    struct Link { int stream, track_id, global_id; float cost; int relinked; };
+    struct Entry { int global_id, n_rows, last_held, index, head; };
 
     Identity(yds_trk *const *handles, int n_streams, float max_dist_in, int max_rows)
         : max_rows(max_rows) {
@@ -292,6 +292,7 @@ public:
         flood = (float)(md + 1e-5);                                           // linear_assignment.py:52
         const int S = n_streams;
         pair.resize(S);
+        rem.resize(S);
         pair_cap.assign(S, 0);
         src.ensure((size_t)S);
         counts.ensure(IC_COUNT);
@@ -317,10 +318,12 @@ public:
         return true;
     }
 
-    // forget every pair; the counter keeps counting
+    // forget every pair and every remembered identity; the id counter and the update counter keep counting
     void reset() {
         for (size_t s = 0; s < pair.size(); ++s)
             if (pair_cap[s]) YDS_HIP(hipMemset(pair[s].p, 0, (size_t)pair_cap[s] * 2 * sizeof(int)));
+        clear_memory();
+        memset(mcounts, 0, sizeof(mcounts));
         first.assign(trks.size() + 1, 0);
         ids_track.clear(); ids_global.clear(); links.clear();
         n_linked = n_fresh = n_deferred = 0;
@@ -329,6 +332,7 @@ public:
 
     void enqueue_collect(hipStream_t s) override {
         const int S = (int)trks.size();
+        ++n_updates;
         cap_total = 0;
         max_cap = 0;
         for (int a = 0; a < S; ++a) {
@@ -338,9 +342,11 @@ public:
                 YDS_HIP(hipMemset(p.p, 0, (size_t)v.capacity * 2 * sizeof(int)));
                 if (pair_cap[a]) YDS_HIP(hipMemcpy(p.p, pair[a].p, (size_t)pair_cap[a] * 2 * sizeof(int), hipMemcpyDeviceToDevice));
                 pair[a] = std::move(p);
+                if (mem.max_ids) grow_rem(a, pair_cap[a], v.capacity);
                 pair_cap[a] = v.capacity;
             }
-            src.p[a] = IdentSrc{v.gallery, v.slot, v.id, v.state, v.n_feat, v.n_tracks_dev, pair[a].p, v.budget, v.capacity};
+            src.p[a] = IdentSrc{v.gallery, v.slot, v.id, v.state, v.n_feat, v.n_tracks_dev, v.hits, pair[a].p, mem.max_ids ? rem[a].p : nullptr,
+                                v.budget, v.capacity};
             cap_total += v.capacity;
             max_cap = std::max(max_cap, v.capacity);
         }
@@ -353,14 +359,27 @@ public:
         dev.link_col = take(); dev.fresh_rank = take(); dev.rows = take(); dev.cols = take(); dev.misc = take();
         dev.next_id = next_id.p;
         hl.ensure((size_t)S + 1 + 2 * (size_t)cap_total);
-        lk.ensure(4 * (size_t)cap_total);
+        lk.ensure(5 * (size_t)cap_total);
         hipLaunchKernelGGL(ident_collect_kernel, dim3(1), dim3(256), 0, s, src.p, S, max_rows, cap_total, gdesc.p, dev, counts.p, hl.p);
+        if (mem.max_ids) {
+            // ---- the memory's steps 2-4 behind the collect, ahead of the caller's synchronisation: bookkeeping, then the row copies
+            int P = 1;
+            while (P < cap_total) P <<= 1;
+            if ((size_t)cap_total * kMemArrays + P > mem_arrays.n) mem_arrays.alloc(((size_t)cap_total * kMemArrays + P) * 2);
+            int *b = mem_arrays.p;
+            auto takem = [&]() { int *r = b; b += cap_total; return r; };
+            mem.ent_of = takem(); mem.first_g = takem(); mem.g_ent = takem(); mem.g_rank = takem(); mem.g_pos = takem();
+            mem.sortbuf = b;
+            mem.u = n_updates;
+            hipLaunchKernelGGL(ident_book_kernel, dim3(1), dim3(256), 0, s, src.p, gdesc.p, S, cap_total, dev, mem, counts.p);
+            if (cap_total) hipLaunchKernelGGL(ident_remember_kernel, dim3(cap_total), dim3(128), 0, s, src.p, gdesc.p, dev, mem);
+        }
         YDS_HIP(hipGetLastError());
     }
 
     void finish(hipStream_t s) override {
         const int S = (int)trks.size();
-        const int T = counts.p[IC_T], N = counts.p[IC_NADM], Q = counts.p[IC_Q];
+        const int T = counts.p[IC_T], N = counts.p[IC_NADM], Q = counts.p[IC_Q], E = mem.max_ids, ldd = T + E;
         n_deferred = counts.p[IC_NNEW] - N;
         n_linked = n_fresh = 0;
         links.clear();
@@ -370,11 +389,12 @@ public:
             int P = 1;
             while (P < T) P <<= 1;
             const int R = std::min(N, max_cap);                               // the most new tracks one stream can bring
-            const size_t lsap_need = (size_t)std::max(std::max(R, T), 1) * LSAP_STATE_BYTES;
+            // (columns: at most one per held id and one per bank entry; the LSAP state is sized by the larger side)
+            const size_t lsap_need = (size_t)std::max(std::max(R, ldd), 1) * LSAP_STATE_BYTES;
             qn.ensure((size_t)Q * EMB);
-            dist.ensure((size_t)Q * T);
-            D2.ensure((size_t)N * T);
-            cost.ensure((size_t)R * T);
+            dist.ensure((size_t)Q * ldd);
+            D2.ensure((size_t)N * ldd);
+            cost.ensure((size_t)R * ldd);
             if ((size_t)P * sizeof(int) > LSAP_LDS_MAX) sort_global.ensure((size_t)P);
             if (lsap_need > LSAP_LDS_MAX) lsap_scratch.ensure(lsap_need);
             static bool attr_set = false;
@@ -384,9 +404,10 @@ public:
             }
             if (timing) YDS_HIP(hipEventRecord(ev0, s));
             hipLaunchKernelGGL(ident_gather_kernel, dim3(N), dim3(256), 0, s, gdesc.p, dev, qn.p);
-            hipLaunchKernelGGL(gallery_min_dist_kernel, dim3(T, (Q + GALLERY_SLAB - 1) / GALLERY_SLAB), dim3(256), 0, s, gdesc.p, S, qn.p, Q, dist.p, T);
-            hipLaunchKernelGGL(ident_reduce_kernel, dim3((T + 255) / 256, N), dim3(256), 0, s, dist.p, dev, T, D2.p);
-            hipLaunchKernelGGL(ident_resolve_kernel, dim3(1), dim3(256), LSAP_LDS_MAX, s, src.p, gdesc.p, S, N, T, P, dev, D2.p, max_dist, flood, cost.p,
+            hipLaunchKernelGGL(gallery_min_dist_kernel, dim3(T, (Q + GALLERY_SLAB - 1) / GALLERY_SLAB), dim3(256), 0, s, gdesc.p, S, qn.p, Q, dist.p, ldd);
+            if (E) launch_bank_dist(mem.R, bank_grid(Q, strip), s, (const float *)mem.rows, (const int *)mem.n, E, strip, (const float *)qn.p, Q, dist.p + T, ldd);
+            hipLaunchKernelGGL(ident_reduce_kernel, dim3((ldd + 255) / 256, N), dim3(256), 0, s, dist.p, dev, ldd, D2.p);
+            hipLaunchKernelGGL(ident_resolve_kernel, dim3(1), dim3(256), LSAP_LDS_MAX, s, src.p, gdesc.p, S, N, T, P, dev, mem, D2.p, max_dist, flood, cost.p,
                                (size_t)P * sizeof(int) > LSAP_LDS_MAX ? sort_global.p : nullptr, lsap_need > LSAP_LDS_MAX ? lsap_scratch.p : nullptr,
                                (int)LSAP_LDS_MAX, cap_total, counts.p, hl.p, lk.p);
             if (timing) YDS_HIP(hipEventRecord(ev1, s));
@@ -403,14 +424,208 @@ public:
             for (int k = 0; k < n_linked; ++k) {
                 float c;
                 memcpy(&c, lk.p + 3 * (size_t)cap_total + k, 4);
-                links.push_back(Link{lk.p[k], lk.p[cap_total + k], lk.p[2 * (size_t)cap_total + k], c});
+                links.push_back(Link{lk.p[k], lk.p[cap_total + k], lk.p[2 * (size_t)cap_total + k], c, E ? lk.p[4 * (size_t)cap_total + k] : 0});
             }
         }
+        if (E) for (int k = 0; k < 7; ++k) mcounts[k] = counts.p[IC_M_ENTRIES + k];
         // ---- the host copy of the map
         const int n_conf = counts.p[IC_NCONF];
         first.assign(hl.p, hl.p + S + 1);
         ids_track.assign(hl.p + S + 1, hl.p + S + 1 + n_conf);
         ids_global.assign(hl.p + S + 1 + cap_total, hl.p + S + 1 + cap_total + n_conf);
+    }
+
+    // ---------------------------------------------------------------------------------------- the memory (yds_identity_set_memory)
+    dim3 bank_grid(int Q, int strip_len) const {
+        const int n_tiles = (mem.max_ids * mem.R + 31) / 32;
+        return dim3((n_tiles + strip_len - 1) / strip_len, (Q + GALLERY_SLAB - 1) / GALLERY_SLAB);
+    }
+
+    // rem of stream a for `cap` slots, the first `keep` kept (the tracker grew: its slots keep their numbers)
+    void grow_rem(int a, int keep, int cap) {
+        DevBuf<int> r((size_t)cap);
+        YDS_HIP(hipMemset(r.p, 0, (size_t)cap * sizeof(int)));
+        if (keep && rem[a].p) YDS_HIP(hipMemcpy(r.p, rem[a].p, (size_t)keep * sizeof(int), hipMemcpyDeviceToDevice));
+        rem[a] = std::move(r);
+    }
+
+    // every entry free, every holder's `remembered` void
+    void clear_memory() {
+        if (!mem.max_ids) return;
+        YDS_HIP(hipMemset(mem_entries.p, 0, (size_t)mem.max_ids * kMemEntryArrays * sizeof(int)));
+        for (size_t s = 0; s < rem.size(); ++s)
+            if (rem[s].p) YDS_HIP(hipMemset(rem[s].p, 0, rem[s].n * sizeof(int)));
+    }
+
+    void set_memory(int max_ids, int rows_per_id, int ttl) {
+        const char *who = "identity_set_memory";
+        if (max_ids < 0 || max_ids > kMaxMemoryIds) fail("%s: max_ids = %d outside [0, %d]", who, max_ids, kMaxMemoryIds);
+        if (max_ids && !(rows_per_id == 1 || rows_per_id == 2 || rows_per_id == 4 || rows_per_id == 8 || rows_per_id == 16 || rows_per_id == 32))
+            fail("%s: rows_per_id = %d, must be one of 1, 2, 4, 8, 16, 32 (whole entries tile a 32-row tile)", who, rows_per_id);
+        if (user && *user && user_busy && user_busy(*user))
+            fail("%s: the map's pipeline has a look-ahead pass in flight (consume it with a step first)", who);
+        mem = IdentMem{};
+        bank.release();
+        mem_entries.release();
+        mem_arrays.release();
+        for (auto &r : rem) r.release();
+        memset(mcounts, 0, sizeof(mcounts));
+        if (!max_ids) return;
+        try {
+            bank.alloc((size_t)max_ids * rows_per_id * EMB);
+            mem_entries.alloc((size_t)max_ids * kMemEntryArrays);
+            for (size_t a = 0; a < rem.size(); ++a)
+                if (pair_cap[a]) grow_rem((int)a, 0, pair_cap[a]);
+        } catch (const std::exception &e) {
+            bank.release();
+            mem_entries.release();
+            for (auto &r : rem) r.release();
+            fail("%s: no memory for %d ids of %d rows: %s", who, max_ids, rows_per_id, e.what());
+        }
+        int *b = mem_entries.p;
+        auto take = [&]() { int *r = b; b += max_ids; return r; };
+        mem.rows = bank.p;
+        mem.gid = take(); mem.n = take(); mem.head = take(); mem.last = take(); mem.live = take(); mem.cnt = take(); mem.pool = take(); mem.dcol = take();
+        mem.max_ids = max_ids; mem.R = rows_per_id; mem.ttl = ttl < 0 ? -1 : ttl;
+        clear_memory();
+    }
+
+    // gid | n | head | last | live of every entry, from the device (a call between steps: nothing of the map is in flight)
+    std::vector<int> fetch_entries() const {
+        std::vector<int> h((size_t)mem.max_ids * 5);
+        if (mem.max_ids) YDS_HIP(hipMemcpy(h.data(), mem_entries.p, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+        return h;
+    }
+
+    // the used entries, ascending by id
+    std::vector<Entry> entries() const {
+        const std::vector<int> h = fetch_entries();
+        const int E = mem.max_ids;
+        std::vector<Entry> out;
+        for (int e = 0; e < E; ++e)
+            if (h[e] > 0) out.push_back(Entry{h[e], h[E + e], h[3 * (size_t)E + e], e, h[2 * (size_t)E + e]});
+        std::sort(out.begin(), out.end(), [](const Entry &a, const Entry &b) { return a.global_id < b.global_id; });
+        return out;
+    }
+
+    // rows of one id, oldest first
+    void memory_rows(int global_id, float *rows_out, int cap, int *n_rows) const {
+        const char *who = "identity_get_memory_rows";
+        if (!mem.max_ids) fail("%s: the map has no memory (yds_identity_set_memory)", who);
+        if (!n_rows) fail("%s: n_rows is NULL", who);
+        for (const Entry &e : entries()) {
+            if (e.global_id != global_id) continue;
+            *n_rows = e.n_rows;
+            if (e.n_rows > cap) fail("%s: cap = %d too small for %d rows (the needed size is in *n_rows)", who, cap, e.n_rows);
+            if (e.n_rows && !rows_out) fail("%s: rows_out is NULL", who);
+            const int R = mem.R, first = e.n_rows < R ? 0 : e.head;
+            for (int k = 0; k < e.n_rows; ++k)
+                YDS_HIP(hipMemcpy(rows_out + (size_t)k * EMB, bank.p + ((size_t)e.index * R + (first + k) % R) * EMB, EMB * sizeof(float), hipMemcpyDeviceToHost));
+            return;
+        }
+        fail("%s: the memory holds no id %d", who, global_id);
+    }
+
+    // one departed entry per array under the next fresh ids; all or nothing
+    void enrol(const float *rows_host, const int *n_rows, int n_arrays, int32_t *ids_out) {
+        const char *who = "identity_enrol";
+        if (!mem.max_ids) fail("%s: the map has no memory (yds_identity_set_memory)", who);
+        if (n_arrays < 0 || (n_arrays && (!rows_host || !n_rows || !ids_out))) fail("%s: NULL argument", who);
+        if (user && *user && user_busy && user_busy(*user)) fail("%s: the map's pipeline has a look-ahead pass in flight (consume it with a step first)", who);
+        size_t total = 0;
+        for (int a = 0; a < n_arrays; ++a) {
+            if (n_rows[a] < 1) fail("%s: array %d has %d rows, at least one is needed", who, a, n_rows[a]);
+            total += (size_t)n_rows[a];
+        }
+        for (size_t r = 0; r < total; ++r) {
+            double ss = 0.0;
+            for (int k = 0; k < EMB; ++k) ss += (double)rows_host[r * EMB + k] * rows_host[r * EMB + k];
+            if (!(ss > 0.0) || !std::isfinite(ss) || !std::isfinite((float)std::sqrt(ss)))
+                fail("%s: row %zu has a zero or non-finite norm", who, r);
+        }
+        if (!n_arrays) return;
+        // ---- entries: the free ones in index order, then the departed ones by (last_held, id) - the update's own eviction rule
+        std::vector<int> h = fetch_entries();
+        const int E = mem.max_ids, R = mem.R;
+        std::vector<int> pool, departed;
+        for (int e = 0; e < E; ++e) {
+            if (h[e] == 0) pool.push_back(e);
+            else if (!h[4 * (size_t)E + e]) departed.push_back(e);
+        }
+        std::sort(departed.begin(), departed.end(), [&](int a, int b) {
+            const int la = h[3 * (size_t)E + a], lb = h[3 * (size_t)E + b];
+            return la != lb ? la < lb : h[a] < h[b];
+        });
+        pool.insert(pool.end(), departed.begin(), departed.end());
+        if ((int)pool.size() < n_arrays)
+            fail("%s: %d identities do not fit: the memory of %d ids has %zu entries free or departed, every other one has a live holder", who, n_arrays, E,
+                 pool.size());
+        // ---- rows: normalised on the device by the tracker's own kernel, the last R of each array to ring positions 0 .. n - 1
+        enrol_stage.ensure(total * EMB);
+        enrol_n.ensure(total * EMB);
+        YDS_HIP(hipMemcpyAsync(enrol_stage.p, rows_host, total * EMB * sizeof(float), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(normalize_rows_kernel, dim3(((int)total + 3) / 4), dim3(256), 0, stream, (const float *)enrol_stage.p, (const int *)nullptr, enrol_n.p,
+                           (int)total, 1);
+        YDS_HIP(hipGetLastError());
+        int next = 0;
+        YDS_HIP(hipMemcpyAsync(&next, next_id.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        YDS_HIP(hipStreamSynchronize(stream));
+        size_t r0 = 0;
+        for (int a = 0; a < n_arrays; ++a) {
+            const int e = pool[a], n = std::min(n_rows[a], R);
+            YDS_HIP(hipMemcpyAsync(bank.p + (size_t)e * R * EMB, enrol_n.p + (r0 + n_rows[a] - n) * EMB, (size_t)n * EMB * sizeof(float), hipMemcpyDeviceToDevice,
+                                   stream));
+            h[e] = next + a; h[E + e] = n; h[2 * (size_t)E + e] = n % R; h[3 * (size_t)E + e] = n_updates; h[4 * (size_t)E + e] = 0;
+            ids_out[a] = next + a;
+            r0 += (size_t)n_rows[a];
+        }
+        next += n_arrays;
+        YDS_HIP(hipMemcpyAsync(mem_entries.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        YDS_HIP(hipMemcpyAsync(next_id.p, &next, sizeof(int), hipMemcpyHostToDevice, stream));
+        YDS_HIP(hipStreamSynchronize(stream));
+    }
+
+    // the bank kernel on its own: dist [Q][entries] over the used entries ascending by id
+    void memory_distances(const float *queries, int on_device, int Q, float *dist_out, int32_t *gid_out, int cap, int *n_entries, int strip_len = 0,
+                          int iters = 0, float *us_out = nullptr) {
+        const char *who = "identity_memory_distances";
+        if (!mem.max_ids) fail("%s: the map has no memory (yds_identity_set_memory)", who);
+        if (Q < 1 || Q > 4096) fail("%s: Q = %d outside [1, 4096]", who, Q);
+        if (!queries || !n_entries) fail("%s: NULL argument", who);
+        const std::vector<Entry> used = entries();
+        *n_entries = (int)used.size();
+        if ((int)used.size() > cap) fail("%s: cap = %d too small for %zu entries (the needed size is in *n_entries)", who, cap, used.size());
+        if (used.size() && (!dist_out || !gid_out)) fail("%s: an output array is NULL", who);
+        const int E = mem.max_ids;
+        qn.ensure((size_t)Q * EMB);
+        dist.ensure((size_t)Q * E);
+        const float *src = queries;
+        if (!on_device) {
+            enrol_stage.ensure((size_t)Q * EMB);
+            YDS_HIP(hipMemcpyAsync(enrol_stage.p, queries, (size_t)Q * EMB * sizeof(float), hipMemcpyHostToDevice, stream));
+            src = enrol_stage.p;
+        }
+        hipLaunchKernelGGL(normalize_rows_kernel, dim3((Q + 3) / 4), dim3(256), 0, stream, src, (const int *)nullptr, qn.p, Q, 1);
+        const int sl = strip_len > 0 ? strip_len : strip;
+        const dim3 grid = bank_grid(Q, sl);
+        launch_bank_dist(mem.R, grid, stream, (const float *)mem.rows, (const int *)mem.n, E, sl, (const float *)qn.p, Q, dist.p, E);
+        for (int i = 0; i < iters; ++i) {                                     // (measurement aid: the kernel alone, HIP events around each)
+            YDS_HIP(hipEventRecord(ev0, stream));
+            launch_bank_dist(mem.R, grid, stream, (const float *)mem.rows, (const int *)mem.n, E, sl, (const float *)qn.p, Q, dist.p, E);
+            YDS_HIP(hipEventRecord(ev1, stream));
+            YDS_HIP(hipStreamSynchronize(stream));
+            float ms = 0.f;
+            YDS_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+            us_out[i] = ms * 1e3f;
+        }
+        YDS_HIP(hipGetLastError());
+        std::vector<float> host((size_t)Q * E);
+        YDS_HIP(hipMemcpyAsync(host.data(), dist.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
+        YDS_HIP(hipStreamSynchronize(stream));
+        for (size_t k = 0; k < used.size(); ++k) {
+            gid_out[k] = used[k].global_id;
+            for (int q = 0; q < Q; ++q) dist_out[(size_t)q * used.size() + k] = host[(size_t)q * E + used[k].index];
+        }
     }
 
     void update() {
@@ -435,6 +650,13 @@ public:
     hipStream_t stream = nullptr;                 // of the stand-alone update
     std::vector<DevBuf<int>> pair;                // per stream [slots][2]: owner track id, global id
     std::vector<int> pair_cap;
+    // the memory (mem.max_ids = 0: none, and none of these is allocated)
+    std::vector<DevBuf<int>> rem;                 // per stream [slots]: the holder's hits at its last remembered row
+    DevBuf<float> bank, enrol_stage, enrol_n;
+    DevBuf<int> mem_entries, mem_arrays;
+    IdentMem mem{};
+    int n_updates = 0, strip = kBankStrip;
+    int mcounts[7] = {0, 0, 0, 0, 0, 0, 0};       // entries, departed, relinked, remembered rows, expired, evicted, unremembered
     PinBuf<IdentSrc> src;
     PinBuf<int> counts, hl, lk;
     DevBuf<GalleryDesc> gdesc;
@@ -510,6 +732,71 @@ int yds_identity_last_counts(yds_ident *h, int *n_linked, int *n_fresh, int *n_d
     if (n_linked) *n_linked = I->n_linked;
     if (n_fresh) *n_fresh = I->n_fresh;
     if (n_deferred) *n_deferred = I->n_deferred;
+    YDS_API_END
+}
+int yds_identity_set_memory(yds_ident *h, int max_ids, int rows_per_id, int ttl) {
+    YDS_API_BEGIN
+    impl(h)->set_memory(max_ids, rows_per_id, ttl);
+    YDS_API_END
+}
+int yds_identity_enrol(yds_ident *h, const float *rows, const int32_t *n_rows, int n_arrays, int32_t *global_id_out) {
+    YDS_API_BEGIN
+    impl(h)->enrol(rows, n_rows, n_arrays, global_id_out);
+    YDS_API_END
+}
+int yds_identity_get_memory(yds_ident *h, int32_t *global_id, int32_t *n_rows, int32_t *last_held, int cap, int *n) {
+    YDS_API_BEGIN
+    const yds::Identity *I = impl(h);
+    if (!n) yds::fail("identity_get_memory: n is NULL");
+    const std::vector<yds::Identity::Entry> used = I->entries();
+    const int m = (int)used.size();
+    *n = m;
+    if (m > cap) yds::fail("identity_get_memory: cap = %d too small for %d entries (the needed size is in *n)", cap, m);
+    if (m && (!global_id || !n_rows || !last_held)) yds::fail("identity_get_memory: an output array is NULL");
+    for (int k = 0; k < m; ++k) { global_id[k] = used[k].global_id; n_rows[k] = used[k].n_rows; last_held[k] = used[k].last_held; }
+    YDS_API_END
+}
+int yds_identity_get_memory_rows(yds_ident *h, int global_id, float *rows_out, int cap, int *n_rows) {
+    YDS_API_BEGIN
+    impl(h)->memory_rows(global_id, rows_out, cap, n_rows);
+    YDS_API_END
+}
+int yds_identity_memory_distances(yds_ident *h, const float *queries, int queries_on_device, int Q, float *dist_out, int32_t *global_id_out, int cap,
+                                  int *n_entries) {
+    YDS_API_BEGIN
+    impl(h)->memory_distances(queries, queries_on_device, Q, dist_out, global_id_out, cap, n_entries);
+    YDS_API_END
+}
+int yds_identity_memory_bench(yds_ident *h, const float *queries_dev, int Q, int strip_len, int iters, float *us_out) {
+    YDS_API_BEGIN
+    yds::Identity *I = impl(h);
+    if (iters < 1 || !us_out || strip_len < 0) yds::fail("identity_memory_bench: iters = %d, strip_len = %d", iters, strip_len);
+    const size_t E = (size_t)I->mem.max_ids;
+    std::vector<float> d((size_t)Q * std::max<size_t>(E, 1));
+    std::vector<int32_t> g(std::max<size_t>(E, 1));
+    int n = 0;
+    I->memory_distances(queries_dev, 1, Q, d.data(), g.data(), (int)E, &n, strip_len, iters, us_out);
+    YDS_API_END
+}
+int yds_identity_last_relinked(yds_ident *h, int32_t *stream, int32_t *track_id, int32_t *global_id, float *cost, int cap, int *n) {
+    YDS_API_BEGIN
+    const yds::Identity *I = impl(h);
+    if (!n) yds::fail("identity_last_relinked: n is NULL");
+    int m = 0;
+    for (const auto &l : I->links) m += l.relinked ? 1 : 0;
+    *n = m;
+    if (m > cap) yds::fail("identity_last_relinked: cap = %d too small for %d links (the needed size is in *n)", cap, m);
+    if (m && (!stream || !track_id || !global_id || !cost)) yds::fail("identity_last_relinked: an output array is NULL");
+    int k = 0;
+    for (const auto &l : I->links)
+        if (l.relinked) { stream[k] = l.stream; track_id[k] = l.track_id; global_id[k] = l.global_id; cost[k] = l.cost; ++k; }
+    YDS_API_END
+}
+int yds_identity_last_memory_counts(yds_ident *h, int32_t *counts7) {
+    YDS_API_BEGIN
+    const yds::Identity *I = impl(h);
+    if (!counts7) yds::fail("identity_last_memory_counts: counts7 is NULL");
+    for (int k = 0; k < 7; ++k) counts7[k] = I->mcounts[k];
     YDS_API_END
 }
 int yds_identity_set_timing(yds_ident *h, int on) {

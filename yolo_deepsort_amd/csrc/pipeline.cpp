@@ -203,6 +203,7 @@ public:
         YDS_HIP(hipEventCreateWithFlags(&ev_reid_done, hipEventDisableTiming));
     }
     ~Pipeline() {
+        *self = nullptr;
         (void)hipEventDestroy(ev_feat);
         (void)hipEventDestroy(ev_reid_done);
     }
@@ -616,9 +617,15 @@ public:
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_identities while a look-ahead pass is in flight (consume it with a step first)");
         if (i && !i->bound_to(trks.data(), (int)trks.size()))
             fail("pipeline: the identity map was not created over this pipeline's %zu trackers in stream order", trks.size());
+        if (identities) identities->user.reset();
         identities = i;
+        if (i) {
+            i->user = self;
+            i->user_busy = [](void *p) { const Pipeline *me = static_cast<const Pipeline *>(p); return me->pending.frames || me->ahead.reid_in_flight; };
+        }
     }
     IdentityIface *identities = nullptr;
+    std::shared_ptr<void *> self = std::make_shared<void *>(this);      // what a map bound to this pipeline asks; cleared by ~Pipeline
     ActionsIface *actions = nullptr;
     std::vector<double> next_times;               // set_frame_times: times of the next step's frames (empty: count / 25)
     std::vector<int64_t> frames_seen;             // frames every stream was handed since the pipeline was made

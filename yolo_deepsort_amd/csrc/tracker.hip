@@ -353,7 +353,7 @@ public:
     int num_tracks() const override { return T_host; }
     GalleryView gallery_view() const override {
         const TrackTable t = table_at(table.p, capacity);
-        return GalleryView{gallery.p, t.slot, t.id, t.state, t.n_feat, budget, T_host, metric, max_dist, meta.p + M_T, capacity, unbounded ? 1 : 0};
+        return GalleryView{gallery.p, t.slot, t.id, t.state, t.n_feat, budget, T_host, metric, max_dist, meta.p + M_T, capacity, unbounded ? 1 : 0, t.hits};
     }
 
     static TrackTable table_at(int *base, int cap) {

@@ -593,7 +593,8 @@ class VideoDetector:
             if real_show and cv2 is not None:
                 cv2.destroyAllWindows()
 
-    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False):
+    def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False,
+                       identity_memory=None):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -623,9 +624,21 @@ class VideoDetector:
         global_ids=True keeps one identity per person ACROSS the streams (MultiStreamPipeline.set_identities with the tracker's
         own matching threshold): read it with stream_identities() between the yields.  The yielded items are the same either way:
         track ids stay per stream.  Limits (identity.py): the tracker needs the cosine metric and a finite nn_budget (ValueError
-        otherwise); only live tracks hold an identity."""
+        otherwise); only live tracks hold an identity, unless identity_memory=dict(ids=..., rows=8, ttl=None) gives the map a memory
+        of departed identities (identity.IdentityMap's memory_ids / memory_rows / memory_ttl; ValueError without global_ids=True):
+        stream_identity_map() between the yields returns the map itself, for enrol(), memory() and last_relinked()."""
         from . import _lib, pipeline as pl
+        from .identity import check_memory
         sources = list(sources)
+        memory = {}
+        if identity_memory is not None:
+            if not global_ids:
+                raise ValueError("VideoDetector.detect_streams: identity_memory needs global_ids=True")
+            unknown = set(identity_memory) - {"ids", "rows", "ttl"}
+            if unknown or "ids" not in identity_memory:
+                raise ValueError("VideoDetector.detect_streams: identity_memory is dict(ids=..., rows=..., ttl=...), got %r" % (identity_memory,))
+            memory = dict(memory_ids=identity_memory["ids"], memory_rows=identity_memory.get("rows", 8), memory_ttl=identity_memory.get("ttl"))
+            check_memory(**memory)
         stream_win_sizes = pl.check_stream_win_sizes(len(sources), self.image_detector.win_size, stream_win_sizes, "VideoDetector.detect_streams")
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
@@ -659,7 +672,7 @@ class VideoDetector:
         if actions_dev is not None:
             pipe.set_actions(actions_dev)
         if global_ids:
-            pipe.set_identities(True)
+            pipe.set_identities(True, **memory)
         live = [self._is_live(src) for src in sources]
         n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
@@ -753,6 +766,14 @@ class VideoDetector:
         if getattr(pipe, "identities", None) is None:
             raise ValueError("VideoDetector.stream_identities needs detect_streams(..., global_ids=True)")
         return pipe.last_identities(stream)
+
+    def stream_identity_map(self):
+        """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,
+        and for a generator started without global_ids): enrol(), memory(), last_relinked() and the other reads go through it."""
+        pipe = self._live_streams_pipe("stream_identity_map")
+        if getattr(pipe, "identities", None) is None:
+            raise ValueError("VideoDetector.stream_identity_map needs detect_streams(..., global_ids=True)")
+        return pipe.identities
 
     @staticmethod
     def _source_len(video_path):

@@ -239,11 +239,12 @@ class MultiStreamPipeline(Pipeline):
         _lib.check(_lib.load().yds_pipeline_set_stream_windows(self._h, int(stream), ww, wh, float(overlap)))
         self.stream_win_sizes[int(stream)] = None if win_size is None else (ww, wh)
 
-    def set_identities(self, on=True, max_dist=None, max_rows=4096):
+    def set_identities(self, on=True, max_dist=None, max_rows=4096, memory_ids=0, memory_rows=8, memory_ttl=None):
         """Global ids across the streams (identity.IdentityMap over this pipeline's trackers), updated behind every following step:
         one small launch ahead of the step's synchronisation, and the resolve sequence with one more synchronisation only in the
         steps that admit a new track.  ``on`` may also be an IdentityMap made over exactly these trackers in stream order (its
-        identities are kept); False / None switches the stage off.  max_dist=None: the first tracker's matching threshold.  The
+        identities are kept); False / None switches the stage off.  max_dist=None: the first tracker's matching threshold;
+        memory_ids > 0 gives the new map a memory of departed identities (identity.IdentityMap; 0, the default: none).  The
         step's own return value does not change: read ``last_identities()``.  Refused (YdsError) while a look-ahead pass is in
         flight and for a map over other trackers."""
         from .identity import IdentityMap
@@ -251,7 +252,8 @@ class MultiStreamPipeline(Pipeline):
         if isinstance(on, IdentityMap):
             ident = on
         elif on:
-            ident = IdentityMap(self.deepsorts, max_dist=max_dist, max_rows=max_rows)
+            ident = IdentityMap(self.deepsorts, max_dist=max_dist, max_rows=max_rows, memory_ids=memory_ids, memory_rows=memory_rows,
+                                memory_ttl=memory_ttl)
         _lib.check(_lib.load().yds_pipeline_set_identities(self._h, None if ident is None else ident.handle))
         self.identities = ident                             # (keeps the handle alive while the pipeline names it)
         return ident
