@@ -474,6 +474,15 @@ int yds_conv_run_view(int variant, int n, int h, int w, int cin, int cout, int k
 int yds_conv_run_half(int variant, int n, int h, int w, int cin, int cout, int ksize, int stride, int act, int res_mode,
                       const int *view, int fmt_x, int fmt_y, const float *x_nhwc, const float *w_okkc, const float *bias,
                       const float *res_nhwc, float sentinel, float *y_nchw, float *y2_nchw);
+/* parity tests: the kernels that exist only as fused multi-layer launches, on the caller's tensors.  kind 0 = the detector's layers
+ * 0 + 1 (3x3/s1 RGB->32, 3x3/s2 32->64; x [n,h,w,4], y [n,64,ho,wo], ho = (h - 1) / 2 + 1), kind 1 = its first residual block (1x1
+ * 64->32, 3x3 32->64, shortcut to the input; x [n,h,w,64], y [n,64,h,w]), kind 2 = the ReID stem (3x3 RGB->64, activation,
+ * MaxPool(3, 2, 1); x [n,h,w,4], y [n,64,(h - 1) / 2 + 1,(w - 1) / 2 + 1]; w_b / bias_b unused, either conv math).  Weights
+ * [cout][kh][kw][cin] as in yds_conv_run, both layers with activation `act`.  half = 1: the single-term instantiation; fmt = 0 (H16
+ * activations, fp32 RGB) or 2 (F16 activations: half mode only; kind 0: the output, kind 1: input, shortcut and output).  The entry
+ * calls the fused launcher itself and fails with its message where the launch does not apply: no other kernel can stand in. */
+int yds_conv_run_fused(int kind, int n, int h, int w, int act, int half, int fmt, const float *x_nhwc, const float *w_a,
+                       const float *bias_a, const float *w_b, const float *bias_b, float *y_nchw);
 
 /* ---- action identification on the device ----------------------------------------------------------------------
  * yds_actions_create  <- ActionIdentify(actions, max_age, max_size) (action/action_Identify.py:4-13), one orbit cache (:8, a dict

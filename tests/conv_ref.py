@@ -285,6 +285,200 @@ def half_refs():
     return tuple(HalfRef(r.case, r.x, r.w, r.bias, r.res) for r in case_refs()) + tuple(HalfRef(c, *make_case(rng, *c[:7], c[8])) for c in HALF_CASES)
 
 
+# ---- the fused stem kernels -----------------------------------------------------------------------------------------------------------
+# conv_stem2.hip (detector layers 0 + 1), conv_block1.hip (first residual block), conv_first.hip (ReID stem conv + max-pool, and the
+# direct first layer).  Each is a composition; a mutant rounds ONE operand of ONE stage and is carried through the whole composition
+# in float64.  Operands (N(m, v) = mean, VARIANCE): images U(0, 1) RGB with channel 3 zero, "u8" cases quantised to k / 255; block
+# input N(0, 1); weights N(0, 2 / K), the 3x3 of the block - the conv whose result the shortcut is added to - at a quarter of that
+# variance; biases N(0, 0.5).
+FUSED_KINDS = {"stem2": 0, "block1": 1, "pool": 2}          # yds_conv_run_fused's `kind`; "direct" goes through yds_conv_run
+FUSED_SEEDS = {"stem2": 71, "block1": 73, "pool": 79, "direct": 83}
+FUSED_CASES = {  # n, h, w (of the kernel's input), act, filters of the direct kernel, "u8" = an image quantised to k / 255
+    "stem2": [(n, h, w, act, 0, "") for (n, h, w) in ((1, 16, 32), (2, 37, 45), (1, 3, 5), (1, 2, 1), (5, 96, 320)) for act in ("leaky", "mish")]
+             + [(2, 37, 45, "leaky", 0, "u8")],
+    "block1": [(n, h, w, act, 0, "") for (n, h, w) in ((1, 8, 16), (2, 19, 27), (1, 3, 5), (1, 1, 1), (3, 80, 176)) for act in ("leaky", "mish")],
+    "pool": [(n, h, w, act, 0, "") for (n, h, w) in ((2, 128, 64), (1, 37, 45), (1, 3, 5), (1, 1, 1), (12, 128, 64)) for act in ("relu", "leaky")]
+            + [(2, 128, 64, "relu", 0, "u8")],
+    "direct": [(n, h, w, act, cout, "") for cout in (32, 64)
+               for (n, h, w, act) in ((1, 8, 32, "leaky"), (1, 1, 1, "mish"), (2, 19, 45, "linear"), (2, 19, 45, "leaky"), (2, 19, 45, "mish"), (2, 19, 45, "relu"))]
+              + [(2, 19, 45, "leaky", 32, "u8"), (2, 520, 520, "leaky", 32, "")],          # 2210 tiles of 8 x 32 against a grid of 2048
+}
+
+
+def h16_round(v):
+    """a float64 value as an H16 record keeps it: hi + lo, both fp16 (split_x)"""
+    hi, lo = split_x(v)
+    return hi + lo
+
+
+def emu_pre(x, w, k, s):
+    """the bare convolution as the three-term split product, accumulated exactly: the operands are split here, so an intermediate
+    handed from stage to stage is re-split to hi + lo as the kernels' LDS rows hold it"""
+    xh, xl = split_x(x)
+    wh, wl = split_w(w)
+    return conv_pre(xh, wh, k, s) + conv_pre(xh, wl, k, s) + conv_pre(xl, wh, k, s)
+
+
+def pool_ref(c):
+    """MaxPool2d(3, 2, 1) with -inf padding on an NHWC tensor, float64"""
+    n, h, w, ch = c.shape
+    hp, wp = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    p = np.full((n, 2 * hp + 1, 2 * wp + 1, ch), -np.inf)
+    p[:, 1:1 + h, 1:1 + w] = c
+    out = np.full((n, hp, wp, ch), -np.inf)
+    for dy in range(3):
+        for dx in range(3):
+            out = np.maximum(out, p[:, dy:dy + 2 * hp:2, dx:dx + 2 * wp:2])
+    return out
+
+
+_ID = ("x", "wa", "h", "wb", "res", "y")
+
+
+def fused_eval(kind, x, wa, ba, wb, bb, act, pre=conv_pre, m=None):
+    """One fused kernel's composition -> NCHW float64.  `pre` evaluates each bare convolution; m maps an operand's name - x, wa
+    (first conv's weights), h (the intermediate), wb, res (the shortcut's read of x), y (the result) - to what a mutant does to it."""
+    m = m or {}
+    assert set(m) <= set(_ID), m
+    f = {k: m.get(k) or (lambda v: v) for k in _ID}
+    nhwc = lambda y: y.transpose(0, 2, 3, 1)
+    if kind == "stem2":
+        h = nhwc(epilogue(pre(f["x"](x), f["wa"](wa), 3, 1), ba, act, None, 0))
+        y = epilogue(pre(f["h"](h), f["wb"](wb), 3, 2), bb, act, None, 0)
+    elif kind == "block1":
+        h = nhwc(epilogue(pre(f["x"](x), f["wa"](wa), 1, 1), ba, act, None, 0))
+        y = epilogue(pre(f["h"](h), f["wb"](wb), 3, 1), bb, act, f["res"](np.asarray(x, np.float64)), 1)
+    elif kind == "pool":
+        y = pool_ref(nhwc(epilogue(pre(f["x"](x), f["wa"](wa), 3, 1), ba, act, None, 0))).transpose(0, 3, 1, 2)
+    else:
+        assert kind == "direct", kind
+        y = epilogue(pre(f["x"](x), f["wa"](wa), 3, 1), ba, act, None, 0)
+    return f["y"](y)
+
+
+FUSED_MUTANTS = {  # name -> (operand, what the kernel would read instead): one lost lo half each
+    "stem2": {"x": x_hat, "wa": w_hat, "h": x_hat, "wb": w_hat, "y": x_hat},
+    "block1": {"x": x_hat, "wa": w_hat, "h": x_hat, "wb": w_hat, "y": x_hat, "res": x_hat},
+    "pool": {"x": x_hat, "wa": w_hat, "y": x_hat},
+    "direct": {"x": x_hat, "wa": w_hat, "y": x_hat},
+}
+
+
+def make_fused_case(rng, kind, n, h, w, cout, u8):
+    """the operands of one FUSED_CASES entry (module comment above): x NHWC, (wa, ba), (wb, bb) or (None, None)"""
+    gauss = lambda var, *shape: (rng.standard_normal(shape) * np.sqrt(var)).astype(F32)
+    if kind == "block1":
+        x = rng.standard_normal((n, h, w, 64)).astype(F32)
+        return x, gauss(2 / 64, 32, 64), gauss(0.5, 32), gauss(2 / 288 / 4, 64, 288), gauss(0.5, 64)
+    x = np.zeros((n, h, w, 4), F32)
+    x[..., :3] = rng.uniform(0, 1, (n, h, w, 3))
+    if u8:
+        x = (np.round(x * 255) / np.float32(255)).astype(F32)
+    if kind == "stem2":
+        return x, gauss(2 / 36, 32, 36), gauss(0.5, 32), gauss(2 / 288, 64, 288), gauss(0.5, 64)
+    c = 64 if kind == "pool" else cout
+    return x, gauss(2 / 36, c, 36), gauss(0.5, c), None, None
+
+
+class FusedRef:
+    """One fused case: operands, the float64 composition `want`, its `scale`, `mut` = the smallest error of FUSED_MUTANTS[kind]
+    (`mutant_err` by name; `mutant(name)` evaluates one again), and `err_fp32`, the composition with fp32_pre for each convolution."""
+
+    def __init__(self, kind, case, x, wa, ba, wb, bb):
+        self.kind, self.case = kind, case
+        self.x, self.wa, self.ba, self.wb, self.bb = x, wa, ba, wb, bb
+        self.act = ACT[case[3]]
+        self.want = fused_eval(kind, x, wa, ba, wb, bb, self.act)
+        self.scale = float(np.abs(self.want).max())
+        self.mutant_err = {nme: self.err(self.mutant(nme)) for nme in FUSED_MUTANTS[kind]}
+        self.mut = float(min(self.mutant_err.values()))
+        self.err_fp32 = self.err(self.fp32())
+        for a in (x, wa, ba, wb, bb, self.want):
+            if a is not None:
+                a.setflags(write=False)
+
+    def err(self, got):
+        return float(np.abs(got - self.want).max())
+
+    def mutant(self, name):
+        if name == "y":
+            return x_hat(self.want)
+        return fused_eval(self.kind, self.x, self.wa, self.ba, self.wb, self.bb, self.act, m={name: FUSED_MUTANTS[self.kind][name]})
+
+    def fp32(self):
+        """every convolution in fp32 on the CPU, the rest in float64, rounded to fp32"""
+        return fused_eval(self.kind, self.x, self.wa, self.ba, self.wb, self.bb, self.act, pre=fp32_pre).astype(F32).astype(np.float64)
+
+    def emulated(self):
+        """the three-term arithmetic with exact accumulation: the intermediate re-split between the stages, the shortcut and the
+        result as an H16 tensor holds them"""
+        return fused_eval(self.kind, self.x, self.wa, self.ba, self.wb, self.bb, self.act, pre=emu_pre, m={"res": h16_round, "y": h16_round})
+
+
+@functools.lru_cache(maxsize=None)
+def fused_refs(kind):
+    """FusedRef of every entry of FUSED_CASES[kind] (one RandomState(FUSED_SEEDS[kind]) stream in list order); once per process"""
+    rng = np.random.RandomState(FUSED_SEEDS[kind])
+    return tuple(FusedRef(kind, c, *make_fused_case(rng, kind, c[0], c[1], c[2], c[4], c[5])) for c in FUSED_CASES[kind])
+
+
+# ---- the fused kernels in half mode: stage one exact in every arithmetic -----------------------------------------------------------
+# The HALF instantiations round the LDS intermediate to its hi half, a discontinuous step that no composed reference pins on generic
+# operands (test_gpu_conv_fused.py's docstring).  Here stage one is exact instead: small dyadic inputs and weights and a bias that keeps
+# every intermediate positive (leaky = identity) on a grid that fp16(h / 256) holds exactly.  Stage two then is a plain half-mode conv.
+FUSED_HALF_CASES = [  # kind, n, h, w
+    ("stem2", 1, 16, 32), ("stem2", 2, 37, 45), ("block1", 1, 8, 16), ("block1", 2, 19, 27),
+]
+
+
+class FusedHalfRef:
+    """operands of one FUSED_HALF_CASES entry, the exact intermediate `h` (NHWC) and, per tensor format, the half-mode _Arith:
+    want = stage two on h with w_hat(wb) in float64 (shortcut x_hat(x) where the tensors are F16), the mutant = stage two with
+    the unrounded wb, fp32 = stage two with fp32_pre on the rounded operands"""
+
+    def __init__(self, rng, kind, n, h, w):
+        self.kind, self.case, self.act = kind, (kind, n, h, w), ACT["leaky"]
+        if kind == "stem2":
+            self.x = np.zeros((n, h, w, 4), F32)
+            self.x[..., :3] = rng.randint(0, 8, (n, h, w, 3)) / 8
+            self.wa = (rng.randint(-2, 3, (32, 36)) / 4).astype(F32)
+            self.ba = np.full(32, 12, F32)
+            self.wb = (rng.standard_normal((64, 288)) * np.sqrt(2 / 288) / 12).astype(F32)
+        else:
+            self.x = (rng.randint(-4, 5, (n, h, w, 64)) / 4).astype(F32)
+            self.wa = (rng.randint(-2, 3, (32, 64)) / 4).astype(F32)
+            self.ba = np.full(32, 32, F32)
+            self.wb = (rng.standard_normal((64, 288)) * np.sqrt(2 / 288) / 32).astype(F32)
+        self.bb = (rng.standard_normal(64) * np.sqrt(0.5)).astype(F32)
+        self.h = self.stage_one(conv_pre)
+        self._arith = {}
+        for a in (self.x, self.wa, self.ba, self.wb, self.bb, self.h):
+            a.setflags(write=False)
+
+    def stage_one(self, pre):
+        """the intermediate with `pre` for the convolution (3x3 of the stem, 1x1 of the block; stride 1) -> NHWC float64"""
+        return epilogue(pre(self.x, self.wa, 3 if self.kind == "stem2" else 1, 1), self.ba, self.act, None, 0).transpose(0, 2, 3, 1)
+
+    def _stage_two(self, pre, wb, fmt):
+        if self.kind == "stem2":
+            return epilogue(pre(self.h, wb, 3, 2), self.bb, self.act, None, 0)
+        res = x_hat(self.x) if fmt == FMT_F16 else np.asarray(self.x, np.float64)
+        return epilogue(pre(self.h, wb, 3, 1), self.bb, self.act, res, 1)
+
+    def half(self, fmt=FMT_AUTO):
+        fmt = fmt if self.kind == "block1" else FMT_AUTO          # without a shortcut the format changes no operand
+        if fmt not in self._arith:
+            self._arith[fmt] = _Arith(self.case, self._stage_two(conv_pre, w_hat(self.wb), fmt), (self._stage_two(conv_pre, self.wb, fmt),),
+                                      self._stage_two(fp32_pre, w_hat(self.wb), fmt).astype(F32).astype(np.float64))
+        return self._arith[fmt]
+
+
+@functools.lru_cache(maxsize=None)
+def fused_half_refs():
+    rng = np.random.RandomState(89)
+    return tuple(FusedHalfRef(rng, *c) for c in FUSED_HALF_CASES)
+
+
 # ---- host restatement of plan_tile_map (csrc/conv_common.h): the XCD grid with the smallest per-K-step footprint ---------------------
 def plan_tile_map(M, cout, BM, BN):
     """-> (tiles_m, tiles_n, xm, rm, rn)"""

@@ -1,5 +1,5 @@
-"""The conv kernel tests' bound, checked on the CPU: for every case of conv_ref.CASES the reference arithmetic alone separates from
-the mutants that tests/test_gpu_conv_variants.py has to catch.  A case whose data makes mut / 16 meaningless fails here, not on the GPU."""
+"""The conv kernel tests' bound, checked on the CPU: for every case of conv_ref.CASES (and FUSED_CASES, the fused stem kernels' cases) the
+reference arithmetic alone separates from the mutants that tests/test_gpu_conv_variants.py (test_gpu_conv_fused.py) has to catch.  A case whose data makes mut / 16 meaningless fails here, not on the GPU."""
 import numpy as np
 import pytest
 
@@ -92,3 +92,64 @@ def test_half_operands_and_ulp16():
     assert hr.res_mode == 0 and hr.half(R.FMT_F16) is hr.half(R.FMT_AUTO)
     assert R.half_formats((1, 1, 1, 64, 64, 3, 1, "relu", 2)) == [(0, 0), (0, 2), (2, 0), (2, 2)]
     assert R.half_formats((1, 1, 1, 96, 160, 3, 2, "mish", 0)) == [(0, 0)] and R.half_formats((1, 1, 1, 32, 64, 3, 1, "mish", 0)) == [(0, 0), (0, 2)]
+
+
+# ---- the fused stem kernels (tests/test_gpu_conv_fused.py) ----------------------------------------------------------------------------
+_FUSED = [(kind, i) for kind in ("stem2", "block1", "pool", "direct") for i in range(len(R.FUSED_CASES[kind]))]
+
+
+@pytest.mark.parametrize("kind,i", _FUSED, ids=[kind + "-" + "x".join(str(c) for c in R.FUSED_CASES[kind][i] if c != "" and c != 0) for kind, i in _FUSED])
+def test_fused_reference_arithmetic_separates_from_the_mutants(kind, i):
+    """Every case of conv_ref.FUSED_CASES: the three-term composition (exact accumulation, the intermediate re-split to hi + lo
+    between the stages, shortcut and result as H16 holds them) and the plain fp32 CPU composition both sit at or below mut / 64, where
+    mut is the smallest float64 error of the mutants that round one operand of one stage (FUSED_MUTANTS)."""
+    r = R.fused_refs(kind)[i]
+    assert r.case == R.FUSED_CASES[kind][i] and set(r.mutant_err) == set(R.FUSED_MUTANTS[kind])
+    emu = r.err(r.emulated())
+    print(f"{kind} {r.case}: scale {r.scale:.2f} mut {r.mut:.2e} mut/scale {r.mut / r.scale:.1e} | f16x3 emulation mut/{r.mut / max(emu, 1e-30):.0f} "
+          f"fp32 mut/{r.mut / max(r.err_fp32, 1e-30):.0f} | mutants / scale " + ", ".join(f"{k} {v / r.scale:.1e}" for k, v in r.mutant_err.items()))
+    assert r.mut > 0 and np.isfinite(r.mut)
+    assert r.mut < 1e-3 * r.scale          # every mutant's smallest error passes the older bar: only mut / 16 can catch it
+    assert emu <= r.mut / 64, (kind, r.case, emu, r.mut)
+    assert r.err_fp32 <= r.mut / 64, (kind, r.case, r.err_fp32, r.mut)
+    if r.case[5] == "u8":
+        assert np.array_equal(np.round(r.x * 255), r.x * np.float32(255)) and r.x[..., :3].max() > 0.9
+    if kind != "block1":
+        assert not r.x[..., 3].any() and 0 <= r.x.min() and r.x.max() <= 1
+
+
+@pytest.mark.parametrize("kind", ["stem2", "block1", "pool", "direct"])
+def test_fused_hold_fails_on_every_mutant(kind):
+    """What tests/test_gpu_conv_fused.py does with a kernel's output (`_hold`) fails on every mutant tensor of every case - a kernel
+    that loses the lo half of any one operand cannot pass - and accepts both reference arithmetics."""
+    import test_gpu_conv_fused as G
+    for r in R.fused_refs(kind):
+        worst = G._FusedWorst()
+        G._hold(worst, kind, r.case, r.emulated(), r)
+        G._hold(worst, kind, r.case, r.fp32(), r)
+        for name in R.FUSED_MUTANTS[kind]:
+            with pytest.raises(AssertionError, match="above mut / 16"):
+                G._hold(worst, kind, (r.case, name), r.mutant(name), r)
+
+
+def test_fused_half_construction_is_exact():
+    """conv_ref.FusedHalfRef: the intermediate is positive (leaky is the identity), equals its own hi half, and the fp32 pipeline
+    reproduces it bit for bit, so half mode's rounding of the LDS patch changes nothing; stage two in fp32 on the rounded operands sits
+    at or below mut / 64, also beyond half a spacing once stored as F16; `_hold` fails on the mutant."""
+    import test_gpu_conv_fused as G
+    for hr in R.fused_half_refs():
+        assert hr.h.min() > 0 and hr.h.max() < (24 if hr.kind == "stem2" else 64)
+        assert np.array_equal(R.x_hat(hr.h), hr.h) and np.array_equal(R.x_hat(hr.x), hr.x)
+        assert np.array_equal(hr.stage_one(R.fp32_pre), hr.h)
+        assert np.array_equal(hr.stage_one(R.emu_pre), hr.h)
+        for fmt in (R.FMT_AUTO, R.FMT_F16):
+            a = hr.half(fmt)
+            stored = R.x_hat(a.fp32)
+            print(f"{hr.case} fmt {fmt}: scale {a.scale:.2f} mut/scale {a.mut / a.scale:.1e} | fp32 mut/{a.mut / max(a.err_fp32, 1e-30):.0f}, "
+                  f"as F16 beyond half an ulp mut/{a.mut / max(a.err_f16(stored), 1e-30):.0f}")
+            assert 0 < a.mut < 1e-3 * a.scale
+            assert a.err_fp32 <= a.mut / 64 and a.err_f16(stored) <= a.mut / 64, (hr.case, fmt, a.err_fp32, a.mut)
+            mutant = hr._stage_two(R.conv_pre, hr.wb, fmt)
+            for f16 in (False, True):
+                with pytest.raises(AssertionError, match="above mut / 16"):
+                    G._hold(G._FusedWorst(), hr.kind, hr.case, R.x_hat(mutant) if f16 else mutant, a, f16=f16)

@@ -73,6 +73,7 @@ SIGNATURES = {
     "yds_conv_run": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "yds_conv_run_view": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P]),
     "yds_conv_run_half": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "yds_conv_run_fused": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "yds_nms": (_I, [_P, _I, _F, _F, _I, _I, _P, _I, _P]),
     "yds_nms_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),
     "yds_nms_merge_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),

@@ -2,7 +2,7 @@
 // on the caller's tensors (the kernel tests).  Both build the same case - input and residual (pre-split where the kernels take them
 // that way), weights, output - and differ in what they do with the launch.  yds_conv_run_view is yds_conv_run on channel slices of
 // wider buffers and on the merged launch of two convolutions; yds_conv_run_half is that entry in half mode (single-term fp16 operands,
-// optionally 2-byte F16 tensors).
+// optionally 2-byte F16 tensors); yds_conv_run_fused launches the kernels that exist only as fused multi-layer launches.
 #include "conv_common.h"
 #include "conv_weights.h"
 #include "h16.h"
@@ -68,7 +68,8 @@ struct ConvCase {
     // x_nhwc [n, h, w, x_ld], w_okkc [cout][ksize * ksize * cin], bias [cout], res_nhwc [n, ho, wo, r_ld] (read when res_mode): host;
     // vw == nullptr: dense tensors (x_ld = cin, r_ld = cout), the output row padded to a multiple of 4.  With views the output
     // buffers start out filled with `sentinel`.  fmt_x / fmt_y (yds_conv_run_half): 0 = the format picked here (H16 where h16_ok, else
-    // fp32), FMT_F16 = 2-byte activations; the residual and the second output of a merged launch follow fmt_y.
+    // fp32), FMT_F16 = 2-byte activations; the residual and the second output of a merged launch follow fmt_y.  x_nhwc == nullptr: the
+    // input is described (shape, format, ld) but has no storage - the second layer of a fused launch, whose input lives in LDS only.
     ConvCase(int n, int h, int w, int cin, int cout, int ksize, int stride, int act, const float *x_nhwc, const float *w_okkc, const float *bias,
              const float *res_nhwc, int res_mode, const CaseViews *vw = nullptr, float sentinel = 0.f, int fmt_x = 0, int fmt_y = 0) {
         const int pad = (ksize - 1) / 2, ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
@@ -82,7 +83,8 @@ struct ConvCase {
         View x_whole{nullptr, n, h, w, d.x_ld, d.x_ld, fmt_x == FMT_F16 ? FMT_F16 : (f16 && h16_ok(cin, d.x_ld, d.x_off)) ? FMT_H16 : FMT_F32};
         const int yfmt = fmt_y == FMT_F16 ? FMT_F16 : (f16 && h16_ok(c1, d.y_ld, d.y_off) && h16_ok(c2, d.y2_ld, d.y2_off)) ? FMT_H16 : FMT_F32;
         y_whole = View{nullptr, n, ho, wo, d.y_ld, d.y_ld, yfmt};
-        put(x_whole, x_nhwc, raw[0], x);
+        if (x_nhwc) put(x_whole, x_nhwc, raw[0], x);
+        else x_whole.ld = fmt_slots(x_whole.fmt, d.x_ld);
         a.x = slice(x_whole, d.x_off, cin);
         if (vw) {
             const std::vector<float> fill(y_whole.pixels() * (size_t)std::max(d.y_ld, d.y2_ld), sentinel);
@@ -227,6 +229,54 @@ int yds_conv_run_half(int variant, int n, int h, int w, int cin, int cout, int k
     launch_conv(c.a, nullptr, variant);
     nhwc_to_host(view ? c.y_whole : c.a.y, y_nchw, nullptr);
     if (merged) nhwc_to_host(c.y2_whole, y2_nchw, nullptr);
+    YDS_API_END
+}
+
+int yds_conv_run_fused(int kind, int n, int h, int w, int act, int half, int fmt, const float *x_nhwc, const float *w_a, const float *bias_a,
+                       const float *w_b, const float *bias_b, float *y_nchw) {
+    YDS_API_BEGIN
+    using namespace yds;
+    if (kind < 0 || kind > 2) fail("conv_run_fused: kind is 0 (stem2), 1 (block1) or 2 (stem conv + pool), got %d", kind);
+    if (n < 1 || h < 1 || w < 1) fail("conv_run_fused: bad shape %d x %d x %d", n, h, w);
+    if (fmt != 0 && fmt != FMT_F16) fail("conv_run_fused: fmt is 0 (the planner's format) or %d (F16)", (int)FMT_F16);
+    if (kind == 2) {
+        // the ReID stem: 3x3 RGB -> 64, activation, MaxPool(3, 2, 1); the case's output buffer has the convolution's size, the kernel
+        // fills the pooled tensor at its start
+        if (half || fmt) fail("conv_run_fused: the stem conv + pool has no half mode and writes no F16 tensor");
+        ConvCase c(n, h, w, 4, 64, 3, 1, act, x_nhwc, w_a, bias_a, nullptr, RES_NONE);
+        launch_conv_pool(make_conv_args(c.a), nullptr);
+        View pooled = c.a.y;
+        pooled.h = (h - 1) / 2 + 1;
+        pooled.w = (w - 1) / 2 + 1;
+        nhwc_to_host(pooled, y_nchw, nullptr);
+        return 0;
+    }
+    if (conv_math() != MATH_F16X3) fail("conv_run_fused: the fused stem and the fused block are f16x3 kernels (conv math f16x3 required)");
+    if (!w_b || !bias_b) fail("conv_run_fused: kind %d takes two convolutions", kind);
+    if (fmt == FMT_F16 && !half) fail("conv_run_fused: F16 tensors exist in half mode only");
+    const int terms = half ? 1 : 3;
+    if (kind == 0) {
+        // layers 0 + 1 of the detector: the RGB input is fp32, fmt is the output's format
+        ConvCase c0(n, h, w, 4, 32, 3, 1, act, x_nhwc, w_a, bias_a, nullptr, RES_NONE);
+        ConvCase c1(n, h, w, 32, 64, 3, 2, act, nullptr, w_b, bias_b, nullptr, RES_NONE, nullptr, 0.f, 0, fmt);
+        c0.a.terms = c1.a.terms = terms;
+        ConvKernelArgs k0 = make_conv_args(c0.a), k1 = make_conv_args(c1.a);
+        k1.w = reinterpret_cast<const float *>(c1.a.w16);
+        launch_conv_stem2(k0, k1, nullptr);
+        nhwc_to_host(c1.a.y, y_nchw, nullptr);
+    } else {
+        // the first residual block: input, shortcut and output are one format (H16, or F16 in half mode); the shortcut IS the input
+        ConvCase c2(n, h, w, 64, 32, 1, 1, act, x_nhwc, w_a, bias_a, nullptr, RES_NONE, nullptr, 0.f, fmt, 0);
+        ConvCase c3(n, h, w, 32, 64, 3, 1, act, nullptr, w_b, bias_b, nullptr, RES_NONE, nullptr, 0.f, 0, fmt);
+        c3.a.res = c2.a.x;
+        c3.a.res_mode = RES_AFTER_ACT;
+        c2.a.terms = c3.a.terms = terms;
+        ConvKernelArgs k2 = make_conv_args(c2.a), k3 = make_conv_args(c3.a);
+        k2.w = reinterpret_cast<const float *>(c2.a.w16);
+        k3.w = reinterpret_cast<const float *>(c3.a.w16);
+        launch_conv_block1(k2, k3, nullptr);
+        nhwc_to_host(c3.a.y, y_nchw, nullptr);
+    }
     YDS_API_END
 }
 
