@@ -31,6 +31,7 @@ typedef struct yds_net yds_net;     /* Darknet detector      (yolo3/models/model
 typedef struct yds_reid yds_reid;   /* ReID extractor        (deep_sort/deep/feature_extractor.py) */
 typedef struct yds_trk yds_trk;     /* DeepSORT tracker      (deep_sort/sort/tracker.py:8-176)      */
 typedef struct yds_pipe yds_pipe;   /* detect+ReID+associate (yolo3/detect/video_detect.py:134-157) */
+typedef struct yds_zones yds_zones; /* per-stream zone / line tables and counters (no reference counterpart) */
 typedef struct yds_act yds_act;     /* per-stream orbit caches + action predicates (action/action_Identify.py:4-47) */
 typedef struct yds_ident yds_ident; /* cross-camera identity map over S trackers (no reference counterpart)                  */
 typedef struct yds_comm yds_comm;  /* RCCL communicator of the stream-sharded multi-GPU run (no reference counterpart) */
@@ -534,6 +535,77 @@ int yds_actions_last_us(yds_act *, float *us);
 int yds_pipeline_set_actions(yds_pipe *, yds_act *);
 int yds_pipeline_set_frame_times(yds_pipe *, const double *t_host, int n);
 int yds_pipeline_last_actions(yds_pipe *, int32_t *out4_host, int cap, int *n_out);
+
+/* ---- zones and counting lines on the device ------------------------------------------------------------------------------------------
+ * No reference counterpart (the reference has no geometry); yolo_deepsort_amd/zones.py ZoneMonitor restates the rules below in Python
+ * ints and every comparison with it is exact equality: all geometry is int64.
+ * Geometry, per stream, in that stream's frame pixels: at most YDS_ZONE_MAX_ZONES zones - a polygon of 3..YDS_ZONE_MAX_VERTICES
+ *   integer vertices, a class id (-1 = any class), min_sightings in [1, 255] - and at most YDS_ZONE_MAX_LINES lines - two integer points
+ *   A != B and a class id.  Every coordinate lies in [-YDS_ZONE_COORD_LIMIT, YDS_ZONE_COORD_LIMIT].
+ * Anchor: a row x1, y1, x2, y2, id, class gives the DOUBLED foot point X = x1 + x2, Y = 2 * y2 (twice the orbit's foot point, as an
+ *   integer), each component clamped to [-2^24, 2^24]; vertices are doubled before use.
+ * Inside: the even-odd rule over the edges (Vi, Vj), j = i + 1 mod n.  An edge counts only if (yi > Y) != (yj > Y); then
+ *   s = (xj - xi) * (Y - yi) - (X - xi) * (yj - yi) toggles the answer when s > 0 if yj > yi, else when s < 0.  Of an axis-parallel
+ *   square the left edge, the top edge and the top-left vertex are inside, the right and bottom edges and the other vertices outside.
+ * Cross, the move P -> C against a line: with o = the orientation (Vx - Ux) * (Wy - Uy) - (Vy - Uy) * (Wx - Ux) of a triple U, V, W,
+ *   sP = o of A, B, P >= 0 and sC = o of A, B, C >= 0; no crossing if sP == sC; otherwise N, Q = P, C if sC, else C, P, and it is a
+ *   crossing iff (o of N, Q, A >= 0) != (o of N, Q, B >= 0): FORWARD if sC, else BACKWARD.  A point on the line belongs to the >= 0 side
+ *   (for a line drawn left to right: the side below it in the image), the segment contains A and not B, a move along the line or of
+ *   zero length is no crossing, and the crossing of C -> P is always the opposite of that of P -> C.
+ * State: per stream a table in insertion order; an entry holds track id, the class of the registering row, age, the last point and
+ *   its time, and per zone an inside bit, a streak count and an enter time.
+ * One frame of a stream at time t: rows whose id is unknown are registered at the end of the table in row order; then the entries are
+ *   handled in table order.  A SEEN entry with a previous point tests every class-matching line in ascending order (YDS_ZONE_CROSS_FWD /
+ *   _CROSS_BACK); then for every class-matching zone in ascending order now = Inside of its new point: if now differs from the
+ *   inside bit the streak grows by one and, on reaching min_sightings, the bit flips and the streak returns to 0 - a flip to inside
+ *   stores t as the enter time (YDS_ZONE_ENTER), a flip to outside emits YDS_ZONE_EXIT with dwell = t - enter time - and if now equals
+ *   the bit the streak returns to 0; point and t are stored, age = 0.  A registering row is its first sighting: no line test, bits
+ *   outside, so with min_sightings = 1 a track first seen inside a zone enters at once.  An UNSEEN entry ages; at age >= max_age it
+ *   emits YDS_ZONE_LOST for every zone whose bit is set, in ascending order, with dwell = its last seen time - enter time, and leaves
+ *   the table, the others keeping their order.
+ * Events: int32 [m][6] = frame tag, track id, class id, kind, zone or line index, 0 and double [m][2] = t, dwell (0 unless the kind
+ *   is EXIT or LOST); frames in the order given, within a frame entry-major, per entry lines before zones.
+ * Counters: int32, per stream, cumulative since creation or reset, kept on the device: per zone occupancy, entries, exits, lost; per
+ *   line forward, backward.  Dwell sums are not kept (a double sum depends on its order): the host sums the events' dwell values.
+ * yds_zones_create     <- the tables of n_streams streams in HBM, no zones and no lines yet; max_age >= 1.
+ * yds_zones_set_stream <- the geometry of one stream (-1: of all), uploaded once: zone z holds vertices [zone_ptr[z], zone_ptr[z + 1])
+ *                         of zone_xy [V][2]; line_xy [L][4] = Ax, Ay, Bx, By.  Resets that stream's table and counters.  Geometry
+ *                         outside the limits above is refused with a message, before anything is uploaded.
+ * yds_zones_reset      <- an empty table and zero counters for one stream, or all of them (-1).
+ * yds_zones_update     <- n_frames frames in ONE launch and one synchronisation: frame f belongs to stream stream_of[f], holds rows
+ *                         [first[f], first[f + 1]) of rows6_host and carries time frame_time[f]; the tag of its events is f.  One
+ *                         workgroup per stream that has frames walks them in the order given; a stream without frames is untouched.
+ *                         An id twice in one frame is refused; more than cap events is an error naming the count (the tables have
+ *                         advanced).
+ * yds_zones_get_counts <- zone4 [Z][4] and line2 [L][2] of one stream.
+ * yds_zones_get_tracks <- the table of one stream in insertion order: ids, ages, inside bits (bit z: zone z; tests, debugging).
+ * yds_zones_set_timing / _last_us: measurement aid - HIP events around the launch; device time of the last one in us. */
+enum { YDS_ZONE_ENTER = 0, YDS_ZONE_EXIT = 1, YDS_ZONE_LOST = 2, YDS_ZONE_CROSS_FWD = 3, YDS_ZONE_CROSS_BACK = 4 };
+#define YDS_ZONE_MAX_ZONES 32
+#define YDS_ZONE_MAX_LINES 32
+#define YDS_ZONE_MAX_VERTICES 16
+#define YDS_ZONE_COORD_LIMIT (1 << 20)
+yds_zones *yds_zones_create(int n_streams, int max_age);
+void yds_zones_destroy(yds_zones *);
+int yds_zones_set_stream(yds_zones *, int stream, const int32_t *zone_ptr, const int32_t *zone_xy, const int32_t *zone_class,
+                         const int32_t *zone_min_sightings, int n_zones, const int32_t *line_xy, const int32_t *line_class, int n_lines);
+int yds_zones_reset(yds_zones *, int stream);
+int yds_zones_update(yds_zones *, const int32_t *rows6_host, const int32_t *first, const int32_t *stream_of, const double *frame_time,
+                     int n_frames, int32_t *ev6_host, double *evt2_host, int cap, int *n_out);
+int yds_zones_get_counts(yds_zones *, int stream, int32_t *zone4, int32_t *line2);
+int yds_zones_get_tracks(yds_zones *, int stream, int32_t *ids, int32_t *ages, int32_t *inside_mask, int cap, int *n);
+int yds_zones_set_timing(yds_zones *, int on);
+int yds_zones_last_us(yds_zones *, float *us);
+/* The zone stage inside a pipeline step.
+ * yds_pipeline_set_zones: with a handle of at least as many streams as the pipeline, every step adds ONE launch behind the action
+ *   launch (if there is one), ahead of the identity collect launch and of the step's one synchronisation; it reads each frame's rows
+ *   from the tracker's result block, in the stream's own frame pixels in every entry (uniform, mixed sizes, windows).  Frame times as
+ *   for the action stage (yds_pipeline_set_frame_times, else k / 25.0).  A frame the tracker was not called for is not seen; a frame
+ *   with zero rows ages every entry of its stream.  NULL switches the stage off; without it a step runs the launches it always ran.
+ *   Refused while a look-ahead pass is in flight and for a handle of fewer streams than the pipeline.
+ * yds_pipeline_last_zone_events: the events of the last step (the tag is the frame of the step), already on the host. */
+int yds_pipeline_set_zones(yds_pipe *, yds_zones *);
+int yds_pipeline_last_zone_events(yds_pipe *, int32_t *ev6_host, double *evt2_host, int cap, int *n_out);
 
 /* ---- cross-camera identities: one global id per person, kept on the device ---------------------------------------------------------
  * No reference counterpart (the reference tracks one camera); tests/identity_ref.py restates the rules below in numpy / scipy.

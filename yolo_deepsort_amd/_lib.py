@@ -189,6 +189,17 @@ SIGNATURES = {
     "yds_identity_last_memory_counts": (_I, [_P, _P]),
     "yds_pipeline_set_identities": (_I, [_P, _P]),
     "yds_pipeline_last_identities": (_I, [_P, _I, _P, _P, _I, _P]),
+    "yds_zones_create": (_P, [_I, _I]),
+    "yds_zones_destroy": (None, [_P]),
+    "yds_zones_set_stream": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I]),
+    "yds_zones_reset": (_I, [_P, _I]),
+    "yds_zones_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "yds_zones_get_counts": (_I, [_P, _I, _P, _P]),
+    "yds_zones_get_tracks": (_I, [_P, _I, _P, _P, _P, _I, _P]),
+    "yds_zones_set_timing": (_I, [_P, _I]),
+    "yds_zones_last_us": (_I, [_P, _P]),
+    "yds_pipeline_set_zones": (_I, [_P, _P]),
+    "yds_pipeline_last_zone_events": (_I, [_P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -292,6 +292,22 @@ struct ActionsIface {
     std::vector<int32_t> rows4, first;
 };
 
+// --------------------------------------------------------------------------------------------- zones
+// Implemented in zones.hip: per stream a table of tracks with, per zone, an inside bit, a debounce streak and an enter time, advanced
+// over the frames of a call by ONE launch over the same frame descriptors as the action stage (row_time is not read: every row of a
+// frame carries the frame's time t).
+struct ZonesIface {
+    virtual ~ZonesIface() {}
+    virtual int streams() const = 0;
+    // asynchronous on s: grows the tables, one launch; the events land in pinned host memory
+    virtual void enqueue(const ActFrame *fr, int n, hipStream_t s) = 0;
+    // after the caller synchronised s: the events of that call, frame k = events [first[k], first[k + 1]) of ev6 (tag, id, class, kind,
+    // zone or line, 0) and evt2 (t, dwell)
+    virtual void collect() = 0;
+    std::vector<int32_t> ev6, first;
+    std::vector<double> evt2;
+};
+
 // --------------------------------------------------------------------------------------------- tracker
 // Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
 // What a reader of a tracker's appearance galleries needs (gallery_search.hip): device pointers into the tracker's own state, valid
@@ -348,6 +364,9 @@ struct TrackerGroupIface {
     // the action stage of the NEXT step_batch (nullptr: none): one more launch behind the last round, before the step's one
     // synchronisation; frame_times[b] = time of frame b of that step.  Cleared by the step.
     virtual void set_actions(ActionsIface *act, const double *frame_times) = 0;
+    // the zone stage of the NEXT step_batch (nullptr: none): one more launch behind the action launch (if there is one), ahead of the
+    // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
+    virtual void set_zones(ZonesIface *zones, const double *frame_times) = 0;
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
     // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)
@@ -363,3 +382,4 @@ struct yds_reid { yds::ReidNet *r; };
 struct yds_trk { yds::TrackerIface *t; };
 struct yds_act { yds::ActionsIface *a; };
 struct yds_ident { yds::IdentityIface *i; };
+struct yds_zones { yds::ZonesIface *z; };

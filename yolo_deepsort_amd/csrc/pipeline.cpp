@@ -569,25 +569,30 @@ public:
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
         if (!multi) stream_of.assign(batch, 0);
-        // the action stage (set_actions): frame b carries the caller's time for it, else its stream's frame count / 25
+        // the action and zone stages (set_actions, set_zones): frame b carries the caller's time for it, else its stream's frame
+        // count / 25
         std::vector<double> times;
         if ((int)frames_seen.size() < (int)trks.size()) frames_seen.resize(trks.size(), 0);
         const std::vector<double> given = std::move(next_times);      // (they name this step's frames, whatever becomes of it)
         next_times.clear();
-        if (actions) {
+        if (actions || zones) {
             if (!given.empty() && (int)given.size() != batch)
                 fail("pipeline: %zu frame times for a step of %d frames (yds_pipeline_set_frame_times)", given.size(), batch);
             times.resize(batch);
             std::vector<int64_t> seen(frames_seen);
             for (int b = 0; b < batch; ++b) times[b] = given.empty() ? (double)seen[stream_of[b]]++ / 25.0 : given[b];
-            group->set_actions(actions, times.data());
+            if (actions) group->set_actions(actions, times.data());
+            if (zones) group->set_zones(zones, times.data());
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
         last_actions.clear();
+        last_zone_ev6.clear();
+        last_zone_evt2.clear();
         if (identities) group->set_identities(identities);
         group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
                           cur.payload.data(), skip.data(), out6, cap, counts);
         if (actions) last_actions = actions->rows4;
+        if (zones) { last_zone_ev6 = zones->ev6; last_zone_evt2 = zones->evt2; }
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
@@ -612,6 +617,17 @@ public:
         actions = a;
         last_actions.clear();
     }
+    // ---- the zone stage (yds_pipeline_set_zones): zones and counting lines of every stream, in that stream's own frame pixels ----
+    void set_zones(ZonesIface *z) {
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_zones while a look-ahead pass is in flight (consume it with a step first)");
+        if (z && z->streams() < (int)trks.size()) fail("pipeline: a zones handle of %d streams for a pipeline of %zu", z->streams(), trks.size());
+        zones = z;
+        last_zone_ev6.clear();
+        last_zone_evt2.clear();
+    }
+    ZonesIface *zones = nullptr;
+    std::vector<int32_t> last_zone_ev6;           // zone events of the last step [m][6]: frame of the step, id, class, kind, zone or line, 0
+    std::vector<double> last_zone_evt2;           //                              [m][2]: t, dwell
     // ---- the identity stage (yds_pipeline_set_identities): global ids over the streams' trackers, updated behind every step ----
     void set_identities(IdentityIface *i) {
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_identities while a look-ahead pass is in flight (consume it with a step first)");
@@ -797,6 +813,23 @@ int yds_pipeline_last_actions(yds_pipe *p, int32_t *out4_host, int cap, int *n_o
     if (n_out) *n_out = m;
     if (m > cap) yds::fail("pipeline: %d action rows exceed the caller's capacity %d", m, cap);
     if (m) memcpy(out4_host, r.data(), r.size() * sizeof(int32_t));
+    YDS_API_END
+}
+int yds_pipeline_set_zones(yds_pipe *p, yds_zones *z) {
+    YDS_API_BEGIN
+    p->p->set_zones(z ? z->z : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_last_zone_events(yds_pipe *p, int32_t *ev6_host, double *evt2_host, int cap, int *n_out) {
+    YDS_API_BEGIN
+    const std::vector<int32_t> &r = p->p->last_zone_ev6;
+    const int m = (int)(r.size() / 6);
+    if (n_out) *n_out = m;
+    if (m > cap) yds::fail("pipeline: %d zone events exceed the caller's capacity %d", m, cap);
+    if (m) {
+        memcpy(ev6_host, r.data(), r.size() * sizeof(int32_t));
+        memcpy(evt2_host, p->p->last_zone_evt2.data(), p->p->last_zone_evt2.size() * sizeof(double));
+    }
     YDS_API_END
 }
 int yds_pipeline_set_identities(yds_pipe *p, yds_ident *i) {

@@ -594,7 +594,7 @@ class VideoDetector:
                 cv2.destroyAllWindows()
 
     def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False,
-                       identity_memory=None):
+                       identity_memory=None, zones=None, zone_max_age=30):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -626,7 +626,13 @@ class VideoDetector:
         track ids stay per stream.  Limits (identity.py): the tracker needs the cosine metric and a finite nn_budget (ValueError
         otherwise); only live tracks hold an identity, unless identity_memory=dict(ids=..., rows=8, ttl=None) gives the map a memory
         of departed identities (identity.IdentityMap's memory_ids / memory_rows / memory_ttl; ValueError without global_ids=True):
-        stream_identity_map() between the yields returns the map itself, for enrol(), memory() and last_relinked()."""
+        stream_identity_map() between the yields returns the map itself, for enrol(), memory() and last_relinked().
+        zones: zones and counting lines ON THE DEVICE inside the step (MultiStreamPipeline.set_zones) - one (zones, lines) pair of
+        zones.Zone / zones.Line lists for all streams, a list with one pair per stream, a zones.ZoneMonitor (its geometry and
+        max_age) or a zones.DeviceZoneMonitor (its geometry and max_age; never its tables): every stream starts with an empty
+        table, entries leave after zone_max_age unseen processed frames, geometry is in the stream's own frame pixels, frame times
+        are those of the action stage.  Read stream_zone_events() and stream_zone_counts() between the yields; the yielded items
+        do not change.  ValueError naming zones for geometry the device refuses."""
         from . import _lib, pipeline as pl
         from .identity import check_memory
         sources = list(sources)
@@ -650,6 +656,16 @@ class VideoDetector:
                 actions_dev = actions_dev.clone(max(len(sources), 1))
             else:
                 actions_dev = self.action_id.to_device(max(len(sources), 1))
+        zones_dev = None
+        if zones is not None:                            # (ValueError naming zones for what the device refuses)
+            from . import zones as zn
+            if isinstance(zones, zn.DeviceZoneMonitor):      # fresh tables, one per stream: never the caller's own
+                if zones.n_streams < len(sources):
+                    raise ValueError("zones: a DeviceZoneMonitor of %d streams for %d sources" % (zones.n_streams, len(sources)))
+                zones, zone_max_age = zones.geometry[:max(len(sources), 1)], zones.max_age
+            elif isinstance(zones, zn.ZoneMonitor):
+                zones, zone_max_age = zones.geometry, zones.max_age
+            zones_dev = zn.DeviceZoneMonitor(zones, zone_max_age, max(len(sources), 1))
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -673,6 +689,9 @@ class VideoDetector:
             pipe.set_actions(actions_dev)
         if global_ids:
             pipe.set_identities(True, **memory)
+        if zones_dev is not None:
+            pipe.set_zones(zones_dev)
+        self._stream_zone_events = [[] for _ in range(S)]
         live = [self._is_live(src) for src in sources]
         n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
@@ -718,13 +737,17 @@ class VideoDetector:
                     if dev is None or dev.nbytes < batch.nbytes:
                         dev = _lib.DeviceBuffer(batch.nbytes)
                     _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
-                    if actions_dev is not None:
+                    if actions_dev is not None or zones_dev is not None:
                         pipe.set_frame_times([t for _, _, p, t in items if p])
                     if mixed_sizes:
                         outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
                     else:
                         outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
                 step_acts = pipe.last_actions() if actions_dev is not None and procs else None
+                if zones_dev is not None:                   # the events of this step's processed frames, per stream in time order
+                    self._stream_zone_events = [[] for _ in range(S)]
+                    for (s, _), evs in zip(procs, pipe.last_zone_events() if procs else []):
+                        self._stream_zone_events[s].append(evs)
                 out, k = [], 0
                 for s, frame, proc, _ in items:
                     if proc:
@@ -766,6 +789,30 @@ class VideoDetector:
         if getattr(pipe, "identities", None) is None:
             raise ValueError("VideoDetector.stream_identities needs detect_streams(..., global_ids=True)")
         return pipe.last_identities(stream)
+
+    def _zones_pipe(self, who):
+        pipe = self._live_streams_pipe(who)
+        if getattr(pipe, "zones", None) is None:
+            raise ValueError("VideoDetector.%s needs detect_streams(..., zones=...)" % who)
+        return pipe
+
+    def stream_zone_events(self, stream=None):
+        """The zone events of the last step of the running detect_streams(zones=...) generator, between two of its yields
+        (ValueError outside, and for a generator started without zones): for ``stream`` one entry per frame of it that the step
+        processed, in time order - that frame's ``[(track_id, class_id, kind, zone or line name, t, dwell), ...]``, None where
+        the detector returned None - or a list of such lists, one per stream; MultiStreamPipeline.last_zone_events."""
+        self._zones_pipe("stream_zone_events")
+        per = self._stream_zone_events
+        if stream is None:
+            return [list(e) for e in per]
+        if int(stream) < 0 or int(stream) >= len(per):
+            raise ValueError("VideoDetector.stream_zone_events: stream %d outside [0, %d)" % (int(stream), len(per)))
+        return list(per[int(stream)])
+
+    def stream_zone_counts(self, stream=None):
+        """The zone and line counters of the running detect_streams(zones=...) generator, between two of its yields (ValueError
+        outside, and for a generator started without zones): MultiStreamPipeline.zone_counts."""
+        return self._zones_pipe("stream_zone_counts").zone_counts(stream)
 
     def stream_identity_map(self):
         """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,

@@ -85,8 +85,10 @@ class Pipeline:
         return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step(
             self._h, frames_dev, next_frames_dev, h, w, batch, out, self.cap, counts))
 
-    def _run(self, n, select_next, call):
-        """One step of n frames: call(out, counts) is the library entry that fills int32 out [n,cap,6] and counts [n]."""
+    def _run(self, n, select_next, call, streams=None):
+        """One step of n frames: call(out, counts) is the library entry that fills int32 out [n,cap,6] and counts [n]; streams: the
+        stream of every frame (a multi-stream step), kept for last_zone_events()."""
+        self._zone_streams = None if streams is None else [int(v) for v in streams]
         out = np.zeros((n, self.cap, 6), np.int32)
         counts = np.zeros(n, np.int32)
         if select_next is not None:
@@ -136,6 +138,52 @@ class Pipeline:
         for r in rows[:n.value]:
             per[int(r[0])].append((int(r[1]), int(r[2]), dev.names[int(r[3])]))
         return per
+
+    def set_zones(self, zones=None, max_age=30):
+        """The zone stage of every following step: ``zones`` is a zones.DeviceZoneMonitor of at least as many streams as the
+        pipeline (its tables are used as they are), a zones.ZoneMonitor (its geometry and max_age go to the device, fresh tables,
+        for every stream), one (zones, lines) pair for all streams or a list with one pair per stream; None switches the stage
+        off.  Geometry is in each stream's own frame pixels.  A step then adds one launch behind the association and
+        ``last_zone_events()`` holds its events; the step's own return value does not change.  ValueError naming zones for
+        anything the device refuses; refused (YdsError) while a look-ahead pass is in flight."""
+        from .zones import as_device_zones
+        dev = None if zones is None else as_device_zones(zones, getattr(self, "n_streams", 1), max_age)
+        _lib.check(_lib.load().yds_pipeline_set_zones(self._h, None if dev is None else dev.handle))
+        self.zones = dev                                    # (keeps the handle alive while the pipeline names it)
+        self._zone_streams = None
+        return dev
+
+    def last_zone_events(self):
+        """Per frame of the last step: ``[(track_id, class_id, kind, zone or line name (index without one), t, dwell), ...]`` as
+        ZoneMonitor.update returns it, ``[]`` where nothing happened, None where the frame's rows were None (the stage did not
+        see that frame).  Already on the host."""
+        dev, counts = getattr(self, "zones", None), getattr(self, "_last_counts", None)
+        if dev is None or counts is None:
+            return None
+        n = C.c_int(0)
+        lib = _lib.load()
+        lib.yds_pipeline_last_zone_events(self._h, None, None, 0, C.byref(n))      # (asks for the count; refuses to copy when it is not 0)
+        ev6, evt2 = np.zeros((max(n.value, 1), 6), np.int32), np.zeros((max(n.value, 1), 2), np.float64)
+        _lib.check(lib.yds_pipeline_last_zone_events(self._h, _lib.ptr(ev6), _lib.ptr(evt2), len(ev6), C.byref(n)))
+        streams = getattr(self, "_zone_streams", None) or [0] * len(counts)
+        per = [None if counts[b] < 0 else [] for b in range(len(counts))]
+        for r, t in zip(ev6[:n.value], evt2[:n.value]):
+            b = int(r[0])
+            per[b] += dev.name_events(streams[b], [r], [t])
+        return per
+
+    def zone_counts(self, stream=None):
+        """(per zone [occupancy, entries, exits, lost], per line [forward, backward]) of ``stream``, read from the device, or a
+        list of such pairs for all streams; None when the stage is off."""
+        dev = getattr(self, "zones", None)
+        if dev is None:
+            return None
+        n = getattr(self, "n_streams", 1)
+        if stream is None:
+            return [dev.counts(s) for s in range(n)] if hasattr(self, "n_streams") else dev.counts(0)
+        if int(stream) < 0 or int(stream) >= n:
+            raise ValueError("zone_counts: stream %d outside [0, %d)" % (int(stream), n))
+        return dev.counts(int(stream))
 
     def _search_trackers(self):
         return getattr(self, "deepsorts", None) or [self.ds]
@@ -290,7 +338,7 @@ class MultiStreamPipeline(Pipeline):
         int32 [m,6] (None when the detector found nothing and that stream's tracker was not called)."""
         s = self._streams(stream_of_frame)
         return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi(
-            self._h, frames_dev, next_frames_dev, h, w, s.size, _lib.ptr(s), out, self.cap, counts))
+            self._h, frames_dev, next_frames_dev, h, w, s.size, _lib.ptr(s), out, self.cap, counts), s)
 
     def step_host(self, frames, stream_of_frame, next_frames=None, select_next=None):
         """frames / next_frames: uint8 [n,h,w,3] HOST arrays, as Pipeline.step_host; frame i of stream stream_of_frame[i]."""
@@ -299,7 +347,7 @@ class MultiStreamPipeline(Pipeline):
         if s.size != n:
             raise ValueError("MultiStreamPipeline: %d frames but %d stream ids" % (n, s.size))
         return self._run(n, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_host(
-            self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, n, _lib.ptr(s), out, self.cap, counts))
+            self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, n, _lib.ptr(s), out, self.cap, counts), s)
 
 
     def _layout(self, n, frame_off, frame_hw):
@@ -316,7 +364,7 @@ class MultiStreamPipeline(Pipeline):
         s = self._streams(stream_of_frame)
         off, hw = self._layout(s.size, frame_off, frame_hw)
         return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_mixed(
-            self._h, frames_dev, next_frames_dev, _lib.ptr(off), _lib.ptr(hw), int(frames_bytes), s.size, _lib.ptr(s), out, self.cap, counts))
+            self._h, frames_dev, next_frames_dev, _lib.ptr(off), _lib.ptr(hw), int(frames_bytes), s.size, _lib.ptr(s), out, self.cap, counts), s)
 
     def step_host_mixed(self, frames, stream_of_frame, next_frames=None, select_next=None):
         """frames: a list of uint8 [h, w, 3] HOST arrays of any sizes, frame i of stream stream_of_frame[i], or the triple
@@ -335,7 +383,7 @@ class MultiStreamPipeline(Pipeline):
         assert block.dtype == np.uint8 and block.flags["C_CONTIGUOUS"]
         self._keep = (block, nxt)
         return self._run(s.size, select_next, lambda out, counts: _lib.load().yds_pipeline_step_multi_mixed_host(
-            self._h, _lib.ptr(block), _lib.ptr(nxt), _lib.ptr(off), _lib.ptr(hw), block.nbytes, s.size, _lib.ptr(s), out, self.cap, counts))
+            self._h, _lib.ptr(block), _lib.ptr(nxt), _lib.ptr(off), _lib.ptr(hw), block.nbytes, s.size, _lib.ptr(s), out, self.cap, counts), s)
 
 
 def conv_timing(net, mode=0):
