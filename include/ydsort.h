@@ -422,6 +422,41 @@ int yds_swap_rb(uint8_t *frames_dev, size_t pixels);
 int yds_overlay_tracks_bgr(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
                            const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host,
                            const uint8_t *font_host, int n_glyphs, int thickness, int scale, uint8_t *out_host);
+/* ---- anonymised output (yolo_deepsort_amd/privacy.py is the definition; csrc/anonymize.hip) ---------------------------------------
+ * The two entries above with a MASK that is applied before anything is drawn: order = mask, then outlines / plates / text, then
+ * the FPS text.  rects_host [total][4] int32 = xa, ya, xb, yb: a rectangle covers rows [max(ya,0), min(yb+1,h)) and columns
+ * [max(xa,0), min(xb+1,w)) (the filled rectangle of label_draw.py); rect_ptr_host [n_out + 1]: rectangles of output frame i =
+ * [rect_ptr[i], rect_ptr[i+1]), any count; U = their union.  mask_mode 1 = pixelate: cells of mask_block x mask_block pixels
+ * (2..64) anchored at the frame's origin, edge cells partial; per channel v = (2 S + cnt) / (2 cnt), S = the sum of the ORIGINAL
+ * values of the whole cell, cnt its pixels; every pixel of cell & U takes v.  2 = fill: every pixel of U takes mask_color
+ * (c0 | c1 << 8 | c2 << 16 in the RGB image's channel order, like a box colour).  0 = no mask: exactly the entries above (which
+ * forward here with no mask and launch nothing more than they did).  Results do not depend on the order or overlap of the
+ * rectangles.  A call whose rectangles touch no frame launches no mask kernel; otherwise one launch on the overlay's stream - on
+ * out_dev behind the reversed copy (yds_overlay_tracks_masked), in place on the staged slots (yds_overlay_tracks_bgr_masked).
+ * Both take the staged frame count n_src >= 1 and range-check every slot against it. */
+int yds_overlay_tracks_masked(const uint8_t *frames_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w,
+                              const int32_t *boxes_host, const int32_t *box_ptr_host, const uint8_t *text_host, int n_text,
+                              const int32_t *fps_host, const uint8_t *font_host, int n_glyphs, int thickness, int scale,
+                              const int32_t *rects_host, const int32_t *rect_ptr_host, int mask_mode, int mask_block, uint32_t mask_color,
+                              uint8_t *out_dev, uint8_t *out_host);
+int yds_overlay_tracks_bgr_masked(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w,
+                                  const int32_t *boxes_host, const int32_t *box_ptr_host, const uint8_t *text_host, int n_text,
+                                  const int32_t *fps_host, const uint8_t *font_host, int n_glyphs, int thickness, int scale,
+                                  const int32_t *rects_host, const int32_t *rect_ptr_host, int mask_mode, int mask_block,
+                                  uint32_t mask_color, uint8_t *out_host);
+/* The mask alone, IN PLACE on frames resident in HBM (h*w*3 bytes apart) - no overlay, no copy: frame slot_host[i] of the n_src
+ * frames is masked with the rectangles [rect_ptr[i], rect_ptr[i+1]), i in [0, n).  mode 1 | 2 and block as above; color = the three
+ * bytes as they land in memory, byte 0 lowest (the caller knows the frames' channel order).  Slots are range-checked and must be
+ * distinct.  Synchronous, on a stream of its own. */
+int yds_anonymize_frames(uint8_t *frames_dev, int n_src, const int32_t *slot_host, int n, int h, int w, const int32_t *rects_host,
+                         const int32_t *rect_ptr_host, int mode, int block, uint32_t color);
+/* The post-NMS, class-masked detections of the LAST step (every step entry: plain, window, mixed, multi-stream), per frame of the
+ * step, in that frame's own pixels: rows5_host [cap][5] = x, y, w, h, class in frame order, counts_host [frames of the step] =
+ * rows of each frame.  What the tracker was handed - it shows only Confirmed tracks, so a person who has just appeared is in
+ * these rows before any tracker row names them.  A copy of host vectors the step built: no device work, no synchronisation.
+ * counts_host is always filled; the rows are copied when rows5_host is given (NULL: ask for the counts first).  Returns the total
+ * number of rows, or -1 (no step has run; more rows than cap). */
+int yds_pipeline_last_detections(yds_pipe *, float *rows5_host, int cap, int32_t *counts_host);
 /* Per tile-variant totals of the implicit-GEMM conv kernel (yds_conv_num_variants instantiations):
  * duration in us, launch count and algorithmic flops, measured with HIP events recorded around every
  * launch on the handle's stream.  mode 1 = zero the counters and start timing, 2 = stop, 0 = read. */

@@ -200,6 +200,10 @@ SIGNATURES = {
     "yds_zones_last_us": (_I, [_P, _P]),
     "yds_pipeline_set_zones": (_I, [_P, _P]),
     "yds_pipeline_last_zone_events": (_I, [_P, _P, _P, _I, _P]),
+    "yds_overlay_tracks_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P, _P]),
+    "yds_overlay_tracks_bgr_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
+    "yds_anonymize_frames": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32]),
+    "yds_pipeline_last_detections": (_I, [_P, _P, _I, _P]),
 }
 
 _lib = None

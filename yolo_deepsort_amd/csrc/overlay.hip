@@ -8,7 +8,9 @@
 // Pixel semantics are those of label_draw.py in this package (cv2.rectangle geometry, a 5 x 7 bitmap font at an integer pixel
 // scale standing in for cv2's Hershey face), bit for bit: tests/test_gpu_video_detect.py compares the two.
 // Order: boxes are drawn in list order, a later box over an earlier one, exactly like the sequential host loop - one workgroup
-// owns a frame and separates the steps with barriers.
+// owns a frame and separates the steps with barriers.  The masked entries (anonymised output, anonymize.hip) put one launch ahead
+// of the draw kernel on the same stream: mask first, then everything that is drawn.
+#include "anonymize_dev.h"
 #include "common.h"
 
 #include <mutex>
@@ -129,6 +131,7 @@ struct OverlayState {
     hipStream_t stream = nullptr;
     DevBuf<int> boxes, box_ptr, fps, slots;
     DevBuf<uint8_t> text, font;
+    Anonymizer anon;                     // the masked entries: people are pixelated or filled over before anything is drawn (anonymize.hip)
     OverlayState() { YDS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); }
 };
 OverlayState &state() {
@@ -189,42 +192,50 @@ yds::DrawArgs overlay_tables(yds::OverlayState &s, const int32_t *src_slot_host,
     s.font.upload(font_host, (size_t)n_glyphs * 7, s.stream);
     return yds::DrawArgs{s.boxes.p, s.box_ptr.p, s.text.p, s.fps.p, s.font.p, h, w, thickness, scale};
 }
-}  // namespace
 
-int yds_overlay_tracks(const uint8_t *frames_dev, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
-                       const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
-                       int n_glyphs, int thickness, int scale, uint8_t *out_dev, uint8_t *out_host) {
-    YDS_API_BEGIN
-    if (n_out <= 0) return 0;
+// The mask of a masked entry, checked and turned into its tile list before anything is enqueued (mk NULL or mode 0: no mask).
+// The colour arrives in the RGB image's channel order like the class colours and lands channel-reversed on the BGR result.
+bool overlay_mask(yds::OverlayState &s, const yds::MaskSpec *mk, int n_out, int h, int w) {
+    if (!mk || mk->mode == yds::MASK_NONE) return false;
+    yds::MaskSpec m = *mk;
+    m.color = ((mk->color >> 16) & 0xff) | (mk->color & 0xff00) | ((mk->color & 0xff) << 16);
+    return s.anon.prepare(n_out, h, w, m) > 0;
+}
+
+// both RGB entries: n_src > 0 range-checks the slots (the masked entry), 0 does not (the entry of round 5, which never knew the count)
+void overlay_rgb(const uint8_t *frames_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                 const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
+                 int n_glyphs, int thickness, int scale, const yds::MaskSpec *mk, uint8_t *out_dev, uint8_t *out_host) {
     if (!frames_dev || !out_dev) yds::fail("overlay: NULL argument");
     yds::OverlayState &s = yds::state();
     std::lock_guard<std::mutex> lock(s.mu);                      // held until the stream has drained: the scratch is shared
-    const yds::DrawArgs a = overlay_tables(s, src_slot_host, 0, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness, scale);
+    const bool masked = overlay_mask(s, mk, n_out, h, w);
+    const yds::DrawArgs a = overlay_tables(s, src_slot_host, n_src, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness, scale);
     const size_t frame_bytes = (size_t)h * w * 3;
     const int aligned = frame_bytes % 12 == 0 && ((uintptr_t)frames_dev % 4) == 0 && ((uintptr_t)out_dev % 4) == 0;
     const unsigned bx = (unsigned)std::min<size_t>((frame_bytes / 12 + 255) / 256 + 1, 2048);
     yds::overlay_copy_kernel<<<dim3(bx, n_out), 256, 0, s.stream>>>(frames_dev, s.slots.p, out_dev, frame_bytes, aligned);
     YDS_HIP(hipGetLastError());
+    if (masked) s.anon.launch(s.stream, out_dev, frame_bytes, nullptr);      // on the BGR copies, ahead of everything that is drawn
     yds::overlay_draw_kernel<<<n_out, 256, 0, s.stream>>>(out_dev, frame_bytes, a, nullptr);
     YDS_HIP(hipGetLastError());
     if (out_host) YDS_HIP(hipMemcpyAsync(out_host, out_dev, frame_bytes * n_out, hipMemcpyDeviceToHost, s.stream));
     YDS_HIP(hipStreamSynchronize(s.stream));
-    YDS_API_END
 }
 
-int yds_overlay_tracks_bgr(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
-                           const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
-                           int n_glyphs, int thickness, int scale, uint8_t *out_host) {
-    YDS_API_BEGIN
-    if (n_out <= 0) return 0;
+void overlay_bgr(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                 const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
+                 int n_glyphs, int thickness, int scale, const yds::MaskSpec *mk, uint8_t *out_host) {
     if (!frames_bgr_dev || !out_host || n_src < 1) yds::fail("overlay: NULL argument");
     yds::OverlayState &s = yds::state();
     std::lock_guard<std::mutex> lock(s.mu);
+    const bool masked = overlay_mask(s, mk, n_out, h, w);
     const yds::DrawArgs a = overlay_tables(s, src_slot_host, n_src, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness, scale);
     for (int i = 0; i < n_out; ++i)
         for (int j = 0; j < i; ++j)
             if (src_slot_host[i] == src_slot_host[j]) yds::fail("overlay: frames %d and %d would be drawn on the same staged slot %d", j, i, src_slot_host[i]);
     const size_t frame_bytes = (size_t)h * w * 3;
+    if (masked) s.anon.launch(s.stream, frames_bgr_dev, frame_bytes, s.slots.p);   // in place, ahead of everything that is drawn
     yds::overlay_draw_kernel<<<n_out, 256, 0, s.stream>>>(frames_bgr_dev, frame_bytes, a, s.slots.p);
     YDS_HIP(hipGetLastError());
     // results leave in the caller's frame order: runs of consecutive slots go out as one copy (all of them when every frame was processed)
@@ -236,6 +247,58 @@ int yds_overlay_tracks_bgr(uint8_t *frames_bgr_dev, int n_src, const int32_t *sr
         i = j;
     }
     YDS_HIP(hipStreamSynchronize(s.stream));
+}
+
+void mask_spec(yds::MaskSpec &mk, const int32_t *rects_host, const int32_t *rect_ptr_host, int mode, int block, uint32_t color) {
+    if (mode != yds::MASK_NONE && mode != yds::MASK_PIXELATE && mode != yds::MASK_FILL) yds::fail("overlay: mask mode %d (0 = none, 1 = pixelate, 2 = fill)", mode);
+    mk.rects_host = rects_host; mk.rect_ptr_host = rect_ptr_host; mk.mode = mode; mk.block = block; mk.color = color;
+}
+}  // namespace
+
+int yds_overlay_tracks(const uint8_t *frames_dev, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                       const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
+                       int n_glyphs, int thickness, int scale, uint8_t *out_dev, uint8_t *out_host) {
+    YDS_API_BEGIN
+    if (n_out <= 0) return 0;
+    overlay_rgb(frames_dev, 0, src_slot_host, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness, scale,
+                nullptr, out_dev, out_host);
+    YDS_API_END
+}
+
+int yds_overlay_tracks_bgr(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                           const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
+                           int n_glyphs, int thickness, int scale, uint8_t *out_host) {
+    YDS_API_BEGIN
+    if (n_out <= 0) return 0;
+    overlay_bgr(frames_bgr_dev, n_src, src_slot_host, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness,
+                scale, nullptr, out_host);
+    YDS_API_END
+}
+
+int yds_overlay_tracks_masked(const uint8_t *frames_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                              const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host, const uint8_t *font_host,
+                              int n_glyphs, int thickness, int scale, const int32_t *rects_host, const int32_t *rect_ptr_host, int mask_mode,
+                              int mask_block, uint32_t mask_color, uint8_t *out_dev, uint8_t *out_host) {
+    YDS_API_BEGIN
+    if (n_out <= 0) return 0;
+    if (n_src < 1) yds::fail("overlay: %d staged frames", n_src);
+    yds::MaskSpec mk;
+    mask_spec(mk, rects_host, rect_ptr_host, mask_mode, mask_block, mask_color);
+    overlay_rgb(frames_dev, n_src, src_slot_host, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness, scale,
+                &mk, out_dev, out_host);
+    YDS_API_END
+}
+
+int yds_overlay_tracks_bgr_masked(uint8_t *frames_bgr_dev, int n_src, const int32_t *src_slot_host, int n_out, int h, int w, const int32_t *boxes_host,
+                                  const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host,
+                                  const uint8_t *font_host, int n_glyphs, int thickness, int scale, const int32_t *rects_host,
+                                  const int32_t *rect_ptr_host, int mask_mode, int mask_block, uint32_t mask_color, uint8_t *out_host) {
+    YDS_API_BEGIN
+    if (n_out <= 0) return 0;
+    yds::MaskSpec mk;
+    mask_spec(mk, rects_host, rect_ptr_host, mask_mode, mask_block, mask_color);
+    overlay_bgr(frames_bgr_dev, n_src, src_slot_host, n_out, h, w, boxes_host, box_ptr_host, text_host, n_text, fps_host, font_host, n_glyphs, thickness,
+                scale, &mk, out_host);
     YDS_API_END
 }
 

@@ -815,6 +815,26 @@ int yds_pipeline_last_actions(yds_pipe *p, int32_t *out4_host, int cap, int *n_o
     if (m) memcpy(out4_host, r.data(), r.size() * sizeof(int32_t));
     YDS_API_END
 }
+int yds_pipeline_last_detections(yds_pipe *p, float *rows5_host, int cap, int32_t *counts_host) {
+    try {
+        if (!p || !counts_host) yds::fail("pipeline: NULL argument");
+        const yds::Pipeline::Dets &d = p->p->cur;                 // (finish_detector filled it on the host; the step has returned)
+        if (d.batch < 1) yds::fail("pipeline: no step has run");
+        const int total = (int)d.payload.size();
+        for (int b = 0; b < d.batch; ++b) counts_host[b] = d.first[b + 1] - d.first[b];
+        if (rows5_host) {
+            if (total > cap) yds::fail("pipeline: %d detections exceed the caller's capacity %d", total, cap);
+            for (int i = 0; i < total; ++i) {
+                memcpy(rows5_host + (size_t)i * 5, d.tlwh.data() + (size_t)i * 4, 4 * sizeof(float));
+                rows5_host[(size_t)i * 5 + 4] = d.payload[i];
+            }
+        }
+        return total;
+    } catch (const std::exception &e) {
+        yds::set_error(e.what());
+        return -1;
+    }
+}
 int yds_pipeline_set_zones(yds_pipe *p, yds_zones *z) {
     YDS_API_BEGIN
     p->p->set_zones(z ? z->z : nullptr);

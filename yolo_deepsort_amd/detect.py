@@ -209,7 +209,7 @@ def _transform(frame):
 class VideoDetector:
     def __init__(self, model, class_path, thickness=2, font_path=None, font_size=10, thres=0.7, nms_thres=0.4,
                  skip_frames=-1, fourcc="mp4v", class_mask=None, win_size=None, overlap=0.15, tracker=None,
-                 action_id=None, half=False, batch_frames=None, device_overlay=True, batch_windows=False):
+                 action_id=None, half=False, batch_frames=None, device_overlay=True, batch_windows=False, anonymize=None):
         # batch_frames (not in the reference): with a tracker, read that many frames ahead and run them through the batched device
         # pipeline (csrc/pipeline.cpp) - same results per frame, yielded in order, several times the frame rate of the frame-by-frame
         # path.  None (default, round 5) = by source: AUTO_BATCH frames for a file / an .npy / an iterable of frames - the reference
@@ -219,7 +219,10 @@ class VideoDetector:
         # batch_windows (not in the reference): with win_size set, run the batched pipeline in window mode (pipeline.Pipeline(win_size=...):
         # windows cut, merged and tracked on the device) wherever a detector without win_size would take the batched path.  False
         # (default): a detector with win_size keeps the frame-by-frame loop, as before.
+        # anonymize (not in the reference): a privacy.Anonymize - people are pixelated or filled over in every yielded image BEFORE
+        # anything is drawn on it; the yielded rows and actions do not change.  None (default): off.
         self.batch_windows = bool(batch_windows)
+        self.anonymize = anonymize
         self.batch_frames = None if batch_frames is None else max(1, int(batch_frames))
         self.device_overlay = bool(device_overlay) and not os.environ.get("YDS_HOST_OVERLAY")
         self._pipe = None
@@ -300,6 +303,7 @@ class VideoDetector:
         :137-154 ran, i.e. the detector returned rows and a tracker is set)."""
         detections = self.image_detector.detect(frame)
         self._tracked = detections is not None and self.tracker is not None
+        self._last_dets = None                                 # x, y, w, h, class of what the tracker is handed (the anonymise option)
         if self._tracked:
             det = detections.numpy() if hasattr(detections, "numpy") else detections
             boxs = p1p2Toxywh(det[:, :4])
@@ -308,6 +312,8 @@ class VideoDetector:
             if self.class_mask is not None:
                 mask = reduce(lambda a, b: a | b, [class_ids == m for m in self.class_mask])
                 boxs, confidences, class_ids = boxs[mask], confidences[mask], class_ids[mask]
+            if getattr(self, "anonymize", None) is not None:
+                self._last_dets = np.concatenate([np.asarray(boxs, np.float32).reshape(-1, 4), np.asarray(class_ids, np.float32).reshape(-1, 1)], 1)
             if hasattr(self.tracker, "extractor"):
                 self.tracker.frame_source = self.image_detector.model       # lets update() crop from the detector's device copy
             detections = self.tracker.update(boxs.astype(np.float32), confidences, frame, class_ids)
@@ -332,11 +338,20 @@ class VideoDetector:
         if group:
             yield group
 
-    def _render_host(self, frame, hold_detections, fps_text):
-        """video_detect.py:161-186 on the host: overlay (on a copy: callers may hand in their own frame arrays), RGB -> BGR, FPS text."""
+    def _render_host(self, frame, hold_detections, fps_text, detections=None):
+        """video_detect.py:161-186 on the host: overlay (on a copy: callers may hand in their own frame arrays), RGB -> BGR, FPS text.
+        With the anonymise option the mask comes first (privacy.anonymize on the copy; detections: the post-NMS rows x, y, w, h,
+        class of the frame the held rows came from), then outlines, plates and text, then the FPS text."""
         image = frame
+        anon = getattr(self, "anonymize", None)
+        if anon is not None:
+            from . import privacy
+            rects = privacy.mask_rects(anon, frame.shape[0], frame.shape[1], hold_detections, detections)
+            if rects:
+                image = privacy.anonymize(frame, rects, anon)
         if hold_detections is not None and len(hold_detections):
-            image = frame.copy()
+            if image is frame:
+                image = frame.copy()
             if self.tracker is not None:
                 self.label_drawer.draw_labels_by_trackers(image, hold_detections, only_rect=False)
             else:
@@ -346,11 +361,11 @@ class VideoDetector:
             put_text(result, fps_text, (3, 15), 2, (255, 0, 0))
         return result
 
-    def _render(self, frame, hold_detections, show_fps):
+    def _render(self, frame, hold_detections, show_fps, detections=None):
         now = time.time()
         text = self._fps_tick(now - self._fps_prev)
         self._fps_prev = now
-        return self._render_host(frame, hold_detections, text if show_fps else None)
+        return self._render_host(frame, hold_detections, text if show_fps else None, detections)
 
     def _fps_tick(self, dt):
         """The FPS counter of video_detect.py:176-182 advanced by one yielded frame that took `dt` seconds; returns the text to show."""
@@ -418,16 +433,20 @@ class VideoDetector:
         """Output stage of one staged batch: a list of BGR frames in group order.  Device form: csrc/overlay.hip over the frames in
         HBM; host form (device_overlay=False / YDS_HOST_OVERLAY: A/B runs and tests): label_draw.py on the staged copy."""
         h, w, n = cur["h"], cur["w"], len(holds)
+        anon = getattr(self, "anonymize", None)
+        dets = cur.get("dets") if anon is not None else None          # per frame: the detections its held rows came with (_run_engine)
         if self.device_overlay:
             from .label_draw import DeviceOverlay
             if getattr(self, "_overlay", None) is None:
                 self._overlay = DeviceOverlay(self.label_drawer)
             return self._overlay.render(cur["blk"]["dev"].offset(0), cur["slot_of"], h, w, holds, fps_texts,
-                                        bgr_frames=cur["blk"].get("n", n) if bgr else 0)
+                                        bgr_frames=cur["blk"].get("n", n) if bgr else 0, privacy=anon, detections=dets,
+                                        n_frames=cur["blk"].get("n", n))
         stage = cur["blk"]["pin"].array[:n * h * w * 3].reshape(n, h, w, 3)
         if bgr:
             stage = stage[..., ::-1]
-        return [self._render_host(np.ascontiguousarray(stage[cur["slot_of"][i]]), holds[i], fps_texts[i] if fps_texts else None) for i in range(n)]
+        return [self._render_host(np.ascontiguousarray(stage[cur["slot_of"][i]]), holds[i], fps_texts[i] if fps_texts else None,
+                                  dets[i] if dets else None) for i in range(n)]
 
     def _detect_batched(self, video_path, show_fps=True, skip_secs=0, batch_frames=None):
         """detect() through the batched pipeline: identical per-frame results, frames are read batch_frames ahead (the reference itself
@@ -518,7 +537,8 @@ class VideoDetector:
                 except queue.Full:
                     pass
         try:
-            hold_detections, actions = None, []
+            hold_detections, actions, hold_dets = None, [], None
+            masking = getattr(self, "anonymize", None) is not None     # the frame's detections travel with its held rows
             u = self.host_us
             t0 = time.perf_counter()
             cur = take()
@@ -532,12 +552,14 @@ class VideoDetector:
                 if n:
                     ahead = nxt["blk"]["dev"].offset(0) if nxt is not None and (nxt["h"], nxt["w"], nxt["n_proc"]) == (h, w, n) else None
                     outs = self._pipe.step(cur["blk"]["dev"].offset(0), h, w, n, ahead)
+                step_dets = self._pipe.last_detections() if masking and n else None
                 u["wait_frames"] += (t1 - t0) * 1e6
                 u["step"] += (time.perf_counter() - t1) * 1e6
-                holds, acts, k = [], [], 0
+                holds, acts, dets, k = [], [], [], 0
                 for proc in cur["flags"]:
                     if proc:
                         o = outs[k]
+                        hold_dets = step_dets[k] if step_dets is not None else None
                         k += 1
                         hold_detections = None if o is None else (o if len(o) else [])
                         if hold_detections is not None:        # video_detect.py:137-154; a detector-None frame leaves `actions` as it was
@@ -546,6 +568,9 @@ class VideoDetector:
                         actions = []                           # :158-159
                     holds.append(hold_detections)
                     acts.append(actions)
+                    dets.append(hold_dets)
+                if masking:
+                    cur["dets"] = dets
                 t2 = time.perf_counter()
                 give((cur, holds, acts))
                 u["wait_consumer"] += (time.perf_counter() - t2) * 1e6
@@ -684,6 +709,7 @@ class VideoDetector:
         lib = _lib.load()
         its = [iter(self._frames(src)) for src in sources]
         since, hold, alive = [0] * S, [None] * S, [True] * S
+        masking, hold_dets = getattr(self, "anonymize", None) is not None, [None] * S      # the anonymise option: rendered on the host here
         shape, dev = None, None
         if actions_dev is not None:
             pipe.set_actions(actions_dev)
@@ -744,6 +770,7 @@ class VideoDetector:
                     else:
                         outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
                 step_acts = pipe.last_actions() if actions_dev is not None and procs else None
+                step_dets = pipe.last_detections() if masking and procs else None
                 if zones_dev is not None:                   # the events of this step's processed frames, per stream in time order
                     self._stream_zone_events = [[] for _ in range(S)]
                     for (s, _), evs in zip(procs, pipe.last_zone_events() if procs else []):
@@ -754,11 +781,13 @@ class VideoDetector:
                         o = outs[k]
                         if step_acts is not None and step_acts[k] is not None:   # a detector-None frame leaves the previous value
                             acts[s] = step_acts[k]
+                        if step_dets is not None:
+                            hold_dets[s] = step_dets[k]
                         k += 1
                         hold[s] = None if o is None else (o if len(o) else [])
                     else:
                         acts[s] = []                        # video_detect.py:158-159
-                    out.append((s, self._render(frame, hold[s], show_fps), hold[s], acts[s]))
+                    out.append((s, self._render(frame, hold[s], show_fps, hold_dets[s]), hold[s], acts[s]))
                 if out:
                     yield out
         finally:
@@ -845,17 +874,18 @@ class VideoDetector:
         if bf > 1 and (self._batchable() or (getattr(self, "batch_windows", False) and self._batchable_windows())):
             yield from self._detect_batched(video_path, show_fps, skip_secs, bf)
             return
-        hold_detections, actions, frames = None, [], 0
+        hold_detections, actions, frames, hold_dets = None, [], 0, None
         for frame in self._frames(video_path, skip_secs):
             if frame is None:
                 break
             if frames % self.skip_frames == 0:
                 hold_detections = self.process(frame)
+                hold_dets = self._last_dets
                 if self._tracked:                          # video_detect.py:137-154; otherwise `actions` keeps its previous value
                     actions = self.action_id.update(hold_detections) if self.action_id is not None else []
                 frames = 0
             else:
                 actions = []
-            result = self._render(frame, hold_detections, show_fps)
+            result = self._render(frame, hold_detections, show_fps, hold_dets)
             frames += 1
             yield result, hold_detections, actions

@@ -210,16 +210,29 @@ class DeviceOverlay:
                 self._labels.clear()
         return codes
 
-    def render(self, frames_dev, src_slots, h, w, holds, fps_texts=None, only_rect=False, bgr_frames=0):
+    def render(self, frames_dev, src_slots, h, w, holds, fps_texts=None, only_rect=False, bgr_frames=0, privacy=None, detections=None,
+               n_frames=None):
         """frames_dev: device pointer of uint8 RGB frames, h*w*3 bytes apart; output i shows frame src_slots[i] with the tracker
         rows holds[i] (int32 [m,6], or None / empty: nothing drawn).  Returns a list of BGR uint8 [h,w,3] arrays (views of one
         pinned block that stays alive as long as any of them does).
         bgr_frames = n > 0: the n staged frames are ALREADY BGR (a decoder's order): they are drawn on in place and copied out - no
-        reversed device copy (yds_overlay_tracks_bgr); the staged frames are consumed."""
+        reversed device copy (yds_overlay_tracks_bgr); the staged frames are consumed.
+        privacy: a privacy.Anonymize - the people of every frame are pixelated or filled over BEFORE anything is drawn
+        (privacy.mask_rects of holds[i] and detections[i], the frame's post-NMS detections [m,5] or None; the masked entries
+        yds_overlay_tracks_masked / _bgr_masked, which range-check the slots against n_frames staged frames - default: bgr_frames,
+        else max slot + 1).  None (default): today's path through today's entries."""
         from . import _lib
         n = len(holds)
         if n == 0:
             return []
+        mask = None
+        if privacy is not None:
+            from . import privacy as pv
+            dets = detections if detections is not None else [None] * n
+            if len(dets) != n:
+                raise ValueError("DeviceOverlay.render: %d detection lists for %d frames" % (len(dets), n))
+            mask = pv.pack_rects([pv.mask_rects(privacy, h, w, holds[i], dets[i]) for i in range(n)]) + pv.device_args(privacy, False)
+            n_src = int(n_frames) if n_frames else (int(bgr_frames) if bgr_frames else int(max(src_slots)) + 1)
         d = self.drawer
         colors, ncol = d.colors, len(d.colors)
         boxes, ptr, texts, toff = [], [0], [], 0
@@ -251,18 +264,26 @@ class DeviceOverlay:
         nbytes = n * h * w * 3
         blk = self._pinned(nbytes)
         scale = max(1, int(round(2 * (h / 1000.))))                      # draw_rects_and_labels' font_size = img.shape[0] / 1000.
+        tables = (_lib.ptr(boxes_a), _lib.ptr(ptr_a), _lib.ptr(text), toff, _lib.ptr(fps), _lib.ptr(self.font), len(self.font),
+                  int(d.thickness), scale)
+        if mask is not None:
+            rect_table, rect_ptr = mask[:2]                                  # (named: alive until the call has returned)
+            mask = (_lib.ptr(rect_table), _lib.ptr(rect_ptr)) + mask[2:]
         if bgr_frames:
-            _lib.check(_lib.load().yds_overlay_tracks_bgr(frames_dev, int(bgr_frames), _lib.ptr(slots), n, h, w, _lib.ptr(boxes_a), _lib.ptr(ptr_a),
-                                                          _lib.ptr(text), toff, _lib.ptr(fps), _lib.ptr(self.font), len(self.font),
-                                                          int(d.thickness), scale, blk.ptr))
+            if mask is None:
+                _lib.check(_lib.load().yds_overlay_tracks_bgr(frames_dev, int(bgr_frames), _lib.ptr(slots), n, h, w, *tables, blk.ptr))
+            else:
+                _lib.check(_lib.load().yds_overlay_tracks_bgr_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, blk.ptr))
             out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
             del blk
             return [out[i] for i in range(n)]
         if self._out_dev is None or self._out_dev.nbytes < nbytes:
             self._out_dev = _lib.DeviceBuffer(nbytes)
-        _lib.check(_lib.load().yds_overlay_tracks(frames_dev, _lib.ptr(slots), n, h, w, _lib.ptr(boxes_a), _lib.ptr(ptr_a), _lib.ptr(text), toff,
-                                                  _lib.ptr(fps), _lib.ptr(self.font), len(self.font), int(d.thickness), scale,
-                                                  self._out_dev.ptr, blk.ptr))
+        if mask is None:
+            _lib.check(_lib.load().yds_overlay_tracks(frames_dev, _lib.ptr(slots), n, h, w, *tables, self._out_dev.ptr, blk.ptr))
+        else:
+            _lib.check(_lib.load().yds_overlay_tracks_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, self._out_dev.ptr,
+                                                             blk.ptr))
         out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
         del blk
         return [out[i] for i in range(n)]

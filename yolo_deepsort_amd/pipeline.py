@@ -139,6 +139,25 @@ class Pipeline:
             per[int(r[0])].append((int(r[1]), int(r[2]), dev.names[int(r[3])]))
         return per
 
+    def last_detections(self):
+        """Per frame of the last step (any step entry: plain, window, mixed, multi-stream): float32 [n, 5] = x, y, w, h, class of the
+        post-NMS, class-masked detections in the frame's own pixels - what the tracker was handed ([0, 5] where the detector
+        returned nothing).  The tracker shows only Confirmed tracks, so a person who has just appeared is in these rows before
+        any tracker row names them (privacy.Anonymize(include_detections=True)).  Already on the host: no device work."""
+        counts = getattr(self, "_last_counts", None)
+        if counts is None:
+            return None
+        lib = _lib.load()
+        per = np.zeros(len(counts), np.int32)
+        total = lib.yds_pipeline_last_detections(self._h, None, 0, _lib.ptr(per))
+        if total < 0:
+            raise _lib.YdsError(_lib.last_error())
+        rows = np.zeros((max(total, 1), 5), np.float32)
+        if lib.yds_pipeline_last_detections(self._h, _lib.ptr(rows), len(rows), _lib.ptr(per)) < 0:
+            raise _lib.YdsError(_lib.last_error())
+        ends = np.cumsum(per)
+        return [rows[e - c:e].copy() for c, e in zip(per.tolist(), ends.tolist())]
+
     def set_zones(self, zones=None, max_age=30):
         """The zone stage of every following step: ``zones`` is a zones.DeviceZoneMonitor of at least as many streams as the
         pipeline (its tables are used as they are), a zones.ZoneMonitor (its geometry and max_age go to the device, fresh tables,
