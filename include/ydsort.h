@@ -112,10 +112,10 @@ int yds_darknet_get_input(yds_net *, int batch, float *nchw_host);              
  *            cap 300; greedy kernel = torchvision.ops.boxes.nms semantics) and
  *            resize_boxes :12-19 when frame_h > 0 (scale to frame pixels).
  * out6: [cap,6] (x1,y1,x2,y2,score,cls) sorted by score; *n_out = rows written (0 <=> None). */
-int yds_nms(yds_net *, int image, float conf_thres, float iou_thres, int frame_h, int frame_w,
+int yds_nms(yds_net *, int image, float conf_thres, double iou_thres, int frame_h, int frame_w,
             float *out6_host, int cap, int *n_out);
 /* same on caller-provided predictions [n_boxes, attrs] (host) */
-int yds_nms_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres,
+int yds_nms_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, double iou_thres,
                  float *out6_host, int cap, int *n_out);
 
 /* ---- sliding-window detection ----------------------------------------
@@ -128,15 +128,15 @@ int yds_nms_pred(const float *pred_host, int n_boxes, int attrs, float conf_thre
  *                        in corner form.  The merge branch is reproduced as it behaves, not as it was meant: it only
  *                        takes effect when 1 or all candidates survive, see DESIGN.md. */
 int yds_detect_tiled(yds_net *, const uint8_t *rgb_hwc_host, int h, int w, const int32_t *tiles_xyhw, int n_tiles,
-                     float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out);
-int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres,
+                     float conf_thres, double iou_thres, float *out6_host, int cap, int *n_out);
+int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, double iou_thres,
                        float *out6_host, int cap, int *n_out);
 /* yds_nms_merge_pred_batched <- the same function for n_frames images in ONE launch sequence, entirely on the device: the launch the
  *                        window-mode pipeline uses (yds_pipeline_set_windows) with the frames described uniformly - n_boxes
  *                        corner-form rows per image, blockIdx.y = image, the merge branch as a kernel (one workgroup per image,
  *                        the kernel yds_nms_merge_pred runs for its one image) before the results are published.
  *                        pred_host [n_frames, n_boxes, attrs]; out6_host [n_frames, cap, 6]; n_out[n_frames] rows per image. */
-int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres,
+int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, double iou_thres,
                                float *out6_host, int cap, int *n_out);
 /* yds_nms_ragged_pred     <- both functions above for frames of different row counts in ONE launch sequence: the launch of a pipeline
  *                        pass with a slot plan (window mode, a window setting per stream, a mixed layout).  Frame f is rows [row0[f], row0[f] + n_rows[f]) of pred_host
@@ -144,7 +144,7 @@ int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes
  *                        runs for it; its kept boxes are multiplied by (scale[2f], scale[2f+1]).  The kernels read these descriptors on
  *                        the device.  out6_host [n_frames, cap, 6], n_out [n_frames]. */
 int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, int n_frames, const uint64_t *row0, const int32_t *n_rows,
-                        const int32_t *corner_merge, const float *scale, float conf_thres, float iou_thres, float *out6_host, int cap,
+                        const int32_t *corner_merge, const float *scale, float conf_thres, double iou_thres, float *out6_host, int cap,
                         int *n_out);
 
 /* ---- ReID: crop + Extractor + Net(reid=True) --------------------------------------------
@@ -291,7 +291,7 @@ int yds_tracker_get_slots(yds_trk *, int32_t *slots, int cap);
  * (the following call must then pass the same pointer and batch as frames_dev).
  * class_mask: list of class ids kept (NULL/0 = keep all).  out6: [batch, cap, 6] int32,
  * counts[batch] rows per frame (-1 = detector returned None, tracker not called). */
-yds_pipe *yds_pipeline_create(yds_net *, yds_reid *, yds_trk *, float conf_thres, float nms_thres,
+yds_pipe *yds_pipeline_create(yds_net *, yds_reid *, yds_trk *, float conf_thres, double nms_thres,
                               const int32_t *class_mask, int n_mask);
 void yds_pipeline_destroy(yds_pipe *);
 int yds_pipeline_step(yds_pipe *, const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w,
@@ -313,7 +313,7 @@ int yds_pipeline_step_host(yds_pipe *, const uint8_t *frames_host, const uint8_t
  * stream stepped alone.  out6 / counts are per frame, in frame order, as in yds_pipeline_step (-1 = detector returned None, that
  * stream's tracker not called).  yds_pipeline_step / _step_host refuse a multi-stream pipeline and the _multi entries refuse a
  * single-stream one; every other yds_pipeline_* call applies to both. */
-yds_pipe *yds_pipeline_create_multi(yds_net *, yds_reid *, yds_trk *const *trks, int n_streams, float conf_thres, float nms_thres,
+yds_pipe *yds_pipeline_create_multi(yds_net *, yds_reid *, yds_trk *const *trks, int n_streams, float conf_thres, double nms_thres,
                                     const int32_t *class_mask, int n_mask);
 int yds_pipeline_step_multi(yds_pipe *, const uint8_t *frames_dev, const uint8_t *next_frames_dev, int h, int w, int n_frames,
                             const int32_t *stream_of_frame, int32_t *out6_host, int cap, int32_t *counts_host);

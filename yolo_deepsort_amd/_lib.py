@@ -23,6 +23,7 @@ class YdsError(RuntimeError):
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
+_D = C.c_double
 _SZ = C.c_size_t
 _I64 = C.c_int64
 
@@ -74,11 +75,11 @@ SIGNATURES = {
     "yds_conv_run_view": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P]),
     "yds_conv_run_half": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
     "yds_conv_run_fused": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "yds_nms": (_I, [_P, _I, _F, _F, _I, _I, _P, _I, _P]),
-    "yds_nms_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),
-    "yds_nms_merge_pred": (_I, [_P, _I, _I, _F, _F, _P, _I, _P]),
-    "yds_nms_merge_pred_batched": (_I, [_P, _I, _I, _I, _F, _F, _P, _I, _P]),
-    "yds_detect_tiled": (_I, [_P, _P, _I, _I, _P, _I, _F, _F, _P, _I, _P]),
+    "yds_nms": (_I, [_P, _I, _F, _D, _I, _I, _P, _I, _P]),
+    "yds_nms_pred": (_I, [_P, _I, _I, _F, _D, _P, _I, _P]),
+    "yds_nms_merge_pred": (_I, [_P, _I, _I, _F, _D, _P, _I, _P]),
+    "yds_nms_merge_pred_batched": (_I, [_P, _I, _I, _I, _F, _D, _P, _I, _P]),
+    "yds_detect_tiled": (_I, [_P, _P, _I, _I, _P, _I, _F, _D, _P, _I, _P]),
     "yds_reid_create": (_P, [_I]),
     "yds_reid_destroy": (None, [_P]),
     "yds_reid_load_tensor": (_I, [_P, C.c_char_p, _P, _P, _I]),
@@ -125,11 +126,11 @@ SIGNATURES = {
     "yds_kalman_gating": (_I, [_P, _P, _I, _P, _I, _P]),
     "yds_iou_cost": (_I, [_P, _I, _P, _I, _P]),
     "yds_cosine_min_cost": (_I, [_P, _P, _I, _P, _I, _I, _P]),
-    "yds_pipeline_create": (_P, [_P, _P, _P, _F, _F, _P, _I]),
+    "yds_pipeline_create": (_P, [_P, _P, _P, _F, _D, _P, _I]),
     "yds_pipeline_destroy": (None, [_P]),
     "yds_pipeline_step": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "yds_pipeline_step_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P]),
-    "yds_pipeline_create_multi": (_P, [_P, _P, _P, _I, _F, _F, _P, _I]),
+    "yds_pipeline_create_multi": (_P, [_P, _P, _P, _I, _F, _D, _P, _I]),
     "yds_pipeline_step_multi": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "yds_pipeline_step_multi_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "yds_pipeline_prefetch_host": (_I, [_P, _P, _I, _I, _I]),
@@ -151,7 +152,7 @@ SIGNATURES = {
     "yds_reid_front_grid_crops": (_I, []),
     "yds_pipeline_step_multi_mixed": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
     "yds_pipeline_step_multi_mixed_host": (_I, [_P, _P, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
-    "yds_nms_ragged_pred": (_I, [_P, _SZ, _I, _I, _P, _P, _P, _P, _F, _F, _P, _I, _P]),
+    "yds_nms_ragged_pred": (_I, [_P, _SZ, _I, _I, _P, _P, _P, _P, _F, _D, _P, _I, _P]),
     "yds_pipeline_set_stream_windows": (_I, [_P, _I, _I, _I, C.c_double]),
     "yds_pipeline_slot_pred": (_I, [_P, _P, _SZ, _P]),
     "yds_gallery_search": (_I, [_P, _I, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P]),

@@ -184,23 +184,23 @@ public:
     // asynchronous form: launch() enqueues the kernels, the last of which stores the results into pinned host memory; collect() reads
     // them after the caller synchronised the stream.  One kernel set and one launch sequence, the frames described in one of two ways:
     // uniformly (the plain pipeline pass: no table, no merge kernel unless u.merge) ...
-    void launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, float iou_thres, int cap, hipStream_t s);
+    void launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, double iou_thres, int cap, hipStream_t s);
     // ... or by a table `fr` [n_frames] (slot_plan.h) which the kernels read on the device, for frames that differ in row count and
     // form - per frame corner form or not, the merge branch or not, its own (sx, sy); max_rows: the largest n_rows, total_rows: the
     // largest row0 + n_rows (box_count is addressed like the prediction block)
     void launch(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
-                float iou_thres, int cap, hipStream_t s);
+                double iou_thres, int cap, hipStream_t s);
     int collect(int frame, float *out6_host, int cap);
     void resize(int max_candidates, int n_frames);       // (re)allocates; contents are lost
     int needed(int n_frames) const;                       // largest candidate count of the last launch (after the caller's sync)
     static constexpr int kMaxCandidates = 1 << 18;
     // returns number of rows written to out6_host (<= cap); rows sorted by score, boxes in model pixels
     // scaled by (sx, sy) when scale is requested (resize_boxes).
-    int run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float sx, float sy,
+    int run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, double iou_thres, float sx, float sy,
             float *out6_host, int cap, hipStream_t s);
     // merge=True / is_p1p2=True form used by the sliding-window detector: corner-form boxes, the reference's merge branch (the same
     // kernel behind the sweep that a windowed pipeline pass runs)
-    int run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap, hipStream_t s);
+    int run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, double iou_thres, float *out6_host, int cap, hipStream_t s);
     int max_cand, frames;
     DevBuf<float> cand;          // [max_cand, 6]   x1,y1,x2,y2,score,cls in candidate order
     DevBuf<float> sorted;        // [max_cand, 6]   score order

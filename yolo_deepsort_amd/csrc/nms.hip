@@ -4,6 +4,8 @@
 // multi-label NMS) + resize_boxes (:12-19).  The greedy step is torchvision.ops.boxes.nms semantics
 // (third party; call site model_build.py:119): stable sort by score descending, area (x2-x1)*(y2-y1),
 // suppress j when inter/(a_i + a_j - inter) > thr with the threshold held as double.
+// The threshold is a double from the C ABI down to the mask kernel (0.4 as a float is above 0.4 and would keep an IoU of exactly
+// 2/5); the merge branch compares in fp32 as the reference does there, and so does the confidence threshold.
 //
 // Pipeline (all sizes stay on device, one host sync at the end):
 //   count   one thread per box: obj > thr, number of classes with cls*obj > thr
@@ -324,7 +326,7 @@ __global__ __launch_bounds__(256) void nms_publish_kernel(const int *counts, con
 // total_rows: the largest row0 + n_rows; merge: some frame may ask for the merge branch.
 template <class Frames>
 static void launch_stages(NmsWorkspace &w, const float *pred_dev, Frames frames, int n_frames, int max_rows, size_t total_rows, bool merge, int attrs,
-                          float conf_thres, float iou_thres, int cap, hipStream_t s) {
+                          float conf_thres, double iou_thres, int cap, hipStream_t s) {
     if (attrs < 6) fail("nms: predictions need at least one class");
     if (n_frames < 1 || max_rows < 1) fail("nms: %d frames of at most %d rows", n_frames, max_rows);
     if (n_frames > w.frames) w.resize(w.max_cand, n_frames);
@@ -335,25 +337,25 @@ static void launch_stages(NmsWorkspace &w, const float *pred_dev, Frames frames,
     hipLaunchKernelGGL(nms_emit_kernel<Frames>, dim3(nb, n_frames), dim3(256), 0, s, pred_dev, frames, attrs, conf_thres, w.box_count.p, max_cand,
                        w.cand.p);
     hipLaunchKernelGGL(nms_rank_kernel, dim3(16, n_frames), dim3(256), 0, s, w.cand.p, w.counts.p, max_cand, w.sorted.p);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, w.sorted.p, w.counts.p, max_cand, (double)iou_thres, w.mask.p, words_ld);
+    hipLaunchKernelGGL(nms_mask_kernel, dim3(64, n_frames), dim3(256), 0, s, w.sorted.p, w.counts.p, max_cand, iou_thres, w.mask.p, words_ld);
     hipLaunchKernelGGL(nms_sweep_kernel<Frames>, dim3(1, n_frames), dim3(256), words_ld * sizeof(unsigned long long), s, w.sorted.p, w.mask.p, words_ld,
                        w.counts.p, max_cand, frames, w.kept.p, cap);
     if (merge)
-        hipLaunchKernelGGL(nms_merge_kernel<Frames>, dim3(n_frames), dim3(256), 0, s, w.cand.p, w.sorted.p, w.counts.p, max_cand, iou_thres, frames,
+        hipLaunchKernelGGL(nms_merge_kernel<Frames>, dim3(n_frames), dim3(256), 0, s, w.cand.p, w.sorted.p, w.counts.p, max_cand, (float)iou_thres, frames,
                            w.kept.p);
     // results land in pinned host memory; the caller synchronises the stream (or an event) before collect()
     hipLaunchKernelGGL(nms_publish_kernel, dim3(n_frames), dim3(256), 0, s, w.counts.p, w.kept.p, w.h_counts, w.h_kept, std::min(cap, (int)MAX_DET));
     YDS_HIP(hipGetLastError());
 }
 
-void NmsWorkspace::launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, float iou_thres, int cap,
+void NmsWorkspace::launch(const float *pred_dev, const NmsUniform &u, int n_frames, int attrs, float conf_thres, double iou_thres, int cap,
                           hipStream_t s) {
     launch_stages(*this, pred_dev, u, n_frames, u.n_boxes, (size_t)std::max(frames, n_frames) * u.n_boxes, u.merge != 0, attrs, conf_thres,
                   iou_thres, cap, s);
 }
 
 void NmsWorkspace::launch(const float *pred_dev, const NmsFrame *fr, int n_frames, int max_rows, size_t total_rows, int attrs, float conf_thres,
-                          float iou_thres, int cap, hipStream_t s) {
+                          double iou_thres, int cap, hipStream_t s) {
     launch_stages(*this, pred_dev, fr, n_frames, max_rows, total_rows, true, attrs, conf_thres, iou_thres, cap, s);
 }
 
@@ -375,7 +377,7 @@ int NmsWorkspace::collect(int frame, float *out6_host, int cap) {
     return n;
 }
 
-int NmsWorkspace::run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float sx, float sy,
+int NmsWorkspace::run(const float *pred_dev, int n_boxes, int attrs, float conf_thres, double iou_thres, float sx, float sy,
                       float *out6_host, int cap, hipStream_t s) {
     launch_grown(*this, 1, s, [&] { launch(pred_dev, NmsUniform{n_boxes, 0, 0, sx, sy}, 1, attrs, conf_thres, iou_thres, cap, s); });
     return collect(0, out6_host, cap);
@@ -383,7 +385,7 @@ int NmsWorkspace::run(const float *pred_dev, int n_boxes, int attrs, float conf_
 
 // soft_non_max_suppression(merge=True, is_p1p2=True): corner-form boxes, the merge branch (nms_merge_body) behind a sweep that keeps
 // MAX_DET rows whatever `cap` is - the branch depends on the kept count
-int NmsWorkspace::run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap,
+int NmsWorkspace::run_merge(const float *pred_dev, int n_boxes, int attrs, float conf_thres, double iou_thres, float *out6_host, int cap,
                             hipStream_t s) {
     launch_grown(*this, 1, s, [&] { launch(pred_dev, NmsUniform{n_boxes, 1, 1, 1.f, 1.f}, 1, attrs, conf_thres, iou_thres, MAX_DET, s); });
     return collect(0, out6_host, cap);
@@ -409,7 +411,7 @@ yds::NmsWorkspace &frames_workspace(int n_frames) {
 
 extern "C" {
 
-int yds_nms(yds_net *n, int image, float conf_thres, float iou_thres, int frame_h, int frame_w, float *out6_host, int cap, int *n_out) {
+int yds_nms(yds_net *n, int image, float conf_thres, double iou_thres, int frame_h, int frame_w, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::Darknet *d = n->d;
     if (image < 0 || image >= d->batch_max) yds::fail("nms: image %d outside batch", image);
@@ -422,7 +424,7 @@ int yds_nms(yds_net *n, int image, float conf_thres, float iou_thres, int frame_
 }
 
 int yds_detect_tiled(yds_net *n, const uint8_t *rgb_hwc_host, int h, int w, const int32_t *tiles_xyhw, int n_tiles, float conf_thres,
-                     float iou_thres, float *out6_host, int cap, int *n_out) {
+                     double iou_thres, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::Darknet *d = n->d;
     d->forward_tiles_host(rgb_hwc_host, h, w, tiles_xyhw, n_tiles);
@@ -430,7 +432,7 @@ int yds_detect_tiled(yds_net *n, const uint8_t *rgb_hwc_host, int h, int w, cons
     YDS_API_END
 }
 
-int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out) {
+int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, double iou_thres, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::DevBuf<float> pred;
     pred.upload(pred_host, (size_t)n_boxes * attrs);
@@ -440,7 +442,7 @@ int yds_nms_merge_pred(const float *pred_host, int n_boxes, int attrs, float con
 }
 
 int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, int n_frames, const uint64_t *row0, const int32_t *n_rows,
-                        const int32_t *corner_merge, const float *scale, float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out) {
+                        const int32_t *corner_merge, const float *scale, float conf_thres, double iou_thres, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
     if (n_frames < 1) yds::fail("nms: %d frames", n_frames);
     std::vector<yds::NmsFrame> fr(n_frames);
@@ -463,7 +465,7 @@ int yds_nms_ragged_pred(const float *pred_host, size_t total_rows, int attrs, in
     YDS_API_END
 }
 
-int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host,
+int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes, int attrs, float conf_thres, double iou_thres, float *out6_host,
                                int cap, int *n_out) {
     YDS_API_BEGIN
     if (n_frames < 1 || n_boxes < 1) yds::fail("nms: %d frames of %d boxes", n_frames, n_boxes);
@@ -479,7 +481,7 @@ int yds_nms_merge_pred_batched(const float *pred_host, int n_frames, int n_boxes
     YDS_API_END
 }
 
-int yds_nms_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, float iou_thres, float *out6_host, int cap, int *n_out) {
+int yds_nms_pred(const float *pred_host, int n_boxes, int attrs, float conf_thres, double iou_thres, float *out6_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::DevBuf<float> pred;
     pred.upload(pred_host, (size_t)n_boxes * attrs);

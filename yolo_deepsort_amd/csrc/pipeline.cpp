@@ -194,7 +194,7 @@ private:
 class Pipeline {
 public:
     // trks: the tracker of every stream; multi: made by yds_pipeline_create_multi (a step names the stream of each frame)
-    Pipeline(Darknet *net, ReidNet *reid, std::vector<TrackerIface *> trks, bool multi, float conf, float nms_iou, const int32_t *mask, int n_mask)
+    Pipeline(Darknet *net, ReidNet *reid, std::vector<TrackerIface *> trks, bool multi, float conf, double nms_iou, const int32_t *mask, int n_mask)
         : net(net), reid(reid), trks(std::move(trks)), group(make_tracker_group()), multi(multi), conf(conf), nms_thres(nms_iou),
           class_mask(mask, mask + n_mask), deep_min(getenv("YDS_PIPE_DEEP_MIN") ? atoi(getenv("YDS_PIPE_DEEP_MIN")) : 64),
           stager(net->stream, reid->stream) {
@@ -653,7 +653,8 @@ public:
     std::unique_ptr<TrackerGroupIface> group;     // the association driver of all of them
     const bool multi;                             // yds_pipeline_create_multi: the step_multi entries, else the plain ones
     std::vector<int32_t> stream_of;
-    float conf, nms_thres;
+    float conf;
+    double nms_thres;                             // held as double down to the mask kernel, like the reference's threshold
     std::vector<int32_t> class_mask;
     const int deep_min;                           // crowded-scene order from this many detections per frame (YDS_PIPE_DEEP_MIN, read per pipeline)
     DetSlot det[2];
@@ -706,13 +707,13 @@ static void pipeline_step_mixed(yds_pipe *p, bool host, const uint8_t *frames, c
 
 extern "C" {
 
-yds_pipe *yds_pipeline_create(yds_net *n, yds_reid *r, yds_trk *t, float conf_thres, float nms_thres, const int32_t *class_mask, int n_mask) {
+yds_pipe *yds_pipeline_create(yds_net *n, yds_reid *r, yds_trk *t, float conf_thres, double nms_thres, const int32_t *class_mask, int n_mask) {
     YDS_API_BEGIN
     if (!n || !r || !t) yds::fail("pipeline: NULL handle");
     return new yds_pipe{new yds::Pipeline(n->d, r->r, {t->t}, false, conf_thres, nms_thres, class_mask, class_mask ? n_mask : 0)};
     YDS_API_END_PTR
 }
-yds_pipe *yds_pipeline_create_multi(yds_net *n, yds_reid *r, yds_trk *const *trks, int n_streams, float conf_thres, float nms_thres,
+yds_pipe *yds_pipeline_create_multi(yds_net *n, yds_reid *r, yds_trk *const *trks, int n_streams, float conf_thres, double nms_thres,
                                     const int32_t *class_mask, int n_mask) {
     YDS_API_BEGIN
     if (!n || !r || !trks) yds::fail("pipeline: NULL handle");
