@@ -167,6 +167,50 @@ class DarknetOracle:
         return self.load_weights_array(weights, cutoff)
 
     # ---- forward -----------------------------------------------------
+    def step(self, i, x, outs, img_dim, inject=None):
+        """Layer i alone: ``x`` is the previous layer's output (the image for layer 0), ``outs`` maps a layer index to that
+        layer's output for routes and shortcuts (negative indices count back from i).  forward() is this, chained."""
+        d, p = self.module_defs[i], self.params[i]
+        t = d["type"]
+
+        def at(l):
+            l = int(l)
+            return outs[l if l >= 0 else i + l]
+        if t == "convolutional":
+            x = conv2d_nchw(x, p["w"], None if p["bn"] else p["bias"], p["stride"], p["pad"])
+            if p["bn"]:
+                x = batchnorm_eval(x, p["gamma"], p["beta"], p["mean"], p["var"])
+            if p["act"] == "leaky":
+                x = leaky(x)
+            elif p["act"] == "mish":
+                x = mish(x)
+        elif t == "maxpool":
+            k, s = int(d["size"]), int(d["stride"])
+            if k == 2 and s == 1:
+                # models.py:61-63 ZeroPad2d((0,1,0,1)) then MaxPool2d(2,1,pad 0)
+                B, C, H, W = x.shape
+                xz = np.zeros((B, C, H + 1, W + 1), F32)
+                xz[:, :, :H, :W] = x
+                x = maxpool_nchw(xz, 2, 1, 0)
+            else:
+                x = maxpool_nchw(x, k, s, (k - 1) // 2)
+        elif t == "upsample":
+            s = int(d["stride"])
+            x = np.ascontiguousarray(x.repeat(s, axis=2).repeat(s, axis=3))
+        elif t == "route":
+            x = np.concatenate([at(l) for l in d["layers"].split(",")], 1)
+            if "groups" in d:
+                g, gid = int(d["groups"]), int(d["group_id"])
+                c = x.shape[1] // g
+                x = np.ascontiguousarray(x[:, gid * c:(gid + 1) * c])
+        elif t == "shortcut":
+            x = x + at(d["from"])
+        elif t == "yolo":
+            if inject is not None:
+                x = inject(i, x)
+            x = yolo_decode(x, p["anchors"], p["classes"], img_dim)
+        return x
+
     def forward(self, x, keep_layers=False, inject=None):
         """x: [B,3,H,W] fp32 -> [B,N,5+C].  ``inject`` (optional) is a callable
         (layer_index, head_tensor NCHW) -> head_tensor applied to the raw head
@@ -174,41 +218,9 @@ class DarknetOracle:
         x = np.ascontiguousarray(x, dtype=F32)
         img_dim = (x.shape[2], x.shape[3])
         outs, yolo_out = [], []
-        for i, (d, p) in enumerate(zip(self.module_defs, self.params)):
-            t = d["type"]
-            if t == "convolutional":
-                x = conv2d_nchw(x, p["w"], None if p["bn"] else p["bias"], p["stride"], p["pad"])
-                if p["bn"]:
-                    x = batchnorm_eval(x, p["gamma"], p["beta"], p["mean"], p["var"])
-                if p["act"] == "leaky":
-                    x = leaky(x)
-                elif p["act"] == "mish":
-                    x = mish(x)
-            elif t == "maxpool":
-                k, s = int(d["size"]), int(d["stride"])
-                if k == 2 and s == 1:
-                    # models.py:61-63 ZeroPad2d((0,1,0,1)) then MaxPool2d(2,1,pad 0)
-                    B, C, H, W = x.shape
-                    xz = np.zeros((B, C, H + 1, W + 1), F32)
-                    xz[:, :, :H, :W] = x
-                    x = maxpool_nchw(xz, 2, 1, 0)
-                else:
-                    x = maxpool_nchw(x, k, s, (k - 1) // 2)
-            elif t == "upsample":
-                s = int(d["stride"])
-                x = np.ascontiguousarray(x.repeat(s, axis=2).repeat(s, axis=3))
-            elif t == "route":
-                x = np.concatenate([outs[int(l)] for l in d["layers"].split(",")], 1)
-                if "groups" in d:
-                    g, gid = int(d["groups"]), int(d["group_id"])
-                    c = x.shape[1] // g
-                    x = np.ascontiguousarray(x[:, gid * c:(gid + 1) * c])
-            elif t == "shortcut":
-                x = outs[-1] + outs[int(d["from"])]
-            elif t == "yolo":
-                if inject is not None:
-                    x = inject(i, x)
-                x = yolo_decode(x, p["anchors"], p["classes"], img_dim)
+        for i, d in enumerate(self.module_defs):
+            x = self.step(i, x, outs, img_dim, inject)
+            if d["type"] == "yolo":
                 yolo_out.append(x)
             outs.append(x)
         self.layer_outputs = outs if keep_layers else None

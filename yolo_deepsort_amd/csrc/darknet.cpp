@@ -176,7 +176,8 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
     }
     for (int i = 1; i < L; ++i) {
         Layer &l = layers[i];
-        if (l.type == L_SHORTCUT && layers[i - 1].type == L_CONV && readers[i - 1] == 1 && l.refs[1] != i - 1) {
+        // (the conv epilogues add a residual after leaky / mish only: a linear conv keeps its own launch and the add runs after it)
+        if (l.type == L_SHORTCUT && layers[i - 1].type == L_CONV && readers[i - 1] == 1 && l.refs[1] != i - 1 && layers[i - 1].act != ACT_LINEAR) {
             layers[i - 1].fused_res = l.refs[1];
             l.fused = true;
             l.root = i - 1;          // view of the conv's (post-add) buffer
@@ -242,13 +243,19 @@ Darknet::Darknet(const std::string &cfg_text, int img_h, int img_w, int batch_ma
         int off = 0, o = owner_of(j, off);
         if (off % 32 || layers[j].c % 32) h16_ok[o] = 0;
     }
-    // a concatenation fed by copies must share the copied tensors' format: demote both sides to fp32 on mismatch
-    for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i < L; ++i)
-            for (auto &cp : layers[i].copies) {
-                int off = 0, o = owner_of(cp.first, off);
-                if (o >= 0 && h16_ok[o] != h16_ok[i]) h16_ok[o] = h16_ok[i] = 0;
-            }
+    // a concatenation fed by copies must share the copied tensors' format, and so must an upsample and its source (both kernels
+    // move bytes): demote both sides to fp32 on mismatch, until nothing changes (a demotion can unsettle an earlier pair)
+    for (bool changed = true; changed;) {
+        changed = false;
+        auto tie = [&](int a, int b) {
+            if (a >= 0 && b >= 0 && h16_ok[a] != h16_ok[b]) { h16_ok[a] = h16_ok[b] = 0; changed = true; }
+        };
+        for (int i = 0; i < L; ++i) {
+            int off = 0;
+            for (auto &cp : layers[i].copies) tie(owner_of(cp.first, off), i);
+            if (layers[i].type == L_UPSAMPLE && layers[i].src >= 0) tie(owner_of(layers[i].src, off), owner_of(i, off));
+        }
+    }
     for (int i = 0; i < L; ++i) {
         Layer &l = layers[i];
         bool owns = (is_producer(i) && !storage[i].redirected) || l.concat();
