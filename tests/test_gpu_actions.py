@@ -66,6 +66,36 @@ def test_streams_interleaved_in_one_call_equal_each_stream_alone():
     assert dev.orbits(2) == [] and len(dev.orbits(0)) > 0
 
 
+def test_a_call_that_names_some_streams_out_of_order_keeps_every_cache_apart():
+    """The host's bookkeeping per call: a handle of 3 streams; a call with all three; one with streams 2 and 0 in that order (two
+    workgroups, for streams 0 and 2, and a frame order that is not the bucket order), with a frame of no rows and an id that reaches
+    max_age = 1 and leaves; stream 1 alone (workgroup 0 is stream 1); streams 1 and 2.  Every stream has its own ids and box
+    widths, and after every call the rows per frame and all three caches equal three host clones, the streams without frames
+    included."""
+    acts = [A.BreakInto(0, 0), A.Glide(1, (2, 2)), A.BreakInto(1, 1)]
+    dev = A.DeviceActionIdentify(acts, max_age=1, max_size=3, n_streams=3)
+    hosts = [A.ActionIdentify(acts, max_age=1, max_size=3) for _ in range(3)]
+    row = lambda s, k, x: [x, 0, x + 10 + s, 40 + k, 10 * s + k, k % 2]      # noqa: E731
+
+    def feed(frames):
+        rows = [np.array(r, np.int32).reshape(-1, 6) for _, r, _ in frames]
+        got = dev.update_batch(rows, [s for s, _, _ in frames], [t for _, _, t in frames])
+        want = [as_tuples(hosts[s].update(r, t)) for (s, _, t), r in zip(frames, rows)]
+        assert got == want
+        for s in range(3):
+            assert dev.orbits(s) == _host_orbits(hosts[s]), s
+        return want
+    assert feed([(s, [row(s, k, 100 * k) for k in range(3 + s)], 0.5) for s in range(3)]) == [[], [], []]
+    w = feed([(2, [row(2, 0, 5), row(2, 1, 108), row(2, 2, 200), row(2, 4, 430), row(2, 7, 0)], 1.0), (0, [], 1.0),
+              (0, [row(0, 5, 7), row(0, 1, 9)], 1.5)])
+    assert [r[0] for r in w[0]] == [20, 22, 24] and w[1:] == [[], []]
+    assert [[o[0] for o in _host_orbits(h)] for h in hosts] == [[5, 1], [10, 11, 12, 13], [20, 21, 22, 24, 27]]      # 23, then 0, 1, 2 left
+    w = feed([(1, [row(1, 1, 104), row(1, 2, 230), row(1, 0, 0), row(1, 6, 60)], 2.0)])
+    assert [r[0] for r in w[0]] == [10, 12] and [o[0] for o in _host_orbits(hosts[1])] == [10, 11, 12, 16]
+    w = feed([(1, [row(1, 1, 110), row(1, 6, 66)], 2.5), (2, [row(2, 1, 116)], 2.5)])
+    assert w == [[(11, 1, "glide"), (11, 1, "break_into"), (16, 0, "break_into")], [(21, 1, "glide"), (21, 1, "break_into")]]
+
+
 # ------------------------------------------------------------------------------------------------ 3. randomised against the host module
 @pytest.mark.parametrize("max_age,max_size,n_ids", [(3, 4, 300), (1, 2, 400), (2, 16, 300), (3, 1, 300)])
 def test_random_scene_equals_the_host_module(max_age, max_size, n_ids):

@@ -134,6 +134,27 @@ def test_streams_interleaved_in_one_call_equal_each_stream_alone():
     dev.close()
 
 
+def test_a_call_that_names_some_streams_out_of_order_keeps_every_table_apart():
+    """The host's bookkeeping per call: three calls over a handle of 3 streams - all three streams; then streams 2 and 0 in that
+    order (two workgroups, for streams 0 and 2, and a frame order that is not the bucket order) with a frame of no rows and an entry
+    that reaches max_age = 1 and leaves; then stream 1 alone (workgroup 0 is stream 1).  Every stream's ids and places differ, and
+    after every call all three tables and counters are compared, the streams without frames included."""
+    dev = Z.DeviceZoneMonitor(([Z.Zone(SQUARE)], [Z.Line((150, 0), (150, 300))]), max_age=1, n_streams=3)
+    hosts = [dev.host(s) for s in range(3)]
+    at = lambda s, k, x2: box_at(x2, 110 + 10 * k + s, tid=10 * s + k, cls=k % 2)      # noqa: E731 - doubled x: the zone is [200, 400), the line 300
+    ev = _feed(dev, hosts, [(s, [at(s, k, 260 if k % 2 else 450) for k in range(3 + s)], 0.0) for s in range(3)])
+    assert [len(e) for e in ev] == [1, 2, 2] and [len(h.tracks()) for h in hosts] == [3, 4, 5]
+    ev = _feed(dev, hosts, [(2, [at(2, 0, 340), at(2, 1, 340), at(2, 2, 450), at(2, 4, 150), at(2, 7, 260)], 1.0), (0, [], 1.0),
+                            (0, [at(0, 5, 260), at(0, 1, 450)], 2.0)])
+    assert [len(e) for e in ev] == [5, 1, 1] and kind_counts(ev) == [3, 0, 2, 1, 1]
+    assert [e[0] for e in ev[0] + ev[1] if e[2] == Z.LOST] == [23, 1]                 # 23 was not seen; the empty frame retires 0, 1, 2
+    assert [[t[0] for t in h.tracks()] for h in hosts] == [[5, 1], [10, 11, 12, 13], [20, 21, 22, 24, 27]]
+    ev = _feed(dev, hosts, [(1, [at(1, 1, 450), at(1, 2, 450), at(1, 0, 260), at(1, 6, 340)], 3.0)])
+    assert kind_counts(ev) == [2, 1, 1, 1, 1] and [t[0] for t in hosts[1].tracks()] == [10, 11, 12, 16]
+    assert [h.counts() for h in hosts] == [([[1, 2, 0, 1]], [[0, 0]]), ([[2, 4, 1, 1]], [[1, 1]]), ([[3, 4, 0, 1]], [[1, 1]])]
+    dev.close()
+
+
 def test_lifecycle_ageing_returns_and_resets():
     geo = ([Z.Zone(SQUARE, name="hall")], [Z.Line((150, 0), (150, 300))])
     dev = Z.DeviceZoneMonitor(geo, max_age=3, n_streams=2)

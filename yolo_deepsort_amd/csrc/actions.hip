@@ -9,13 +9,10 @@
 // once (they may sit in pinned host memory: a tracker result block), updates / registers / ages / drops entries with ordered
 // compactions (tracker_dev.h compact_ordered), and emits (frame, id, class, action) rows entry-major, action-minor - count, prefix,
 // write - straight into a pinned result block.  All arithmetic is double in the operation order of the Python expressions (the tree
-// is built with -ffp-contract=off), so the rows equal the host module's.
-#include "tracker_dev.h"
+// is built with -ffp-contract=off), so the rows equal the host module's.  What the stage shares with the zone stage - the workgroup's
+// table steps, the host's bookkeeping per call - is track_stage.h.
+#include "track_stage.h"
 #include "ydsort.h"
-
-#include <limits.h>
-
-#include <memory>
 
 namespace yds {
 
@@ -83,15 +80,12 @@ __global__ __launch_bounds__(256) void act_update_kernel(const ActWork *works, c
     __syncthreads();
     for (int f = W.f0; f < W.f1; ++f) {
         const ActFrameDev F = frames[f];
-        const int R = F.n_p ? min(max(*F.n_p, 0), F.n) : F.n;
-        for (int k = tid; k < R * 6; k += 256) W.srows[k] = F.rows[k];
+        const int R = stage_frame_rows(F.rows, F.n_p, F.n, W.srows);
         for (int j = tid; j < R; j += 256) W.stime[j] = F.row_time ? F.row_time[j] : F.t;
         __syncthreads();
         // ---- cached ids: Orbit.update (orbit.py:22-25), else age += 1 (action_Identify.py:27-34)
         for (int e = tid; e < n; e += 256) {
-            const int id = T.id[e];
-            int j = 0;
-            while (j < R && W.srows[j * 6 + 4] != id) ++j;
+            const int j = find_row(W.srows, R, T.id[e]);
             if (j == R) { T.age[e] += 1; continue; }
             const int *r = W.srows + j * 6;
             const int len = T.len[e], head = T.head[e];
@@ -105,16 +99,9 @@ __global__ __launch_bounds__(256) void act_update_kernel(const ActWork *works, c
             T.age[e] = 0;
         }
         // ---- unknown ids are registered in row order, no point yet (action_Identify.py:23-25)
-        const int added = compact_ordered(R, s_cnt, [&](int j) {
-            const int id = W.srows[j * 6 + 4];
-            for (int e = 0; e < n; ++e) if (T.id[e] == id) return false;
-            return true;
-        }, [&](int j, int r) {
-            const int e = n + r;
-            if (e >= cap) return;                                                 // (the host sized the table for every row of the call)
-            T.id[e] = W.srows[j * 6 + 4]; T.cls[e] = W.srows[j * 6 + 5]; T.age[e] = 0; T.len[e] = 0; T.head[e] = 0;
+        const int n_all = register_unknown(R, n, cap, s_cnt, T.id, W.srows, [&](int e, const int *r) {
+            T.id[e] = r[4]; T.cls[e] = r[5]; T.age[e] = 0; T.len[e] = 0; T.head[e] = 0;
         });
-        const int n_all = min(n + added, cap);
         __syncthreads();
         // ---- entries that reached max_age leave, the rest keep their order (only an entry that just aged has age > 0 tested)
         auto keep = [&](int e) { const int a = T.age[e]; return !(a > 0 && a >= max_age); };
@@ -122,18 +109,13 @@ __global__ __launch_bounds__(256) void act_update_kernel(const ActWork *works, c
         for (int base = 0; base < n; base += 256) dead += __syncthreads_count(base + tid < n && !keep(base + tid));
         int n_live = n_all;
         if (dead) {
-            n_live = compact_ordered(n_all, s_cnt, keep, [&](int e, int r) {
-                const int d = cap + r;
-                T.id[d] = T.id[e]; T.cls[d] = T.cls[e]; T.age[d] = T.age[e]; T.len[d] = T.len[e]; T.head[d] = T.head[e];
+            auto move = [&](int d, int e) { T.id[d] = T.id[e]; T.cls[d] = T.cls[e]; T.age[d] = T.age[e]; T.len[d] = T.len[e]; T.head[d] = T.head[e]; };
+            n_live = retire(n_all, cap, s_cnt, keep, [&](int d, int e) {
+                move(d, e);
                 const double *src = T.pts + (size_t)e * ms * 3;
                 double *dst = T.pts + (size_t)d * ms * 3;
                 for (int k = 0; k < ms * 3; ++k) dst[k] = src[k];
-            });
-            __syncthreads();
-            for (int e = tid; e < n_live; e += 256) {
-                const int d = cap + e;
-                T.id[e] = T.id[d]; T.cls[e] = T.cls[d]; T.age[e] = T.age[d]; T.len[e] = T.len[d]; T.head[e] = T.head[d];
-            }
+            }, move);
             for (size_t k = tid; k < (size_t)n_live * ms * 3; k += 256) T.pts[k] = T.pts[(size_t)cap * ms * 3 + k];
             __syncthreads();
         }
@@ -156,11 +138,10 @@ __global__ __launch_bounds__(256) void act_update_kernel(const ActWork *works, c
     if (tid == 0) { *T.count = n; res[W.res_count] = n; }
 }
 
-class Actions : public ActionsIface {
+class Actions : public TrackStage<ActionsIface> {
 public:
     Actions(int S, const int32_t *kind, const int32_t *class_id, const double *param, int A, int max_age, int max_size)
-        : S(S), A(A), max_age(max_age), ms(max_size), tabs(S), count_host(S, 0) {
-        if (S < 1) fail("actions: %d streams", S);
+        : TrackStage("actions", S), A(A), max_age(max_age), ms(max_size), tabs(S) {
         if (A < 0 || A > YDS_ACT_MAX_ACTIONS) fail("actions: %d actions outside [0,%d]", A, YDS_ACT_MAX_ACTIONS);
         if (max_size < 1 || max_size > YDS_ACT_MAX_SIZE) fail("actions: max_size %d outside [1,%d]", max_size, YDS_ACT_MAX_SIZE);
         std::vector<ActDesc> d(std::max(A, 1));
@@ -170,20 +151,7 @@ public:
         }
         acts.alloc(d.size());
         YDS_HIP(hipMemcpy(acts.p, d.data(), d.size() * sizeof(ActDesc), hipMemcpyHostToDevice));
-        counts.alloc(S);
-        YDS_HIP(hipMemset(counts.p, 0, S * sizeof(int)));
-        own_stream = make_stream(true);
-        YDS_HIP(hipEventCreate(&ev0));
-        YDS_HIP(hipEventCreate(&ev1));
     }
-    ~Actions() override {
-        if (in_host) (void)hipHostFree(in_host);
-        if (res_host) (void)hipHostFree(res_host);
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-    }
-    int streams() const override { return S; }
 
     struct Tab {
         DevBuf<int> ints;         // id | cls | age | len | head, [2][cap] each
@@ -195,158 +163,74 @@ public:
         const size_t c2 = 2 * (size_t)t.cap;
         return ActTab{t.ints.p, t.ints.p + c2, t.ints.p + 2 * c2, t.ints.p + 3 * c2, t.ints.p + 4 * c2, t.pts.p, counts.p + s, t.cap};
     }
-    // room for `need` entries; nothing of this handle is in flight between calls (every call ends behind a synchronisation)
     void grow(int s, int need) {
-        Tab &t = tabs[s];
-        if (need <= t.cap) return;
-        int c = std::max(t.cap, 64);
-        while (c < need) c *= 2;
-        Tab nt;
-        nt.cap = c;
-        nt.ints.alloc(10 * (size_t)c);
-        nt.pts.alloc(2 * (size_t)c * ms * 3);
-        const int n = count_host[s];
-        if (n) {
-            for (int fld = 0; fld < 5; ++fld)
-                YDS_HIP(hipMemcpy(nt.ints.p + (size_t)fld * 2 * c, t.ints.p + (size_t)fld * 2 * t.cap, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice));
-            YDS_HIP(hipMemcpy(nt.pts.p, t.pts.p, (size_t)n * ms * 3 * sizeof(double), hipMemcpyDeviceToDevice));
-        }
-        t = std::move(nt);
+        const size_t n = count_host[s];
+        grow_table(tabs[s], need, n, [&](Tab &nt) {
+            nt.ints.alloc(10 * (size_t)nt.cap);
+            nt.pts.alloc(2 * (size_t)nt.cap * ms * 3);
+        }, [&](Tab &nt, const Tab &t) {
+            copy_live(nt.ints, t.ints, n, 5, nt.cap, t.cap);
+            copy_live(nt.pts, t.pts, n * ms * 3);
+        });
     }
 
     void enqueue(const ActFrame *fr, int n, hipStream_t s) override { enqueue_ex(fr, n, s, nullptr, 0, nullptr, 0); }
 
-    // rows_host / time_host (the stand-alone entry): host arrays that travel to the device inside the call's input block; the frames'
-    // rows6 / row_time then point INTO those host arrays and are translated to the block's device addresses
-
+    // rows_host / time_host (the stand-alone entry): host arrays that travel to the device inside the call's input block (open_blocks)
     void enqueue_ex(const ActFrame *fr, int n, hipStream_t s, const int32_t *rows_host, size_t n_rows_host, const double *time_host, size_t n_time_host) {
-        pending_n = n;
-        order.clear();
-        if (n <= 0) return;
-        // ---- frames by stream, order kept; a workgroup per stream with frames
-        std::vector<int> n_of(S, 0), rows_of(S, 0);
-        int max_rows = 1;
+        const StagePlan P = plan(fr, n, [&](int st, int need) { grow(st, need); });
+        if (!P.n_wg) return;
+        // ---- blocks: input = works | frames | row times | rows, result = frame counts | entry counts | rows
+        const size_t works_b = (size_t)P.n_wg * sizeof(ActWork), time_off = works_b + (size_t)n * sizeof(ActFrameDev);
+        size_t res_total = (size_t)n + P.n_wg;
+        pending_rows.resize(n);
+        pending_cap.resize(n);
         for (int i = 0; i < n; ++i) {
-            if (fr[i].stream < 0 || fr[i].stream >= S) fail("actions: frame %d names stream %d outside [0,%d)", i, fr[i].stream, S);
-            if (fr[i].n_rows < 0) fail("actions: frame %d has %d rows", i, fr[i].n_rows);
-            ++n_of[fr[i].stream];
-            rows_of[fr[i].stream] += fr[i].n_rows;
-            max_rows = std::max(max_rows, fr[i].n_rows);
+            pending_rows[i] = res_total;
+            pending_cap[i] = fr[i].n_rows * A;
+            res_total += (size_t)fr[i].n_rows * A * 4;
         }
-        std::vector<int> wg_of(S, -1), start(S, 0);
-        int n_wg = 0, acc = 0;
-        for (int st = 0; st < S; ++st) {
-            if (!n_of[st]) continue;
-            wg_of[st] = n_wg++;
-            start[st] = acc;
-            acc += n_of[st];
-            grow(st, count_host[st] + rows_of[st]);
-        }
-        order.assign(n, 0);                       // order[slot in the sorted list] = frame of the call
-        {
-            std::vector<int> fill(start);
-            for (int i = 0; i < n; ++i) order[fill[fr[i].stream]++] = i;
-        }
-        // ---- blocks: input = works | frames | payload (8-byte aligned pieces), result = frame counts | entry counts | rows
-        const size_t works_b = (size_t)n_wg * sizeof(ActWork), frames_b = (size_t)n * sizeof(ActFrameDev);
-        const size_t time_off = works_b + frames_b, rows_off = time_off + n_time_host * sizeof(double);
-        const size_t in_total = rows_off + n_rows_host * 6 * sizeof(int32_t);
-        size_t res_total = (size_t)n + n_wg;
-        std::vector<size_t> res_rows(n);
-        for (int i = 0; i < n; ++i) { res_rows[i] = res_total; res_total += (size_t)fr[i].n_rows * A * 4; }
-        if (res_total > (size_t)INT_MAX) fail("actions: result block of %zu ints", res_total);
-        if (in_total > in_cap) {
-            if (in_host) (void)hipHostFree(in_host);
-            in_host = nullptr;
-            in_cap = in_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&in_host, in_cap));
-            in_dev.alloc(in_cap);
-        }
-        if (res_total > res_cap) {
-            if (res_host) (void)hipHostFree(res_host);
-            res_host = nullptr;
-            res_cap = res_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&res_host, res_cap * sizeof(int)));
-        }
-        if ((size_t)n_wg * max_rows * 6 > srows.n) { srows.alloc((size_t)n_wg * max_rows * 6 * 2); }
-        if ((size_t)n_wg * max_rows > stime.n) { stime.alloc((size_t)n_wg * max_rows * 2); }
-        const int32_t *rows_dev = reinterpret_cast<const int32_t *>(in_dev.p + rows_off);
+        open_blocks(P, time_off + n_time_host * sizeof(double), rows_host, n_rows_host, res_total);
+        if ((size_t)P.n_wg * P.max_rows > stime.n) stime.alloc((size_t)P.n_wg * P.max_rows * 2);
         const double *time_dev = reinterpret_cast<const double *>(in_dev.p + time_off);
-        ActWork *w = reinterpret_cast<ActWork *>(in_host);
-        ActFrameDev *fd = reinterpret_cast<ActFrameDev *>(in_host + works_b);
-        for (int st = 0; st < S; ++st) {
-            if (wg_of[st] < 0) continue;
-            const int k = wg_of[st];
-            w[k] = ActWork{dev_tab(st), start[st], start[st] + n_of[st], srows.p + (size_t)k * max_rows * 6, stime.p + (size_t)k * max_rows, n + k};
+        ActWork *w = reinterpret_cast<ActWork *>(in_host.p);
+        ActFrameDev *fd = reinterpret_cast<ActFrameDev *>(in_host.p + works_b);
+        for (int k = 0; k < P.n_wg; ++k) {
+            const int st = wg_stream[k];
+            w[k] = ActWork{dev_tab(st), P.start[st], P.start[st] + P.n_of[st], wg_srows(k), stime.p + (size_t)k * P.max_rows, n + k};
         }
         for (int e = 0; e < n; ++e) {
-            const ActFrame &f = fr[order[e]];
+            const ActFrame &f = fr[P.order[e]];
             ActFrameDev d;
-            // rows6 / row_time of the stand-alone entry are offsets into the uploaded payload, marked by rows_host
-            d.rows = rows_host ? rows_dev + (f.rows6 - rows_host) : f.rows6;
+            d.rows = dev_rows(f);
             d.n_p = f.n_rows_p;
+            // (row_time of the stand-alone entry points into time_host, which travels in the block like the rows)
             d.row_time = f.row_time ? (time_host ? time_dev + (f.row_time - time_host) : f.row_time) : nullptr;
             d.t = f.t; d.n = f.n_rows; d.tag = f.tag;
-            d.res_n = order[e];
-            d.res_rows = (int)res_rows[order[e]];
+            d.res_n = P.order[e];
+            d.res_rows = (int)pending_rows[P.order[e]];
             fd[e] = d;
         }
-        if (n_time_host) memcpy(in_host + time_off, time_host, n_time_host * sizeof(double));
-        if (n_rows_host) memcpy(in_host + rows_off, rows_host, n_rows_host * 6 * sizeof(int32_t));
-        wg_stream.assign(n_wg, 0);
-        for (int st = 0; st < S; ++st) if (wg_of[st] >= 0) wg_stream[wg_of[st]] = st;
-        pending_rows.assign(res_rows.begin(), res_rows.end());
-        pending_cap.resize(n);
-        for (int i = 0; i < n; ++i) pending_cap[i] = fr[i].n_rows * A;
-        YDS_HIP(hipMemcpyAsync(in_dev.p, in_host, in_total, hipMemcpyHostToDevice, s));
-        if (timing) YDS_HIP(hipEventRecord(ev0, s));
-        hipLaunchKernelGGL(act_update_kernel, dim3(n_wg), dim3(256), 0, s, reinterpret_cast<const ActWork *>(in_dev.p),
-                           reinterpret_cast<const ActFrameDev *>(in_dev.p + works_b), acts.p, A, max_age, ms, res_host);
-        YDS_HIP(hipGetLastError());
-        if (timing) { YDS_HIP(hipEventRecord(ev1, s)); timed = true; }
+        if (n_time_host) memcpy(in_host.p + time_off, time_host, n_time_host * sizeof(double));
+        submit(s, [&] {
+            hipLaunchKernelGGL(act_update_kernel, dim3(P.n_wg), dim3(256), 0, s, reinterpret_cast<const ActWork *>(in_dev.p),
+                               reinterpret_cast<const ActFrameDev *>(in_dev.p + works_b), acts.p, A, max_age, ms, res_host.p);
+        });
     }
 
     void collect() override {
-        const int n = pending_n;
         rows4.clear();
-        first.assign(std::max(n, 0) + 1, 0);
-        if (n <= 0) return;
-        for (int i = 0; i < n; ++i) {
-            const int m = res_host[i];
-            if (m < 0 || m > pending_cap[i]) fail("actions: frame %d reports %d rows, %d possible", i, m, pending_cap[i]);
-            const int *r = res_host + pending_rows[i];
+        collect_counts("rows", [&](int i, int m) {
+            const int *r = res_host.p + pending_rows[i];
             rows4.insert(rows4.end(), r, r + (size_t)m * 4);
-            first[i + 1] = first[i] + m;
-        }
-        for (size_t k = 0; k < wg_stream.size(); ++k) count_host[wg_stream[k]] = res_host[n + k];
-        pending_n = 0;
+        });
     }
 
-    void reset(int stream) {
-        if (stream < -1 || stream >= S) fail("actions: stream %d outside [-1,%d)", stream, S);
-        for (int s = 0; s < S; ++s) {
-            if (stream >= 0 && s != stream) continue;
-            YDS_HIP(hipMemset(counts.p + s, 0, sizeof(int)));
-            count_host[s] = 0;
-        }
-    }
-
-    int S, A, max_age, ms;
+    int A, max_age, ms;
     std::vector<Tab> tabs;
-    std::vector<int> count_host;                  // entries of every stream after the last collected call
     DevBuf<ActDesc> acts;
-    DevBuf<int> counts, srows;
-    DevBuf<double> stime;
-    DevBuf<char> in_dev;
-    char *in_host = nullptr;
-    int *res_host = nullptr;
-    size_t in_cap = 0, res_cap = 0;
-    int pending_n = 0;
-    std::vector<int> order, wg_stream, pending_cap;
-    std::vector<size_t> pending_rows;
-    hipStream_t own_stream = nullptr;             // the stand-alone entry's
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timing = false, timed = false;
+    DevBuf<double> stime;                         // staging [n_wg][max rows of a frame]
+    std::vector<size_t> pending_rows;             // of the call in flight: where every frame's rows begin in the result block
 };
 
 }  // namespace yds
@@ -377,63 +261,33 @@ int yds_actions_update(yds_act *a, const int32_t *rows6_host, const int32_t *fir
                        int n_frames, int32_t *out4_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::Actions *A = impl(a);
-    if (n_frames < 0) yds::fail("actions: %d frames", n_frames);
-    if (n_out) *n_out = 0;
-    if (!n_frames) return 0;
-    if (!first || !stream_of) yds::fail("actions: NULL frame table");
-    if (first[0] != 0) yds::fail("actions: first[0] = %d", first[0]);
-    const int n_rows = first[n_frames];
-    if (n_rows && (!rows6_host || !row_time)) yds::fail("actions: NULL rows");
-    std::vector<yds::ActFrame> fr(n_frames);
-    std::vector<int32_t> ids;
-    for (int f = 0; f < n_frames; ++f) {
-        const int r0 = first[f], r1 = first[f + 1];
-        if (r1 < r0) yds::fail("actions: frame %d has first %d > %d", f, r0, r1);
-        ids.clear();
-        for (int r = r0; r < r1; ++r) ids.push_back(rows6_host[(size_t)r * 6 + 4]);
-        std::sort(ids.begin(), ids.end());
-        for (size_t k = 1; k < ids.size(); ++k)
-            if (ids[k] == ids[k - 1]) yds::fail("actions: track id %d appears twice in frame %d", ids[k], f);
-        fr[f] = yds::ActFrame{rows6_host + (size_t)r0 * 6, nullptr, r1 - r0, stream_of[f], f, 0.0, row_time + r0};
-    }
-    A->enqueue_ex(fr.data(), n_frames, A->own_stream, rows6_host, (size_t)n_rows, row_time, (size_t)n_rows);
-    YDS_HIP(hipStreamSynchronize(A->own_stream));
-    A->collect();
-    const int m = (int)(A->rows4.size() / 4);
-    if (n_out) *n_out = m;
-    if (m > cap) yds::fail("actions: %d action rows exceed the caller's capacity %d", m, cap);
+    const std::vector<yds::ActFrame> fr = yds::csr_frames("actions", rows6_host, first, stream_of, row_time, true, n_frames, n_out);
+    if (fr.empty()) return 0;
+    const size_t n_rows = first[n_frames];
+    A->enqueue_ex(fr.data(), n_frames, A->own_stream, rows6_host, n_rows, row_time, n_rows);
+    A->finish_alone();
+    const int m = A->give_count("action rows", (int)(A->rows4.size() / 4), cap, n_out);
     if (m) memcpy(out4_host, A->rows4.data(), (size_t)m * 4 * sizeof(int32_t));
     YDS_API_END
 }
 int yds_actions_get_orbits(yds_act *a, int stream, int32_t *ids, int32_t *ages, int32_t *lens, int cap, int *n) {
     YDS_API_BEGIN
     yds::Actions *A = impl(a);
-    if (stream < 0 || stream >= A->S) yds::fail("actions: stream %d outside [0,%d)", stream, A->S);
-    const int m = A->count_host[stream];
-    if (n) *n = m;
-    if (m > cap) yds::fail("actions: %d orbits exceed the caller's capacity %d", m, cap);
-    if (m) {
-        const yds::ActTab t = A->dev_tab(stream);
-        if (ids) YDS_HIP(hipMemcpy(ids, t.id, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-        if (ages) YDS_HIP(hipMemcpy(ages, t.age, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-        if (lens) YDS_HIP(hipMemcpy(lens, t.len, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-    }
+    const int m = A->table_count(stream, "orbits", cap, n);
+    const yds::ActTab t = A->dev_tab(stream);
+    A->column_out(ids, t.id, m);
+    A->column_out(ages, t.age, m);
+    A->column_out(lens, t.len, m);
     YDS_API_END
 }
 int yds_actions_set_timing(yds_act *a, int on) {
     YDS_API_BEGIN
-    impl(a)->timing = on != 0;
-    impl(a)->timed = false;
+    impl(a)->timer.set(on != 0);
     YDS_API_END
 }
 int yds_actions_last_us(yds_act *a, float *us) {
     YDS_API_BEGIN
-    yds::Actions *A = impl(a);
-    if (!A->timed) yds::fail("actions: no timed launch (yds_actions_set_timing, then a call)");
-    float ms = 0;
-    YDS_HIP(hipEventSynchronize(A->ev1));
-    YDS_HIP(hipEventElapsedTime(&ms, A->ev0, A->ev1));
-    *us = ms * 1e3f;
+    *us = impl(a)->timer.us("actions");
     YDS_API_END
 }
 

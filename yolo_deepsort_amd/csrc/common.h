@@ -72,6 +72,19 @@ template <typename T> struct DevBuf {
     }
 };
 
+// ---- pinned host buffer --------------------------------------------------------------------
+template <class T> struct PinBuf {                 // pinned host memory that only grows (contents are not kept)
+    T *p = nullptr;
+    size_t n = 0;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    void ensure(size_t count) {
+        if (count <= n) return;
+        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
+        YDS_HIP(hipHostMalloc((void **)&p, count * sizeof(T)));
+        n = count;
+    }
+};
+
 // ---- NHWC tensor view ----------------------------------------------------------------------
 // fp32, pixel-major: element (n,y,x,c) at p[((n*h + y)*w + x)*ld + c].  ld >= c lets a layer write
 // straight into a channel slice of a wider (concatenated) buffer.

@@ -282,30 +282,27 @@ struct ActFrame {
     double t;
     const double *row_time;
 };
-struct ActionsIface {
-    virtual ~ActionsIface() {}
+// What the driver of a step needs of a per-stream table stage (actions, zones; their shared frame is track_stage.h):
+struct TrackStageIface {
+    virtual ~TrackStageIface() {}
     virtual int streams() const = 0;
-    // asynchronous on s: grows the tables, one launch; the action rows land in pinned host memory
+    // asynchronous on s: grows the tables, one launch; what the stage reports lands in pinned host memory
     virtual void enqueue(const ActFrame *fr, int n, hipStream_t s) = 0;
-    // after the caller synchronised s: the rows of that call, frame k = rows [first[k], first[k + 1]) of rows4 (tag, id, class, action)
+    // after the caller synchronised s: the report of that call, frame k = items [first[k], first[k + 1]) of the stage's vectors
     virtual void collect() = 0;
-    std::vector<int32_t> rows4, first;
+    std::vector<int32_t> first;
+};
+struct ActionsIface : TrackStageIface {
+    std::vector<int32_t> rows4;                   // [m][4] tag, id, class, action
 };
 
 // --------------------------------------------------------------------------------------------- zones
 // Implemented in zones.hip: per stream a table of tracks with, per zone, an inside bit, a debounce streak and an enter time, advanced
 // over the frames of a call by ONE launch over the same frame descriptors as the action stage (row_time is not read: every row of a
 // frame carries the frame's time t).
-struct ZonesIface {
-    virtual ~ZonesIface() {}
-    virtual int streams() const = 0;
-    // asynchronous on s: grows the tables, one launch; the events land in pinned host memory
-    virtual void enqueue(const ActFrame *fr, int n, hipStream_t s) = 0;
-    // after the caller synchronised s: the events of that call, frame k = events [first[k], first[k + 1]) of ev6 (tag, id, class, kind,
-    // zone or line, 0) and evt2 (t, dwell)
-    virtual void collect() = 0;
-    std::vector<int32_t> ev6, first;
-    std::vector<double> evt2;
+struct ZonesIface : TrackStageIface {
+    std::vector<int32_t> ev6;                     // [m][6] tag, id, class, kind, zone or line, 0
+    std::vector<double> evt2;                     // [m][2] t, dwell
 };
 
 // --------------------------------------------------------------------------------------------- tracker

@@ -1,6 +1,6 @@
 // What the readers of the trackers' appearance galleries share (gallery_search.hip: the search calls, identity.hip: the identity map):
 // the descriptor of one tracker as the kernels see it, the distance kernel (defined in gallery_search.hip and launched from either
-// unit through its host stub), the order-preserving bits of a distance and the pinned host buffer both units return results in.
+// unit through its host stub), and the order-preserving bits of a distance.
 #pragma once
 #include "tracker_dev.h"
 
@@ -24,17 +24,4 @@ __device__ __forceinline__ unsigned ordered_bits(float v) {
     const unsigned u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-
-template <class T> struct PinBuf {                 // pinned host memory that only grows (contents are not kept)
-    T *p = nullptr;
-    size_t n = 0;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    void ensure(size_t count) {
-        if (count <= n) return;
-        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-        YDS_HIP(hipHostMalloc((void **)&p, count * sizeof(T)));
-        n = count;
-    }
-};
-
 }  // namespace yds

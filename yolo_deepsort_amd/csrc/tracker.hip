@@ -507,8 +507,8 @@ public:
         if (stream) (void)hipStreamDestroy(stream);
     }
     void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
-    void set_actions(ActionsIface *a, const double *frame_times) override { act = a; act_times_in = frame_times; }
-    void set_zones(ZonesIface *z, const double *frame_times) override { zon = z; zon_times_in = frame_times; }
+    void set_actions(ActionsIface *a, const double *frame_times) override { stages[0] = a; stage_times[0] = frame_times; }
+    void set_zones(ZonesIface *z, const double *frame_times) override { stages[1] = z; stage_times[1] = frame_times; }
     void set_identities(IdentityIface *i) override { ident = i; }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
@@ -518,9 +518,12 @@ public:
         std::vector<Tracker::FrameIn> fr;
         std::vector<int32_t *> outs;
         std::vector<int> caps, cnt, which, st;
-        struct ClearActions { TrackerGroup &g; ~ClearActions() { g.act = nullptr; g.act_times_in = nullptr; g.act_tag.clear(); g.act_time.clear(); } } clear_actions{*this};
-        struct ClearZones { TrackerGroup &g; ~ClearZones() { g.zon = nullptr; g.zon_times_in = nullptr; } } clear_zones{*this};
-        const double *times_in = act ? act_times_in : zon_times_in;          // (the pipeline hands both stages the same times)
+        struct ClearStages {
+            TrackerGroup &g;
+            ~ClearStages() { g.stages[0] = g.stages[1] = nullptr; g.stage_times[0] = g.stage_times[1] = nullptr; g.act_tag.clear(); g.act_time.clear(); }
+        } clear_stages{*this};
+        const bool staged = stages[0] || stages[1];
+        const double *times_in = stages[0] ? stage_times[0] : stage_times[1];   // (the pipeline hands both stages the same times)
         struct ClearIdentities { TrackerGroup &g; ~ClearIdentities() { g.ident = nullptr; } } clear_identities{*this};
         if (ident && !ident->bound_to(trk, S)) fail("tracker group: the identity map was not made over this step's trackers in this order");
         for (int b = 0; b < n; ++b) {
@@ -532,11 +535,11 @@ public:
             caps.push_back(cap);
             which.push_back(b);
             st.push_back(stream_of[b]);
-            if (act || zon) { act_tag.push_back(b); act_time.push_back(times_in ? times_in[b] : 0.0); }
+            if (staged) { act_tag.push_back(b); act_time.push_back(times_in ? times_in[b] : 0.0); }
         }
         cnt.assign(fr.size(), 0);
-        if (act && fr.empty()) { act->enqueue(nullptr, 0, stream); act->collect(); }      // (no frame ran: the stage reports no rows)
-        if (zon && fr.empty()) { zon->enqueue(nullptr, 0, stream); zon->collect(); }
+        for (TrackStageIface *sg : stages)
+            if (sg && fr.empty()) { sg->enqueue(nullptr, 0, stream); sg->collect(); }     // (no frame ran: the stage reports nothing)
         if (ident && fr.empty()) {                                  // (no frame ran: deferred tracks are still taken up)
             ident->enqueue_collect(stream);
             YDS_HIP(hipStreamSynchronize(stream));
@@ -683,26 +686,24 @@ public:
             if (maxD) hipLaunchKernelGGL(trk_back_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
         }
         YDS_HIP(hipGetLastError());
-        // ---- the action stage (set_actions): one launch over the step's frames, reading each frame's row count and rows where the
-        //      association kernels stored them (the pinned result blocks), its own rows behind the same synchronisation
-        const bool with_actions = act && (int)act_tag.size() == n, with_zones = zon && (int)act_tag.size() == n;
-        if (with_actions || with_zones) {
+        // ---- the table stages (set_actions, then set_zones): one launch each over the step's frames, reading each frame's row count and
+        //      rows where the association kernels stored them (the pinned result blocks), their own reports behind the same
+        //      synchronisation
+        const bool staged = (stages[0] || stages[1]) && (int)act_tag.size() == n;
+        if (staged) {
             std::vector<ActFrame> af(n);
             for (int i = 0; i < n; ++i) {
                 const int *r = res_host + res_off[i];
                 af[i] = ActFrame{r + M_COUNT, r + M_NOUT, T_ub[i] + frames[i].D, stream_of[i], act_tag[i], act_time[i], nullptr};
             }
-            if (with_actions) act->enqueue(af.data(), n, stream);
-            // ---- the zone stage (set_zones): one launch over the same descriptors, behind the action launch
-            if (with_zones) zon->enqueue(af.data(), n, stream);
+            for (TrackStageIface *sg : stages) if (sg) sg->enqueue(af.data(), n, stream);
         }
         // ---- the identity stage (set_identities): its collect launch reads the tables as the last round leaves them; what it counts
         //      comes back with the same synchronisation
         if (ident) ident->enqueue_collect(stream);
         // (the result blocks are in host memory already: a device-to-host copy command would queue behind frame uploads)
         YDS_HIP(hipStreamSynchronize(stream));
-        if (with_actions) act->collect();
-        if (with_zones) zon->collect();
+        for (TrackStageIface *sg : stages) if (sg && staged) sg->collect();
         for (int i = 0; i < n; ++i) {
             const int *r = res_host + res_off[i];
             const int m = r[M_NOUT];
@@ -716,10 +717,9 @@ public:
     }
 
     hipStream_t stream = nullptr;
-    ActionsIface *act = nullptr;                  // the action stage of the step being run (set_actions; step_batch clears it)
+    TrackStageIface *stages[2] = {nullptr, nullptr};   // the action and the zone stage of the step being run, in launch order (set_actions, set_zones; step_batch clears them)
+    const double *stage_times[2] = {nullptr, nullptr};
     IdentityIface *ident = nullptr;               // the identity stage of the step being run (set_identities; step_batch clears it)
-    ZonesIface *zon = nullptr;                    // the zone stage of the step being run (set_zones; step_batch clears it)
-    const double *act_times_in = nullptr, *zon_times_in = nullptr;
     std::vector<int> act_tag;                     // per frame that runs: its index in the step, its time
     std::vector<double> act_time;
     DevBuf<int> in_dev;

@@ -1,6 +1,6 @@
 // Zones and counting lines on the device: per video stream a table of tracks in HBM - id, class, age, last doubled foot point and its
 // time, and per zone an inside bit, a debounce streak and an enter time - advanced by one launch per call, beside the action stage
-// (actions.hip) and shaped like it.
+// (actions.hip) and built on the same frame (track_stage.h).
 //
 // There is no reference counterpart; the rules are written down in include/ydsort.h (the zones block) and restated in Python ints by
 // yolo_deepsort_amd/zones.py ZoneMonitor, which every device test compares against with exact equality: all geometry is int64.
@@ -9,12 +9,10 @@
 // handles the entries in table order, one thread per entry: a seen entry tests every class-matching line against the move from its
 // last point and every class-matching zone against its new point, an unseen entry ages.  What an entry emits is kept as five 32-bit
 // masks in registers; the events go count, prefix, write - entry-major, lines before zones - straight into a pinned result block.
-// Entries that reached max_age then leave by an ordered compaction (tracker_dev.h compact_ordered).  Counters are summed in LDS and
+// Entries that reached max_age then leave by an ordered compaction (track_stage.h retire).  Counters are summed in LDS and
 // added to the stream's counters in HBM once per call.
-#include "tracker_dev.h"
+#include "track_stage.h"
 #include "ydsort.h"
-
-#include <limits.h>
 
 #include <memory>
 
@@ -89,25 +87,6 @@ __device__ __forceinline__ bool zone_inside(long long x, long long y, const int 
 }
 __device__ __forceinline__ int clamp_anchor(long long v) { return (int)(v < -ANCHOR_LIMIT ? -ANCHOR_LIMIT : v > ANCHOR_LIMIT ? ANCHOR_LIMIT : v); }
 
-// exclusive prefix of v over the 256 threads of the workgroup; chunk = the sum (to every thread).  s_cnt: LDS int[4].
-__device__ __forceinline__ int block_prefix(int v, int *s_cnt, int &chunk) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_cnt[wave] = x;
-    __syncthreads();
-    int woff = 0;
-    chunk = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int c = s_cnt[w]; if (w < wave) woff += c; chunk += c; }
-    __syncthreads();
-    return woff + x - v;
-}
-
 __global__ __launch_bounds__(256) void zone_update_kernel(const ZoneWork *works, const ZoneFrameDev *frames, int max_age, int *res, int ev_base,
                                                           double *res_t) {
     __shared__ int s_cnt[4];
@@ -123,21 +102,13 @@ __global__ __launch_bounds__(256) void zone_update_kernel(const ZoneWork *works,
     const ZoneGeo &G = *reinterpret_cast<const ZoneGeo *>(s_geo);
     for (int f = W.f0; f < W.f1; ++f) {
         const ZoneFrameDev F = frames[f];
-        const int R = F.n_p ? min(max(*F.n_p, 0), F.n) : F.n;
-        for (int k = tid; k < R * 6; k += 256) W.srows[k] = F.rows[k];
+        const int R = stage_frame_rows(F.rows, F.n_p, F.n, W.srows);
         __syncthreads();
         // ---- rows whose id is unknown are registered at the end of the table in row order: bit outside, no streak
-        const int added = compact_ordered(R, s_cnt, [&](int j) {
-            const int id = W.srows[j * 6 + 4];
-            for (int e = 0; e < n; ++e) if (T.id[e] == id) return false;
-            return true;
-        }, [&](int j, int r) {
-            const int e = n + r;
-            if (e >= cap) return;                                                 // (the host sized the table for every row of the call)
-            T.id[e] = W.srows[j * 6 + 4]; T.cls[e] = W.srows[j * 6 + 5]; T.age[e] = 0; T.mask[e] = 0u;
+        const int n_all = register_unknown(R, n, cap, s_cnt, T.id, W.srows, [&](int e, const int *r) {
+            T.id[e] = r[4]; T.cls[e] = r[5]; T.age[e] = 0; T.mask[e] = 0u;
             for (int z = 0; z < ZMAX; ++z) T.streak[(size_t)e * ZMAX + z] = 0;
         });
-        const int n_all = min(n + added, cap);
         __syncthreads();
         // ---- entries in table order, a thread each; the events of a chunk of 256 entries go count, prefix, write
         int *out6 = res + ev_base + (size_t)F.ev_off * 6;
@@ -150,8 +121,7 @@ __global__ __launch_bounds__(256) void zone_update_kernel(const ZoneWork *works,
             int id = 0, cls = 0;
             if (e < n_all) {
                 id = T.id[e]; cls = T.cls[e];
-                int j = 0;
-                while (j < R && W.srows[j * 6 + 4] != id) ++j;
+                const int j = find_row(W.srows, R, id);
                 if (j == R) {                                                     // unseen: ages, LOST from every zone it is inside
                     const int a = T.age[e] + 1;
                     T.age[e] = a;
@@ -220,21 +190,17 @@ __global__ __launch_bounds__(256) void zone_update_kernel(const ZoneWork *works,
         // ---- entries that reached max_age leave, the rest keep their order (only an entry that just aged has age > 0)
         int n_live = n_all;
         if (dead) {
-            n_live = compact_ordered(n_all, s_cnt, [&](int e) { const int a = T.age[e]; return !(a > 0 && a >= max_age); }, [&](int e, int r) {
-                const int d = cap + r;
+            auto move = [&](int d, int e) {
                 T.id[d] = T.id[e]; T.cls[d] = T.cls[e]; T.age[d] = T.age[e]; T.px[d] = T.px[e]; T.py[d] = T.py[e]; T.mask[d] = T.mask[e];
                 T.pt[d] = T.pt[e];
+            };
+            n_live = retire(n_all, cap, s_cnt, [&](int e) { const int a = T.age[e]; return !(a > 0 && a >= max_age); }, [&](int d, int e) {
+                move(d, e);
                 for (int z = 0; z < ZMAX; ++z) {
                     T.streak[(size_t)d * ZMAX + z] = T.streak[(size_t)e * ZMAX + z];
                     T.enter[(size_t)d * ZMAX + z] = T.enter[(size_t)e * ZMAX + z];
                 }
-            });
-            __syncthreads();
-            for (int e = tid; e < n_live; e += 256) {
-                const int d = cap + e;
-                T.id[e] = T.id[d]; T.cls[e] = T.cls[d]; T.age[e] = T.age[d]; T.px[e] = T.px[d]; T.py[e] = T.py[d]; T.mask[e] = T.mask[d];
-                T.pt[e] = T.pt[d];
-            }
+            }, move);
             for (size_t k = tid; k < (size_t)n_live * ZMAX; k += 256) {
                 T.streak[k] = T.streak[(size_t)cap * ZMAX + k];
                 T.enter[k] = T.enter[(size_t)cap * ZMAX + k];
@@ -247,30 +213,15 @@ __global__ __launch_bounds__(256) void zone_update_kernel(const ZoneWork *works,
     if (tid == 0) { *T.count = n; res[W.res_count] = n; }
 }
 
-class Zones : public ZonesIface {
+class Zones : public TrackStage<ZonesIface> {
 public:
-    Zones(int S, int max_age) : S(S), max_age(max_age), tabs(S), count_host(S, 0), nz(S, 0), nl(S, 0) {
-        if (S < 1) fail("zones: %d streams", S);
+    Zones(int S, int max_age) : TrackStage("zones", S), max_age(max_age), tabs(S), nz(S, 0), nl(S, 0) {
         if (max_age < 1) fail("zones: max_age %d < 1", max_age);
         geo.alloc(S);
         YDS_HIP(hipMemset(geo.p, 0, S * sizeof(ZoneGeo)));                       // (no zones, no lines until set_stream)
-        counts.alloc(S);
-        YDS_HIP(hipMemset(counts.p, 0, S * sizeof(int)));
         ctr.alloc((size_t)S * N_CTR);
         YDS_HIP(hipMemset(ctr.p, 0, (size_t)S * N_CTR * sizeof(int)));
-        own_stream = make_stream(true);
-        YDS_HIP(hipEventCreate(&ev0));
-        YDS_HIP(hipEventCreate(&ev1));
     }
-    ~Zones() override {
-        if (in_host) (void)hipHostFree(in_host);
-        if (res_host) (void)hipHostFree(res_host);
-        if (res_t_host) (void)hipHostFree(res_t_host);
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-    }
-    int streams() const override { return S; }
 
     struct Tab {
         DevBuf<int> ints;         // id | cls | age | px | py | mask, [2][cap] each
@@ -284,32 +235,24 @@ public:
         return ZoneTab{t.ints.p, t.ints.p + c2, t.ints.p + 2 * c2, t.ints.p + 3 * c2, t.ints.p + 4 * c2,
                        reinterpret_cast<uint32_t *>(t.ints.p + 5 * c2), t.pt.p, t.streak.p, t.enter.p, counts.p + s, ctr.p + (size_t)s * N_CTR, t.cap};
     }
-    // room for `need` entries; nothing of this handle is in flight between calls (every call ends behind a synchronisation)
     void grow(int s, int need) {
-        Tab &t = tabs[s];
-        if (need <= t.cap) return;
-        int c = std::max(t.cap, 64);
-        while (c < need) c *= 2;
-        Tab nt;
-        nt.cap = c;
-        nt.ints.alloc(12 * (size_t)c);
-        nt.pt.alloc(2 * (size_t)c);
-        nt.enter.alloc(2 * (size_t)c * ZMAX);
-        nt.streak.alloc(2 * (size_t)c * ZMAX);
-        const int n = count_host[s];
-        if (n) {
-            for (int fld = 0; fld < 6; ++fld)
-                YDS_HIP(hipMemcpy(nt.ints.p + (size_t)fld * 2 * c, t.ints.p + (size_t)fld * 2 * t.cap, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice));
-            YDS_HIP(hipMemcpy(nt.pt.p, t.pt.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice));
-            YDS_HIP(hipMemcpy(nt.enter.p, t.enter.p, (size_t)n * ZMAX * sizeof(double), hipMemcpyDeviceToDevice));
-            YDS_HIP(hipMemcpy(nt.streak.p, t.streak.p, (size_t)n * ZMAX, hipMemcpyDeviceToDevice));
-        }
-        t = std::move(nt);
+        const size_t n = count_host[s];
+        grow_table(tabs[s], need, n, [&](Tab &nt) {
+            nt.ints.alloc(12 * (size_t)nt.cap);
+            nt.pt.alloc(2 * (size_t)nt.cap);
+            nt.enter.alloc(2 * (size_t)nt.cap * ZMAX);
+            nt.streak.alloc(2 * (size_t)nt.cap * ZMAX);
+        }, [&](Tab &nt, const Tab &t) {
+            copy_live(nt.ints, t.ints, n, 6, nt.cap, t.cap);
+            copy_live(nt.pt, t.pt, n);
+            copy_live(nt.enter, t.enter, n * ZMAX);
+            copy_live(nt.streak, t.streak, n * ZMAX);
+        });
     }
 
     void set_stream(int stream, const int32_t *zptr, const int32_t *zxy, const int32_t *zcls, const int32_t *zmin, int Z, const int32_t *lxy,
                     const int32_t *lcls, int L) {
-        if (stream < -1 || stream >= S) fail("zones: stream %d outside [-1,%d)", stream, S);
+        check_stream(stream, -1);
         if (Z < 0 || Z > ZMAX) fail("zones: %d zones outside [0,%d]", Z, ZMAX);
         if (L < 0 || L > LMAX) fail("zones: %d lines outside [0,%d]", L, LMAX);
         if (Z && (!zptr || !zxy || !zcls || !zmin)) fail("zones: NULL zone geometry");
@@ -348,49 +291,19 @@ public:
     }
 
     void reset(int stream) {
-        if (stream < -1 || stream >= S) fail("zones: stream %d outside [-1,%d)", stream, S);
-        for (int s = 0; s < S; ++s) {
-            if (stream >= 0 && s != stream) continue;
-            YDS_HIP(hipMemset(counts.p + s, 0, sizeof(int)));
-            YDS_HIP(hipMemset(ctr.p + (size_t)s * N_CTR, 0, N_CTR * sizeof(int)));
-            count_host[s] = 0;
-        }
+        TrackStage::reset(stream);
+        YDS_HIP(hipMemset(ctr.p + (size_t)std::max(stream, 0) * N_CTR, 0, (size_t)(stream < 0 ? S : 1) * N_CTR * sizeof(int)));
     }
 
     void enqueue(const ActFrame *fr, int n, hipStream_t s) override { enqueue_ex(fr, n, s, nullptr, 0); }
 
-    // rows_host (the stand-alone entry): a host array that travels to the device inside the call's input block; the frames' rows6 then
-    // point INTO that array and are translated to the block's device addresses
+    // rows_host (the stand-alone entry): a host array that travels to the device inside the call's input block (open_blocks)
     void enqueue_ex(const ActFrame *fr, int n, hipStream_t s, const int32_t *rows_host, size_t n_rows_host) {
-        pending_n = n;
-        if (n <= 0) return;
-        // ---- frames by stream, order kept; a workgroup per stream with frames
-        std::vector<int> n_of(S, 0), rows_of(S, 0);
-        int max_rows = 1;
-        for (int i = 0; i < n; ++i) {
-            if (fr[i].stream < 0 || fr[i].stream >= S) fail("zones: frame %d names stream %d outside [0,%d)", i, fr[i].stream, S);
-            if (fr[i].n_rows < 0) fail("zones: frame %d has %d rows", i, fr[i].n_rows);
-            ++n_of[fr[i].stream];
-            rows_of[fr[i].stream] += fr[i].n_rows;
-            max_rows = std::max(max_rows, fr[i].n_rows);
-        }
-        std::vector<int> wg_of(S, -1), start(S, 0);
-        int n_wg = 0, acc = 0;
-        for (int st = 0; st < S; ++st) {
-            if (!n_of[st]) continue;
-            wg_of[st] = n_wg++;
-            start[st] = acc;
-            acc += n_of[st];
-            grow(st, count_host[st] + rows_of[st]);
-        }
-        std::vector<int> order(n, 0);             // order[slot in the sorted list] = frame of the call
-        {
-            std::vector<int> fill(start);
-            for (int i = 0; i < n; ++i) order[fill[fr[i].stream]++] = i;
-        }
+        const StagePlan P = plan(fr, n, [&](int st, int need) { grow(st, need); });
+        if (!P.n_wg) return;
         // ---- the most events a frame can emit: every entry it can meet (the table before the call + the rows so far), at each zone
         //      and line of its stream
-        std::vector<size_t> ev_off(n);
+        pending_off.resize(n);
         pending_cap.resize(n);
         size_t ev_total = 0;
         {
@@ -400,106 +313,58 @@ public:
                 held[st] += fr[i].n_rows;
                 const size_t c = held[st] * (size_t)(nz[st] + nl[st]);
                 if (c > (size_t)INT_MAX) fail("zones: frame %d may emit %zu events", i, c);
-                ev_off[i] = ev_total;
+                pending_off[i] = ev_total;
                 pending_cap[i] = (int)c;
                 ev_total += c;
             }
         }
-        // ---- blocks: input = works | frames | rows (8-byte aligned pieces); results = frame counts | entry counts | events [m][6]
-        //      (int) and [m][2] (double)
-        const size_t works_b = (size_t)n_wg * sizeof(ZoneWork), frames_b = (size_t)n * sizeof(ZoneFrameDev);
-        const size_t rows_off = works_b + frames_b, in_total = rows_off + n_rows_host * 6 * sizeof(int32_t);
-        const size_t ev_base = (size_t)n + n_wg, res_total = ev_base + ev_total * 6;
-        if (res_total > (size_t)INT_MAX) fail("zones: result block of %zu ints", res_total);
-        if (in_total > in_cap) {
-            if (in_host) (void)hipHostFree(in_host);
-            in_host = nullptr;
-            in_cap = in_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&in_host, in_cap));
-            in_dev.alloc(in_cap);
-        }
-        if (res_total > res_cap) {
-            if (res_host) (void)hipHostFree(res_host);
-            res_host = nullptr;
-            res_cap = res_total * 2;
-            YDS_HIP(hipHostMalloc((void **)&res_host, res_cap * sizeof(int)));
-        }
-        if (ev_total * 2 + 2 > res_t_cap) {
-            if (res_t_host) (void)hipHostFree(res_t_host);
-            res_t_host = nullptr;
-            res_t_cap = (ev_total * 2 + 2) * 2;
-            YDS_HIP(hipHostMalloc((void **)&res_t_host, res_t_cap * sizeof(double)));
-        }
-        if ((size_t)n_wg * max_rows * 6 > srows.n) srows.alloc((size_t)n_wg * max_rows * 6 * 2);
-        const int32_t *rows_dev = reinterpret_cast<const int32_t *>(in_dev.p + rows_off);
-        ZoneWork *w = reinterpret_cast<ZoneWork *>(in_host);
-        ZoneFrameDev *fd = reinterpret_cast<ZoneFrameDev *>(in_host + works_b);
-        for (int st = 0; st < S; ++st) {
-            if (wg_of[st] < 0) continue;
-            const int k = wg_of[st];
-            w[k] = ZoneWork{dev_tab(st), geo.p + st, start[st], start[st] + n_of[st], srows.p + (size_t)k * max_rows * 6, n + k};
+        // ---- blocks: input = works | frames | rows; results = frame counts | entry counts | events [m][6] (int) and [m][2] (double)
+        const size_t works_b = (size_t)P.n_wg * sizeof(ZoneWork);
+        pending_base = (size_t)n + P.n_wg;
+        open_blocks(P, works_b + (size_t)n * sizeof(ZoneFrameDev), rows_host, n_rows_host, pending_base + ev_total * 6);
+        if (ev_total * 2 + 2 > res_t_host.n) res_t_host.ensure((ev_total * 2 + 2) * 2);
+        ZoneWork *w = reinterpret_cast<ZoneWork *>(in_host.p);
+        ZoneFrameDev *fd = reinterpret_cast<ZoneFrameDev *>(in_host.p + works_b);
+        for (int k = 0; k < P.n_wg; ++k) {
+            const int st = wg_stream[k];
+            w[k] = ZoneWork{dev_tab(st), geo.p + st, P.start[st], P.start[st] + P.n_of[st], wg_srows(k), n + k};
         }
         for (int e = 0; e < n; ++e) {
-            const ActFrame &f = fr[order[e]];
+            const ActFrame &f = fr[P.order[e]];
             ZoneFrameDev d;
-            d.rows = rows_host ? rows_dev + (f.rows6 - rows_host) : f.rows6;
+            d.rows = dev_rows(f);
             d.n_p = f.n_rows_p;
             d.t = f.t; d.n = f.n_rows; d.tag = f.tag;
-            d.res_n = order[e];
-            d.ev_off = (int)ev_off[order[e]];
-            d.ev_cap = pending_cap[order[e]];
+            d.res_n = P.order[e];
+            d.ev_off = (int)pending_off[P.order[e]];
+            d.ev_cap = pending_cap[P.order[e]];
             fd[e] = d;
         }
-        if (n_rows_host) memcpy(in_host + rows_off, rows_host, n_rows_host * 6 * sizeof(int32_t));
-        wg_stream.assign(n_wg, 0);
-        for (int st = 0; st < S; ++st) if (wg_of[st] >= 0) wg_stream[wg_of[st]] = st;
-        pending_off.assign(ev_off.begin(), ev_off.end());
-        pending_base = ev_base;
-        YDS_HIP(hipMemcpyAsync(in_dev.p, in_host, in_total, hipMemcpyHostToDevice, s));
-        if (timing) YDS_HIP(hipEventRecord(ev0, s));
-        hipLaunchKernelGGL(zone_update_kernel, dim3(n_wg), dim3(256), 0, s, reinterpret_cast<const ZoneWork *>(in_dev.p),
-                           reinterpret_cast<const ZoneFrameDev *>(in_dev.p + works_b), max_age, res_host, (int)ev_base, res_t_host);
-        YDS_HIP(hipGetLastError());
-        if (timing) { YDS_HIP(hipEventRecord(ev1, s)); timed = true; }
+        submit(s, [&] {
+            hipLaunchKernelGGL(zone_update_kernel, dim3(P.n_wg), dim3(256), 0, s, reinterpret_cast<const ZoneWork *>(in_dev.p),
+                               reinterpret_cast<const ZoneFrameDev *>(in_dev.p + works_b), max_age, res_host.p, (int)pending_base, res_t_host.p);
+        });
     }
 
     void collect() override {
-        const int n = pending_n;
         ev6.clear();
         evt2.clear();
-        first.assign(std::max(n, 0) + 1, 0);
-        if (n <= 0) return;
-        for (int i = 0; i < n; ++i) {
-            const int m = res_host[i];
-            if (m < 0 || m > pending_cap[i]) fail("zones: frame %d reports %d events, %d possible", i, m, pending_cap[i]);
-            const int *r = res_host + pending_base + pending_off[i] * 6;
-            const double *t = res_t_host + pending_off[i] * 2;
+        collect_counts("events", [&](int i, int m) {
+            const int *r = res_host.p + pending_base + pending_off[i] * 6;
+            const double *t = res_t_host.p + pending_off[i] * 2;
             ev6.insert(ev6.end(), r, r + (size_t)m * 6);
             evt2.insert(evt2.end(), t, t + (size_t)m * 2);
-            first[i + 1] = first[i] + m;
-        }
-        for (size_t k = 0; k < wg_stream.size(); ++k) count_host[wg_stream[k]] = res_host[n + k];
-        pending_n = 0;
+        });
     }
 
-    int S, max_age;
+    int max_age;
     std::vector<Tab> tabs;
-    std::vector<int> count_host;                  // entries of every stream after the last collected call
     std::vector<int> nz, nl;                      // zones / lines of every stream
     DevBuf<ZoneGeo> geo;
-    DevBuf<int> counts, ctr, srows;
-    DevBuf<char> in_dev;
-    char *in_host = nullptr;
-    int *res_host = nullptr;
-    double *res_t_host = nullptr;
-    size_t in_cap = 0, res_cap = 0, res_t_cap = 0;
-    int pending_n = 0;
-    size_t pending_base = 0;
-    std::vector<int> wg_stream, pending_cap;
-    std::vector<size_t> pending_off;
-    hipStream_t own_stream = nullptr;             // the stand-alone entry's
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timing = false, timed = false;
+    DevBuf<int> ctr;
+    PinBuf<double> res_t_host;
+    size_t pending_base = 0;                      // of the call in flight: where the events begin in the int result block ...
+    std::vector<size_t> pending_off;              // ... and every frame's first event
 };
 
 }  // namespace yds
@@ -534,31 +399,11 @@ int yds_zones_update(yds_zones *z, const int32_t *rows6_host, const int32_t *fir
                      int n_frames, int32_t *ev6_host, double *evt2_host, int cap, int *n_out) {
     YDS_API_BEGIN
     yds::Zones *Zn = impl(z);
-    if (n_frames < 0) yds::fail("zones: %d frames", n_frames);
-    if (n_out) *n_out = 0;
-    if (!n_frames) return 0;
-    if (!first || !stream_of || !frame_time) yds::fail("zones: NULL frame table");
-    if (first[0] != 0) yds::fail("zones: first[0] = %d", first[0]);
-    const int n_rows = first[n_frames];
-    if (n_rows && !rows6_host) yds::fail("zones: NULL rows");
-    std::vector<yds::ActFrame> fr(n_frames);
-    std::vector<int32_t> ids;
-    for (int f = 0; f < n_frames; ++f) {
-        const int r0 = first[f], r1 = first[f + 1];
-        if (r1 < r0) yds::fail("zones: frame %d has first %d > %d", f, r0, r1);
-        ids.clear();
-        for (int r = r0; r < r1; ++r) ids.push_back(rows6_host[(size_t)r * 6 + 4]);
-        std::sort(ids.begin(), ids.end());
-        for (size_t k = 1; k < ids.size(); ++k)
-            if (ids[k] == ids[k - 1]) yds::fail("zones: track id %d appears twice in frame %d", ids[k], f);
-        fr[f] = yds::ActFrame{rows6_host + (size_t)r0 * 6, nullptr, r1 - r0, stream_of[f], f, frame_time[f], nullptr};
-    }
-    Zn->enqueue_ex(fr.data(), n_frames, Zn->own_stream, rows6_host, (size_t)n_rows);
-    YDS_HIP(hipStreamSynchronize(Zn->own_stream));
-    Zn->collect();
-    const int m = (int)(Zn->ev6.size() / 6);
-    if (n_out) *n_out = m;
-    if (m > cap) yds::fail("zones: %d events exceed the caller's capacity %d", m, cap);
+    const std::vector<yds::ActFrame> fr = yds::csr_frames("zones", rows6_host, first, stream_of, frame_time, false, n_frames, n_out);
+    if (fr.empty()) return 0;
+    Zn->enqueue_ex(fr.data(), n_frames, Zn->own_stream, rows6_host, (size_t)first[n_frames]);
+    Zn->finish_alone();
+    const int m = Zn->give_count("events", (int)(Zn->ev6.size() / 6), cap, n_out);
     if (m) {
         memcpy(ev6_host, Zn->ev6.data(), (size_t)m * 6 * sizeof(int32_t));
         memcpy(evt2_host, Zn->evt2.data(), (size_t)m * 2 * sizeof(double));
@@ -568,7 +413,7 @@ int yds_zones_update(yds_zones *z, const int32_t *rows6_host, const int32_t *fir
 int yds_zones_get_counts(yds_zones *z, int stream, int32_t *zone4, int32_t *line2) {
     YDS_API_BEGIN
     yds::Zones *Zn = impl(z);
-    if (stream < 0 || stream >= Zn->S) yds::fail("zones: stream %d outside [0,%d)", stream, Zn->S);
+    Zn->check_stream(stream);
     int c[yds::N_CTR];
     YDS_HIP(hipMemcpy(c, Zn->ctr.p + (size_t)stream * yds::N_CTR, sizeof c, hipMemcpyDeviceToHost));
     if (zone4) memcpy(zone4, c, (size_t)Zn->nz[stream] * 4 * sizeof(int32_t));
@@ -578,32 +423,21 @@ int yds_zones_get_counts(yds_zones *z, int stream, int32_t *zone4, int32_t *line
 int yds_zones_get_tracks(yds_zones *z, int stream, int32_t *ids, int32_t *ages, int32_t *inside_mask, int cap, int *n) {
     YDS_API_BEGIN
     yds::Zones *Zn = impl(z);
-    if (stream < 0 || stream >= Zn->S) yds::fail("zones: stream %d outside [0,%d)", stream, Zn->S);
-    const int m = Zn->count_host[stream];
-    if (n) *n = m;
-    if (m > cap) yds::fail("zones: %d tracks exceed the caller's capacity %d", m, cap);
-    if (m) {
-        const yds::ZoneTab t = Zn->dev_tab(stream);
-        if (ids) YDS_HIP(hipMemcpy(ids, t.id, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-        if (ages) YDS_HIP(hipMemcpy(ages, t.age, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-        if (inside_mask) YDS_HIP(hipMemcpy(inside_mask, t.mask, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
-    }
+    const int m = Zn->table_count(stream, "tracks", cap, n);
+    const yds::ZoneTab t = Zn->dev_tab(stream);
+    Zn->column_out(ids, t.id, m);
+    Zn->column_out(ages, t.age, m);
+    Zn->column_out(inside_mask, t.mask, m);
     YDS_API_END
 }
 int yds_zones_set_timing(yds_zones *z, int on) {
     YDS_API_BEGIN
-    impl(z)->timing = on != 0;
-    impl(z)->timed = false;
+    impl(z)->timer.set(on != 0);
     YDS_API_END
 }
 int yds_zones_last_us(yds_zones *z, float *us) {
     YDS_API_BEGIN
-    yds::Zones *Zn = impl(z);
-    if (!Zn->timed) yds::fail("zones: no timed launch (yds_zones_set_timing, then a call)");
-    float ms = 0;
-    YDS_HIP(hipEventSynchronize(Zn->ev1));
-    YDS_HIP(hipEventElapsedTime(&ms, Zn->ev0, Zn->ev1));
-    *us = ms * 1e3f;
+    *us = impl(z)->timer.us("zones");
     YDS_API_END
 }
 
