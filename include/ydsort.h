@@ -32,6 +32,7 @@ typedef struct yds_reid yds_reid;   /* ReID extractor        (deep_sort/deep/fea
 typedef struct yds_trk yds_trk;     /* DeepSORT tracker      (deep_sort/sort/tracker.py:8-176)      */
 typedef struct yds_pipe yds_pipe;   /* detect+ReID+associate (yolo3/detect/video_detect.py:134-157) */
 typedef struct yds_zones yds_zones; /* per-stream zone / line tables and counters (no reference counterpart) */
+typedef struct yds_heatmap yds_heatmap; /* per-stream heat map layers and track tables (no reference counterpart) */
 typedef struct yds_act yds_act;     /* per-stream orbit caches + action predicates (action/action_Identify.py:4-47) */
 typedef struct yds_ident yds_ident; /* cross-camera identity map over S trackers (no reference counterpart)                  */
 typedef struct yds_comm yds_comm;  /* RCCL communicator of the stream-sharded multi-GPU run (no reference counterpart) */
@@ -641,6 +642,78 @@ int yds_zones_last_us(yds_zones *, float *us);
  * yds_pipeline_last_zone_events: the events of the last step (the tag is the frame of the step), already on the host. */
 int yds_pipeline_set_zones(yds_pipe *, yds_zones *);
 int yds_pipeline_last_zone_events(yds_pipe *, int32_t *ev6_host, double *evt2_host, int cap, int *n_out);
+
+/* ---- heat maps on the device: where people stand, walk and linger ------------------------------------------------------------------
+ * No reference counterpart; yolo_deepsort_amd/heatmap.py (HeatMap, levels, render) restates the rules below in Python ints / numpy
+ * int64 and every comparison with it is exact equality: everything is integer arithmetic except one double subtraction and one
+ * double product per dwell credit.  The layers only grow (no decay) and cells are squares of image pixels (no ground plane).
+ * Spec, per stream: frames of h x w pixels, cell in {4, 8, 16, 32, 64, 128} pixels, class_id >= -1 (-1 = any class);
+ *   gw = ceil(w / cell), gh = ceil(h / cell), gw * gh <= YDS_HEATMAP_MAX_CELLS.
+ * State, per stream: five int64 layers [gh][gw] - YDS_HEAT_PRESENCE, _VISITS, _DWELL_US, _FLOW_X, _FLOW_Y - and a table of tracks in
+ *   insertion order; an entry holds track id, age, cell, the time of its last sighting and its last foot point.
+ * One processed frame (rows x1, y1, x2, y2, id, class; time t) of a stream:
+ *   1. rows whose class does not match the spec are ignored entirely: they never enter the table.
+ *   2. a matching row gives the zones' DOUBLED foot point F = (x1 + x2, 2 * y2), each component clamped to [-2^24, 2^24].
+ *   3. its cell is (F.y // (2 cell)) * gw + F.x // (2 cell) (floor division) when both quotients lie inside the grid, else -1
+ *      (outside); a row outside still keeps its table entry.
+ *   4. a known id was "seen last frame" iff its age before this frame is 0.  If so and its previous cell >= 0:
+ *      dwell_us[previous cell] += max(0, rint((t - t_last) * 1e6)), rint rounding half to even; if so and cell >= 0:
+ *      flow_x[cell] += F.x - F_prev.x and flow_y likewise (doubled pixels).  A gap is not dwell: an entry with age > 0 credits
+ *      neither.  If cell >= 0 and cell != previous cell: visits[cell] += 1.
+ *   5. an unknown id is registered at the end of the table (row order); if cell >= 0: visits[cell] += 1.
+ *   6. if cell >= 0: presence[cell] += 1.
+ *   7. the entry becomes (age 0, cell, t, F).
+ *   8. entries not seen in this frame age by one; an entry with age > max_age leaves the table, the others keeping their order, so
+ *      the same id returning later is a new visit.
+ *   9. a frame the tracker was not called for is not seen: nothing ages.  A frame with zero rows ages every entry.
+ * Render, in place on uint8 frames of h * w * 3 bytes resident in HBM and addressed by slot like yds_anonymize_frames; frame i takes
+ *   the grid of stream stream_of[i], whose spec must be of h x w.  layer: presence, visits or dwell_us.  vmax = 0: the layer's
+ *   current maximum over that stream's grid, reduced on the device, 1 when nothing is positive; else vmax in [1, 2^47].
+ *   level = (min(max(v, 0), vmax) * 65535) // vmax per cell.  For pixel (x, y), c = cell: U = 2x + 1 - c, i0 = U // (2c) (floor,
+ *   may be -1), fx = U - 2c * i0, ia = clamp(i0, 0, gw - 1), ib = clamp(i0 + 1, 0, gw - 1); the same in y gives ja, jb, fy;
+ *   num = (2c - fx)(2c - fy) L[ja][ia] + fx (2c - fy) L[ja][ib] + (2c - fx) fy L[jb][ia] + fx fy L[jb][ib];
+ *   k = num // (4 c^2 * 257), 0..255.  k == 0: the pixel stays untouched; else per byte b
+ *   out = (alpha * lut[k][b] + (256 - alpha) * src[b] + 128) >> 8, alpha in [1, 256], lut [256][3] uint8 as the bytes land in memory.
+ *   A bilinear field between cell centres: no cell edges show, empty areas keep the picture.
+ * yds_heatmap_create     <- n_streams streams without a spec; max_age >= 1.
+ * yds_heatmap_set_stream <- the spec of one stream: fresh zero layers and an empty table for it.  Refused by name: a cell outside the
+ *                           set, a grid of more than YDS_HEATMAP_MAX_CELLS cells, a stream outside [0, n_streams), class_id < -1.
+ * yds_heatmap_reset      <- zero layers and an empty table for one stream, or all of them (-1).
+ * yds_heatmap_update     <- n_frames frames in ONE launch and one synchronisation, the frame table as for yds_zones_update; a stream
+ *                           without a spec and an id twice in one frame are refused before the launch.  counted_out [n_frames] (may
+ *                           be NULL): the rows of each frame that were of its stream's class.
+ * yds_heatmap_get_layers <- out5 [5][gh][gw] of one stream; cap in values.
+ * yds_heatmap_get_max    <- the maximum of one layer (0..4) of one stream, reduced on the device.
+ * yds_heatmap_get_tracks <- the table of one stream in insertion order: ids, ages, cells, xy2 [m][2] doubled foot points, t (each
+ *                           may be NULL); *n = the count, more than cap is an error naming it.
+ * yds_heatmap_render     <- the render above for n frames, frame i in slot slot_host[i] of n_src; synchronous on the handle's own
+ *                           stream; two launches (levels, pixels) whatever n.  Refused by name before anything launches: a slot
+ *                           outside [0, n_src) or named twice, a stream outside the handle or without a spec, (h, w) other than
+ *                           that stream's spec, a layer that is not renderable, vmax outside [0, 2^47], alpha outside [1, 256].
+ *                           vmax = 0 with a reduced maximum above 2^47 is refused too, after the launches: no frame was touched.
+ * yds_heatmap_set_timing / _last_us: measurement aid - HIP events around the update launch (what = 0) and around the two launches
+ *                           of a render (what = 1); device time of the last one in us.
+ * yds_pipeline_set_heatmap: with a handle of at least as many streams as the pipeline, each with a spec, every step adds ONE launch
+ *   behind the zone launch (if there is one), ahead of the identity collect launch and of the step's one synchronisation; it reads
+ *   the same tracker rows and frame times as the zone stage in every entry (plain, window, mixed sizes, per-stream windows).  NULL
+ *   switches the stage off; without it a step runs the launches it always ran.  Refused while a look-ahead pass is in flight. */
+enum { YDS_HEAT_PRESENCE = 0, YDS_HEAT_VISITS = 1, YDS_HEAT_DWELL_US = 2, YDS_HEAT_FLOW_X = 3, YDS_HEAT_FLOW_Y = 4 };
+#define YDS_HEATMAP_MAX_CELLS 65536
+#define YDS_HEATMAP_VMAX_LIMIT (1ll << 47)
+yds_heatmap *yds_heatmap_create(int n_streams, int max_age);
+void yds_heatmap_destroy(yds_heatmap *);
+int yds_heatmap_set_stream(yds_heatmap *, int stream, int h, int w, int cell, int class_id);
+int yds_heatmap_reset(yds_heatmap *, int stream);
+int yds_heatmap_update(yds_heatmap *, const int32_t *rows6_host, const int32_t *first, const int32_t *stream_of, const double *frame_time,
+                       int n_frames, int32_t *counted_out);
+int yds_heatmap_get_layers(yds_heatmap *, int stream, int64_t *out5, size_t cap);
+int yds_heatmap_get_max(yds_heatmap *, int stream, int layer, int64_t *out);
+int yds_heatmap_get_tracks(yds_heatmap *, int stream, int32_t *ids, int32_t *ages, int32_t *cells, int32_t *xy2, double *t, int cap, int *n);
+int yds_heatmap_render(yds_heatmap *, uint8_t *frames_dev, int n_src, const int32_t *slot_host, const int32_t *stream_of_host, int n, int h,
+                       int w, int layer, int64_t vmax, int alpha, const uint8_t *lut_host);
+int yds_heatmap_set_timing(yds_heatmap *, int on);
+int yds_heatmap_last_us(yds_heatmap *, int what, float *us);
+int yds_pipeline_set_heatmap(yds_pipe *, yds_heatmap *);
 
 /* ---- cross-camera identities: one global id per person, kept on the device ---------------------------------------------------------
  * No reference counterpart (the reference tracks one camera); tests/identity_ref.py restates the rules below in numpy / scipy.

@@ -201,6 +201,18 @@ SIGNATURES = {
     "yds_zones_last_us": (_I, [_P, _P]),
     "yds_pipeline_set_zones": (_I, [_P, _P]),
     "yds_pipeline_last_zone_events": (_I, [_P, _P, _P, _I, _P]),
+    "yds_heatmap_create": (_P, [_I, _I]),
+    "yds_heatmap_destroy": (None, [_P]),
+    "yds_heatmap_set_stream": (_I, [_P, _I, _I, _I, _I, _I]),
+    "yds_heatmap_reset": (_I, [_P, _I]),
+    "yds_heatmap_update": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "yds_heatmap_get_layers": (_I, [_P, _I, _P, _SZ]),
+    "yds_heatmap_get_max": (_I, [_P, _I, _I, _P]),
+    "yds_heatmap_get_tracks": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "yds_heatmap_render": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I64, _I, _P]),
+    "yds_heatmap_set_timing": (_I, [_P, _I]),
+    "yds_heatmap_last_us": (_I, [_P, _I, _P]),
+    "yds_pipeline_set_heatmap": (_I, [_P, _P]),
     "yds_overlay_tracks_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P, _P]),
     "yds_overlay_tracks_bgr_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
     "yds_anonymize_frames": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32]),

@@ -282,7 +282,7 @@ struct ActFrame {
     double t;
     const double *row_time;
 };
-// What the driver of a step needs of a per-stream table stage (actions, zones; their shared frame is track_stage.h):
+// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps; their shared frame is track_stage.h):
 struct TrackStageIface {
     virtual ~TrackStageIface() {}
     virtual int streams() const = 0;
@@ -303,6 +303,15 @@ struct ActionsIface : TrackStageIface {
 struct ZonesIface : TrackStageIface {
     std::vector<int32_t> ev6;                     // [m][6] tag, id, class, kind, zone or line, 0
     std::vector<double> evt2;                     // [m][2] t, dwell
+};
+
+// --------------------------------------------------------------------------------------------- heat maps
+// Implemented in heatmap.hip: per stream a grid of int64 layers and a table of tracks with the cell, time and foot point of their last
+// sighting, advanced over the frames of a call by ONE launch over the same frame descriptors as the zone stage.  It reports nothing
+// per event: `counted` and `first` only say how many rows of each frame were of the stream's class.
+struct HeatmapIface : TrackStageIface {
+    virtual bool has_spec(int stream) const = 0;  // yds_heatmap_set_stream has been called for it
+    std::vector<int32_t> counted;                 // [n] rows counted per frame
 };
 
 // --------------------------------------------------------------------------------------------- tracker
@@ -364,6 +373,9 @@ struct TrackerGroupIface {
     // the zone stage of the NEXT step_batch (nullptr: none): one more launch behind the action launch (if there is one), ahead of the
     // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
     virtual void set_zones(ZonesIface *zones, const double *frame_times) = 0;
+    // the heat map stage of the NEXT step_batch (nullptr: none): one more launch behind the zone launch (if there is one), ahead of the
+    // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
+    virtual void set_heatmap(HeatmapIface *heat, const double *frame_times) = 0;
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
     // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)
@@ -380,3 +392,4 @@ struct yds_trk { yds::TrackerIface *t; };
 struct yds_act { yds::ActionsIface *a; };
 struct yds_ident { yds::IdentityIface *i; };
 struct yds_zones { yds::ZonesIface *z; };
+struct yds_heatmap { yds::HeatmapIface *h; };

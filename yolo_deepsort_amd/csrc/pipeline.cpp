@@ -569,13 +569,13 @@ public:
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
         if (!multi) stream_of.assign(batch, 0);
-        // the action and zone stages (set_actions, set_zones): frame b carries the caller's time for it, else its stream's frame
+        // the action, zone and heat map stages (set_actions, set_zones, set_heatmap): frame b carries the caller's time for it, else its stream's frame
         // count / 25
         std::vector<double> times;
         if ((int)frames_seen.size() < (int)trks.size()) frames_seen.resize(trks.size(), 0);
         const std::vector<double> given = std::move(next_times);      // (they name this step's frames, whatever becomes of it)
         next_times.clear();
-        if (actions || zones) {
+        if (actions || zones || heat) {
             if (!given.empty() && (int)given.size() != batch)
                 fail("pipeline: %zu frame times for a step of %d frames (yds_pipeline_set_frame_times)", given.size(), batch);
             times.resize(batch);
@@ -583,6 +583,7 @@ public:
             for (int b = 0; b < batch; ++b) times[b] = given.empty() ? (double)seen[stream_of[b]]++ / 25.0 : given[b];
             if (actions) group->set_actions(actions, times.data());
             if (zones) group->set_zones(zones, times.data());
+            if (heat) group->set_heatmap(heat, times.data());
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
         last_actions.clear();
@@ -625,6 +626,15 @@ public:
         last_zone_ev6.clear();
         last_zone_evt2.clear();
     }
+    // ---- the heat map stage (yds_pipeline_set_heatmap): every stream's grid in that stream's own frame pixels ----
+    void set_heatmap(HeatmapIface *h) {
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_heatmap while a look-ahead pass is in flight (consume it with a step first)");
+        if (h && h->streams() < (int)trks.size()) fail("pipeline: a heatmap handle of %d streams for a pipeline of %zu", h->streams(), trks.size());
+        for (int s = 0; h && s < (int)trks.size(); ++s)
+            if (!h->has_spec(s)) fail("pipeline: stream %d of the heatmap handle has no spec (yds_heatmap_set_stream)", s);
+        heat = h;
+    }
+    HeatmapIface *heat = nullptr;
     ZonesIface *zones = nullptr;
     std::vector<int32_t> last_zone_ev6;           // zone events of the last step [m][6]: frame of the step, id, class, kind, zone or line, 0
     std::vector<double> last_zone_evt2;           //                              [m][2]: t, dwell
@@ -839,6 +849,11 @@ int yds_pipeline_last_detections(yds_pipe *p, float *rows5_host, int cap, int32_
 int yds_pipeline_set_zones(yds_pipe *p, yds_zones *z) {
     YDS_API_BEGIN
     p->p->set_zones(z ? z->z : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_set_heatmap(yds_pipe *p, yds_heatmap *h) {
+    YDS_API_BEGIN
+    p->p->set_heatmap(h ? h->h : nullptr);
     YDS_API_END
 }
 int yds_pipeline_last_zone_events(yds_pipe *p, int32_t *ev6_host, double *evt2_host, int cap, int *n_out) {

@@ -619,7 +619,7 @@ class VideoDetector:
                 cv2.destroyAllWindows()
 
     def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False,
-                       identity_memory=None, zones=None, zone_max_age=30):
+                       identity_memory=None, zones=None, zone_max_age=30, heatmap=None, heatmap_max_age=30):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -657,7 +657,13 @@ class VideoDetector:
         max_age) or a zones.DeviceZoneMonitor (its geometry and max_age; never its tables): every stream starts with an empty
         table, entries leave after zone_max_age unseen processed frames, geometry is in the stream's own frame pixels, frame times
         are those of the action stage.  Read stream_zone_events() and stream_zone_counts() between the yields; the yielded items
-        do not change.  ValueError naming zones for geometry the device refuses."""
+        do not change.  ValueError naming zones for geometry the device refuses.
+        heatmap: heat maps ON THE DEVICE inside the step (MultiStreamPipeline.set_heatmap) - one heatmap.HeatSpec for all streams, a
+        list with one per stream, a heatmap.HeatMap (its spec and max_age) or a heatmap.DeviceHeatMap (its specs and max_age; never
+        its layers): every stream starts with zero layers and an empty table, entries leave after heatmap_max_age unseen processed
+        frames, frame times are those of the action stage.  Read stream_heatmaps() between the yields; the yielded items and images
+        do not change: blending a layer into a frame is the caller's (heatmap.render on the host; DeviceHeatMap.render is for
+        frames kept in HBM).  ValueError naming heatmap for a spec the device refuses."""
         from . import _lib, pipeline as pl
         from .identity import check_memory
         sources = list(sources)
@@ -691,6 +697,16 @@ class VideoDetector:
             elif isinstance(zones, zn.ZoneMonitor):
                 zones, zone_max_age = zones.geometry, zones.max_age
             zones_dev = zn.DeviceZoneMonitor(zones, zone_max_age, max(len(sources), 1))
+        heat_dev = None
+        if heatmap is not None:                          # (ValueError naming heatmap for what the device refuses)
+            from . import heatmap as hm
+            if isinstance(heatmap, hm.DeviceHeatMap):        # fresh layers and tables, one per stream: never the caller's own
+                if heatmap.n_streams < len(sources):
+                    raise ValueError("heatmap: a DeviceHeatMap of %d streams for %d sources" % (heatmap.n_streams, len(sources)))
+                heatmap, heatmap_max_age = heatmap.specs[:max(len(sources), 1)], heatmap.max_age
+            elif isinstance(heatmap, hm.HeatMap):
+                heatmap, heatmap_max_age = heatmap.spec, heatmap.max_age
+            heat_dev = hm.DeviceHeatMap(heatmap, heatmap_max_age, max(len(sources), 1))
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -717,6 +733,8 @@ class VideoDetector:
             pipe.set_identities(True, **memory)
         if zones_dev is not None:
             pipe.set_zones(zones_dev)
+        if heat_dev is not None:
+            pipe.set_heatmap(heat_dev)
         self._stream_zone_events = [[] for _ in range(S)]
         live = [self._is_live(src) for src in sources]
         n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
@@ -763,7 +781,7 @@ class VideoDetector:
                     if dev is None or dev.nbytes < batch.nbytes:
                         dev = _lib.DeviceBuffer(batch.nbytes)
                     _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
-                    if actions_dev is not None or zones_dev is not None:
+                    if actions_dev is not None or zones_dev is not None or heat_dev is not None:
                         pipe.set_frame_times([t for _, _, p, t in items if p])
                     if mixed_sizes:
                         outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
@@ -842,6 +860,15 @@ class VideoDetector:
         """The zone and line counters of the running detect_streams(zones=...) generator, between two of its yields (ValueError
         outside, and for a generator started without zones): MultiStreamPipeline.zone_counts."""
         return self._zones_pipe("stream_zone_counts").zone_counts(stream)
+
+    def stream_heatmaps(self, layer="presence", stream=None):
+        """The heat maps of the running detect_streams(heatmap=...) generator, between two of its yields (ValueError outside, and
+        for a generator started without heatmap): ``layer`` of ``stream`` as int64 [gh, gw], read from the device, or a list with
+        one grid per stream; layer=None: all five layers [5, gh, gw]; MultiStreamPipeline.heatmap."""
+        pipe = self._live_streams_pipe("stream_heatmaps")
+        if getattr(pipe, "heat", None) is None:
+            raise ValueError("VideoDetector.stream_heatmaps needs detect_streams(..., heatmap=...)")
+        return pipe.heatmap(stream, layer)
 
     def stream_identity_map(self):
         """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,

@@ -204,6 +204,34 @@ class Pipeline:
             raise ValueError("zone_counts: stream %d outside [0, %d)" % (int(stream), n))
         return dev.counts(int(stream))
 
+    def set_heatmap(self, heatmap=None, max_age=30):
+        """The heat map stage of every following step: ``heatmap`` is a heatmap.DeviceHeatMap of at least as many streams as the
+        pipeline (its layers and tables are used as they are), a heatmap.HeatMap (its spec and max_age go to the device, fresh
+        layers, for every stream), one heatmap.HeatSpec for all streams or a list with one per stream; None switches the stage
+        off.  A step then adds one launch behind the association and ``heatmap()`` reads the layers; the step's own return value
+        does not change.  ValueError naming heatmap for anything the device refuses; refused (YdsError) while a look-ahead pass is
+        in flight."""
+        from .heatmap import as_device_heatmap
+        dev = None if heatmap is None else as_device_heatmap(heatmap, getattr(self, "n_streams", 1), max_age)
+        _lib.check(_lib.load().yds_pipeline_set_heatmap(self._h, None if dev is None else dev.handle))
+        self.heat = dev                                     # (keeps the handle alive while the pipeline names it)
+        return dev
+
+    def heatmap(self, stream=None, layer=None):
+        """The layers of ``stream`` as the last step left them, read from the device: int64 [5, gh, gw], or [gh, gw] for a named
+        ``layer``; stream=None: a list with one such array per stream (the single-stream Pipeline: its one array).  None when the
+        stage is off."""
+        dev = getattr(self, "heat", None)
+        if dev is None:
+            return None
+        n = getattr(self, "n_streams", 1)
+        one = (lambda s: dev.layers(s)) if layer is None else (lambda s: dev.layer(s, layer))
+        if stream is None:
+            return [one(s) for s in range(n)] if hasattr(self, "n_streams") else one(0)
+        if int(stream) < 0 or int(stream) >= n:
+            raise ValueError("heatmap: stream %d outside [0, %d)" % (int(stream), n))
+        return one(int(stream))
+
     def _search_trackers(self):
         return getattr(self, "deepsorts", None) or [self.ds]
 
