@@ -451,6 +451,43 @@ int yds_overlay_tracks_bgr_masked(uint8_t *frames_bgr_dev, int n_src, const int3
  * distinct.  Synchronous, on a stream of its own. */
 int yds_anonymize_frames(uint8_t *frames_dev, int n_src, const int32_t *slot_host, int n, int h, int w, const int32_t *rects_host,
                          const int32_t *rect_ptr_host, int mode, int block, uint32_t color);
+/* ---- the output stage for frames of DIFFERENT sizes in one device buffer (cameras of mixed sizes, detect_streams) ----------------
+ * The three entries above with a per-frame geometry: staged frame j of the n_src frames is uint8 [frame_hw_host[j][0],
+ * frame_hw_host[j][1], 3] at frames_dev + frame_off_host[j], any byte offset, inside a buffer of frames_bytes bytes.  Pixel
+ * semantics are those of the uniform entries, each frame at its own size: the font scale of a frame is
+ * max(1, rint(2 * (h / 1000.))) with ties to even, what label_draw.py's draw_rects_and_labels computes from img.shape[0] / 1000.;
+ * mask cells and tiles are anchored at each frame's own origin.  Every entry carries the mask arguments (mask_mode 0 = none,
+ * rects_host may then be NULL); box, text, FPS and rectangle tables are those of the uniform entries, per OUTPUT frame.
+ * yds_overlay_tracks_mixed      output i = the channel-reversed copy of frame src_slot_host[i] (a slot may be named twice), written
+ *                               at out_dev + sum_{j<i} 3 h_j w_j (the sizes of the outputs before it: packed back to back), then
+ *                               masked and drawn on; out_bytes = the size of out_dev, which must hold all outputs; out_host (optional)
+ *                               receives the packed result.  The copy is ragged work: a workgroup takes a 48 KiB piece of one
+ *                               frame, 16-byte accesses where both bases are 16-aligned, else dwords, else bytes, per frame.
+ * yds_overlay_tracks_bgr_mixed  frames already in the result's channel order: masked and drawn on IN PLACE and copied to out_host,
+ *                               packed in output order (frames that are neighbours in the buffer and in the order leave in one
+ *                               copy); slots must be distinct; the staged frames are consumed.
+ * yds_anonymize_frames_mixed    the mask alone, in place; color = the three bytes as they land in memory; slots distinct.
+ * Refused before anything is enqueued (yds_last_error says which): h or w < 1, a frame that ends past frames_bytes, staged
+ * frames that overlap (the in-place entries), a slot outside [0, n_src), duplicate slots (the in-place entries), a short
+ * out_bytes, and every table error the uniform entries refuse.  Synchronous. */
+int yds_overlay_tracks_mixed(const uint8_t *frames_dev, size_t frames_bytes, int n_src, const uint64_t *frame_off_host,
+                             const int32_t *frame_hw_host, const int32_t *src_slot_host, int n_out, const int32_t *boxes_host,
+                             const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host,
+                             const uint8_t *font_host, int n_glyphs, int thickness, const int32_t *rects_host,
+                             const int32_t *rect_ptr_host, int mask_mode, int mask_block, uint32_t mask_color, uint8_t *out_dev,
+                             size_t out_bytes, uint8_t *out_host);
+int yds_overlay_tracks_bgr_mixed(uint8_t *frames_bgr_dev, size_t frames_bytes, int n_src, const uint64_t *frame_off_host,
+                                 const int32_t *frame_hw_host, const int32_t *src_slot_host, int n_out, const int32_t *boxes_host,
+                                 const int32_t *box_ptr_host, const uint8_t *text_host, int n_text, const int32_t *fps_host,
+                                 const uint8_t *font_host, int n_glyphs, int thickness, const int32_t *rects_host,
+                                 const int32_t *rect_ptr_host, int mask_mode, int mask_block, uint32_t mask_color, uint8_t *out_host);
+int yds_anonymize_frames_mixed(uint8_t *frames_dev, size_t frames_bytes, int n_src, const uint64_t *frame_off_host,
+                               const int32_t *frame_hw_host, const int32_t *slot_host, int n, const int32_t *rects_host,
+                               const int32_t *rect_ptr_host, int mode, int block, uint32_t color);
+/* Measurement (tools/): with timing on, every yds_overlay_tracks* call brackets its device work - table uploads, kernels, result
+ * copy - with two events on the overlay's stream; yds_overlay_last_us returns the last call's span in microseconds (0 before any). */
+int yds_overlay_set_timing(int on);
+int yds_overlay_last_us(float *us);
 /* The post-NMS, class-masked detections of the LAST step (every step entry: plain, window, mixed, multi-stream), per frame of the
  * step, in that frame's own pixels: rows5_host [cap][5] = x, y, w, h, class in frame order, counts_host [frames of the step] =
  * rows of each frame.  What the tracker was handed - it shows only Confirmed tracks, so a person who has just appeared is in

@@ -217,6 +217,11 @@ SIGNATURES = {
     "yds_overlay_tracks_bgr_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
     "yds_anonymize_frames": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32]),
     "yds_pipeline_last_detections": (_I, [_P, _P, _I, _P]),
+    "yds_overlay_tracks_mixed": (_I, [_P, _SZ, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, C.c_uint32, _P, _SZ, _P]),
+    "yds_overlay_tracks_bgr_mixed": (_I, [_P, _SZ, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
+    "yds_anonymize_frames_mixed": (_I, [_P, _SZ, _I, _P, _P, _P, _I, _P, _P, _I, _I, C.c_uint32]),
+    "yds_overlay_set_timing": (_I, [_I]),
+    "yds_overlay_last_us": (_I, [_P]),
 }
 
 _lib = None

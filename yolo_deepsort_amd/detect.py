@@ -206,6 +206,92 @@ def _transform(frame):
     return None if frame is None else np.ascontiguousarray(frame[:, :, ::-1])
 
 
+def stream_groups(its, frames_per_stream, skip_frames, mixed_sizes=False, live=None, source_fps=None, clock=time.time):
+    """The steps of detect_streams, formed exactly as its host loop forms them, without a GPU: a generator of lists of
+    (stream, frame, processed, frame time) in yield order.  its: one frame iterator per stream; one step takes from every
+    stream that is still running up to frames_per_stream frames that pass the skip_frames gate (the frames the gate skips
+    come along, in time order); a stream that ends drops out; a step without frames is not yielded.  Frame times: clock() at
+    read for a live stream (live[s]), else the stream's frame index over its rate - source_fps() right after the stream's first
+    frame was read, 25 where that gives nothing.  Shapes: all frames one uint8 [h, w, 3] shape, or with mixed_sizes one per
+    stream; ValueError otherwise, naming the stream."""
+    S, F = len(its), int(frames_per_stream)
+    live = [False] * S if live is None else list(live)
+    shapes, shape = [None] * S, None
+    since, alive, n_read, rate = [0] * S, [True] * S, [0] * S, [None] * S
+    while any(alive):
+        items = []
+        for s in range(S):
+            n_proc = 0
+            while alive[s] and n_proc < F:
+                frame = next(its[s], None)
+                if frame is None:
+                    alive[s] = False
+                    break
+                if rate[s] is None:
+                    rate[s] = float((source_fps() if source_fps is not None else None) or 25.0)
+                t_frame = clock() if live[s] else n_read[s] / rate[s]
+                n_read[s] += 1
+                frame = np.asarray(frame)
+                if mixed_sizes:
+                    if shapes[s] is None:
+                        shapes[s] = frame.shape
+                    if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+                        raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
+                                         % (s, shapes[s], frame.shape, frame.dtype))
+                elif shape is None:
+                    shape = frame.shape
+                if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
+                    raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
+                                     "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
+                proc = since[s] % skip_frames == 0
+                if proc:
+                    since[s] = 0
+                since[s] += 1
+                n_proc += proc
+                items.append((s, frame, proc, t_frame))
+        if items:
+            yield items
+
+
+STAGE_ALIGN = 256          # a mixed step's frames start at multiples of this in the staging block (the mixed entries take any offset)
+
+
+def stage_plan(items, mixed_sizes=False):
+    """Where the frames of one step (stream_groups) go in a staging block: processed frames first, in step order - the
+    pipeline wants them in front, and its look-ahead reads nothing behind them - the skipped ones behind.  A dict: slot_of
+    (item index -> slot), order (slot -> item index), n_proc, streams (stream of every processed frame, in slot order), off
+    (uint64 [n], byte offset of every slot), hw (int32 [n, 2]), nbytes (the end of the last frame), proc_bytes (the end of the
+    last processed frame) and mixed.  A uniform step packs its frames h * w * 3 bytes apart, which is the layout the uniform
+    entries take; a mixed step starts every frame at a multiple of STAGE_ALIGN."""
+    order = [i for i, it in enumerate(items) if it[2]] + [i for i, it in enumerate(items) if not it[2]]
+    n_proc = sum(1 for it in items if it[2])
+    slot_of = [0] * len(items)
+    for slot, i in enumerate(order):
+        slot_of[i] = slot
+    hw = np.array([items[i][1].shape[:2] for i in order], np.int32).reshape(-1, 2)
+    off, at, proc_bytes = np.zeros(len(order), np.uint64), 0, 0
+    for slot in range(len(order)):
+        if mixed_sizes:
+            at = (at + STAGE_ALIGN - 1) // STAGE_ALIGN * STAGE_ALIGN
+        off[slot] = at
+        at += 3 * int(hw[slot][0]) * int(hw[slot][1])
+        if slot < n_proc:
+            proc_bytes = at
+    return dict(slot_of=slot_of, order=order, n_proc=n_proc, streams=[items[i][0] for i in order[:n_proc]], off=off, hw=hw, nbytes=at,
+                proc_bytes=proc_bytes, mixed=bool(mixed_sizes))
+
+
+def same_composition(cur, nxt):
+    """The look-ahead decision of detect_streams: may the detector pass of the step planned as `nxt` be enqueued with the step
+    planned as `cur` (stage_plan dicts)?  Only when both process the same number of frames of the same streams at the same
+    offsets and sizes: a stream that ended, skip phases that differ or another layout give False, and the step passes None."""
+    if cur is None or nxt is None:
+        return False
+    n = cur["n_proc"]
+    return bool(n > 0 and nxt["n_proc"] == n and cur["mixed"] == nxt["mixed"] and cur["streams"] == nxt["streams"]
+                and np.array_equal(cur["hw"][:n], nxt["hw"][:n]) and np.array_equal(cur["off"][:n], nxt["off"][:n]))
+
+
 class VideoDetector:
     def __init__(self, model, class_path, thickness=2, font_path=None, font_size=10, thres=0.7, nms_thres=0.4,
                  skip_frames=-1, fourcc="mp4v", class_mask=None, win_size=None, overlap=0.15, tracker=None,
@@ -663,7 +749,16 @@ class VideoDetector:
         its layers): every stream starts with zero layers and an empty table, entries leave after heatmap_max_age unseen processed
         frames, frame times are those of the action stage.  Read stream_heatmaps() between the yields; the yielded items and images
         do not change: blending a layer into a frame is the caller's (heatmap.render on the host; DeviceHeatMap.render is for
-        frames kept in HBM).  ValueError naming heatmap for a spec the device refuses."""
+        frames kept in HBM).  ValueError naming heatmap for a spec the device refuses.
+        device_overlay (the constructor's flag, on by default; YDS_HOST_OVERLAY turns it off) runs the generator as a staged engine
+        (_detect_streams_device): a reader thread forms the steps and uploads them from pinned staging blocks, the step runs on the
+        caller's thread in lock-step with the yields and takes the next staged step along for its early detector pass, and the
+        output stage - the anonymise mask, the overlay, RGB -> BGR, the FPS text - is one call on the device over the staged block
+        (DeviceOverlay.render, render_mixed for mixed_sizes).  The yielded items and everything read between the yields are the
+        same either way; the images are views of a pinned block and the FPS text advances by the step's time over its frames.
+        With global_ids no step carries a look-ahead pass: stream_identity_map() hands out the map, and changing it between the
+        yields (enrol, set_memory) is refused by the library while such a pass is in flight.  device_overlay=False keeps the host
+        loop below."""
         from . import _lib, pipeline as pl
         from .identity import check_memory
         sources = list(sources)
@@ -715,18 +810,12 @@ class VideoDetector:
         S = len(sources)
         if S == 0:
             return
-        shapes = [None] * S                              # mixed_sizes: the shape each stream started with
         F = int(frames_per_stream) if frames_per_stream else (1 if any(self._is_live(src) for src in sources) else max(1, self.AUTO_BATCH // S))
         det = self.image_detector
         if det.model.batch_max < S * F:
             det.model.set_batch_max(S * F)
         pipe = pl.MultiStreamPipeline(det.model, [self.tracker.clone() for _ in range(S)], det.thres, det.nms_thres, class_mask=self.class_mask,
                                       win_size=det.win_size, overlap=det.overlap, stream_win_sizes=stream_win_sizes)
-        lib = _lib.load()
-        its = [iter(self._frames(src)) for src in sources]
-        since, hold, alive = [0] * S, [None] * S, [True] * S
-        masking, hold_dets = getattr(self, "anonymize", None) is not None, [None] * S      # the anonymise option: rendered on the host here
-        shape, dev = None, None
         if actions_dev is not None:
             pipe.set_actions(actions_dev)
         if global_ids:
@@ -736,10 +825,22 @@ class VideoDetector:
         if heat_dev is not None:
             pipe.set_heatmap(heat_dev)
         self._stream_zone_events = [[] for _ in range(S)]
-        live = [self._is_live(src) for src in sources]
-        n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
         try:
+            if self.device_overlay:                          # staged uploads, look-ahead, the output stage on the device
+                yield from self._detect_streams_device(pipe, sources, F, show_fps, mixed_sizes,
+                                                       actions_dev is not None or zones_dev is not None or heat_dev is not None,
+                                                       zones_dev is not None, actions_dev is not None, lookahead=not global_ids)
+                return
+            # the host loop (device_overlay=False / YDS_HOST_OVERLAY)
+            shapes = [None] * S                              # mixed_sizes: the shape each stream started with
+            lib = _lib.load()
+            its = [iter(self._frames(src)) for src in sources]
+            since, hold, alive = [0] * S, [None] * S, [True] * S
+            masking, hold_dets = getattr(self, "anonymize", None) is not None, [None] * S      # the anonymise option: rendered on the host here
+            shape, dev = None, None
+            live = [self._is_live(src) for src in sources]
+            n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
             while any(alive):
                 items = []                                   # (stream, frame, processed) in yield order
                 for s in range(S):
@@ -810,6 +911,167 @@ class VideoDetector:
                     yield out
         finally:
             self._streams_pipe = None                    # the generator ended, was closed or raised
+
+    @staticmethod
+    def _stage_streams(groups, mixed_sizes, out_q, free_q, stop):
+        """Reader thread of detect_streams' device form: every step of `groups` (stream_groups) is planned (stage_plan), copied into
+        a pinned staging block at the plan's offsets and uploaded to the block's HBM buffer (a synchronous copy on this thread, the
+        GIL released).  The generator hands the blocks back through free_q; blk["dev"] / blk["pin"] are reallocated only when a
+        group outgrows them.  An exception travels through out_q and is raised again on the generator's thread."""
+        import queue
+        from . import _lib
+
+        def give(item):                                        # never blocks past a stop request
+            while not stop.is_set():
+                try:
+                    out_q.put(item, timeout=0.1)
+                    return
+                except queue.Full:
+                    pass
+        try:
+            lib = _lib.load()
+            for items in groups:
+                if stop.is_set():
+                    return
+                plan = stage_plan(items, mixed_sizes)
+                blk = free_q.get()
+                if blk is None or stop.is_set():
+                    return
+                nbytes = plan["nbytes"]
+                if blk["dev"] is None or blk["dev"].nbytes < nbytes:
+                    blk["dev"] = _lib.DeviceBuffer(nbytes)
+                    blk["pin"] = _lib.PinnedArray((nbytes,), np.uint8)
+                stage = blk["pin"].array
+                for slot, i in enumerate(plan["order"]):
+                    f, o = items[i][1], int(plan["off"][slot])
+                    np.copyto(stage[o:o + f.size].reshape(f.shape), f)
+                _lib.check(lib.yds_memcpy_h2d(blk["dev"].ptr, _lib.ptr(stage[:nbytes]), nbytes))
+                give(dict(blk=blk, plan=plan, items=[(s, proc, t) for s, _, proc, t in items]))
+            give(None)
+        except BaseException as e:                             # noqa: BLE001 - re-raised on the generator's thread
+            give(e)
+
+    def _detect_streams_device(self, pipe, sources, F, show_fps, mixed_sizes, timed, zones_on, actions_on, lookahead=True):
+        """detect_streams with the output stage on the device (device_overlay).  A reader thread forms, stages and uploads the
+        steps (_stage_streams: a ring of four blocks - one being filled, one queued, the two the step holds); THIS thread runs the
+        step in lock-step with the yields, so that whatever is read between the yields (zone events and counts, identities, heat
+        maps, search, link) is the state right after the yielded step.  Overlap comes from look-ahead: when the next step is
+        already staged and has the same composition (same_composition), its HBM buffer goes along as next_frames_dev and the
+        device runs its detector pass while the host renders and the consumer works; with a live source the next step is never
+        waited for.  The output stage is ONE call over the staged block, processed and skipped frames alike
+        (DeviceOverlay.render / render_mixed), with the mask first when the anonymise option is on.  Sources that are all captures
+        or files are staged as the decoder's BGR (set_frame_order(True)) and drawn on in place; any iterable keeps RGB staging
+        and the reversed copy.  lookahead=False (detect_streams with global_ids): no step carries a look-ahead pass - the
+        identity map is the caller's to change between the yields (stream_identity_map().enrol, set_memory), which the library
+        refuses while such a pass is in flight."""
+        import queue
+        import threading
+        from .label_draw import DeviceOverlay
+        S = len(sources)
+        bgr = not any(hasattr(src, "__iter__") and not isinstance(src, (str, bytes)) and not hasattr(src, "isOpened") for src in sources)
+        pipe.set_frame_order(bgr)
+        live = [self._is_live(src) for src in sources]
+        its = [iter(self._frames(src, transform=not bgr)) for src in sources]
+        groups = stream_groups(its, F, self.skip_frames, mixed_sizes, live, lambda: getattr(self, "_source_fps", None))
+        out_q, free_q, stop = queue.Queue(maxsize=1), queue.Queue(), threading.Event()
+        for _ in range(4):
+            free_q.put(dict(dev=None, pin=None))
+        reader = threading.Thread(target=self._stage_streams, args=(groups, mixed_sizes, out_q, free_q, stop), daemon=True)
+        self._streams_reader = reader
+        reader.start()
+        nothing = object()                                     # "no step is staged yet" (a live source is never waited for)
+
+        def take(block):
+            while True:
+                try:
+                    item = out_q.get(timeout=0.1) if block else out_q.get_nowait()
+                except queue.Empty:
+                    if not block:
+                        return nothing
+                    if not reader.is_alive() and out_q.empty():
+                        return None
+                    continue
+                return item                                    # (an exception of the reader included: it is raised in its turn)
+        if getattr(self, "_overlay", None) is None:
+            self._overlay = DeviceOverlay(self.label_drawer)
+        anon = getattr(self, "anonymize", None)
+        hold, acts, hold_dets = [None] * S, [[] for _ in range(S)], [None] * S
+        wait_next = not any(live)
+        self.streams_lookahead = [0, 0]                        # steps that carried a look-ahead pass, steps run (tools/, tests)
+        t_prev = time.time()
+        try:
+            cur, nxt = take(True), nothing
+            while cur is not None:
+                if isinstance(cur, BaseException):            # after everything staged before it was yielded, as on the host form
+                    raise cur
+                if nxt is nothing:
+                    nxt = take(wait_next)
+                plan, items, dev = cur["plan"], cur["items"], cur["blk"]["dev"]
+                n, outs = plan["n_proc"], []
+                h, w = int(plan["hw"][0][0]), int(plan["hw"][0][1])
+                if n:
+                    ahead = None
+                    if lookahead and isinstance(nxt, dict) and same_composition(plan, nxt["plan"]):
+                        ahead = nxt["blk"]["dev"].offset(0)
+                    self.streams_lookahead[0] += ahead is not None
+                    self.streams_lookahead[1] += 1
+                    if timed:
+                        pipe.set_frame_times([t for _, p, t in items if p])
+                    if mixed_sizes:
+                        outs = pipe.step_mixed(dev.offset(0), plan["off"][:n], plan["hw"][:n], plan["streams"], plan["proc_bytes"], ahead)
+                    else:
+                        outs = pipe.step(dev.offset(0), h, w, plan["streams"], ahead)
+                step_acts = pipe.last_actions() if actions_on and n else None
+                step_dets = pipe.last_detections() if anon is not None and n else None
+                if zones_on:                                # the events of this step's processed frames, per stream in time order
+                    self._stream_zone_events = [[] for _ in range(S)]
+                    for s, evs in zip(plan["streams"], pipe.last_zone_events() if n else []):
+                        self._stream_zone_events[s].append(evs)
+                holds, dets, out_acts, k = [], [], [], 0
+                for s, proc, _ in items:                    # the bookkeeping of the host loop, frame by frame
+                    if proc:
+                        o = outs[k]
+                        if step_acts is not None and step_acts[k] is not None:
+                            acts[s] = step_acts[k]
+                        if step_dets is not None:
+                            hold_dets[s] = step_dets[k]
+                        k += 1
+                        hold[s] = None if o is None else (o if len(o) else [])
+                    else:
+                        acts[s] = []
+                    holds.append(hold[s])
+                    dets.append(hold_dets[s])
+                    out_acts.append(acts[s])
+                now = time.time()
+                dt = (now - t_prev) / len(items)
+                t_prev = now
+                fps = [self._fps_tick(dt) for _ in items]
+                kw = dict(privacy=anon, detections=dets if anon is not None else None)
+                if mixed_sizes:
+                    images = self._overlay.render_mixed(dev.offset(0), plan["nbytes"], plan["off"], plan["hw"], plan["slot_of"], holds,
+                                                        fps if show_fps else None, bgr=bgr, **kw)
+                else:
+                    images = self._overlay.render(dev.offset(0), plan["slot_of"], h, w, holds, fps if show_fps else None,
+                                                  bgr_frames=len(items) if bgr else 0, n_frames=len(items), **kw)
+                free_q.put(cur["blk"])
+                out = [(items[i][0], images[i], holds[i], out_acts[i]) for i in range(len(items))]
+                del images
+                yield out
+                cur, nxt = (take(True), nothing) if nxt is nothing else (nxt, nothing)
+        finally:
+            stop.set()
+            free_q.put(None)
+            try:                                             # unblock a reader waiting on the full hand-over
+                while True:
+                    out_q.get_nowait()
+            except queue.Empty:
+                pass
+            reader.join(timeout=5)
+            for it in its:                                   # ends the decoder threads of file / capture sources
+                try:
+                    it.close()
+                except Exception:                            # noqa: BLE001 - a reader that did not stop in time still runs the iterator
+                    pass
 
     def _live_streams_pipe(self, who):
         pipe = getattr(self, "_streams_pipe", None)

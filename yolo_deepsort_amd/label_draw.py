@@ -155,6 +155,30 @@ def encode_text(text):
     return np.array([_GLYPH_CODE.get(ch.lower(), _GLYPH_CODE["_"]) for ch in text], dtype=np.uint8)
 
 
+def frame_scale(h):
+    """Font pixels per dot of a frame of height h: draw_rects_and_labels' scale at font_size = img.shape[0] / 1000."""
+    return max(1, int(round(2 * (h / 1000.))))
+
+
+def draw_tables_host(image_bgr, boxes, text, fps_row, thickness, scale):
+    """What the device does with ONE output frame's rows of the overlay tables, in numpy, in place on the BGR image: boxes int32
+    [m, 8] in list order (yds_overlay_tracks: corners, colour in the RGB image's channel order, label offset, label length or -1),
+    text = the glyph codes, fps_row = (offset, length).  The definition the tables are tested against without a GPU; on the
+    same rows it equals draw_rects / draw_rects_and_labels on the RGB image followed by the reversal and the FPS put_text."""
+    def decode(off, ln):
+        return "".join(_GLYPH_ORDER[c] for c in np.asarray(text[off:off + ln]).tolist())
+    for x1, y1, x2, y2, col, loff, llen, _ in np.asarray(boxes, dtype=np.int64).reshape(-1, 8).tolist():
+        color = ((col >> 16) & 0xff, (col >> 8) & 0xff, col & 0xff)           # lands channel-reversed
+        rectangle(image_bgr, (x1, y1), (x2, y2), color, thickness)
+        if llen >= 0:
+            fw, fh = 6 * llen * scale, 7 * scale
+            rectangle(image_bgr, (x1, max(0, y1 - 3 - fh)), (x1 + fw, max(y1, 3 + fh)), color, -1)
+            put_text(image_bgr, decode(loff, llen), (x1, max(y1 - 3, fh)), scale, (0, 0, 0))
+    if fps_row[1] > 0:
+        put_text(image_bgr, decode(int(fps_row[0]), int(fps_row[1])), (3, 15), 2, (255, 0, 0))
+    return image_bgr
+
+
 class _PinnedBlock:
     """A pinned host block (yds_host_alloc) whose lifetime follows the numpy arrays made of it: np.asarray(block) and every
     view of that keep the block alive; it is handed back to the runtime when the last one is gone."""
@@ -225,14 +249,57 @@ class DeviceOverlay:
         n = len(holds)
         if n == 0:
             return []
-        mask = None
-        if privacy is not None:
-            from . import privacy as pv
-            dets = detections if detections is not None else [None] * n
-            if len(dets) != n:
-                raise ValueError("DeviceOverlay.render: %d detection lists for %d frames" % (len(dets), n))
-            mask = pv.pack_rects([pv.mask_rects(privacy, h, w, holds[i], dets[i]) for i in range(n)]) + pv.device_args(privacy, False)
+        mask = self._mask_tables(privacy, [(h, w)] * n, holds, detections, "render")
+        if mask is not None:
             n_src = int(n_frames) if n_frames else (int(bgr_frames) if bgr_frames else int(max(src_slots)) + 1)
+        boxes_a, ptr_a, text, toff, fps = self._draw_tables(holds, fps_texts, only_rect)
+        d = self.drawer
+        slots = np.ascontiguousarray(src_slots, dtype=np.int32)
+        nbytes = n * h * w * 3
+        blk = self._pinned(nbytes)
+        scale = frame_scale(h)
+        tables = (_lib.ptr(boxes_a), _lib.ptr(ptr_a), _lib.ptr(text), toff, _lib.ptr(fps), _lib.ptr(self.font), len(self.font),
+                  int(d.thickness), scale)
+        if mask is not None:
+            rect_table, rect_ptr = mask[:2]                                  # (named: alive until the call has returned)
+            mask = (_lib.ptr(rect_table), _lib.ptr(rect_ptr)) + mask[2:]
+        if bgr_frames:
+            if mask is None:
+                _lib.check(_lib.load().yds_overlay_tracks_bgr(frames_dev, int(bgr_frames), _lib.ptr(slots), n, h, w, *tables, blk.ptr))
+            else:
+                _lib.check(_lib.load().yds_overlay_tracks_bgr_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, blk.ptr))
+            out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
+            del blk
+            return [out[i] for i in range(n)]
+        if self._out_dev is None or self._out_dev.nbytes < nbytes:
+            self._out_dev = _lib.DeviceBuffer(nbytes)
+        if mask is None:
+            _lib.check(_lib.load().yds_overlay_tracks(frames_dev, _lib.ptr(slots), n, h, w, *tables, self._out_dev.ptr, blk.ptr))
+        else:
+            _lib.check(_lib.load().yds_overlay_tracks_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, self._out_dev.ptr,
+                                                             blk.ptr))
+        out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
+        del blk
+        return [out[i] for i in range(n)]
+
+    @staticmethod
+    def _mask_tables(privacy, sizes, holds, detections, who):
+        """The mask of a call as the entries take it - (rect table, rect_ptr, mode, block, colour) - or None without privacy: the
+        rectangles of output frame i are privacy.mask_rects at that frame's OWN size sizes[i] = (h, w)."""
+        if privacy is None:
+            return None
+        from . import privacy as pv
+        n = len(holds)
+        dets = detections if detections is not None else [None] * n
+        if len(dets) != n:
+            raise ValueError("DeviceOverlay.%s: %d detection lists for %d frames" % (who, len(dets), n))
+        return pv.pack_rects([pv.mask_rects(privacy, sizes[i][0], sizes[i][1], holds[i], dets[i]) for i in range(n)]) + pv.device_args(privacy, False)
+
+    def _draw_tables(self, holds, fps_texts, only_rect):
+        """The box, text and FPS tables of the overlay entries for the output frames holds[i] (include/ydsort.h, yds_overlay_tracks):
+        (boxes int32 [max(total, 1), 8], box_ptr int32 [n + 1], glyph codes uint8, their count, fps int32 [n, 2]).  They do not
+        depend on the frames' sizes: clipping and the font scale are the kernel's, per frame."""
+        n = len(holds)
         d = self.drawer
         colors, ncol = d.colors, len(d.colors)
         boxes, ptr, texts, toff = [], [0], [], 0
@@ -260,30 +327,64 @@ class DeviceOverlay:
         text = np.ascontiguousarray(np.concatenate(texts) if texts else np.zeros(1, np.uint8))
         boxes_a = np.ascontiguousarray(np.array(boxes, dtype=np.int32).reshape(-1, 8)) if boxes else np.zeros((1, 8), np.int32)
         ptr_a = np.ascontiguousarray(ptr, dtype=np.int32)
-        slots = np.ascontiguousarray(src_slots, dtype=np.int32)
-        nbytes = n * h * w * 3
-        blk = self._pinned(nbytes)
-        scale = max(1, int(round(2 * (h / 1000.))))                      # draw_rects_and_labels' font_size = img.shape[0] / 1000.
-        tables = (_lib.ptr(boxes_a), _lib.ptr(ptr_a), _lib.ptr(text), toff, _lib.ptr(fps), _lib.ptr(self.font), len(self.font),
-                  int(d.thickness), scale)
-        if mask is not None:
-            rect_table, rect_ptr = mask[:2]                                  # (named: alive until the call has returned)
-            mask = (_lib.ptr(rect_table), _lib.ptr(rect_ptr)) + mask[2:]
-        if bgr_frames:
-            if mask is None:
-                _lib.check(_lib.load().yds_overlay_tracks_bgr(frames_dev, int(bgr_frames), _lib.ptr(slots), n, h, w, *tables, blk.ptr))
-            else:
-                _lib.check(_lib.load().yds_overlay_tracks_bgr_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, blk.ptr))
-            out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
-            del blk
-            return [out[i] for i in range(n)]
-        if self._out_dev is None or self._out_dev.nbytes < nbytes:
-            self._out_dev = _lib.DeviceBuffer(nbytes)
+        return boxes_a, ptr_a, text, toff, fps
+
+    def mixed_tables(self, frame_hw, src_slots, holds, fps_texts=None, only_rect=False, privacy=None, detections=None):
+        """Everything render_mixed hands to the device, built on the host alone (no library call): a dict with the draw tables of
+        _draw_tables (boxes, box_ptr, text, n_text, fps), slots int32 [n], sizes [(h, w)] and scales [int] of the OUTPUT frames -
+        output i has the size of staged frame src_slots[i] and the font scale frame_scale(h) - out_off (packed byte offsets of the
+        outputs, uint64 [n]), out_bytes, and mask (None, or the rect table, rect_ptr, mode, block, colour with every frame's
+        rectangles taken at its own size)."""
+        n = len(holds)
+        slots = np.ascontiguousarray(src_slots, dtype=np.int32).reshape(-1)
+        hw = np.ascontiguousarray(frame_hw, dtype=np.int32).reshape(-1, 2)
+        if slots.size != n:
+            raise ValueError("DeviceOverlay.render_mixed: %d slots for %d frames" % (slots.size, n))
+        if n and (slots.min() < 0 or slots.max() >= len(hw)):
+            raise ValueError("DeviceOverlay.render_mixed: slots must lie in [0, %d), got %s" % (len(hw), slots.tolist()))
+        sizes = [(int(hw[s][0]), int(hw[s][1])) for s in slots]
+        boxes_a, ptr_a, text, toff, fps = self._draw_tables(holds, fps_texts, only_rect)
+        nbytes = np.array([3 * h * w for h, w in sizes], np.uint64)
+        out_off = np.zeros(n, np.uint64)
+        out_off[1:] = np.cumsum(nbytes)[:-1]
+        return dict(boxes=boxes_a, box_ptr=ptr_a, text=text, n_text=toff, fps=fps, slots=slots, sizes=sizes,
+                    scales=[frame_scale(h) for h, _ in sizes], out_off=out_off, out_bytes=int(nbytes.sum()),
+                    mask=self._mask_tables(privacy, sizes, holds, detections, "render_mixed"))
+
+    def render_mixed(self, frames_dev, frames_bytes, frame_off, frame_hw, src_slots, holds, fps_texts=None, only_rect=False, bgr=False,
+                     privacy=None, detections=None):
+        """render() for staged frames of DIFFERENT sizes in one device buffer of frames_bytes bytes: staged frame j is uint8
+        [frame_hw[j][0], frame_hw[j][1], 3] at frames_dev + frame_off[j] (any byte offset); output i shows frame src_slots[i] with
+        the tracker rows holds[i], clipped, scaled (frame_scale) and masked (privacy.mask_rects) at that frame's own size.  Returns
+        a list of BGR uint8 arrays of each frame's own shape, views of one pinned block of the pool.
+        bgr=False: the staged frames are RGB; the outputs are channel-reversed copies (yds_overlay_tracks_mixed; a slot may be
+        named twice).  bgr=True: they are ALREADY BGR, are drawn on in place and consumed (yds_overlay_tracks_bgr_mixed; slots
+        distinct).  YdsError for a layout the entries refuse (include/ydsort.h)."""
+        from . import _lib
+        n = len(holds)
+        if n == 0:
+            return []
+        off = np.ascontiguousarray(frame_off, dtype=np.uint64).reshape(-1)
+        hw = np.ascontiguousarray(frame_hw, dtype=np.int32).reshape(-1, 2)
+        if off.size != len(hw):
+            raise ValueError("DeviceOverlay.render_mixed: %d offsets for %d sizes" % (off.size, len(hw)))
+        t = self.mixed_tables(hw, src_slots, holds, fps_texts, only_rect, privacy, detections)
+        mask = t["mask"]
         if mask is None:
-            _lib.check(_lib.load().yds_overlay_tracks(frames_dev, _lib.ptr(slots), n, h, w, *tables, self._out_dev.ptr, blk.ptr))
+            mask_args = (None, None, 0, 16, 0)
         else:
-            _lib.check(_lib.load().yds_overlay_tracks_masked(frames_dev, n_src, _lib.ptr(slots), n, h, w, *tables, *mask, self._out_dev.ptr,
-                                                             blk.ptr))
-        out = np.asarray(blk)[:nbytes].reshape(n, h, w, 3)
+            mask_args = (_lib.ptr(mask[0]), _lib.ptr(mask[1])) + tuple(mask[2:])
+        blk = self._pinned(t["out_bytes"])
+        lay = (int(frames_bytes), len(hw), _lib.ptr(off), _lib.ptr(hw), _lib.ptr(t["slots"]), n)
+        tables = (_lib.ptr(t["boxes"]), _lib.ptr(t["box_ptr"]), _lib.ptr(t["text"]), t["n_text"], _lib.ptr(t["fps"]), _lib.ptr(self.font),
+                  len(self.font), int(self.drawer.thickness))
+        if bgr:
+            _lib.check(_lib.load().yds_overlay_tracks_bgr_mixed(frames_dev, *lay, *tables, *mask_args, blk.ptr))
+        else:
+            if self._out_dev is None or self._out_dev.nbytes < t["out_bytes"]:
+                self._out_dev = _lib.DeviceBuffer(t["out_bytes"])
+            _lib.check(_lib.load().yds_overlay_tracks_mixed(frames_dev, *lay, *tables, *mask_args, self._out_dev.ptr, self._out_dev.nbytes,
+                                                            blk.ptr))
+        flat = np.asarray(blk)
         del blk
-        return [out[i] for i in range(n)]
+        return [flat[int(o):int(o) + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(t["out_off"].tolist(), t["sizes"])]

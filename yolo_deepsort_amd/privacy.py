@@ -214,3 +214,23 @@ class DeviceAnonymizer:
         mode, block, color = device_args(self.anon, bgr)
         _lib.check(_lib.load().yds_anonymize_frames(frames_dev, n_src, _lib.ptr(slots_a), len(slots_a), int(h), int(w), _lib.ptr(table),
                                                     _lib.ptr(ptr), mode, block, color))
+
+    def apply_mixed(self, frames_dev, frames_bytes, frame_off, frame_hw, slots, rects_per_frame, bgr=False):
+        """apply() for frames of DIFFERENT sizes in one device buffer of frames_bytes bytes (yds_anonymize_frames_mixed): staged
+        frame j is uint8 [frame_hw[j][0], frame_hw[j][1], 3] at frames_dev + frame_off[j], any byte offset; frame slots[i] is
+        masked with rects_per_frame[i] - mask_rects lists made with THAT frame's h, w - its cells anchored at its own origin.
+        Slots must be distinct, the frames must not overlap.  Synchronous."""
+        from . import _lib
+        slots_a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(frame_off, dtype=np.uint64).reshape(-1)
+        hw = np.ascontiguousarray(frame_hw, dtype=np.int32).reshape(-1, 2)
+        if len(slots_a) != len(rects_per_frame):
+            raise ValueError("DeviceAnonymizer.apply_mixed: %d slots for %d rectangle lists" % (len(slots_a), len(rects_per_frame)))
+        if off.size != len(hw):
+            raise ValueError("DeviceAnonymizer.apply_mixed: %d offsets for %d sizes" % (off.size, len(hw)))
+        if len(slots_a) == 0:
+            return
+        table, ptr = pack_rects(rects_per_frame)
+        mode, block, color = device_args(self.anon, bgr)
+        _lib.check(_lib.load().yds_anonymize_frames_mixed(frames_dev, int(frames_bytes), len(hw), _lib.ptr(off), _lib.ptr(hw), _lib.ptr(slots_a),
+                                                          len(slots_a), _lib.ptr(table), _lib.ptr(ptr), mode, block, color))
