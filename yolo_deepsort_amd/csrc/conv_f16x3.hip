@@ -11,10 +11,15 @@
 // yolov3 / yolov4: max 5e-5 of the output scale; a 3-term bf16 split was 10x worse).  The 2^11 pre-scale keeps
 // the low halves in fp16's normal range, the 2^-8 activation scale moves overflow out to 1.6e7.
 //
-// Structure is the fp32 kernel's: NHWC fp32 activations are split on the fly while being staged to LDS (the
-// producer keeps writing plain fp32), weights arrive pre-split as [Cout][K/32][32 hi | 32 lo] fp16 (same bytes as
-// fp32), LDS rows are [64 B hi | 64 B lo | 16 B pad] = 144 B which keeps ds_read_b128 fragment reads conflict
-// free, XCD-aware tile map, compile-time epilogue.
+// Two kernels live here.
+//   conv_igemm_f16x3 (register staged): the fp32 kernel's structure.  NHWC fp32 activations are split on the fly while being
+//     staged to LDS (the producer keeps writing plain fp32), weights arrive pre-split as [Cout][K/32][32 hi | 32 lo] fp16 (same
+//     bytes as fp32), LDS rows are [64 B hi | 64 B lo | 16 B pad] = 144 B which keeps ds_read_b128 fragment reads conflict free,
+//     XCD-aware tile map, compile-time epilogue.  It issues v_mfma_f32_32x32x16_f16.
+//   conv_igemm_f16x3_dma (LDS-DMA, pre-split inputs): both operands go global -> LDS without passing registers, through a ring of
+//     K = 32 stages.  In default arithmetic its K loop issues v_mfma_f32_16x16x32_f16 on 16-row / 16-filter blocks (the form
+//     conv_win16.hip introduced: these layers run at the power limit, and a quarter of the accumulator traffic per flop is fewer
+//     joules per multiply-accumulate); the half-mode tiers and one tile shape keep v_mfma_f32_32x32x16_f16 (dma_body16 below).
 #include "conv_common.h"
 
 #include <map>
@@ -228,12 +233,41 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f16x3(ConvKernelArgs p) {
 //            that iteration t-1 finished reading, then 24 MFMAs per wave on stage t % NS
 //   zero padding: out-of-image taps fetch from a zero page instead of branching
 //   WM x WN waves of 64 threads, each owning a 64x64 (TM = TN = 2) or smaller sub-tile.
+// The above is the 32x32x16 body (half mode: TERMS 1 / 4, and the tile shapes dma_body16 leaves on it).  The 16x16x32 body of the
+// default arithmetic keeps the ring, the pieces, the zero page, the swizzle, the tile map and the split-K entry, and differs in
+// the K step (conv_win16.hip's quadrant schedule):
+//   fragments: lane l reads chunk l >> 4 of the hi (lo: address ^ 64) half of row l & 15 of a 16-row / 16-filter block - the 16
+//            lanes of one chunk read 16 consecutive rows r, whose bank slot ((r & 1) * 8 + (chunk ^ ((r >> 1) & 7))) % 16 takes 16
+//            distinct values: conflict free, and block bases are multiples of 16 rows, so the addresses are loop invariant
+//   step   : one instruction spans the K = 32 of a stage, so the step splits SPATIALLY: halves H0 / H1 of the wave's blocks,
+//            quadrants Q00 Q01 | barrier | Q10 Q11, term-major MFMAs inside a quadrant.  Q00 / Q01 run on the H0 fragments read
+//            during the previous step and read H1; after the barrier (tile t+1 landed, every wave holds stage t in registers) Q10 /
+//            Q11 issue the pieces of tile t+NS into the stage just freed - the ring is NS tiles deep instead of NS-1 - and read the
+//            H0 fragments of step t+1.  No fragment read is exposed at the top of a step.
+//   measured (profiles/dma16_ab.txt): 3-11 % faster on the matrix-bound layers, nothing on the 1x1 layers at their HBM roof.
 
 constexpr int ZERO_PAGE_BYTES = 64 * 1024;                      // >= Cin * 4 + 128 for every layer (checked at launch)
 
 constexpr size_t dma_smem_bytes(int BM, int BN, int NS) {
     return (size_t)NS * (BM + BN) * 128 > conv_stage_bytes(BM, BN) ? (size_t)NS * (BM + BN) * 128 : conv_stage_bytes(BM, BN);
 }
+// Which matrix instruction the K loop of a tile shape issues in default arithmetic (TERMS == 3): true = the 16x16x32 body, false =
+// the 32x32x16 body (which the half-mode tiers always keep).  One row per tile shape; the measurement behind each row is in
+// profiles/dma16_ab.txt.  YDS_DMA16 (tuning aid for A/B builds, -DYDS_DMA16=0 / 1 through YDS_EXTRA_FLAGS): force one body everywhere.
+#ifndef YDS_DMA16
+#define YDS_DMA16 -1
+#endif
+constexpr bool dma_body16(int BM, int BN, int NS) {
+    if (YDS_DMA16 >= 0) return YDS_DMA16 != 0;
+    if (BM == 128 && BN == 128 && NS == 2) return true;
+    if (BM == 256 && BN == 128) return true;
+    if (BM == 128 && BN == 256) return true;
+    if (BM == 128 && BN == 128 && NS == 3) return false;       // one workgroup per CU (96 KB ring): 12-20 % slower with the new body
+    if (BM == 128 && BN == 64) return true;
+    if (BM == 64 && BN == 128) return true;
+    return false;
+}
+
 template <int BM, int BN, int WM, int WN, int NS, int ACT, int RES, int TERMS>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN != 4 || dma_smem_bytes(BM, BN, NS) > 80 * 1024) ? 1 : (dma_smem_bytes(BM, BN, NS) <= 53 * 1024 ? 3 : 2))
 void conv_igemm_f16x3_dma(ConvKernelArgs p, const char *zero_page) {
@@ -337,118 +371,283 @@ void conv_igemm_f16x3_dma(ConvKernelArgs p, const char *zero_page) {
         if (kc >= p.Cin) { kc = 0; if (++kw == p.ksize) { kw = 0; ++kh; } set_tap(); }
     };
 
-    f32x16 acc1[TM][TN], acc2[TM][TN];
+    if constexpr (TERMS == 3 && dma_body16(BM, BN, NS)) {
+        // ---- v_mfma_f32_16x16x32_f16 body (default arithmetic; see the header of this section) ----
+        constexpr int RW = BM / WM, CW = BN / WN;                   // rows / filters per wave
+        constexpr int TM16 = RW / 16, TN16 = CW / 16;               // 16-row / 16-filter blocks per wave
+        constexpr int HM = TM16 / 2, HN = TN16 / 2;                 // blocks per half
+        static_assert(TM16 % 2 == 0 && TN16 % 2 == 0, "the wave tile splits into quadrants");
+        static_assert(NS <= 3, "the drain of the 16x16x32 body counts at most one younger tile");
+        f32x4 acc1[TM16][TN16], acc2[TM16][TN16];                   // hi x hi; hi x lo + lo x hi
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM16; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+            for (int j = 0; j < TN16; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { acc1[i][j][e] = 0.f; acc2[i][j][e] = 0.f; }
+                for (int e = 0; e < 4; ++e) { acc1[i][j][e] = 0.f; acc2[i][j][e] = 0.f; }
 
+        // prologue: the first NS tiles (the mid-step barrier frees a stage one half step earlier than a barrier at the top would)
 #pragma unroll
-    for (int s = 0; s < NS - 1; ++s)
-        if (s < nk) {
+        for (int s = 0; s < NS; ++s)
+            if (s < nk) {
 #pragma unroll
-            for (int q = 0; q < IN; ++q) piece(s, q);
-            advance_tile();
-        }
-    if (STAGGER && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_sleep(STAGGER / 4);
+                for (int q = 0; q < IN; ++q) piece(s, q);
+                advance_tile();
+            }
 
-    // fragment addressing: row = lane & 31 (+ tile offsets, multiples of 32); chunk ids inside a row: hi k 0-7 / 8-15 /
-    // 16-23 / 24-31 = 0..3, lo = 4..7; k-substep s, lane half kb -> chunks 2s+kb (hi) and 4+2s+kb (lo)
-    const int swz = (lane >> 1) & 7, kb = lane >> 5;
-    const int a_frag = (wm * (BM / WM) + (lane & 31)) * ROW, b_frag = A_BYTES + (wn * (BN / WN) + (lane & 31)) * ROW;
-    int pos_hi[2], pos_lo[2];
+        // fragment addressing: lane l reads chunk l >> 4 of the hi half of row l & 15 of a block; block bases are multiples of 16
+        // rows, so the row's swizzle is (lane >> 1) & 7 for every block and stage: the addresses are loop invariant up to the
+        // stage base.  The lo half sits 4 chunks further in the row: position ^ 4, address ^ 64.
+        const int swz = (lane >> 1) & 7, kq = lane >> 4;
+        const int a_hi = (wm * RW + (lane & 15)) * ROW + ((kq ^ swz) << 4), a_lo = a_hi ^ 64;
+        const int b_hi = A_BYTES + (wn * CW + (lane & 15)) * ROW + ((kq ^ swz) << 4), b_lo = b_hi ^ 64;
+        h8 ah[TM16], al[TM16], bh[TN16], bl[TN16];
+        auto read_a = [&](int stage, int i, bool lo) {
+            const h8 v = *reinterpret_cast<const h8 *>(ring + stage * STAGE + i * 16 * ROW + (lo ? a_lo : a_hi));
+            if (lo) al[i] = v; else ah[i] = v;
+        };
+        auto read_b = [&](int stage, int j, bool lo) {
+            const h8 v = *reinterpret_cast<const h8 *>(ring + stage * STAGE + j * 16 * ROW + (lo ? b_lo : b_hi));
+            if (lo) bl[j] = v; else bh[j] = v;
+        };
+        constexpr int NA = 2 * HM, NB = 2 * HN;                     // A / B fragment reads of one half
+        constexpr int NMQ = 3 * HM * HN;                            // MFMAs per quadrant
+        auto mfma = [&](int qa, int qb, int m) {                    // MFMA m of quadrant (A half qa) x (B half qb)
+            const int ij = m % (HM * HN), term = m / (HM * HN), i = qa * HM + ij / HN, j = qb * HN + ij % HN;   // term-major: no back-to-back accumulation into one tile
+            if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc1[i][j], 0, 0, 0);
+            else if (term == 1) acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc2[i][j], 0, 0, 0);
+            else acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc2[i][j], 0, 0, 0);
+        };
+        // Slot plan, one memory instruction after each MFMA (48 or 24 slots per step, 22 to 24 used):
+        //   Q00, Q01 (on H0, read during the previous step): this step's fragments of H1 - B hi, B lo (Q01 needs them first), A hi, A lo
+        //   mid      lgkmcnt(0) + counted vmcnt + s_barrier: tile t+1 landed, every wave holds all of stage t in registers
+        //   Q10, Q11 the IN DMA pieces of tile t+NS into the stage just freed, then the H0 fragments of step t+1.  The B registers of
+        //            H0 are read by Q10, so their reads wait for Q11; the A registers of H0 are free since Q01.  Where the pieces fill
+        //            Q10 (NEED_ORDER: the 64x32 / 32x64 wave tiles) the fragments go in the order the next Q00 needs them.
+        // Slots of Q10 + Q11 per shape (P = piece, a / b = A / B fragment of H0 of step t+1, capital = hi half, . = free; | = Q10 | Q11):
+        //   <128,128,2x2,NS>  HM 2 HN 2 IN 8  NMQ 12  PPPPPPPPAAaa|BBbb........      (A-first, B_START 12)
+        //   <256,128,4x2,3>   HM 2 HN 2 IN 6  NMQ 12  PPPPPPAAaa..|BBbb........      (A-first, B_START 12)
+        //   <128,256,2x4,3>   the same
+        //   <128,64,2x2,2>    HM 2 HN 1 IN 6  NMQ 6   PPPPPP|AABbaa                  (NEED_ORDER)
+        //   <64,128,2x2,2>    HM 1 HN 2 IN 6  NMQ 6   PPPPPP|ABBbba                  (NEED_ORDER)
+        // The 32x32x16 body's start offset of every other workgroup (STAGGER, 384 clocks once per tile) is not carried over.  It was
+        // not measured on its own here: profiles/dma16_ab.txt compares the two bodies as they stand, the sleep included on one side.
+        static_assert(NB + NA <= 2 * NMQ, "Q00 + Q01 hold the fragment reads of H1");
+        constexpr bool NEED_ORDER = IN + HM >= NMQ;
+        constexpr int B_START = IN + NA > NMQ ? IN + NA : NMQ;      // first slot (Q10 = 0) of a B fragment in the A-first order
+        static_assert(NEED_ORDER ? IN + NA + NB <= 2 * NMQ : B_START + NB <= 2 * NMQ, "Q10 + Q11 hold the DMA pieces and the fragment reads of H0");
+        auto pre_op = [&](int stage, int o) {
+            if (o < HN) read_b(stage, HN + o, false);
+            else if (o < NB) read_b(stage, HN + o - HN, true);
+            else if (o < NB + HM) read_a(stage, HM + o - NB, false);
+            else if (o < NB + NA) read_a(stage, HM + o - NB - HM, true);
+        };
+        auto post_op = [&](int stage, int next, int o, auto refill_c, auto next_c) {
+            constexpr bool REFILL = decltype(refill_c)::value, NEXT = decltype(next_c)::value;
+            if (o < IN) { if (REFILL) piece(stage, o); return; }
+            if (!NEXT) return;
+            const int r = o - IN;
+            if (NEED_ORDER) {
+                if (r < HM) read_a(next, r, false);
+                else if (r < HM + HN) read_b(next, r - HM, false);
+                else if (r < HM + NB) read_b(next, r - HM - HN, true);
+                else if (r < NA + NB) read_a(next, r - HM - NB, true);
+            } else {
+                const int rb = o - B_START;
+                if (r < HM) read_a(next, r, false);
+                else if (r < NA) read_a(next, r - HM, true);
+                else if (rb >= 0 && rb < HN) read_b(next, rb, false);
+                else if (rb >= HN && rb < NB) read_b(next, rb - HN, true);
+            }
+        };
+        auto step_head = [&](int stage) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) { pos_hi[s] = ((2 * s + kb) ^ swz) * 16; pos_lo[s] = ((4 + 2 * s + kb) ^ swz) * 16; }
+            for (int m = 0; m < NMQ; ++m) {
+                mfma(0, 0, m);
+                __builtin_amdgcn_sched_barrier(0);
+                pre_op(stage, m);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int m = 0; m < NMQ; ++m) {
+                mfma(0, 1, m);
+                __builtin_amdgcn_sched_barrier(0);
+                pre_op(stage, NMQ + m);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of stage t are complete before it is re-filled
+        };
+        auto step_tail = [&](int stage, int next, auto refill_c, auto next_c) {
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < NMQ; ++m) {
+                mfma(1, 0, m);
+                __builtin_amdgcn_sched_barrier(0);
+                post_op(stage, next, m, refill_c, next_c);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int m = 0; m < NMQ; ++m) {
+                mfma(1, 1, m);
+                __builtin_amdgcn_sched_barrier(0);
+                post_op(stage, next, NMQ + m, refill_c, next_c);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (decltype(refill_c)::value) advance_tile();
+        };
 
-    // The wave issues in order, so memory instructions are placed BETWEEN the MFMAs of a k-substep (each MFMA keeps the
-    // matrix pipe busy for 32 cycles, which pays for one LDS read or one DMA piece): substep 0 carries the fragment
-    // reads of substep 1 and the first half of the next tile's DMA pieces, substep 1 the second half.
-    // sched_barrier(0) pins that order; fragments are double buffered in registers.
-    constexpr int NF = 2 * (TM + TN);                           // fragment reads per substep
-    constexpr int NM = 3 * TM * TN;                             // MFMAs per substep
-    h8 fr[2][NF];                                               // [substep][ah.., al.., bh.., bl..]
-    auto frag_read = [&](const char *st, int s, int f) {
-        const int which = f / 2, lo = f & 1;                    // f = 2*tile + (hi|lo), A tiles first
-        if (TERMS == 1 && lo) return;                           // half mode: hi halves only
-        const int off = which < TM ? a_frag + which * 32 * ROW : b_frag + (which - TM) * 32 * ROW;
-        fr[s][f] = *reinterpret_cast<const h8 *>(st + off + (lo ? pos_lo[s] : pos_hi[s]));
-    };
-    auto mfma = [&](int s, int m) {
-        const int ij = m / 3, term = m % 3, i = ij / TN, j = ij % TN;
-        if (TERMS == 1 && term != 0) return;
-        const h8 ah = fr[s][2 * i], al = fr[s][2 * i + 1], bh = fr[s][2 * (TM + j)], bl = fr[s][2 * (TM + j) + 1];
-        if (TERMS == 4) {                                        // both slots hold hi values (of two channel groups)
-            if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
-            else if (term == 1) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bl, acc1[i][j], 0, 0, 0);
-            return;
-        }
-        if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
-        else if (term == 1) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc2[i][j], 0, 0, 0);
-        else acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc2[i][j], 0, 0, 0);
-    };
-    // slot plan (one memory instruction after each MFMA): substep 0 first issues the DMA pieces of the next tile (as
-    // early as possible: they have to land before the next step), then the first fragments substep 1 needs; substep 1
-    // starts with the MFMAs of tile (0,0) and reads the fragments of the other tiles in its first slots.
-    constexpr int P0 = IN < NM - 4 ? IN : NM - 4;               // pieces issued in substep 0 (4 slots stay for fragments)
-    constexpr int F0 = NM - P0 < NF ? NM - P0 : NF;             // substep-1 fragments read during substep 0
-    static_assert(IN - P0 + NF - F0 <= NM, "not enough MFMA slots for the interleaved memory instructions");
-    // fragment order for substep 1: ah0, al0, bh0, bl0 (tile (0,0)), then bh1, bl1, ..., then ah1, al1, ...
-    auto frag_order = [&](int k) {
-        if (k < 2) return k;                                    // ah0, al0
-        if (k < 4) return 2 * TM + (k - 2);                     // bh0, bl0
-        const int r = k - 4, nb = 2 * (TN - 1);
-        return r < nb ? 2 * TM + 2 + r : 2 + (r - nb);          // remaining B tiles, then remaining A tiles
-    };
-    // one K step; REFILL (compile time) = a further tile exists and is fetched into the stage freed by step t-1
-    auto step = [&](int t, auto refill_c) {
-        constexpr bool REFILL = decltype(refill_c)::value;
-        const char *st = ring + (t % NS) * STAGE;
-        const int fill_stage = (t + NS - 1) % NS;
+        // tile 0 landed (the younger tiles of the prologue stay in flight); H0 fragments of step 0
+        if (nk >= 3 && NS >= 3) wait_vmcnt<2 * IN>(); else if (nk >= 2) wait_vmcnt<IN>(); else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
 #pragma unroll
-        for (int f = 0; f < NF; ++f) frag_read(st, 0, f);
+        for (int i = 0; i < HM; ++i) { read_a(0, i, false); read_a(0, i, true); }
+#pragma unroll
+        for (int j = 0; j < HN; ++j) { read_b(0, j, false); read_b(0, j, true); }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            mfma(0, m);
-            __builtin_amdgcn_sched_barrier(0);
-            if (m < P0) { if (REFILL) piece(fill_stage, m); }
-            else if (m - P0 < F0) frag_read(st, 1, frag_order(m - P0));
-            __builtin_amdgcn_sched_barrier(0);
+
+        int t = 0, stage = 0;
+        for (; t + NS < nk; ++t) {                                 // steady state: NS-2 younger tiles stay in flight
+            const int next = stage + 1 == NS ? 0 : stage + 1;
+            step_head(stage);
+            wait_vmcnt<(NS - 2) * IN>();
+            step_tail(stage, next, std::true_type{}, std::true_type{});
+            stage = next;
         }
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            mfma(1, m);
-            __builtin_amdgcn_sched_barrier(0);
-            if (m < NF - F0) frag_read(st, 1, frag_order(F0 + m));
-            else if (REFILL && P0 + (m - (NF - F0)) < IN) piece(fill_stage, P0 + (m - (NF - F0)));
-            __builtin_amdgcn_sched_barrier(0);
+        for (; t + 1 < nk; ++t) {                                  // drain: nothing left to fetch
+            const int next = stage + 1 == NS ? 0 : stage + 1;
+            step_head(stage);
+            if (NS >= 3 && nk - 2 - t >= 1) wait_vmcnt<(NS >= 3 ? IN : 0)>(); else wait_vmcnt<0>();
+            step_tail(stage, next, std::false_type{}, std::true_type{});
+            stage = next;
         }
-        if (REFILL) advance_tile();
-    };
-    int t = 0;
-    for (; t + NS - 1 < nk; ++t) {                             // steady state: NS-2 younger tiles stay in flight
-        wait_vmcnt<(NS - 2) * IN>();
-        __builtin_amdgcn_s_barrier();
-        step(t, std::true_type{});
+        if (t < nk) {                                              // last step: no further fragments
+            step_head(stage);
+            step_tail(stage, stage, std::false_type{}, std::false_type{});
+        }
+        __syncthreads();                                            // every wave is done with the ring
+#pragma unroll
+        for (int i = 0; i < TM16; ++i)
+#pragma unroll
+            for (int j = 0; j < TN16; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc1[i][j][e] = (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
+        // whole-tile staging: the launcher sizes the LDS as max(ring, BM x (BN+4) floats)
+        conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM16, TN16, NT, true>(p, acc1, reinterpret_cast<float *>(ring), m0, n0, tid);
+    } else {
+        f32x16 acc1[TM][TN], acc2[TM][TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) { acc1[i][j][e] = 0.f; acc2[i][j][e] = 0.f; }
+
+#pragma unroll
+        for (int s = 0; s < NS - 1; ++s)
+            if (s < nk) {
+#pragma unroll
+                for (int q = 0; q < IN; ++q) piece(s, q);
+                advance_tile();
+            }
+        if (STAGGER && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_sleep(STAGGER / 4);
+
+        // fragment addressing: row = lane & 31 (+ tile offsets, multiples of 32); chunk ids inside a row: hi k 0-7 / 8-15 /
+        // 16-23 / 24-31 = 0..3, lo = 4..7; k-substep s, lane half kb -> chunks 2s+kb (hi) and 4+2s+kb (lo)
+        const int swz = (lane >> 1) & 7, kb = lane >> 5;
+        const int a_frag = (wm * (BM / WM) + (lane & 31)) * ROW, b_frag = A_BYTES + (wn * (BN / WN) + (lane & 31)) * ROW;
+        int pos_hi[2], pos_lo[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) { pos_hi[s] = ((2 * s + kb) ^ swz) * 16; pos_lo[s] = ((4 + 2 * s + kb) ^ swz) * 16; }
+
+        // The wave issues in order, so memory instructions are placed BETWEEN the MFMAs of a k-substep (each MFMA keeps the
+        // matrix pipe busy for 32 cycles, which pays for one LDS read or one DMA piece): substep 0 carries the fragment
+        // reads of substep 1 and the first half of the next tile's DMA pieces, substep 1 the second half.
+        // sched_barrier(0) pins that order; fragments are double buffered in registers.
+        constexpr int NF = 2 * (TM + TN);                           // fragment reads per substep
+        constexpr int NM = 3 * TM * TN;                             // MFMAs per substep
+        h8 fr[2][NF];                                               // [substep][ah.., al.., bh.., bl..]
+        auto frag_read = [&](const char *st, int s, int f) {
+            const int which = f / 2, lo = f & 1;                    // f = 2*tile + (hi|lo), A tiles first
+            if (TERMS == 1 && lo) return;                           // half mode: hi halves only
+            const int off = which < TM ? a_frag + which * 32 * ROW : b_frag + (which - TM) * 32 * ROW;
+            fr[s][f] = *reinterpret_cast<const h8 *>(st + off + (lo ? pos_lo[s] : pos_hi[s]));
+        };
+        auto mfma = [&](int s, int m) {
+            const int ij = m / 3, term = m % 3, i = ij / TN, j = ij % TN;
+            if (TERMS == 1 && term != 0) return;
+            const h8 ah = fr[s][2 * i], al = fr[s][2 * i + 1], bh = fr[s][2 * (TM + j)], bl = fr[s][2 * (TM + j) + 1];
+            if (TERMS == 4) {                                        // both slots hold hi values (of two channel groups)
+                if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
+                else if (term == 1) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bl, acc1[i][j], 0, 0, 0);
+                return;
+            }
+            if (term == 0) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc1[i][j], 0, 0, 0);
+            else if (term == 1) acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc2[i][j], 0, 0, 0);
+            else acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc2[i][j], 0, 0, 0);
+        };
+        // slot plan (one memory instruction after each MFMA): substep 0 first issues the DMA pieces of the next tile (as
+        // early as possible: they have to land before the next step), then the first fragments substep 1 needs; substep 1
+        // starts with the MFMAs of tile (0,0) and reads the fragments of the other tiles in its first slots.
+        constexpr int P0 = IN < NM - 4 ? IN : NM - 4;               // pieces issued in substep 0 (4 slots stay for fragments)
+        constexpr int F0 = NM - P0 < NF ? NM - P0 : NF;             // substep-1 fragments read during substep 0
+        static_assert(IN - P0 + NF - F0 <= NM, "not enough MFMA slots for the interleaved memory instructions");
+        // fragment order for substep 1: ah0, al0, bh0, bl0 (tile (0,0)), then bh1, bl1, ..., then ah1, al1, ...
+        auto frag_order = [&](int k) {
+            if (k < 2) return k;                                    // ah0, al0
+            if (k < 4) return 2 * TM + (k - 2);                     // bh0, bl0
+            const int r = k - 4, nb = 2 * (TN - 1);
+            return r < nb ? 2 * TM + 2 + r : 2 + (r - nb);          // remaining B tiles, then remaining A tiles
+        };
+        // one K step; REFILL (compile time) = a further tile exists and is fetched into the stage freed by step t-1
+        auto step = [&](int t, auto refill_c) {
+            constexpr bool REFILL = decltype(refill_c)::value;
+            const char *st = ring + (t % NS) * STAGE;
+            const int fill_stage = (t + NS - 1) % NS;
+#pragma unroll
+            for (int f = 0; f < NF; ++f) frag_read(st, 0, f);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+                mfma(0, m);
+                __builtin_amdgcn_sched_barrier(0);
+                if (m < P0) { if (REFILL) piece(fill_stage, m); }
+                else if (m - P0 < F0) frag_read(st, 1, frag_order(m - P0));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+                mfma(1, m);
+                __builtin_amdgcn_sched_barrier(0);
+                if (m < NF - F0) frag_read(st, 1, frag_order(F0 + m));
+                else if (REFILL && P0 + (m - (NF - F0)) < IN) piece(fill_stage, P0 + (m - (NF - F0)));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (REFILL) advance_tile();
+        };
+        int t = 0;
+        for (; t + NS - 1 < nk; ++t) {                             // steady state: NS-2 younger tiles stay in flight
+            wait_vmcnt<(NS - 2) * IN>();
+            __builtin_amdgcn_s_barrier();
+            step(t, std::true_type{});
+        }
+        for (; t < nk; ++t) {                                       // drain: nothing left to fetch
+            const int younger = nk - 1 - t;
+            if (younger >= 1 && NS >= 3) wait_vmcnt<(NS >= 3 ? IN : 0)>(); else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            step(t, std::false_type{});
+        }
+        __syncthreads();                                            // every wave is done with the ring
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    acc1[i][j][e] = TERMS != 3 ? acc1[i][j][e] * (1.f / A_SCALE) : (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
+        // whole-tile staging: the launcher sizes the LDS as max(ring, BM x (BN+4) floats)
+        conv_epilogue<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true>(p, acc1, reinterpret_cast<float *>(ring), m0, n0, tid);
     }
-    for (; t < nk; ++t) {                                       // drain: nothing left to fetch
-        const int younger = nk - 1 - t;
-        if (younger >= 1 && NS >= 3) wait_vmcnt<(NS >= 3 ? IN : 0)>(); else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        step(t, std::false_type{});
-    }
-    __syncthreads();                                            // every wave is done with the ring
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                acc1[i][j][e] = TERMS != 3 ? acc1[i][j][e] * (1.f / A_SCALE) : (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
-    // whole-tile staging: the launcher sizes the LDS as max(ring, BM x (BN+4) floats)
-    conv_epilogue<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true>(p, acc1, reinterpret_cast<float *>(ring), m0, n0, tid);
 }
 
 static const char *zero_page_dev() {
