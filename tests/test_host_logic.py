@@ -553,24 +553,25 @@ def test_video_generator_control_flow_vs_reference_fixture(case, batch_frames, t
         pipe = Pipe()
         vd._pipe = pipe
         vd._batchable = lambda: True                              # the stand-in tracker plays the package's DeepSort
-        orig = vd._processed_batches
+        orig = vd._video_steps
 
         def spy(*a, **k):
             for grp in orig(*a, **k):
                 bgr = k.get("transform", True) is False                 # a capture source is staged as the decoder's BGR (swapped on the device)
-                pipe.groups.append([index[key(f[..., ::-1] if bgr else f)] for f, proc in grp if proc])
+                pipe.groups.append([index[key(f[..., ::-1] if bgr else f)] for _, f, proc, _ in grp if proc])
                 yield grp
-        vd._processed_batches = spy
+        vd._video_steps = spy
 
         class Buf:
             def offset(self, o):
                 return self
 
         # stand-ins for the two device hooks of the batched path: the staged group stays on the host, the output stage is the host form
-        def upload(blk, group_frames, h, w, bgr):
-            blk.update(dev=Buf(), host=[np.ascontiguousarray(f[..., ::-1]) if bgr else f for f in group_frames])
-        vd._upload_group = upload
-        vd._render_batch = lambda cur, holds, fps, bgr: [vd._render_host(cur["blk"]["host"][cur["slot_of"][i]], holds[i], None) for i in range(len(holds))]
+        def upload(blk, plan, group_frames):
+            blk.update(dev=Buf(), host=list(group_frames))
+        vd._upload_step = upload
+        vd._render_step = lambda cur, holds, dets, fps, bgr: [vd._render_host(np.ascontiguousarray(cur["blk"]["host"][i][..., ::-1]) if bgr
+                                                                              else cur["blk"]["host"][i], holds[i], None) for i in range(len(holds))]
     try:
         clip = _Clip(frames[..., ::-1], sc["fps"])
         got = list(vd.detect(clip, skip_secs=c["skip_secs"], show_fps=False))
@@ -630,8 +631,8 @@ def test_batched_generator_stops_cleanly_when_the_consumer_leaves(tmp_path):
         vd = D.VideoDetector(Model(), str(names), tracker=Tracker(), batch_frames=4)
         vd._pipe = pipe
         vd._batchable = lambda: True                              # the stand-in tracker plays the package's DeepSort
-        vd._upload_group = lambda blk, fr, h, w, bgr: blk.update(dev=Buf(), host=list(fr))
-        vd._render_batch = lambda cur, holds, fps, bgr: [vd._render_host(cur["blk"]["host"][cur["slot_of"][i]], holds[i], None) for i in range(len(holds))]
+        vd._upload_step = lambda blk, plan, fr: blk.update(dev=Buf(), host=list(fr))
+        vd._render_step = lambda cur, holds, dets, fps, bgr: [vd._render_host(cur["blk"]["host"][i], holds[i], None) for i in range(len(holds))]
         return vd
     before = threading.active_count()
     gen = make(Pipe()).detect((np.zeros((48, 64, 3), np.uint8) for _ in range(10000)), show_fps=False)

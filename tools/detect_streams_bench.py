@@ -6,7 +6,7 @@ pass: the generator offers no per-step injection), so every frame carries rows t
 1080 x 1920) and `mixed` (half 1080 x 1920, half 720 x 1280, mixed_sizes=True; the small frames are nearest-pixel sub-samples).
 
 Legs, alternating, --runs of each (a run = one generator consumed to its end; the first --warmup yields are untimed):
-  host        (a) device_overlay=False: the host loop - numpy stack, pageable upload, step without look-ahead, host render per frame
+  host        (a) device_overlay=False: the host loop - one upload per step on the caller's thread, step without look-ahead, host render per frame
   device      (b) device_overlay=True: reader thread + pinned staging, look-ahead, one DeviceOverlay.render / render_mixed per step
   device_anon (b) with anonymize=Anonymize()
   step        (c) the bare MultiStreamPipeline.step / step_mixed on the same frames resident in HBM, with look-ahead: the ceiling

@@ -13,6 +13,8 @@ import numpy as np
 
 from .label_draw import LabelDrawer, put_text
 from .loaders import load_classes
+from .staging import (NOTHING, STAGE_ALIGN, Bookkeeper, give, same_composition, shut_down, skip_gate, stage_plan,  # noqa: F401 - part of this
+                      stage_steps, stream_groups, take)                                                            # module's interface
 
 
 def p1p2Toxywh(x):
@@ -206,90 +208,9 @@ def _transform(frame):
     return None if frame is None else np.ascontiguousarray(frame[:, :, ::-1])
 
 
-def stream_groups(its, frames_per_stream, skip_frames, mixed_sizes=False, live=None, source_fps=None, clock=time.time):
-    """The steps of detect_streams, formed exactly as its host loop forms them, without a GPU: a generator of lists of
-    (stream, frame, processed, frame time) in yield order.  its: one frame iterator per stream; one step takes from every
-    stream that is still running up to frames_per_stream frames that pass the skip_frames gate (the frames the gate skips
-    come along, in time order); a stream that ends drops out; a step without frames is not yielded.  Frame times: clock() at
-    read for a live stream (live[s]), else the stream's frame index over its rate - source_fps() right after the stream's first
-    frame was read, 25 where that gives nothing.  Shapes: all frames one uint8 [h, w, 3] shape, or with mixed_sizes one per
-    stream; ValueError otherwise, naming the stream."""
-    S, F = len(its), int(frames_per_stream)
-    live = [False] * S if live is None else list(live)
-    shapes, shape = [None] * S, None
-    since, alive, n_read, rate = [0] * S, [True] * S, [0] * S, [None] * S
-    while any(alive):
-        items = []
-        for s in range(S):
-            n_proc = 0
-            while alive[s] and n_proc < F:
-                frame = next(its[s], None)
-                if frame is None:
-                    alive[s] = False
-                    break
-                if rate[s] is None:
-                    rate[s] = float((source_fps() if source_fps is not None else None) or 25.0)
-                t_frame = clock() if live[s] else n_read[s] / rate[s]
-                n_read[s] += 1
-                frame = np.asarray(frame)
-                if mixed_sizes:
-                    if shapes[s] is None:
-                        shapes[s] = frame.shape
-                    if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-                        raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
-                                         % (s, shapes[s], frame.shape, frame.dtype))
-                elif shape is None:
-                    shape = frame.shape
-                if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
-                    raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
-                                     "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
-                proc = since[s] % skip_frames == 0
-                if proc:
-                    since[s] = 0
-                since[s] += 1
-                n_proc += proc
-                items.append((s, frame, proc, t_frame))
-        if items:
-            yield items
-
-
-STAGE_ALIGN = 256          # a mixed step's frames start at multiples of this in the staging block (the mixed entries take any offset)
-
-
-def stage_plan(items, mixed_sizes=False):
-    """Where the frames of one step (stream_groups) go in a staging block: processed frames first, in step order - the
-    pipeline wants them in front, and its look-ahead reads nothing behind them - the skipped ones behind.  A dict: slot_of
-    (item index -> slot), order (slot -> item index), n_proc, streams (stream of every processed frame, in slot order), off
-    (uint64 [n], byte offset of every slot), hw (int32 [n, 2]), nbytes (the end of the last frame), proc_bytes (the end of the
-    last processed frame) and mixed.  A uniform step packs its frames h * w * 3 bytes apart, which is the layout the uniform
-    entries take; a mixed step starts every frame at a multiple of STAGE_ALIGN."""
-    order = [i for i, it in enumerate(items) if it[2]] + [i for i, it in enumerate(items) if not it[2]]
-    n_proc = sum(1 for it in items if it[2])
-    slot_of = [0] * len(items)
-    for slot, i in enumerate(order):
-        slot_of[i] = slot
-    hw = np.array([items[i][1].shape[:2] for i in order], np.int32).reshape(-1, 2)
-    off, at, proc_bytes = np.zeros(len(order), np.uint64), 0, 0
-    for slot in range(len(order)):
-        if mixed_sizes:
-            at = (at + STAGE_ALIGN - 1) // STAGE_ALIGN * STAGE_ALIGN
-        off[slot] = at
-        at += 3 * int(hw[slot][0]) * int(hw[slot][1])
-        if slot < n_proc:
-            proc_bytes = at
-    return dict(slot_of=slot_of, order=order, n_proc=n_proc, streams=[items[i][0] for i in order[:n_proc]], off=off, hw=hw, nbytes=at,
-                proc_bytes=proc_bytes, mixed=bool(mixed_sizes))
-
-
-def same_composition(cur, nxt):
-    """The look-ahead decision of detect_streams: may the detector pass of the step planned as `nxt` be enqueued with the step
-    planned as `cur` (stage_plan dicts)?  Only when both process the same number of frames of the same streams at the same
-    offsets and sizes: a stream that ended, skip phases that differ or another layout give False, and the step passes None."""
-    if cur is None or nxt is None:
-        return False
-    n = cur["n_proc"]
-    return bool(n > 0 and nxt["n_proc"] == n and cur["mixed"] == nxt["mixed"] and cur["streams"] == nxt["streams"]
-                and np.array_equal(cur["hw"][:n], nxt["hw"][:n]) and np.array_equal(cur["off"][:n], nxt["off"][:n]))
+def _is_frame_iterable(source):
+    """An iterable of already-decoded RGB frames - not a path, not a capture."""
+    return hasattr(source, "__iter__") and not isinstance(source, (str, bytes)) and not hasattr(source, "isOpened")
 
 
 class VideoDetector:
@@ -365,7 +286,7 @@ class VideoDetector:
     def _frames(self, video_path, skip_secs=0, transform=True):
         """RGB frames of the source (transform=False: a capture / file source's frames as decoded, BGR)."""
         self._source_fps = None
-        if hasattr(video_path, "__iter__") and not isinstance(video_path, (str, bytes)) and not hasattr(video_path, "isOpened"):
+        if _is_frame_iterable(video_path):
             if skip_secs:
                 raise ValueError("skip_secs needs a seekable source (a video file or an .npy path), not an iterable of frames")
             for f in video_path:           # already-decoded RGB frames
@@ -405,24 +326,17 @@ class VideoDetector:
             detections = self.tracker.update(boxs.astype(np.float32), confidences, frame, class_ids)
         return detections
 
-    def _processed_batches(self, video_path, skip_secs=0, transform=True):
-        """Groups of consecutive frames holding up to batch_frames frames that pass the skip_frames gate."""
-        group, n_proc, frames = [], 0, 0
+    def _video_steps(self, video_path, skip_secs=0, transform=True):
+        """The steps of the batched detect(): a single video is a stream group of one - stream_groups' steps of (0, frame,
+        processed, frame time), up to batch_frames frames that pass the skip_frames gate in each."""
         bf = getattr(self, "_batch_now", None) or self.batch_frames or 1
-        for frame in self._frames(video_path, skip_secs, transform):
-            if frame is None:
-                break
-            proc = frames % self.skip_frames == 0
-            if proc:
-                frames = 0
-            frames += 1
-            group.append((frame, proc))
-            n_proc += proc
-            if n_proc == bf:
-                yield group
-                group, n_proc = [], 0
-        if group:
-            yield group
+        return stream_groups([self._frames(video_path, skip_secs, transform)], bf, self.skip_frames,
+                             refusal="VideoDetector: frames of one video must share one uint8 [h, w, 3] shape")
+
+    def _processed_batches(self, video_path, skip_secs=0, transform=True):
+        """_video_steps as lists of (frame, processed): which frames form each batch, for callers that prepare per-batch tables."""
+        for items in self._video_steps(video_path, skip_secs, transform):
+            yield [(frame, proc) for _, frame, proc, _ in items]
 
     def _render_host(self, frame, hold_detections, fps_text, detections=None):
         """video_detect.py:161-186 on the host: overlay (on a copy: callers may hand in their own frame arrays), RGB -> BGR, FPS text.
@@ -463,76 +377,47 @@ class VideoDetector:
             self._fps_cnt = 0
         return self._fps_text
 
-    def _stage_batches(self, video_path, skip_secs, bgr, out_q, free_q, stop):
-        """Reader side of the batched path (its own thread): groups of frames -> a pinned staging block -> HBM (synchronous copy
-        on this thread, the GIL released), channel-swapped there when the source delivers BGR.  The consumer hands the
-        blocks back through free_q once the pipeline and the output stage are done with them."""
-        import queue
-
-        def give(item):                                        # never blocks past a stop request
-            while not stop.is_set():
-                try:
-                    out_q.put(item, timeout=0.1)
-                    return
-                except queue.Full:
-                    pass
-        try:
-            for group in self._processed_batches(video_path, skip_secs, transform=not bgr):
-                if stop.is_set():
-                    return
-                # processed frames first (the pipeline wants them contiguous), the others behind them
-                order = [i for i, (_, proc) in enumerate(group) if proc] + [i for i, (_, proc) in enumerate(group) if not proc]
-                n_proc = sum(1 for _, proc in group if proc)
-                h, w = group[0][0].shape[:2]
-                if any(f.shape != (h, w, 3) or f.dtype != np.uint8 for f, _ in group):
-                    raise ValueError("VideoDetector: frames of one video must share one uint8 [h, w, 3] shape")
-                blk = free_q.get()
-                if blk is None or stop.is_set():
-                    return
-                slot_of = [0] * len(group)
-                for slot, i in enumerate(order):
-                    slot_of[i] = slot
-                self._upload_group(blk, [group[i][0] for i in order], h, w, bgr)
-                give(dict(blk=blk, flags=[proc for _, proc in group], slot_of=slot_of, n_proc=n_proc, h=h, w=w))
-            give(None)
-        except BaseException as e:                             # noqa: BLE001 - re-raised on the consumer's thread
-            give(e)
-
     @staticmethod
-    def _upload_group(blk, frames, h, w, bgr):
-        """The device side of the reader thread: `frames` (slot order) -> the block's pinned staging array -> its HBM buffer, in the
-        source's own channel order (round 6: a BGR source is no longer swapped on the device - Pipeline.set_frame_order makes the
-        front end read it as it is).  blk["dev"] / blk["pin"] are (re)allocated when the group outgrows them."""
+    def _upload_step(blk, plan, frames):
+        """The device part of the reader thread (stage_steps): the frames of one step (step order) -> the block's pinned staging
+        array at the plan's offsets -> its HBM buffer in one copy (synchronous on the calling thread, the GIL released), in the
+        source's own channel order: a BGR source stays BGR in HBM, the pipeline reads it in that order (set_frame_order) and the
+        output stage draws on it.  blk["dev"] / blk["pin"] are (re)allocated only when the step outgrows them."""
         from . import _lib
-        lib = _lib.load()
-        nbytes = len(frames) * h * w * 3
+        nbytes = plan["nbytes"]
         if blk["dev"] is None or blk["dev"].nbytes < nbytes:
             blk["dev"] = _lib.DeviceBuffer(nbytes)
             blk["pin"] = _lib.PinnedArray((nbytes,), np.uint8)
-        stage = blk["pin"].array[:nbytes].reshape(len(frames), h, w, 3)
-        for slot, f in enumerate(frames):
-            np.copyto(stage[slot], f)
-        _lib.check(lib.yds_memcpy_h2d(blk["dev"].ptr, _lib.ptr(stage), nbytes))
-        blk["n"] = len(frames)            # (a BGR source stays BGR in HBM: the pipeline reads it in that order, the output stage draws on it)
+        stage = blk["pin"].array
+        for slot, i in enumerate(plan["order"]):
+            f, o = frames[i], int(plan["off"][slot])
+            np.copyto(stage[o:o + f.size].reshape(f.shape), f)
+        _lib.check(_lib.load().yds_memcpy_h2d(blk["dev"].ptr, _lib.ptr(stage[:nbytes]), nbytes))
 
-    def _render_batch(self, cur, holds, fps_texts, bgr):
-        """Output stage of one staged batch: a list of BGR frames in group order.  Device form: csrc/overlay.hip over the frames in
-        HBM; host form (device_overlay=False / YDS_HOST_OVERLAY: A/B runs and tests): label_draw.py on the staged copy."""
-        h, w, n = cur["h"], cur["w"], len(holds)
+    def _render_step(self, cur, holds, dets, fps_texts, bgr):
+        """Output stage of one staged step (cur: stage_steps' record): a list of BGR frames in yield order, with the anonymise mask
+        first (dets: per frame the detections its held rows came with).  Device form: csrc/overlay.hip over the frames in HBM,
+        uniform or mixed as the step was planned; host form (device_overlay=False / YDS_HOST_OVERLAY in detect(): A/B runs and
+        tests): label_draw.py on the staged copy."""
+        plan, blk, n = cur["plan"], cur["blk"], len(holds)
         anon = getattr(self, "anonymize", None)
-        dets = cur.get("dets") if anon is not None else None          # per frame: the detections its held rows came with (_run_engine)
+        dets = dets if anon is not None else None
         if self.device_overlay:
-            from .label_draw import DeviceOverlay
             if getattr(self, "_overlay", None) is None:
+                from .label_draw import DeviceOverlay
                 self._overlay = DeviceOverlay(self.label_drawer)
-            return self._overlay.render(cur["blk"]["dev"].offset(0), cur["slot_of"], h, w, holds, fps_texts,
-                                        bgr_frames=cur["blk"].get("n", n) if bgr else 0, privacy=anon, detections=dets,
-                                        n_frames=cur["blk"].get("n", n))
-        stage = cur["blk"]["pin"].array[:n * h * w * 3].reshape(n, h, w, 3)
-        if bgr:
-            stage = stage[..., ::-1]
-        return [self._render_host(np.ascontiguousarray(stage[cur["slot_of"][i]]), holds[i], fps_texts[i] if fps_texts else None,
-                                  dets[i] if dets else None) for i in range(n)]
+            if plan["mixed"]:
+                return self._overlay.render_mixed(blk["dev"].offset(0), plan["nbytes"], plan["off"], plan["hw"], plan["slot_of"], holds,
+                                                  fps_texts, bgr=bgr, privacy=anon, detections=dets)
+            return self._overlay.render(blk["dev"].offset(0), plan["slot_of"], int(plan["hw"][0][0]), int(plan["hw"][0][1]), holds, fps_texts,
+                                        bgr_frames=n if bgr else 0, privacy=anon, detections=dets, n_frames=n)
+        stage, out = blk["pin"].array, []
+        for i, slot in enumerate(plan["slot_of"]):
+            o, h, w = int(plan["off"][slot]), int(plan["hw"][slot][0]), int(plan["hw"][slot][1])
+            frame = stage[o:o + 3 * h * w].reshape(h, w, 3)
+            out.append(self._render_host(np.ascontiguousarray(frame[..., ::-1] if bgr else frame), holds[i], fps_texts[i] if fps_texts else None,
+                                         dets[i] if dets else None))
+        return out
 
     def _detect_batched(self, video_path, show_fps=True, skip_secs=0, batch_frames=None):
         """detect() through the batched pipeline: identical per-frame results, frames are read batch_frames ahead (the reference itself
@@ -551,7 +436,7 @@ class VideoDetector:
             self._pipe = pl.Pipeline(det.model, self.tracker, det.thres, det.nms_thres, class_mask=self.class_mask,
                                      win_size=det.win_size, overlap=det.overlap)
         self._batch_now = bf
-        iterable = hasattr(video_path, "__iter__") and not isinstance(video_path, (str, bytes)) and not hasattr(video_path, "isOpened")
+        iterable = _is_frame_iterable(video_path)
         if hasattr(self._pipe, "set_frame_order"):
             self._pipe.set_frame_order(not iterable)              # a capture / file source is staged as the decoder's BGR
         # Three threads, two hand-overs: reader (stage + upload) -> engine (pipeline steps, hold / action bookkeeping in frame order)
@@ -561,7 +446,8 @@ class VideoDetector:
         for _ in range(6):           # one being filled, one in out_q, two with the engine (this batch, the next), one in done_q, one being rendered
             free_q.put(dict(dev=None, pin=None))
         self.host_us = dict(wait_frames=0.0, step=0.0, wait_consumer=0.0, overlay=0.0, wait_engine=0.0, frames=0)
-        reader = threading.Thread(target=self._stage_batches, args=(video_path, skip_secs, not iterable, out_q, free_q, stop), daemon=True)
+        reader = threading.Thread(target=stage_steps, daemon=True, args=(self._video_steps(video_path, skip_secs, transform=iterable), False,
+                                                                          self._upload_step, out_q, free_q, stop))
         engine = threading.Thread(target=self._run_engine, args=(out_q, done_q, stop), daemon=True)
         reader.start()
         engine.start()
@@ -574,96 +460,59 @@ class VideoDetector:
                     raise item
                 if item is None:
                     break
-                cur, holds, acts = item
+                cur, holds, dets, acts = item
                 t1 = time.perf_counter()
                 now = time.time()
                 dt = (now - t_prev) / len(holds)
                 t_prev = now
                 fps = [self._fps_tick(dt) for _ in holds]
-                results = self._render_batch(cur, holds, fps if show_fps else None, not iterable)
+                results = self._render_step(cur, holds, dets, fps if show_fps else None, not iterable)
                 free_q.put(cur["blk"])
                 u = self.host_us
                 u["wait_engine"] += (t1 - t0) * 1e6; u["overlay"] += (time.perf_counter() - t1) * 1e6; u["frames"] += len(holds)
                 for i in range(len(holds)):
                     yield results[i], holds[i], acts[i]
         finally:
-            stop.set()
-            free_q.put(None)
-            for q in (out_q, done_q):                        # unblock a producer waiting on a full hand-over
-                try:
-                    while True:
-                        q.get_nowait()
-                except queue.Empty:
-                    pass
-            engine.join(timeout=5)
-            reader.join(timeout=5)
+            shut_down(stop, free_q, (out_q, done_q), (engine, reader))
 
     def _run_engine(self, out_q, done_q, stop):
-        """Engine thread of the batched path: one pipeline step per staged batch (the next batch handed over for its early detector
+        """Engine thread of the batched path: one pipeline step per staged step (the next one handed over for its early detector
         pass), then the per-frame bookkeeping of video_detect.py:134-159 in frame order - held rows, the action module."""
-        import queue
+        try:
+            book = Bookkeeper()
+            host_actions = self.action_id.update if self.action_id is not None else None
+            masking = getattr(self, "anonymize", None) is not None     # the frame's detections travel with its held rows
+            u = self.host_us
 
-        def take():
-            while True:
-                try:
-                    item = out_q.get(timeout=0.1)
-                except queue.Empty:
-                    if stop.is_set():
-                        return None
-                    continue
+            def staged():
+                item = take(out_q, stop)
                 if isinstance(item, BaseException):
                     raise item
                 return item
-
-        def give(item):
-            while not stop.is_set():
-                try:
-                    done_q.put(item, timeout=0.1)
-                    return
-                except queue.Full:
-                    pass
-        try:
-            hold_detections, actions, hold_dets = None, [], None
-            masking = getattr(self, "anonymize", None) is not None     # the frame's detections travel with its held rows
-            u = self.host_us
             t0 = time.perf_counter()
-            cur = take()
+            cur = staged()
             u["wait_frames"] += (time.perf_counter() - t0) * 1e6
             while cur is not None and not stop.is_set():
                 t0 = time.perf_counter()
-                nxt = take()
+                nxt = staged()
                 t1 = time.perf_counter()
-                outs = []
-                h, w, n = cur["h"], cur["w"], cur["n_proc"]
+                outs, plan = [], cur["plan"]
+                n = plan["n_proc"]
                 if n:
-                    ahead = nxt["blk"]["dev"].offset(0) if nxt is not None and (nxt["h"], nxt["w"], nxt["n_proc"]) == (h, w, n) else None
-                    outs = self._pipe.step(cur["blk"]["dev"].offset(0), h, w, n, ahead)
+                    # (one stream, uniform frames: same_composition is the same h, w and number of processed frames)
+                    ahead = nxt["blk"]["dev"].offset(0) if nxt is not None and same_composition(plan, nxt["plan"]) else None
+                    outs = self._pipe.step(cur["blk"]["dev"].offset(0), int(plan["hw"][0][0]), int(plan["hw"][0][1]), n, ahead)
                 step_dets = self._pipe.last_detections() if masking and n else None
                 u["wait_frames"] += (t1 - t0) * 1e6
                 u["step"] += (time.perf_counter() - t1) * 1e6
-                holds, acts, dets, k = [], [], [], 0
-                for proc in cur["flags"]:
-                    if proc:
-                        o = outs[k]
-                        hold_dets = step_dets[k] if step_dets is not None else None
-                        k += 1
-                        hold_detections = None if o is None else (o if len(o) else [])
-                        if hold_detections is not None:        # video_detect.py:137-154; a detector-None frame leaves `actions` as it was
-                            actions = self.action_id.update(hold_detections) if self.action_id is not None else []
-                    else:
-                        actions = []                           # :158-159
-                    holds.append(hold_detections)
-                    acts.append(actions)
-                    dets.append(hold_dets)
-                if masking:
-                    cur["dets"] = dets
+                result = (cur,) + book.update(cur["items"], outs, step_dets=step_dets, host_actions=host_actions)
                 t2 = time.perf_counter()
-                give((cur, holds, acts))
+                give(done_q, result, stop)
                 u["wait_consumer"] += (time.perf_counter() - t2) * 1e6
                 cur = nxt
-            give(None)
+            give(done_q, None, stop)
         except BaseException as e:                             # noqa: BLE001 - re-raised on the consumer's thread
-            give(e)
+            give(done_q, e, stop)
 
     def detect(self, video_path, output_path=None, skip_secs=0, real_show=False, show_fps=True):
         """Generator of (bgr_image, hold_detections, actions) like video_detect.py:78-199.  output_path: every result is
@@ -759,7 +608,7 @@ class VideoDetector:
         With global_ids no step carries a look-ahead pass: stream_identity_map() hands out the map, and changing it between the
         yields (enrol, set_memory) is refused by the library while such a pass is in flight.  device_overlay=False keeps the host
         loop below."""
-        from . import _lib, pipeline as pl
+        from . import pipeline as pl
         from .identity import check_memory
         sources = list(sources)
         memory = {}
@@ -826,149 +675,62 @@ class VideoDetector:
             pipe.set_heatmap(heat_dev)
         self._stream_zone_events = [[] for _ in range(S)]
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
+        on = dict(timed=actions_dev is not None or zones_dev is not None or heat_dev is not None, zones=zones_dev is not None,
+                  actions=actions_dev is not None)
         try:
             if self.device_overlay:                          # staged uploads, look-ahead, the output stage on the device
-                yield from self._detect_streams_device(pipe, sources, F, show_fps, mixed_sizes,
-                                                       actions_dev is not None or zones_dev is not None or heat_dev is not None,
-                                                       zones_dev is not None, actions_dev is not None, lookahead=not global_ids)
+                yield from self._detect_streams_device(pipe, sources, F, show_fps, mixed_sizes, on, lookahead=not global_ids)
                 return
-            # the host loop (device_overlay=False / YDS_HOST_OVERLAY)
-            shapes = [None] * S                              # mixed_sizes: the shape each stream started with
-            lib = _lib.load()
+            # the host loop (device_overlay=False / YDS_HOST_OVERLAY): every step's processed frames are planned and uploaded as a
+            # step of their own, on this thread; the images are rendered on the host from the frames as they were read
             its = [iter(self._frames(src)) for src in sources]
-            since, hold, alive = [0] * S, [None] * S, [True] * S
-            masking, hold_dets = getattr(self, "anonymize", None) is not None, [None] * S      # the anonymise option: rendered on the host here
-            shape, dev = None, None
-            live = [self._is_live(src) for src in sources]
-            n_read, rate, acts = [0] * S, [None] * S, [[] for _ in range(S)]     # frames read, frame rate, last actions of every stream
-            while any(alive):
-                items = []                                   # (stream, frame, processed) in yield order
-                for s in range(S):
-                    n_proc = 0
-                    while alive[s] and n_proc < F:          # the groups of _processed_batches, per stream
-                        frame = next(its[s], None)
-                        if frame is None:
-                            alive[s] = False
-                            break
-                        if rate[s] is None:                 # (_frames has just opened the source)
-                            rate[s] = float(getattr(self, "_source_fps", None) or 25.0)
-                        t_frame = time.time() if live[s] else n_read[s] / rate[s]
-                        n_read[s] += 1
-                        frame = np.asarray(frame)
-                        if mixed_sizes:
-                            if shapes[s] is None:
-                                shapes[s] = frame.shape
-                            if frame.shape != shapes[s] or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
-                                raise ValueError("VideoDetector.detect_streams: stream %d must keep one uint8 [h, w, 3] shape (%s, then %s %s)"
-                                                 % (s, shapes[s], frame.shape, frame.dtype))
-                        elif shape is None:
-                            shape = frame.shape
-                        if not mixed_sizes and (frame.shape != shape or frame.dtype != np.uint8 or frame.ndim != 3 or shape[2] != 3):
-                            raise ValueError("VideoDetector.detect_streams: every frame of every source must share one uint8 [h, w, 3] shape "
-                                             "(%s, then %s %s in stream %d)" % (shape, frame.shape, frame.dtype, s))
-                        proc = since[s] % self.skip_frames == 0
-                        if proc:
-                            since[s] = 0
-                        since[s] += 1
-                        n_proc += proc
-                        items.append((s, frame, proc, t_frame))
-                procs = [(s, f) for s, f, p, _ in items if p]
-                outs = []
+            book, blk = Bookkeeper(S), dict(dev=None, pin=None)
+            for items in stream_groups(its, F, self.skip_frames, mixed_sizes, [self._is_live(src) for src in sources],
+                                       lambda: getattr(self, "_source_fps", None)):
+                procs = [it for it in items if it[2]]
+                plan = stage_plan(procs, mixed_sizes)
                 if procs:
-                    if mixed_sizes:
-                        batch, off, hw = pl.pack_frames([f for _, f in procs])
-                    else:
-                        batch = np.ascontiguousarray(np.stack([f for _, f in procs], 0))
-                    if dev is None or dev.nbytes < batch.nbytes:
-                        dev = _lib.DeviceBuffer(batch.nbytes)
-                    _lib.check(lib.yds_memcpy_h2d(dev.ptr, _lib.ptr(batch), batch.nbytes))
-                    if actions_dev is not None or zones_dev is not None or heat_dev is not None:
-                        pipe.set_frame_times([t for _, _, p, t in items if p])
-                    if mixed_sizes:
-                        outs = pipe.step_mixed(dev.offset(0), off, hw, [s for s, _ in procs], batch.nbytes)
-                    else:
-                        outs = pipe.step(dev.offset(0), shape[0], shape[1], [s for s, _ in procs])
-                step_acts = pipe.last_actions() if actions_dev is not None and procs else None
-                step_dets = pipe.last_detections() if masking and procs else None
-                if zones_dev is not None:                   # the events of this step's processed frames, per stream in time order
-                    self._stream_zone_events = [[] for _ in range(S)]
-                    for (s, _), evs in zip(procs, pipe.last_zone_events() if procs else []):
-                        self._stream_zone_events[s].append(evs)
-                out, k = [], 0
-                for s, frame, proc, _ in items:
-                    if proc:
-                        o = outs[k]
-                        if step_acts is not None and step_acts[k] is not None:   # a detector-None frame leaves the previous value
-                            acts[s] = step_acts[k]
-                        if step_dets is not None:
-                            hold_dets[s] = step_dets[k]
-                        k += 1
-                        hold[s] = None if o is None else (o if len(o) else [])
-                    else:
-                        acts[s] = []                        # video_detect.py:158-159
-                    out.append((s, self._render(frame, hold[s], show_fps, hold_dets[s]), hold[s], acts[s]))
-                if out:
-                    yield out
+                    self._upload_step(blk, plan, [it[1] for it in procs])
+                holds, dets, acts = book.update([(s, p) for s, _, p, _ in items], *self._streams_step(pipe, plan, [it[3] for it in procs], blk, None, on))
+                yield [(s, self._render(frame, holds[i], show_fps, dets[i]), holds[i], acts[i]) for i, (s, frame, _, _) in enumerate(items)]
         finally:
             self._streams_pipe = None                    # the generator ended, was closed or raised
 
-    @staticmethod
-    def _stage_streams(groups, mixed_sizes, out_q, free_q, stop):
-        """Reader thread of detect_streams' device form: every step of `groups` (stream_groups) is planned (stage_plan), copied into
-        a pinned staging block at the plan's offsets and uploaded to the block's HBM buffer (a synchronous copy on this thread, the
-        GIL released).  The generator hands the blocks back through free_q; blk["dev"] / blk["pin"] are reallocated only when a
-        group outgrows them.  An exception travels through out_q and is raised again on the generator's thread."""
-        import queue
-        from . import _lib
+    def _streams_step(self, pipe, plan, times, blk, ahead, on):
+        """One MultiStreamPipeline step over the processed frames of a planned step (uniform or mixed; times: their frame times;
+        ahead: the next step's HBM buffer for its early detector pass, or None), and what the bookkeeping reads after it:
+        (outs, actions per frame or None, detections per frame or None).  on: which device stages run (timed, zones, actions)."""
+        n, outs = plan["n_proc"], []
+        if n:
+            if on["timed"]:
+                pipe.set_frame_times(times)
+            if plan["mixed"]:
+                outs = pipe.step_mixed(blk["dev"].offset(0), plan["off"][:n], plan["hw"][:n], plan["streams"], plan["proc_bytes"], ahead)
+            else:
+                outs = pipe.step(blk["dev"].offset(0), int(plan["hw"][0][0]), int(plan["hw"][0][1]), plan["streams"], ahead)
+        step_acts = pipe.last_actions() if on["actions"] and n else None
+        step_dets = pipe.last_detections() if getattr(self, "anonymize", None) is not None and n else None
+        if on["zones"]:                                  # the events of this step's processed frames, per stream in time order
+            self._stream_zone_events = [[] for _ in self._stream_zone_events]
+            for s, evs in zip(plan["streams"], pipe.last_zone_events() if n else []):
+                self._stream_zone_events[s].append(evs)
+        return outs, step_acts, step_dets
 
-        def give(item):                                        # never blocks past a stop request
-            while not stop.is_set():
-                try:
-                    out_q.put(item, timeout=0.1)
-                    return
-                except queue.Full:
-                    pass
-        try:
-            lib = _lib.load()
-            for items in groups:
-                if stop.is_set():
-                    return
-                plan = stage_plan(items, mixed_sizes)
-                blk = free_q.get()
-                if blk is None or stop.is_set():
-                    return
-                nbytes = plan["nbytes"]
-                if blk["dev"] is None or blk["dev"].nbytes < nbytes:
-                    blk["dev"] = _lib.DeviceBuffer(nbytes)
-                    blk["pin"] = _lib.PinnedArray((nbytes,), np.uint8)
-                stage = blk["pin"].array
-                for slot, i in enumerate(plan["order"]):
-                    f, o = items[i][1], int(plan["off"][slot])
-                    np.copyto(stage[o:o + f.size].reshape(f.shape), f)
-                _lib.check(lib.yds_memcpy_h2d(blk["dev"].ptr, _lib.ptr(stage[:nbytes]), nbytes))
-                give(dict(blk=blk, plan=plan, items=[(s, proc, t) for s, _, proc, t in items]))
-            give(None)
-        except BaseException as e:                             # noqa: BLE001 - re-raised on the generator's thread
-            give(e)
-
-    def _detect_streams_device(self, pipe, sources, F, show_fps, mixed_sizes, timed, zones_on, actions_on, lookahead=True):
+    def _detect_streams_device(self, pipe, sources, F, show_fps, mixed_sizes, on, lookahead=True):
         """detect_streams with the output stage on the device (device_overlay).  A reader thread forms, stages and uploads the
-        steps (_stage_streams: a ring of four blocks - one being filled, one queued, the two the step holds); THIS thread runs the
+        steps (stage_steps: a ring of four blocks - one being filled, one queued, the two the step holds); THIS thread runs the
         step in lock-step with the yields, so that whatever is read between the yields (zone events and counts, identities, heat
         maps, search, link) is the state right after the yielded step.  Overlap comes from look-ahead: when the next step is
         already staged and has the same composition (same_composition), its HBM buffer goes along as next_frames_dev and the
         device runs its detector pass while the host renders and the consumer works; with a live source the next step is never
-        waited for.  The output stage is ONE call over the staged block, processed and skipped frames alike
-        (DeviceOverlay.render / render_mixed), with the mask first when the anonymise option is on.  Sources that are all captures
-        or files are staged as the decoder's BGR (set_frame_order(True)) and drawn on in place; any iterable keeps RGB staging
-        and the reversed copy.  lookahead=False (detect_streams with global_ids): no step carries a look-ahead pass - the
-        identity map is the caller's to change between the yields (stream_identity_map().enrol, set_memory), which the library
-        refuses while such a pass is in flight."""
+        waited for.  The output stage is ONE call over the staged block, processed and skipped frames alike (_render_step), with
+        the mask first when the anonymise option is on.  Sources that are all captures or files are staged as the decoder's BGR
+        (set_frame_order(True)) and drawn on in place; any iterable keeps RGB staging and the reversed copy.  lookahead=False
+        (detect_streams with global_ids): no step carries a look-ahead pass - the identity map is the caller's to change
+        between the yields (stream_identity_map().enrol, set_memory), which the library refuses while such a pass is in flight."""
         import queue
         import threading
-        from .label_draw import DeviceOverlay
-        S = len(sources)
-        bgr = not any(hasattr(src, "__iter__") and not isinstance(src, (str, bytes)) and not hasattr(src, "isOpened") for src in sources)
+        bgr = not any(_is_frame_iterable(src) for src in sources)
         pipe.set_frame_order(bgr)
         live = [self._is_live(src) for src in sources]
         its = [iter(self._frames(src, transform=not bgr)) for src in sources]
@@ -976,97 +738,39 @@ class VideoDetector:
         out_q, free_q, stop = queue.Queue(maxsize=1), queue.Queue(), threading.Event()
         for _ in range(4):
             free_q.put(dict(dev=None, pin=None))
-        reader = threading.Thread(target=self._stage_streams, args=(groups, mixed_sizes, out_q, free_q, stop), daemon=True)
+        reader = threading.Thread(target=stage_steps, args=(groups, mixed_sizes, self._upload_step, out_q, free_q, stop), daemon=True)
         self._streams_reader = reader
         reader.start()
-        nothing = object()                                     # "no step is staged yet" (a live source is never waited for)
-
-        def take(block):
-            while True:
-                try:
-                    item = out_q.get(timeout=0.1) if block else out_q.get_nowait()
-                except queue.Empty:
-                    if not block:
-                        return nothing
-                    if not reader.is_alive() and out_q.empty():
-                        return None
-                    continue
-                return item                                    # (an exception of the reader included: it is raised in its turn)
-        if getattr(self, "_overlay", None) is None:
-            self._overlay = DeviceOverlay(self.label_drawer)
-        anon = getattr(self, "anonymize", None)
-        hold, acts, hold_dets = [None] * S, [[] for _ in range(S)], [None] * S
-        wait_next = not any(live)
+        book = Bookkeeper(len(sources))
+        wait_next = not any(live)                              # (a live source is never waited for)
         self.streams_lookahead = [0, 0]                        # steps that carried a look-ahead pass, steps run (tools/, tests)
         t_prev = time.time()
         try:
-            cur, nxt = take(True), nothing
+            cur, nxt = take(out_q, stop, reader), NOTHING
             while cur is not None:
                 if isinstance(cur, BaseException):            # after everything staged before it was yielded, as on the host form
                     raise cur
-                if nxt is nothing:
-                    nxt = take(wait_next)
-                plan, items, dev = cur["plan"], cur["items"], cur["blk"]["dev"]
-                n, outs = plan["n_proc"], []
-                h, w = int(plan["hw"][0][0]), int(plan["hw"][0][1])
-                if n:
-                    ahead = None
+                if nxt is NOTHING:
+                    nxt = take(out_q, stop, reader, wait_next)
+                plan, items, ahead = cur["plan"], cur["items"], None
+                if plan["n_proc"]:
                     if lookahead and isinstance(nxt, dict) and same_composition(plan, nxt["plan"]):
                         ahead = nxt["blk"]["dev"].offset(0)
                     self.streams_lookahead[0] += ahead is not None
                     self.streams_lookahead[1] += 1
-                    if timed:
-                        pipe.set_frame_times([t for _, p, t in items if p])
-                    if mixed_sizes:
-                        outs = pipe.step_mixed(dev.offset(0), plan["off"][:n], plan["hw"][:n], plan["streams"], plan["proc_bytes"], ahead)
-                    else:
-                        outs = pipe.step(dev.offset(0), h, w, plan["streams"], ahead)
-                step_acts = pipe.last_actions() if actions_on and n else None
-                step_dets = pipe.last_detections() if anon is not None and n else None
-                if zones_on:                                # the events of this step's processed frames, per stream in time order
-                    self._stream_zone_events = [[] for _ in range(S)]
-                    for s, evs in zip(plan["streams"], pipe.last_zone_events() if n else []):
-                        self._stream_zone_events[s].append(evs)
-                holds, dets, out_acts, k = [], [], [], 0
-                for s, proc, _ in items:                    # the bookkeeping of the host loop, frame by frame
-                    if proc:
-                        o = outs[k]
-                        if step_acts is not None and step_acts[k] is not None:
-                            acts[s] = step_acts[k]
-                        if step_dets is not None:
-                            hold_dets[s] = step_dets[k]
-                        k += 1
-                        hold[s] = None if o is None else (o if len(o) else [])
-                    else:
-                        acts[s] = []
-                    holds.append(hold[s])
-                    dets.append(hold_dets[s])
-                    out_acts.append(acts[s])
+                holds, dets, acts = book.update(items, *self._streams_step(pipe, plan, [t for _, p, t in items if p], cur["blk"], ahead, on))
                 now = time.time()
                 dt = (now - t_prev) / len(items)
                 t_prev = now
                 fps = [self._fps_tick(dt) for _ in items]
-                kw = dict(privacy=anon, detections=dets if anon is not None else None)
-                if mixed_sizes:
-                    images = self._overlay.render_mixed(dev.offset(0), plan["nbytes"], plan["off"], plan["hw"], plan["slot_of"], holds,
-                                                        fps if show_fps else None, bgr=bgr, **kw)
-                else:
-                    images = self._overlay.render(dev.offset(0), plan["slot_of"], h, w, holds, fps if show_fps else None,
-                                                  bgr_frames=len(items) if bgr else 0, n_frames=len(items), **kw)
+                images = self._render_step(cur, holds, dets, fps if show_fps else None, bgr)
                 free_q.put(cur["blk"])
-                out = [(items[i][0], images[i], holds[i], out_acts[i]) for i in range(len(items))]
+                out = [(items[i][0], images[i], holds[i], acts[i]) for i in range(len(items))]
                 del images
                 yield out
-                cur, nxt = (take(True), nothing) if nxt is nothing else (nxt, nothing)
+                cur, nxt = (take(out_q, stop, reader), NOTHING) if nxt is NOTHING else (nxt, NOTHING)
         finally:
-            stop.set()
-            free_q.put(None)
-            try:                                             # unblock a reader waiting on the full hand-over
-                while True:
-                    out_q.get_nowait()
-            except queue.Empty:
-                pass
-            reader.join(timeout=5)
+            shut_down(stop, free_q, (out_q,), (reader,))
             for it in its:                                   # ends the decoder threads of file / capture sources
                 try:
                     it.close()
@@ -1163,18 +867,13 @@ class VideoDetector:
         if bf > 1 and (self._batchable() or (getattr(self, "batch_windows", False) and self._batchable_windows())):
             yield from self._detect_batched(video_path, show_fps, skip_secs, bf)
             return
-        hold_detections, actions, frames, hold_dets = None, [], 0, None
+        # the frame-by-frame loop: a step of one frame; the action module runs where the tracker branch did (process)
+        book, since = Bookkeeper(rows_as_given=True), 0
+        host_actions = None if self.tracker is None else (self.action_id.update if self.action_id is not None else (lambda hold: []))
         for frame in self._frames(video_path, skip_secs):
             if frame is None:
                 break
-            if frames % self.skip_frames == 0:
-                hold_detections = self.process(frame)
-                hold_dets = self._last_dets
-                if self._tracked:                          # video_detect.py:137-154; otherwise `actions` keeps its previous value
-                    actions = self.action_id.update(hold_detections) if self.action_id is not None else []
-                frames = 0
-            else:
-                actions = []
-            result = self._render(frame, hold_detections, show_fps, hold_dets)
-            frames += 1
-            yield result, hold_detections, actions
+            proc, since = skip_gate(since, self.skip_frames)
+            outs = [self.process(frame)] if proc else []
+            (hold,), (dets,), (actions,) = book.update([(0, proc)], outs, step_dets=[self._last_dets] if proc else None, host_actions=host_actions)
+            yield self._render(frame, hold, show_fps, dets), hold, actions
