@@ -229,6 +229,20 @@ int yds_tracker_get_payload(yds_trk *, float *payload, int cap);
 int yds_tracker_get_age(yds_trk *, int32_t *age, int cap);              /* Track.age (track.py:40,115), track-list order */
 int yds_tracker_last_unmatched(yds_trk *, int32_t *um_tracks, int cap_t, int *n_t,
                                int32_t *um_dets, int cap_d, int *n_d);
+/* parity tests: sizes of the tracker's last frame as the association kernel reported them - Tc, D (appearance stage: confirmed
+ * tracks x detections), Tb, Db (IOU stage: candidates x leftover detections) - then the number of storage slots and of free slots */
+int yds_tracker_last_sizes(yds_trk *, int32_t *sizes6);
+/* parity tests: the form the fused association kernel solves an nr x nc assignment problem in, by the library's own rule (one
+ * function, shared with the kernel) at the kernel's LDS size: 0 nothing to solve, 1 / 2 single wavefront, 3 / 4 register-resident
+ * workgroup, 5 / 6 workgroup with its state in LDS, 7 / 8 workgroup with its state in global memory; odd = cost matrix copied into
+ * LDS, even = read from global memory */
+int yds_lsap_fused_form(int nr, int nc);
+/* parity tests: one step of a tracker group, as a pipeline runs it, without a pipeline.  Frame b (of n) belongs to trks[stream_of[b]]
+ * and holds detections first[b] .. first[b + 1] of tlwh [*,4], feats_host [*,512] and payload [*]; a tracker's frames run in the order
+ * given.  skip (optional) [n]: frames whose tracker is not called (counts[b] = -1).  out6 [n][cap][6], counts [n]. */
+int yds_tracker_step_batch(yds_trk *const *trks, int S, int n, const int32_t *stream_of, const float *tlwh_host, const int32_t *first,
+                           const float *feats_host, const float *payload_host, const char *skip, int32_t *out6_host, int cap,
+                           int32_t *counts);
 /* stand-alone association primitives (parity tests call these through the C ABI) */
 int yds_lsap(const float *cost_host, int nr, int nc, int32_t *rows, int32_t *cols, int *n_out);
 /* tuning aid: average duration of `iters` back-to-back LSAP launches on one cost matrix (HIP events) */

@@ -119,6 +119,9 @@ SIGNATURES = {
     "yds_kalman_initiate": (_I, [_P, _I, _P, _P]),
     "yds_kalman_project": (_I, [_P, _P, _I, _P, _P]),
     "yds_tracker_last_unmatched": (_I, [_P, _P, _I, _P, _P, _I, _P]),
+    "yds_tracker_last_sizes": (_I, [_P, _P]),
+    "yds_lsap_fused_form": (_I, [_I, _I]),
+    "yds_tracker_step_batch": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "yds_lsap": (_I, [_P, _I, _I, _P, _P, _P]),
     "yds_lsap_bench": (_I, [_P, _I, _I, _I, _P]),
     "yds_kalman_predict": (_I, [_P, _P, _I]),

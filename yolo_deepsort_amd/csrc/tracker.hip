@@ -453,6 +453,8 @@ public:
         last_um_d.assign(pd, pd + r[M_NUD]);
         T_host = r[M_T];
         max_rows = r[M_MAXFEAT];
+        const int sizes[6] = {r[M_TC], r[M_D], r[M_TB], r[M_DB], capacity, r[M_NFREE]};
+        memcpy(last_sizes, sizes, sizeof sizes);
     }
 
     // stand-alone calls (yds_tracker_step*, DeepSort.update): a step of one frame through a driver of this tracker's own
@@ -488,6 +490,7 @@ public:
     DevBuf<char> lsap_scratch;
     std::vector<std::pair<int, int>> last_matches;
     std::vector<int> last_um_t, last_um_d;
+    int last_sizes[6] = {};                     // of the last synchronised frame: Tc, D, Tb, Db (the two assignment problems), slots, free slots
     std::unique_ptr<TrackerGroupIface> solo;    // driver of the stand-alone calls (a TrackerGroup), made by the first of them
 };
 
@@ -849,6 +852,36 @@ int yds_tracker_last_unmatched(yds_trk *t, int32_t *um_tracks, int cap_t, int *n
     *n_t = (int)a.size(); *n_d = (int)b.size();
     for (size_t i = 0; i < a.size(); ++i) um_tracks[i] = a[i];
     for (size_t i = 0; i < b.size(); ++i) um_dets[i] = b[i];
+    YDS_API_END
+}
+
+int yds_tracker_last_sizes(yds_trk *t, int32_t *sizes6) {
+    YDS_API_BEGIN
+    if (!t || !t->t || !sizes6) yds::fail("tracker_last_sizes: NULL argument");
+    for (int k = 0; k < 6; ++k) sizes6[k] = impl(t)->last_sizes[k];
+    YDS_API_END
+}
+int yds_lsap_fused_form(int nr, int nc) { return (int)yds::lsap_form(nr, nc, (int)yds::LSAP_LDS_MAX, true); }
+int yds_tracker_step_batch(yds_trk *const *trks, int S, int n, const int32_t *stream_of, const float *tlwh, const int32_t *first,
+                           const float *feats_host, const float *payload, const char *skip, int32_t *out6, int cap, int32_t *counts) {
+    YDS_API_BEGIN
+    using namespace yds;
+    if (S < 1 || n < 0 || !trks || (n && (!stream_of || !first || !out6 || !counts))) fail("tracker_step_batch: S = %d, n = %d or a NULL argument", S, n);
+    std::vector<TrackerIface *> t(S);
+    for (int s = 0; s < S; ++s) {
+        if (!trks[s] || !trks[s]->t) fail("tracker_step_batch: tracker %d is NULL", s);
+        t[s] = trks[s]->t;
+    }
+    const int rows = n ? first[n] : 0;
+    if (rows < 0 || (rows && (!tlwh || !feats_host || !payload))) fail("tracker_step_batch: %d detections without their arrays", rows);
+    DevBuf<float> feats;
+    if (rows) {
+        hipStream_t s = g_scratch.stream();
+        feats.upload(feats_host, (size_t)rows * EMB, s);
+        YDS_HIP(hipStreamSynchronize(s));                       // the driver runs on a stream of its own
+    }
+    std::unique_ptr<TrackerGroupIface> group(make_tracker_group());
+    group->step_batch(t.data(), S, n, stream_of, tlwh, first, feats.p, payload, skip, out6, cap, counts);
     YDS_API_END
 }
 

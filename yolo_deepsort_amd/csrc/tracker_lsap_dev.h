@@ -453,24 +453,54 @@ __device__ __forceinline__ void lsap_wave_solve(const float *cost, const float *
 
 constexpr size_t LSAP_WAVE_STATE = (size_t)LSAP_WAVE_COLS * (3 * sizeof(double) + 5 * sizeof(int));
 
-// One problem solved by the calling workgroup of LSAP_NT threads, form chosen from the ACTUAL sizes (they are only known on the
-// device): <= 64 columns the single-wavefront form on wave 0 (the other waves wait at the closing barrier), <= 256 the register-
-// resident form, else the LDS-state form, and with state_global != nullptr the global-state form for problems whose state
-// exceeds the LDS.  smem_bytes = dynamic LDS of the launch (lsap_smem).  Every thread must call; *n_out is written by one thread
-// and is visible to the workgroup after the closing barrier.
+// The solver form of one problem, decided in ONE place from the ACTUAL sizes (they are only known on the device), the dynamic LDS of the
+// launch and whether the caller brought a global scratch region for the solver state:
+//   n = max(nr, nc) <= 64    single wavefront (wave 0; the other waves wait at the closing barrier)
+//   n <= 256                 register-resident workgroup form (fixed LSAP_REG_STATE bytes of LDS state)
+//   n * 48 bytes fit the LDS workgroup form with its state in LDS
+//   else                     workgroup form with its state in the global scratch (LSAP_FORM_NO_SCRATCH when there is none)
+// and in every form the cost matrix is copied into what LDS the state leaves when it fits there, else read from global memory.
+// The values are part of the C ABI (yds_lsap_fused_form, include/ydsort.h).
+enum LsapForm {
+    LSAP_FORM_EMPTY = 0,        // nr <= 0 or nc <= 0: nothing is solved (linear_assignment.py:48-49)
+    LSAP_FORM_WAVE_LDS = 1,
+    LSAP_FORM_WAVE_GLOBAL = 2,
+    LSAP_FORM_REG_LDS = 3,
+    LSAP_FORM_REG_GLOBAL = 4,
+    LSAP_FORM_WG_LDS = 5,       // state in LDS, cost in LDS
+    LSAP_FORM_WG_GLOBAL = 6,    // state in LDS, cost in global memory
+    LSAP_FORM_GSTATE_LDS = 7,   // state in the global scratch, cost in LDS
+    LSAP_FORM_GSTATE_GLOBAL = 8,
+    LSAP_FORM_NO_SCRATCH = 9    // the state exceeds the LDS and there is no global scratch: a host-side sizing error
+};
+__host__ __device__ inline LsapForm lsap_form(int nr, int nc, int smem_bytes, bool has_global_scratch) {
+    if (nr <= 0 || nc <= 0) return LSAP_FORM_EMPTY;
+    const size_t smem = (size_t)smem_bytes, cost = (size_t)nr * nc * sizeof(float);
+    const int n = nr > nc ? nr : nc;
+    if (n <= LSAP_WAVE_COLS) return LSAP_WAVE_STATE + cost <= smem ? LSAP_FORM_WAVE_LDS : LSAP_FORM_WAVE_GLOBAL;
+    if (n <= LSAP_REG_COLS && LSAP_REG_STATE <= smem) return LSAP_REG_STATE + cost <= smem ? LSAP_FORM_REG_LDS : LSAP_FORM_REG_GLOBAL;
+    const size_t state = (size_t)n * LSAP_STATE_BYTES;
+    if (state <= smem) return state + cost <= smem ? LSAP_FORM_WG_LDS : LSAP_FORM_WG_GLOBAL;
+    if (!has_global_scratch) return LSAP_FORM_NO_SCRATCH;
+    return cost <= smem ? LSAP_FORM_GSTATE_LDS : LSAP_FORM_GSTATE_GLOBAL;
+}
+
+// One problem solved by the calling workgroup of LSAP_NT threads in the form lsap_form names.  smem_bytes = dynamic LDS of the launch
+// (lsap_smem); state_global: global scratch for the solver state (nullptr: none).  Every thread must call; *n_out is written by one
+// thread and is visible to the workgroup after the closing barrier.
 __device__ __forceinline__ void lsap_solve_block(const float *cost, int nr0, int nc0, int *row_out, int *col_out, int *n_out, char *state_global,
                                                  int smem_bytes) {
     extern __shared__ __attribute__((aligned(16))) char lsap_smem[];
-    if (nr0 <= 0 || nc0 <= 0) {                                  // linear_assignment.py:48-49 early-out
+    const LsapForm form = lsap_form(nr0, nc0, smem_bytes, state_global != nullptr);
+    switch (form) {
+    case LSAP_FORM_EMPTY:
         if (threadIdx.x == 0) *n_out = 0;
-        __syncthreads();
-        return;
-    }
-    const int n = max(nr0, nc0);
-    if (n <= LSAP_WAVE_COLS) {
+        break;
+    case LSAP_FORM_WAVE_LDS:
+    case LSAP_FORM_WAVE_GLOBAL:
         if (threadIdx.x < 64) {
             float *cost_lds = reinterpret_cast<float *>(lsap_smem + LSAP_WAVE_STATE);
-            if (LSAP_WAVE_STATE + (size_t)nr0 * nc0 * sizeof(float) <= (size_t)smem_bytes) {
+            if (form == LSAP_FORM_WAVE_LDS) {
                 for (int i = threadIdx.x; i < nr0 * nc0; i += 64) cost_lds[i] = cost[i];
                 lsap_wave_solve<true, 1>(cost, cost_lds, nr0, nc0, lsap_smem, row_out, col_out);
             } else {
@@ -478,22 +508,14 @@ __device__ __forceinline__ void lsap_solve_block(const float *cost, int nr0, int
             }
             if (threadIdx.x == 0) *n_out = min(nr0, nc0);
         }
-        __syncthreads();
-        return;
-    }
-    if (n <= LSAP_REG_COLS && LSAP_REG_STATE <= (size_t)smem_bytes) {
-        if (LSAP_REG_STATE + (size_t)nr0 * nc0 * sizeof(float) <= (size_t)smem_bytes) lsap_reg_solve<true>(cost, nr0, nc0, row_out, col_out, n_out);
-        else lsap_reg_solve<false>(cost, nr0, nc0, row_out, col_out, n_out);
-        __syncthreads();
-        return;
-    }
-    const size_t state = (size_t)n * LSAP_STATE_BYTES;
-    if (state <= (size_t)smem_bytes) {
-        if (state + (size_t)nr0 * nc0 * sizeof(float) <= (size_t)smem_bytes) lsap_wg_solve<false, true>(cost, nr0, nc0, row_out, col_out, n_out, nullptr);
-        else lsap_wg_solve<false, false>(cost, nr0, nc0, row_out, col_out, n_out, nullptr);
-    } else {
-        if ((size_t)nr0 * nc0 * sizeof(float) <= (size_t)smem_bytes) lsap_wg_solve<true, true>(cost, nr0, nc0, row_out, col_out, n_out, state_global);
-        else lsap_wg_solve<true, false>(cost, nr0, nc0, row_out, col_out, n_out, state_global);
+        break;
+    case LSAP_FORM_REG_LDS: lsap_reg_solve<true>(cost, nr0, nc0, row_out, col_out, n_out); break;
+    case LSAP_FORM_REG_GLOBAL: lsap_reg_solve<false>(cost, nr0, nc0, row_out, col_out, n_out); break;
+    case LSAP_FORM_WG_LDS: lsap_wg_solve<false, true>(cost, nr0, nc0, row_out, col_out, n_out, nullptr); break;
+    case LSAP_FORM_WG_GLOBAL: lsap_wg_solve<false, false>(cost, nr0, nc0, row_out, col_out, n_out, nullptr); break;
+    case LSAP_FORM_GSTATE_LDS: lsap_wg_solve<true, true>(cost, nr0, nc0, row_out, col_out, n_out, state_global); break;
+    case LSAP_FORM_GSTATE_GLOBAL: lsap_wg_solve<true, false>(cost, nr0, nc0, row_out, col_out, n_out, state_global); break;
+    case LSAP_FORM_NO_SCRATCH: __builtin_trap();
     }
     __syncthreads();
 }
