@@ -102,7 +102,10 @@ struct ConvCase {
         }
         a.y = slice(y_whole, d.y_off, cout);                     // (merged: both filter counts, the first output's pointer and stride)
         if (res_mode) {
-            View r_whole{nullptr, n, ho, wo, d.r_ld, d.r_ld, yfmt};
+            // the residual is pre-split where ITS view allows it (dense tensors: wherever the output is), so a view case can pair an
+            // H16 shortcut with an fp32 output and the reverse
+            const int rfmt = yfmt == FMT_F16 ? FMT_F16 : (f16 && h16_ok(cout, d.r_ld, d.r_off)) ? FMT_H16 : FMT_F32;
+            View r_whole{nullptr, n, ho, wo, d.r_ld, d.r_ld, rfmt};
             put(r_whole, res_nhwc, raw[1], res);
             a.res = slice(r_whole, d.r_off, cout);
             a.res_mode = res_mode;

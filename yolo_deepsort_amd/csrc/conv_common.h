@@ -112,14 +112,152 @@ struct FlatRows {
     int m0;
     __device__ __forceinline__ int operator()(int row) const { return m0 + row; }
 };
+// The f16x3 accumulators come out of the K loop as o * 2^-8 (A_SCALE), and H16 tensors store x * 2^-8.  Linear, LeakyReLU and ReLU
+// commute with a positive scale, so the kernels that opt in (FAST) hand over acc1 + acc2 / LO_SCALE as it is and the epilogue works
+// on scaled values throughout: bias * 2^-8 once per thread, an H16 residual decoded without the unscale, the activation, then
+// h16_encode4_scaled - or one multiply by 2^8 in front of an fp32 store.  Every dropped operation is a multiplication by a power of
+// two, exact unless the scaled value is an fp32 subnormal, so the stored bits are those of the unscaled sequence (NaN, -0 and inf
+// included; tests/test_conv_epilogue_host.py replays both sequences).  Mish is not homogeneous: its values arrive unscaled.
+constexpr bool conv_epilogue_scaled(bool fast, int act) { return fast && act != ACT_MISH; }
+// the activation on a value in the domain SC names; max(o, 0.1 o) is LeakyReLU's select in two instructions (same bits: both forms
+// return o * 0.1 for o <= -0 and NaN, o above)
+template <int ACT, bool SC> __device__ __forceinline__ float conv_epilogue_act(float o) {
+    if (SC && ACT == ACT_LEAKY) return fmaxf(o, o * 0.1f);
+    return apply_act<ACT>(o);                                      // ReLU and linear are the same function of a scaled value
+}
+
+// Sweep of a FULL tile (every row below M, every filter below Cout, all of them bound for one output; flat row map, whole-tile
+// staging): no per-row predicate, no channel tail, no merged-launch test.  Addresses are one 64-bit base per tensor, uniform over the
+// workgroup, plus a 32-bit byte offset per thread that advances by a constant per row step (a tile spans at most BM x ld x 4 bytes).
+// A thread of an H16 output owns EIGHT consecutive channels of a pixel: two 16-byte LDS reads, one 16-byte store of the hi halves
+// and one of the lo halves (the ragged sweep owns four and trades halves with its neighbour lane).  fp32 outputs keep four.
+// (Bank check of the 8-channel read, ds_read_b128 lane groups of MI355X: threads sit 32 bytes apart in a row and rows BN * 4 + 16
+// bytes apart; at BN = 128 the 16 lanes of a group fall on 16 distinct 16-byte slots, at BN = 64 two slots of a group are hit twice, at
+// BN = 256 - one row per 32 lanes - every slot: two-way.  On paper; the <128,256> tile gained like the others.)
+template <int BM, int BN, int WM, int WN, int ACT, int RES, int NT, bool SC, class Store>
+__device__ __forceinline__ void conv_epilogue_full(const ConvKernelArgs &p, Store store, float *stage, int m0, int n0, int tid) {
+    constexpr int ROWS = BM / WM, LD = BN + 4;
+    const int wm = (tid >> 6) / WN;
+    const bool second = p.n_split > 0 && n0 >= p.n_split;          // uniform: the tile lies on one side of the boundary
+    const int y_ld = second ? p.ldy2 : p.ldy, ny0 = second ? n0 - p.n_split : n0;
+    char *const y_tile = reinterpret_cast<char *>((second ? p.y2 : p.y) + (size_t)m0 * y_ld);
+    const char *const r_tile = RES != RES_NONE ? reinterpret_cast<const char *>(p.res + (size_t)m0 * p.ldr) : nullptr;
+    auto sweep = [&](auto yh_c, auto rh_c) {
+        constexpr bool YH = decltype(yh_c)::value, RH = decltype(rh_c)::value;         // H16 (or fp32) output / residual
+        constexpr int CH = YH ? 8 : 4, Q = CH / 4;                  // channels per thread, in quads
+        constexpr int CT = BN / CH, RSTEP = NT / CT, NIT = BM / RSTEP;                 // threads per row, rows per sweep of the workgroup, sweeps
+        static_assert(NT % CT == 0 && BM % RSTEP == 0, "tile width must divide the workgroup");
+        const int c = tid % CT, rr = tid / CT;
+        const int n = n0 + c * CH, ny = ny0 + c * CH;
+        // byte offset of channel ch (a multiple of CH) in a pixel: H16 keeps [32 hi | 32 lo] halves per group of 32 channels
+        auto chan_off = [](bool h16, int ch) { return h16 ? (unsigned)(ch & ~31) * 4u + (unsigned)(ch & 31) * 2u : (unsigned)ch * 4u; };
+        const unsigned y_off = (unsigned)(rr * y_ld) * 4u + chan_off(YH, ny), y_step = (unsigned)(RSTEP * y_ld) * 4u;
+        float bias[CH];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const float4 b = *reinterpret_cast<const float4 *>(p.bias + n + q * 4);
+            bias[q * 4] = b.x; bias[q * 4 + 1] = b.y; bias[q * 4 + 2] = b.z; bias[q * 4 + 3] = b.w;
+        }
+        if (SC) {
+#pragma unroll
+            for (int k = 0; k < CH; ++k) bias[k] *= A_SCALE;
+        }
+        // the residual rows of all sweeps are fetched up front (in flight while the tile goes through LDS); per row and thread
+        // H16: CH hi halves then CH lo halves, fp32: CH floats - Q float4 either way
+        union ResRow { float4 f[Q]; float2 d[2 * Q]; _Float16 h[2 * CH]; float v[CH]; };
+        ResRow rraw[RES != RES_NONE ? NIT : 1];
+        if (RES != RES_NONE) {
+            const unsigned r_off = (unsigned)(rr * p.ldr) * 4u + chan_off(RH, n), r_step = (unsigned)(RSTEP * p.ldr) * 4u;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const char *g = r_tile + (r_off + (unsigned)it * r_step);
+                if (RH && CH == 8) {
+                    rraw[it].f[0] = *reinterpret_cast<const float4 *>(g);
+                    rraw[it].f[Q - 1] = *reinterpret_cast<const float4 *>(g + 64);
+                } else if (RH) {
+                    rraw[it].d[0] = *reinterpret_cast<const float2 *>(g);
+                    rraw[it].d[1] = *reinterpret_cast<const float2 *>(g + 64);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) rraw[it].f[q] = *reinterpret_cast<const float4 *>(g + q * 16);
+                }
+            }
+        }
+        store(stage + wm * ROWS * LD);
+        __syncthreads();
+        const float *st = stage + rr * LD + c * CH;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            float o[CH];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const float4 v = *reinterpret_cast<const float4 *>(st + it * RSTEP * LD + q * 4);
+                o[q * 4] = v.x + bias[q * 4]; o[q * 4 + 1] = v.y + bias[q * 4 + 1]; o[q * 4 + 2] = v.z + bias[q * 4 + 2]; o[q * 4 + 3] = v.w + bias[q * 4 + 3];
+            }
+#pragma unroll
+            for (int k = 0; k < CH; ++k) {
+                float rs = 0.f;
+                if (RES != RES_NONE) {
+                    const ResRow &t = rraw[RES != RES_NONE ? it : 0];
+                    if (RH) {
+                        rs = (float)t.h[k] + (float)t.h[CH + k] * (1.f / H16_LO_SCALE);
+                        if (!SC) rs *= 1.f / H16_A_SCALE;
+                    } else rs = SC ? t.v[k] * A_SCALE : t.v[k];
+                }
+                if (RES == RES_BEFORE_ACT) o[k] += rs;
+                o[k] = conv_epilogue_act<ACT, SC>(o[k]);
+                if (RES == RES_AFTER_ACT) o[k] += rs;
+            }
+            char *g = y_tile + (y_off + (unsigned)it * y_step);
+            if (YH) {
+                union { h16x4 h[2]; float4 f; } hi, lo;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    if (SC) h16_encode4_scaled(o + q * 4, hi.h[q], lo.h[q]);
+                    else h16_encode4(o + q * 4, hi.h[q], lo.h[q]);
+                }
+                *reinterpret_cast<float4 *>(g) = hi.f;
+                *reinterpret_cast<float4 *>(g + 64) = lo.f;
+            } else {
+                if (SC) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] *= 1.f / A_SCALE;
+                }
+                *reinterpret_cast<float4 *>(g) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+        }
+    };
+    // (an FMT_F16 output is a half-mode tensor: those kernels do not take this path)
+    const bool yh = p.fmt_y == FMT_H16, rh = RES != RES_NONE && p.fmt_r == FMT_H16;
+    if (yh) {
+        if (rh) sweep(std::true_type{}, std::true_type{});
+        else sweep(std::true_type{}, std::false_type{});
+    } else {
+        if (rh) sweep(std::false_type{}, std::true_type{});
+        else sweep(std::false_type{}, std::false_type{});
+    }
+}
+
 // ONE_PASS: the staging area holds the WHOLE tile (BM x (BN+4) floats instead of one row of waves): every wave stores its
 // accumulators at once and the workgroup sweeps all rows after a single barrier (2 barriers instead of 2 x WM, no waves
 // idling while one wave row is staged).  The caller sizes the LDS for it (conv_stage_bytes).
 // Store: callable (float *st) that writes THIS wave's accumulator tile into its band of the staging area (row r, column c of
 // the band at st[r * (BN + 4) + c]) - the only part that depends on the MFMA shape's C/D layout.
-template <int BM, int BN, int WM, int WN, int ACT, int RES, int NT, class RowMap, bool ONE_PASS, class Store>
+template <int BM, int BN, int WM, int WN, int ACT, int RES, int NT, class RowMap, bool ONE_PASS, bool FAST, class Store>
 __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Store store, float *stage, RowMap rows, int n0, int tid) {
     constexpr int ROWS = BM / WM, LD = BN + 4, C4 = BN / 4;        // staged rows, padded row length, float4 per row
+    constexpr bool SC = conv_epilogue_scaled(FAST, ACT);           // the staged values are o * 2^-8 (see conv_epilogue_scaled)
+    if constexpr (FAST) {
+        // full tiles of a flat row map whose filters all go to one output take the sweep without predicates; ragged tiles and a
+        // merged launch whose boundary falls inside the tile stay here.  Every operand of the test is uniform: one scalar branch.
+        static_assert(ONE_PASS && std::is_same<RowMap, FlatRows>::value, "the full-tile sweep reads a whole staged tile of consecutive pixels");
+        const int m0 = rows(0);
+        const bool split_inside = p.n_split > n0 && p.n_split < n0 + BN;
+        if (m0 + BM <= p.M && n0 + BN <= p.Cout && !split_inside && p.fmt_y != FMT_F16) {
+            conv_epilogue_full<BM, BN, WM, WN, ACT, RES, NT, SC>(p, store, stage, m0, n0, tid);
+            return;
+        }
+    }
     constexpr int RSTEP = NT / C4;                                   // rows covered by one sweep of the NT threads
     static_assert(NT % C4 == 0 && C4 % 2 == 0 && ROWS % RSTEP == 0, "tile width must divide the workgroup; lane pairs share a row");
     const int wave = tid >> 6, wm = wave / WN;
@@ -137,6 +275,7 @@ __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Stor
         if (n + 1 < p.Cout) bias4.y = p.bias[n + 1];
         if (n + 2 < p.Cout) bias4.z = p.bias[n + 2];
     }
+    if (SC) { bias4.x *= A_SCALE; bias4.y *= A_SCALE; bias4.z *= A_SCALE; bias4.w *= A_SCALE; }
     // The tensor formats are uniform run-time flags; the sweep is instantiated per (output H16?, residual H16?) and entered
     // through ONE uniform branch, so its loops carry no format tests (the generic form spent a third of its instructions on
     // exec-mask bookkeeping and re-tested the formats in every iteration).
@@ -188,19 +327,23 @@ __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Stor
                         union { float2 f; h16x4 h; } uh, ul;
                         uh.f = make_float2(t.x, t.y);
                         ul.f = make_float2(t.z, t.w);
-                        h16_decode4(uh.h, ul.h, rs);
+                        if (SC) h16_decode4_scaled(uh.h, ul.h, rs);
+                        else h16_decode4(uh.h, ul.h, rs);
                     } else if (RS) {
                         union { float2 f; h16x4 h; } uh;
                         uh.f = make_float2(t.x, t.y);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) rs[k] = (float)uh.h[k] * (1.f / H16_A_SCALE);
-                    } else { rs[0] = t.x; rs[1] = t.y; rs[2] = t.z; rs[3] = t.w; }
+                        for (int k = 0; k < 4; ++k) rs[k] = SC ? (float)uh.h[k] : (float)uh.h[k] * (1.f / H16_A_SCALE);
+                    } else {
+                        rs[0] = t.x; rs[1] = t.y; rs[2] = t.z; rs[3] = t.w;
+                        if (SC) { rs[0] *= A_SCALE; rs[1] *= A_SCALE; rs[2] *= A_SCALE; rs[3] *= A_SCALE; }
+                    }
                 }
                 float o[4] = {v.x + bias4.x, v.y + bias4.y, v.z + bias4.z, v.w + bias4.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     if (RES == RES_BEFORE_ACT) o[k] += rs[k];
-                    o[k] = apply_act<ACT>(o[k]);
+                    o[k] = conv_epilogue_act<ACT, SC>(o[k]);
                     if (RES == RES_AFTER_ACT) o[k] += rs[k];
                 }
                 float *yp = y_base + (size_t)m * y_ld;
@@ -209,7 +352,8 @@ __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Stor
                     // issues ONE 16-byte store (even lane: 8 hi halves, odd lane: 8 lo halves) instead of two 8-byte ones.
                     // The trade is a DPP quad permute [1,0,3,2] on the vector ALU (__shfl_xor goes through the LDS crossbar).
                     h16x4 hi, lo;
-                    h16_encode4(o, hi, lo);
+                    if (SC) h16_encode4_scaled(o, hi, lo);
+                    else h16_encode4(o, hi, lo);
                     const bool odd = c4 & 1;
                     union { h16x4 h; int i[2]; } send, recv;
                     send.h = odd ? hi : lo;
@@ -225,7 +369,7 @@ __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Stor
                     // FMT_F16: the even lane of a pair stores both lanes' channel quads, 8 consecutive fp16 = one 16-byte store
                     union { h16x4 h; int i[2]; } mine, other;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) mine.h[k] = (_Float16)(o[k] * H16_A_SCALE);
+                    for (int k = 0; k < 4; ++k) mine.h[k] = SC ? (_Float16)o[k] : (_Float16)(o[k] * H16_A_SCALE);
                     other.i[0] = __builtin_amdgcn_update_dpp(mine.i[0], mine.i[0], 0xB1, 0xF, 0xF, false);
                     other.i[1] = __builtin_amdgcn_update_dpp(mine.i[1], mine.i[1], 0xB1, 0xF, 0xF, false);
                     union { h16x4 h[2]; float4 f; } out;
@@ -233,6 +377,10 @@ __device__ __forceinline__ void conv_epilogue_core(const ConvKernelArgs &p, Stor
                     out.h[1] = other.h;
                     if (live && !(c4 & 1)) *reinterpret_cast<float4 *>(reinterpret_cast<char *>(yp) + ny * 2) = out.f;
                 } else if (live) {
+                    if (SC) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) o[k] *= 1.f / A_SCALE;
+                    }
                     if (n_vec) *reinterpret_cast<float4 *>(yp + ny) = make_float4(o[0], o[1], o[2], o[3]);
                     else { yp[ny] = o[0]; if (n + 1 < p.Cout) yp[ny + 1] = o[1]; if (n + 2 < p.Cout) yp[ny + 2] = o[2]; }
                 }
@@ -273,12 +421,14 @@ __device__ __forceinline__ void conv_epilogue_rows(const ConvKernelArgs &p, f32x
                 for (int e = 0; e < 16; ++e)
                     st[(i * 32 + rsel + (e & 3) + 8 * (e >> 2)) * LD + wn * (BN / WN) + j * 32 + col] = acc[i][j][e];
     };
-    conv_epilogue_core<BM, BN, WM, WN, ACT, RES, NT, RowMap, ONE_PASS>(p, store, stage, rows, n0, tid);
+    conv_epilogue_core<BM, BN, WM, WN, ACT, RES, NT, RowMap, ONE_PASS, false>(p, store, stage, rows, n0, tid);
 }
 
 // 16x16 accumulator fragments (v_mfma_f32_16x16x32_f16): col = lane & 15, row = 4 * (lane >> 4) + e; TM / TN count 16-wide blocks.
 // (Bank check: the four 16-lane groups of a store sit 4 rows = 4 * (BN + 4) floats apart = 16 banks mod 64: conflict free.)
-template <int BM, int BN, int WM, int WN, int ACT, int RES, int TM, int TN, int NT = 256, class RowMap = FlatRows, bool ONE_PASS = false>
+// FAST (the f16x3 kernels on this instruction): the accumulators arrive as conv_epilogue_scaled(true, ACT) says, full tiles take
+// conv_epilogue_full.
+template <int BM, int BN, int WM, int WN, int ACT, int RES, int TM, int TN, int NT = 256, class RowMap = FlatRows, bool ONE_PASS = false, bool FAST = false>
 __device__ __forceinline__ void conv_epilogue16_rows(const ConvKernelArgs &p, f32x4 (&acc)[TM][TN], float *stage, RowMap rows, int n0, int tid) {
     constexpr int LD = BN + 4;
     const int lane = tid & 63, wn = (tid >> 6) % WN;
@@ -292,11 +442,11 @@ __device__ __forceinline__ void conv_epilogue16_rows(const ConvKernelArgs &p, f3
                 for (int e = 0; e < 4; ++e)
                     st[(i * 16 + rsel + e) * LD + wn * (BN / WN) + j * 16 + col] = acc[i][j][e];
     };
-    conv_epilogue_core<BM, BN, WM, WN, ACT, RES, NT, RowMap, ONE_PASS>(p, store, stage, rows, n0, tid);
+    conv_epilogue_core<BM, BN, WM, WN, ACT, RES, NT, RowMap, ONE_PASS, FAST>(p, store, stage, rows, n0, tid);
 }
-template <int BM, int BN, int WM, int WN, int ACT, int RES, int TM, int TN, int NT = 256, bool ONE_PASS = false>
+template <int BM, int BN, int WM, int WN, int ACT, int RES, int TM, int TN, int NT = 256, bool ONE_PASS = false, bool FAST = false>
 __device__ __forceinline__ void conv_epilogue16(const ConvKernelArgs &p, f32x4 (&acc)[TM][TN], float *stage, int m0, int n0, int tid) {
-    conv_epilogue16_rows<BM, BN, WM, WN, ACT, RES, TM, TN, NT, FlatRows, ONE_PASS>(p, acc, stage, FlatRows{m0}, n0, tid);
+    conv_epilogue16_rows<BM, BN, WM, WN, ACT, RES, TM, TN, NT, FlatRows, ONE_PASS, FAST>(p, acc, stage, FlatRows{m0}, n0, tid);
 }
 
 template <int BM, int BN, int WM, int WN, int ACT, int RES, int TM, int TN, int NT = 256, bool ONE_PASS = false>

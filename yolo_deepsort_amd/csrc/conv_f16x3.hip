@@ -531,9 +531,12 @@ void conv_igemm_f16x3_dma(ConvKernelArgs p, const char *zero_page) {
 #pragma unroll
             for (int j = 0; j < TN16; ++j)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc1[i][j][e] = (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
+                for (int e = 0; e < 4; ++e) {
+                    const float os = acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE);
+                    acc1[i][j][e] = conv_epilogue_scaled(true, ACT) ? os : os * (1.f / A_SCALE);   // the epilogue stays in the scaled domain
+                }
         // whole-tile staging: the launcher sizes the LDS as max(ring, BM x (BN+4) floats)
-        conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM16, TN16, NT, true>(p, acc1, reinterpret_cast<float *>(ring), m0, n0, tid);
+        conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM16, TN16, NT, true, true>(p, acc1, reinterpret_cast<float *>(ring), m0, n0, tid);
     } else {
         f32x16 acc1[TM][TN], acc2[TM][TN];
 #pragma unroll

@@ -216,8 +216,11 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 1 : 2) void conv3x3_f1
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc1[i][j][e] = (acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE)) * (1.f / A_SCALE);
-    conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true>(p, acc1, reinterpret_cast<float *>(smem), m0, n0, tid);   // whole-tile staging
+            for (int e = 0; e < 4; ++e) {
+                const float os = acc1[i][j][e] + acc2[i][j][e] * (1.f / LO_SCALE);
+                acc1[i][j][e] = conv_epilogue_scaled(true, ACT) ? os : os * (1.f / A_SCALE);       // the epilogue stays in the scaled domain
+            }
+    conv_epilogue16<BM, BN, WM, WN, ACT, RES, TM, TN, NT, true, true>(p, acc1, reinterpret_cast<float *>(smem), m0, n0, tid);   // whole-tile staging
     clk.end();
 }
 

@@ -58,6 +58,12 @@ __device__ __forceinline__ void h16_decode4(const h16x4 &hi, const h16x4 &lo, fl
     for (int c = 0; c < 4; ++c) v[c] = ((float)hi[c] + (float)lo[c] * (1.f / H16_LO_SCALE)) * (1.f / H16_A_SCALE);
 }
 
+// ... into the scaled domain (x * 2^-8): consumers that go on there skip the unscale
+__device__ __forceinline__ void h16_decode4_scaled(const h16x4 &hi, const h16x4 &lo, float xs[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) xs[c] = (float)hi[c] + (float)lo[c] * (1.f / H16_LO_SCALE);
+}
+
 // pixel: pointer to the pixel's first float slot; c: channel index, multiple of 4
 __device__ __forceinline__ void h16_load4(const float *pixel, int c, float v[4]) {
     const char *g = reinterpret_cast<const char *>(pixel + (c & ~31)) + (c & 31) * 2;
