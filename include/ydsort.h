@@ -766,6 +766,89 @@ int yds_heatmap_set_timing(yds_heatmap *, int on);
 int yds_heatmap_last_us(yds_heatmap *, int what, float *us);
 int yds_pipeline_set_heatmap(yds_pipe *, yds_heatmap *);
 
+/* ---- ground plane: floor-plan positions, speeds and a site-wide map ----------------------------------------------------------------
+ * No reference counterpart; yolo_deepsort_amd/ground.py (GroundMap, project, render_view) restates the rules below in Python ints and
+ * numpy float64 and every comparison with it is exact equality.  One handle is ONE plan shared by all its streams.
+ * 1. Plan, per handle: scale = quanta per plan unit; origin (ox_q, oy_q) and cell edge cell_q in quanta (integers); a grid of gw x gh
+ *    cells, gw * gh <= YDS_HEATMAP_MAX_CELLS, (max(gw, gh) + 2) * cell_q <= YDS_GROUND_MAX_EXTENT_Q (the view render's 32-bit
+ *    arithmetic), |ox_q|, |oy_q| <= 2^30, speed_window K in [1, YDS_GROUND_MAX_WINDOW].  Per stream: H, a 3x3 double matrix from image
+ *    pixels to plan units (row-major), and class_id >= -1 (-1 = any class).  A stream without a spec is skipped: its frames report
+ *    no rows and touch nothing.
+ * 2. The one floating-point step, for an image point (u, v), in double and in this order:
+ *      X = (H00*u + H01*v) + H02, Y = (H10*u + H11*v) + H12, W = (H20*u + H21*v) + H22; px = X / W, py = Y / W;
+ *      qx = llrint(px * scale), qy = llrint(py * scale), rounding half to even.
+ *    The point is OFF PLANE when W > 0 does not hold, when any of these values is not finite, or when |px * scale| or |py * scale|
+ *    exceeds 2^29.  Every operation is the correctly rounded IEEE one (no contraction, no fast-math); no point is derived from its
+ *    neighbour.  Everything after this step is integer arithmetic.
+ * 3. One processed frame (rows x1, y1, x2, y2, id, class; time t) of a stream.  Rows whose class does not match are ignored entirely.
+ *    A matching row gives the foot point u = 0.5 * (x1 + x2), v = y2 and by rule 2 (qx, qy) or off plane.  Its cell is
+ *    cy * gw + cx with cx = floor_div(qx - ox_q, cell_q), cy likewise, when both lie inside the grid; -1 outside; -2 off plane.
+ *    Table, per stream in insertion order: id, age, cell, t_last, travelled (int64 quanta) and a ring of the last K on-plane
+ *    sightings (qx, qy, t).  An unknown id is registered at the end (row order) with age 0, cell -1, an empty ring, travelled 0.
+ *    For a seen entry, with "fresh" = its age before this frame is 0:
+ *      a. fresh and previous cell >= 0: dwell_us[previous cell] += max(0, llrint((t - t_last) * 1e6)).
+ *      b. on plane, fresh and the ring not empty (a sighting after a sighting): d = (qx, qy) - the ring's newest point;
+ *         travelled += isqrt(dx^2 + dy^2) (the exact integer square root); if cell >= 0: flow_x[cell] += dx, flow_y[cell] += dy.
+ *         Otherwise on plane (after a gap, after an off-plane point, a new id): the ring is emptied first, nothing is travelled.
+ *      c. on plane: (qx, qy, t) is pushed (the oldest entry leaves a full ring); with (x0, y0, t0) the ring's OLDEST entry now,
+ *         dt_us = llrint((t - t0) * 1e6), d = (qx - x0, qy - y0): if dt_us > 0, vx = floor_div(dx * 1000000, dt_us), vy likewise,
+ *         speed = isqrt(dx^2 + dy^2) * 1000000 // dt_us (quanta per second), each saturated to +-(2^31 - 1); else speed = -1,
+ *         vx = vy = 0 (a first sighting: the oldest entry is the point itself).  If cell >= 0: visits[cell] += 1 when cell differs
+ *         from the previous cell, presence[cell] += 1.
+ *      d. off plane: the ring is emptied.
+ *      e. the entry becomes (age 0, cell, t_last = t); the row's record is [id, class, qx, qy, vx, vy, speed, cell], off plane
+ *         [id, class, 0, 0, 0, 0, 0, -2].  Records are in the order of the frame's counted rows.
+ *    Entries not seen age by one and leave with age > max_age, the others keeping their order.  A frame the tracker was not called
+ *    for is not seen; a frame with zero rows ages every entry.
+ *    Site grid: ONE [5][gh][gw] int64 grid (the heat map's layers: presence, visits, dwell_us, flow_x, flow_y; flow in quanta) for ALL
+ *    streams: streams add to the same cells with 64-bit integer atomics, so the sums do not depend on the order.
+ * 4. Renders, synchronous on the handle's own stream; layer, vmax, alpha, lut and level = (min(max(v, 0), vmax) * 65535) // vmax as
+ *    for yds_heatmap_render.
+ *    render_plan: the canvas of gh * cell_px x gw * cell_px pixels (cell_px in {4, ..., 128}) takes exactly the heat map render of
+ *      the layer at cell = cell_px (the same two kernels).
+ *    render_view: n frames of h x w * 3 bytes in HBM, frame i in slot slot[i] of n_src with the H of stream stream_of[i].  Pixel
+ *      (x, y) takes its plan point at u = x + 0.5, v = y + 0.5 by rule 2; off plane it keeps the picture.  Else
+ *      a = ((qx - ox_q) * 256) // cell_q - 128, i0 = a >> 8, fx = a & 255; b, j0, fy likewise from qy.  i0 < -1, i0 >= gw, j0 < -1 or
+ *      j0 >= gh keeps the picture; indices are clamped to the grid; with L00 = L[j0][i0], L01 = L[j0][i0 + 1], L10 = L[j0 + 1][i0] ...
+ *      num = (256 - fy) * ((256 - fx) * L00 + fx * L01) + fy * ((256 - fx) * L10 + fx * L11) (fits a uint32),
+ *      k = (num >> 16) // 257; k == 0 keeps the picture, else per byte out = (alpha * lut[k][b] + (256 - alpha) * src[b] + 128) >> 8.
+ * yds_ground_create      <- the plan; streams without a spec.   yds_ground_set_stream <- H9 and class of one stream, an empty table.
+ * yds_ground_reset       <- stream >= 0: an empty table for it, the site grid (every stream's) stands; -1: all tables and a zero grid.
+ * yds_ground_update      <- n_frames frames in ONE launch and one synchronisation, the frame table as for yds_heatmap_update;
+ *                           out8 [m][8] records, first_out [n_frames + 1] (may be NULL) their split by frame, cap in records.
+ * yds_ground_get_layers  <- out5 [5][gh][gw]; cap in values.   yds_ground_get_max <- the maximum of one layer, reduced on the device.
+ * yds_ground_get_tracks  <- the table of one stream (each array may be NULL): ids, ages, cells, lens (ring lengths), travelled,
+ *                           t_last, ring_xy [m][K][2] and ring_t [m][K] oldest first, unused places zero.
+ * yds_ground_set_timing / _last_us: HIP events around the update launch (what = 0) and around a render's launches (what = 1).
+ * yds_pipeline_set_ground: with a handle of at least as many streams as the pipeline every step adds ONE launch behind the heat map
+ *   launch (if there is one), ahead of the identity collect launch and of the step's one synchronisation, in every entry (plain,
+ *   window, mixed sizes, per-stream windows); NULL switches it off.  Refused while a look-ahead pass is in flight.
+ * yds_pipeline_last_ground: the records of the last step and, per record, the frame of the step; already on the host.
+ * Limits: the site grid counts per camera and track - two cameras seeing one person credit twice (the host join
+ *   ground.site_people is the remedy); the foot point is the box's bottom centre, so an occluded foot lands too near; no lens
+ *   distortion model; no decay. */
+typedef struct yds_ground yds_ground;
+#define YDS_GROUND_MAX_WINDOW 16
+#define YDS_GROUND_MAX_EXTENT_Q (1 << 22)
+yds_ground *yds_ground_create(int n_streams, int max_age, int speed_window, int64_t ox_q, int64_t oy_q, int64_t cell_q, int gw, int gh,
+                              double scale);
+void yds_ground_destroy(yds_ground *);
+int yds_ground_set_stream(yds_ground *, int stream, const double *H9, int class_id);
+int yds_ground_reset(yds_ground *, int stream);
+int yds_ground_update(yds_ground *, const int32_t *rows6_host, const int32_t *first, const int32_t *stream_of, const double *frame_time,
+                      int n_frames, int32_t *out8_host, int32_t *first_out, int cap, int *n_out);
+int yds_ground_get_layers(yds_ground *, int64_t *out5, size_t cap);
+int yds_ground_get_max(yds_ground *, int layer, int64_t *out);
+int yds_ground_get_tracks(yds_ground *, int stream, int32_t *ids, int32_t *ages, int32_t *cells, int32_t *lens, int64_t *travelled,
+                          double *t_last, int32_t *ring_xy, double *ring_t, int cap, int *n);
+int yds_ground_render_plan(yds_ground *, uint8_t *canvas_dev, int cell_px, int layer, int64_t vmax, int alpha, const uint8_t *lut_host);
+int yds_ground_render_view(yds_ground *, uint8_t *frames_dev, int n_src, const int32_t *slot_host, const int32_t *stream_of_host, int n,
+                           int h, int w, int layer, int64_t vmax, int alpha, const uint8_t *lut_host);
+int yds_ground_set_timing(yds_ground *, int on);
+int yds_ground_last_us(yds_ground *, int what, float *us);
+int yds_pipeline_set_ground(yds_pipe *, yds_ground *);
+int yds_pipeline_last_ground(yds_pipe *, int32_t *rows8_host, int32_t *frame_host, int cap, int *n_out);
+
 /* ---- cross-camera identities: one global id per person, kept on the device ---------------------------------------------------------
  * No reference counterpart (the reference tracks one camera); tests/identity_ref.py restates the rules below in numpy / scipy.
  * An identity map is bound to an ordered list of S trackers (stream = index), all with the cosine metric and a finite nn_budget.  It

@@ -216,6 +216,20 @@ SIGNATURES = {
     "yds_heatmap_set_timing": (_I, [_P, _I]),
     "yds_heatmap_last_us": (_I, [_P, _I, _P]),
     "yds_pipeline_set_heatmap": (_I, [_P, _P]),
+    "yds_ground_create": (_P, [_I, _I, _I, _I64, _I64, _I64, _I, _I, _D]),
+    "yds_ground_destroy": (None, [_P]),
+    "yds_ground_set_stream": (_I, [_P, _I, _P, _I]),
+    "yds_ground_reset": (_I, [_P, _I]),
+    "yds_ground_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "yds_ground_get_layers": (_I, [_P, _P, _SZ]),
+    "yds_ground_get_max": (_I, [_P, _I, _P]),
+    "yds_ground_get_tracks": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "yds_ground_render_plan": (_I, [_P, _P, _I, _I, _I64, _I, _P]),
+    "yds_ground_render_view": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I64, _I, _P]),
+    "yds_ground_set_timing": (_I, [_P, _I]),
+    "yds_ground_last_us": (_I, [_P, _I, _P]),
+    "yds_pipeline_set_ground": (_I, [_P, _P]),
+    "yds_pipeline_last_ground": (_I, [_P, _P, _P, _I, _P]),
     "yds_overlay_tracks_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P, _P]),
     "yds_overlay_tracks_bgr_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
     "yds_anonymize_frames": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32]),

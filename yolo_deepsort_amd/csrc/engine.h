@@ -282,7 +282,7 @@ struct ActFrame {
     double t;
     const double *row_time;
 };
-// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps; their shared frame is track_stage.h):
+// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps, ground plane; their shared frame is track_stage.h):
 struct TrackStageIface {
     virtual ~TrackStageIface() {}
     virtual int streams() const = 0;
@@ -312,6 +312,16 @@ struct ZonesIface : TrackStageIface {
 struct HeatmapIface : TrackStageIface {
     virtual bool has_spec(int stream) const = 0;  // yds_heatmap_set_stream has been called for it
     std::vector<int32_t> counted;                 // [n] rows counted per frame
+};
+
+// --------------------------------------------------------------------------------------------- ground plane
+// Implemented in ground.hip: ONE site grid of int64 layers on a floor plan shared by all streams, per stream a homography and a table
+// of tracks with a ring of their last plan positions, advanced over the frames of a call by ONE launch over the same frame
+// descriptors as the zone stage.  It reports one int32[8] record per counted row: id, class, qx, qy, vx, vy, speed, cell.
+struct GroundIface : TrackStageIface {
+    virtual bool has_spec(int stream) const = 0;  // yds_ground_set_stream has been called for it (a stream without one is skipped)
+    std::vector<int32_t> rows8;                   // [m][8]
+    std::vector<int32_t> frame_of;                // [m] the tag of the frame every record belongs to
 };
 
 // --------------------------------------------------------------------------------------------- tracker
@@ -376,6 +386,9 @@ struct TrackerGroupIface {
     // the heat map stage of the NEXT step_batch (nullptr: none): one more launch behind the zone launch (if there is one), ahead of the
     // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
     virtual void set_heatmap(HeatmapIface *heat, const double *frame_times) = 0;
+    // the ground plane stage of the NEXT step_batch (nullptr: none): one more launch behind the heat map launch (if there is one),
+    // ahead of the identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
+    virtual void set_ground(GroundIface *ground, const double *frame_times) = 0;
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
     // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)
@@ -393,3 +406,4 @@ struct yds_act { yds::ActionsIface *a; };
 struct yds_ident { yds::IdentityIface *i; };
 struct yds_zones { yds::ZonesIface *z; };
 struct yds_heatmap { yds::HeatmapIface *h; };
+struct yds_ground { yds::GroundIface *g; };

@@ -23,6 +23,7 @@
 // centre, so they are reloaded there and nowhere else.  PX = 16 (three 16-byte accesses per thread) when every address it forms is
 // proved 16-aligned - the frames' base is and W % 16 == 0 (rows and frames are then multiples of 48 bytes); PX = 4 (three dwords)
 // with a 4-aligned base and W % 4 == 0; a byte path otherwise (a 33 x 50 frame, an odd base).
+#include "heat_render.h"
 #include "track_stage.h"
 #include "ydsort.h"
 
@@ -146,14 +147,8 @@ __global__ __launch_bounds__(256) void heat_update_kernel(const HeatWork *works,
 }
 
 // ------------------------------------------------------------------------------------------------------------------ render
-// one stream named in a render call (or asked for its maximum: level == nullptr)
-struct HeatLevelJob {
-    const long long *layer;                       // [gh * gw]
-    uint16_t *level;                              // [gh * gw]
-    long long vmax;                               // 0: the layer's maximum, 1 when nothing is positive
-    int n, gw, gh, lc;                            // cells; lc = log2(cell)
-};
-
+// (HeatLevelJob - one stream named in a render call, or asked for its maximum - the byte blend and a thread's whole-pixel accesses:
+// heat_render.h, shared with the ground plane's renders)
 // res[job] = the layer's maximum; *bad = 1 when the vmax to use exceeds the limit (the levels are then not written and the render
 // kernel touches nothing)
 __global__ __launch_bounds__(256) void heat_levels_kernel(const HeatLevelJob *jobs, long long *res, int *bad) {
@@ -182,26 +177,6 @@ __global__ __launch_bounds__(256) void heat_levels_kernel(const HeatLevelJob *jo
     }
 }
 
-struct HeatRenderArgs {
-    uint8_t *frames;
-    size_t frame_bytes;
-    const int2 *fjobs;                            // per frame of the call: (slot, job)
-    const HeatLevelJob *jobs;
-    const uint32_t *lut;                          // [256] byte 0 | byte 1 << 8 | byte 2 << 16
-    const int *bad;
-    int h, w;
-    uint32_t alpha;
-};
-
-// two bytes per multiply: the even bytes of s and l in the low halves of two 16-bit lanes (a * l + na * s + 128 <= 65408: no carry
-// between the lanes), the odd bytes likewise after a shift
-__device__ __forceinline__ uint32_t heat_blend(uint32_t s, uint32_t l, uint32_t a, uint32_t na) {
-    const uint32_t M = 0x00ff00ffu, C = 0x00800080u;
-    const uint32_t e = (s & M) * na + (l & M) * a + C;
-    const uint32_t o = ((s >> 8) & M) * na + ((l >> 8) & M) * a + C;
-    return ((e >> 8) & M) | (o & ~M);
-}
-
 // PX pixels of one row per thread: 16 (uint4 accesses), 4 (dwords) or 1 (bytes)
 template <int PX> __global__ __launch_bounds__(256) void heat_render_kernel(HeatRenderArgs a) {
     __shared__ uint32_t s_lut[256];
@@ -214,19 +189,8 @@ template <int PX> __global__ __launch_bounds__(256) void heat_render_kernel(Heat
     if (idx >= per_row * (unsigned)a.h) return;
     const int y = (int)(idx / per_row), x0 = (int)(idx - (unsigned)y * per_row) * PX;
     uint8_t *p = a.frames + (size_t)fj.x * a.frame_bytes + ((size_t)y * a.w + x0) * 3;
-    constexpr int NW = PX >= 4 ? PX * 3 / 4 : 1;
-    uint32_t word[NW];
-    if constexpr (PX == 16) {
-        const uint4 *q = reinterpret_cast<const uint4 *>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { const uint4 v = q[i]; word[4 * i] = v.x; word[4 * i + 1] = v.y; word[4 * i + 2] = v.z; word[4 * i + 3] = v.w; }
-    } else if constexpr (PX == 4) {
-        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) word[i] = q[i];
-    } else {
-        word[0] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16;
-    }
+    uint32_t word[HeatWords<PX>::N];
+    heat_load_px<PX>(p, word);
     // the field: k = num / (4 c^2 * 257), num = (2c - fx) * Va + fx * Vb, Va / Vb = the two level columns at this row's fy
     const int lc = J.lc, c = 1 << lc, c2 = 2 * c;
     const int V = 2 * y + 1 - c, j0 = V >> (lc + 1);
@@ -248,34 +212,21 @@ template <int PX> __global__ __launch_bounds__(256) void heat_render_kernel(Heat
         any |= k;
     }
     if (!any) return;                                                             // empty areas keep the picture, and cost no store
-    const uint32_t al = a.alpha, na = 256u - al;
-    if constexpr (PX >= 4) {
-#pragma unroll
-        for (int g = 0; g < PX / 4; ++g) {                                        // pixels c d e f = bytes c0 c1 c2 d0 | d1 d2 e0 e1 | e2 f0 f1 f2
-            const uint32_t l0 = col[4 * g], l1 = col[4 * g + 1], l2 = col[4 * g + 2], l3 = col[4 * g + 3];
-            const uint32_t m0 = (uint32_t)((int32_t)l0 >> 31), m1 = (uint32_t)((int32_t)l1 >> 31), m2 = (uint32_t)((int32_t)l2 >> 31),
-                           m3 = (uint32_t)((int32_t)l3 >> 31);
-            const uint32_t lw[3] = {(l0 & 0xffffffu) | l1 << 24, ((l1 >> 8) & 0xffffu) | l2 << 16, ((l2 >> 16) & 0xffu) | l3 << 8};
-            const uint32_t mw[3] = {(m0 & 0xffffffu) | (m1 & 0xff000000u), (m1 & 0xffffu) | (m2 & 0xffff0000u), (m2 & 0xffu) | (m3 & 0xffffff00u)};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const uint32_t s = word[3 * g + i];
-                word[3 * g + i] = (heat_blend(s, lw[i], al, na) & mw[i]) | (s & ~mw[i]);
-            }
-        }
-        if constexpr (PX == 16) {
-            uint4 *q = reinterpret_cast<uint4 *>(p);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) q[i] = make_uint4(word[4 * i], word[4 * i + 1], word[4 * i + 2], word[4 * i + 3]);
-        } else {
-            uint32_t *q = reinterpret_cast<uint32_t *>(p);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) q[i] = word[i];
-        }
-    } else {
-        const uint32_t v = heat_blend(word[0], col[0], al, na);
-        p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
-    }
+    heat_blend_store_px<PX>(p, word, col, a.alpha, 256u - a.alpha);
+}
+
+void heat_launch_levels(const HeatLevelJob *jobs_dev, int n_jobs, long long *res, int *bad, hipStream_t s) {
+    hipLaunchKernelGGL(heat_levels_kernel, dim3(n_jobs), dim3(256), 0, s, jobs_dev, res, bad);
+}
+
+void heat_launch_render(const HeatRenderArgs &a, int n, hipStream_t s) {
+    const int px = heat_px_per_thread(a.frames, a.w);
+    const size_t threads = (size_t)a.h * (a.w / px);
+    if ((threads + 255) / 256 > 0x7fffffffull) fail("heatmap: frames of %d x %d are too large for one launch", a.h, a.w);
+    const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)n);
+    if (px == 16) hipLaunchKernelGGL(heat_render_kernel<16>, grid, dim3(256), 0, s, a);
+    else if (px == 4) hipLaunchKernelGGL(heat_render_kernel<4>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(heat_render_kernel<1>, grid, dim3(256), 0, s, a);
 }
 
 class Heatmap : public TrackStage<HeatmapIface> {
@@ -393,7 +344,7 @@ public:
         open_render(1, 0);
         jobs_host()[0] = HeatLevelJob{g.layers.p + (size_t)layer * g.cells(), nullptr, 0, (int)g.cells(), g.gw, g.gh, g.lc};
         YDS_HIP(hipMemcpyAsync(r_in_dev.p, r_in_host.p, sizeof(HeatLevelJob), hipMemcpyHostToDevice, own_stream));
-        hipLaunchKernelGGL(heat_levels_kernel, dim3(1), dim3(256), 0, own_stream, reinterpret_cast<const HeatLevelJob *>(r_in_dev.p), r_res.p, bad.p);
+        heat_launch_levels(reinterpret_cast<const HeatLevelJob *>(r_in_dev.p), 1, r_res.p, bad.p, own_stream);
         YDS_HIP(hipGetLastError());
         YDS_HIP(hipStreamSynchronize(own_stream));
         return r_res.p[0];
@@ -438,7 +389,7 @@ public:
             jobs[k] = HeatLevelJob{g.layers.p + (size_t)layer * g.cells(), g.level.p, vmax, (int)g.cells(), g.gw, g.gh, g.lc};
         }
         for (int i = 0; i < n; ++i) fj[i] = make_int2(slot[i], job_of[stream_of[i]]);
-        for (int k = 0; k < 256; ++k) lut32[k] = (uint32_t)lut[3 * k] | (uint32_t)lut[3 * k + 1] << 8 | (uint32_t)lut[3 * k + 2] << 16;
+        heat_pack_lut(lut32, lut);
         const hipStream_t s = own_stream;
         const size_t in_bytes = r_jobs_b + r_fj_b + 256 * sizeof(uint32_t);
         YDS_HIP(hipMemcpyAsync(r_in_dev.p, r_in_host.p, in_bytes, hipMemcpyHostToDevice, s));
@@ -446,16 +397,9 @@ public:
         HeatRenderArgs a{frames, (size_t)h * w * 3, reinterpret_cast<const int2 *>(r_in_dev.p + r_jobs_b),
                          reinterpret_cast<const HeatLevelJob *>(r_in_dev.p), reinterpret_cast<const uint32_t *>(r_in_dev.p + r_jobs_b + r_fj_b),
                          bad.p, h, w, (uint32_t)alpha};
-        const uintptr_t base = reinterpret_cast<uintptr_t>(frames);
-        const int px = base % 16 == 0 && w % 16 == 0 ? 16 : base % 4 == 0 && w % 4 == 0 ? 4 : 1;
-        const size_t threads = (size_t)h * (w / px);
-        if ((threads + 255) / 256 > 0x7fffffffull) fail("heatmap: frames of %d x %d are too large for one launch", h, w);
-        const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)n);
         render_timer.begin(s);
-        hipLaunchKernelGGL(heat_levels_kernel, dim3(n_jobs), dim3(256), 0, s, a.jobs, r_res.p, bad.p);
-        if (px == 16) hipLaunchKernelGGL(heat_render_kernel<16>, grid, dim3(256), 0, s, a);
-        else if (px == 4) hipLaunchKernelGGL(heat_render_kernel<4>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(heat_render_kernel<1>, grid, dim3(256), 0, s, a);
+        heat_launch_levels(a.jobs, n_jobs, r_res.p, bad.p, s);
+        heat_launch_render(a, n, s);
         YDS_HIP(hipGetLastError());
         render_timer.end(s);
         YDS_HIP(hipStreamSynchronize(s));

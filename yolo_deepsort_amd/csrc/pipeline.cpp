@@ -569,13 +569,13 @@ public:
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
         if (!multi) stream_of.assign(batch, 0);
-        // the action, zone and heat map stages (set_actions, set_zones, set_heatmap): frame b carries the caller's time for it, else its stream's frame
+        // the action, zone, heat map and ground plane stages (set_actions, set_zones, set_heatmap, set_ground): frame b carries the caller's time for it, else its stream's frame
         // count / 25
         std::vector<double> times;
         if ((int)frames_seen.size() < (int)trks.size()) frames_seen.resize(trks.size(), 0);
         const std::vector<double> given = std::move(next_times);      // (they name this step's frames, whatever becomes of it)
         next_times.clear();
-        if (actions || zones || heat) {
+        if (actions || zones || heat || ground) {
             if (!given.empty() && (int)given.size() != batch)
                 fail("pipeline: %zu frame times for a step of %d frames (yds_pipeline_set_frame_times)", given.size(), batch);
             times.resize(batch);
@@ -584,16 +584,20 @@ public:
             if (actions) group->set_actions(actions, times.data());
             if (zones) group->set_zones(zones, times.data());
             if (heat) group->set_heatmap(heat, times.data());
+            if (ground) group->set_ground(ground, times.data());
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
         last_actions.clear();
         last_zone_ev6.clear();
         last_zone_evt2.clear();
+        last_ground_rows8.clear();
+        last_ground_frame.clear();
         if (identities) group->set_identities(identities);
         group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
                           cur.payload.data(), skip.data(), out6, cap, counts);
         if (actions) last_actions = actions->rows4;
         if (zones) { last_zone_ev6 = zones->ev6; last_zone_evt2 = zones->evt2; }
+        if (ground) { last_ground_rows8 = ground->rows8; last_ground_frame = ground->frame_of; }
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
@@ -635,6 +639,17 @@ public:
         heat = h;
     }
     HeatmapIface *heat = nullptr;
+    // ---- the ground plane stage (yds_pipeline_set_ground): every stream's rows onto one floor plan; a stream without a spec is skipped ----
+    void set_ground(GroundIface *g) {
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_ground while a look-ahead pass is in flight (consume it with a step first)");
+        if (g && g->streams() < (int)trks.size()) fail("pipeline: a ground handle of %d streams for a pipeline of %zu", g->streams(), trks.size());
+        ground = g;
+        last_ground_rows8.clear();
+        last_ground_frame.clear();
+    }
+    GroundIface *ground = nullptr;
+    std::vector<int32_t> last_ground_rows8;       // ground records of the last step [m][8]: id, class, qx, qy, vx, vy, speed, cell
+    std::vector<int32_t> last_ground_frame;       //                                 [m]: frame of the step
     ZonesIface *zones = nullptr;
     std::vector<int32_t> last_zone_ev6;           // zone events of the last step [m][6]: frame of the step, id, class, kind, zone or line, 0
     std::vector<double> last_zone_evt2;           //                              [m][2]: t, dwell
@@ -854,6 +869,23 @@ int yds_pipeline_set_zones(yds_pipe *p, yds_zones *z) {
 int yds_pipeline_set_heatmap(yds_pipe *p, yds_heatmap *h) {
     YDS_API_BEGIN
     p->p->set_heatmap(h ? h->h : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_set_ground(yds_pipe *p, yds_ground *g) {
+    YDS_API_BEGIN
+    p->p->set_ground(g ? g->g : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_last_ground(yds_pipe *p, int32_t *rows8_host, int32_t *frame_host, int cap, int *n_out) {
+    YDS_API_BEGIN
+    const std::vector<int32_t> &r = p->p->last_ground_rows8;
+    const int m = (int)(r.size() / 8);
+    if (n_out) *n_out = m;
+    if (m > cap) yds::fail("pipeline: %d ground rows exceed the caller's capacity %d", m, cap);
+    if (m) {
+        memcpy(rows8_host, r.data(), r.size() * sizeof(int32_t));
+        memcpy(frame_host, p->p->last_ground_frame.data(), (size_t)m * sizeof(int32_t));
+    }
     YDS_API_END
 }
 int yds_pipeline_last_zone_events(yds_pipe *p, int32_t *ev6_host, double *evt2_host, int cap, int *n_out) {

@@ -1,4 +1,5 @@
-// The frame the per-stream table stages share (actions.hip: orbit caches, zones.hip: zone and line state, heatmap.hip: last cells).  Such a stage keeps one
+// The frame the per-stream table stages share (actions.hip: orbit caches, zones.hip: zone and line state, heatmap.hip: last cells,
+// ground.hip: plan positions).  Such a stage keeps one
 // table of tracks per video stream in HBM, keyed by track id, every field twice (the second copy takes the survivors of a removal).
 // One launch per call advances all tables: a 256-thread workgroup per stream that has frames in the call walks that stream's frames
 // in time order, and what it reports goes straight into a pinned block that the host reads after the step's one synchronisation.

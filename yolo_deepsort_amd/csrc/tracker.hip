@@ -513,6 +513,7 @@ public:
     void set_actions(ActionsIface *a, const double *frame_times) override { stages[0] = a; stage_times[0] = frame_times; }
     void set_zones(ZonesIface *z, const double *frame_times) override { stages[1] = z; stage_times[1] = frame_times; }
     void set_heatmap(HeatmapIface *h, const double *frame_times) override { stages[2] = h; stage_times[2] = frame_times; }
+    void set_ground(GroundIface *g, const double *frame_times) override { stages[3] = g; stage_times[3] = frame_times; }
     void set_identities(IdentityIface *i) override { ident = i; }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
@@ -525,12 +526,12 @@ public:
         struct ClearStages {
             TrackerGroup &g;
             ~ClearStages() {
-                for (int k = 0; k < 3; ++k) { g.stages[k] = nullptr; g.stage_times[k] = nullptr; }
+                for (int k = 0; k < 4; ++k) { g.stages[k] = nullptr; g.stage_times[k] = nullptr; }
                 g.act_tag.clear(); g.act_time.clear();
             }
         } clear_stages{*this};
-        const bool staged = stages[0] || stages[1] || stages[2];
-        const double *times_in = stages[0] ? stage_times[0] : stages[1] ? stage_times[1] : stage_times[2];   // (the pipeline hands every stage the same times)
+        const bool staged = stages[0] || stages[1] || stages[2] || stages[3];
+        const double *times_in = stages[0] ? stage_times[0] : stages[1] ? stage_times[1] : stages[2] ? stage_times[2] : stage_times[3];   // (the pipeline hands every stage the same times)
         struct ClearIdentities { TrackerGroup &g; ~ClearIdentities() { g.ident = nullptr; } } clear_identities{*this};
         if (ident && !ident->bound_to(trk, S)) fail("tracker group: the identity map was not made over this step's trackers in this order");
         for (int b = 0; b < n; ++b) {
@@ -693,10 +694,10 @@ public:
             if (maxD) hipLaunchKernelGGL(trk_back_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
         }
         YDS_HIP(hipGetLastError());
-        // ---- the table stages (set_actions, set_zones, then set_heatmap): one launch each over the step's frames, reading each frame's row count and
+        // ---- the table stages (set_actions, set_zones, set_heatmap, then set_ground): one launch each over the step's frames, reading each frame's row count and
         //      rows where the association kernels stored them (the pinned result blocks), their own reports behind the same
         //      synchronisation
-        const bool staged = (stages[0] || stages[1] || stages[2]) && (int)act_tag.size() == n;
+        const bool staged = (stages[0] || stages[1] || stages[2] || stages[3]) && (int)act_tag.size() == n;
         if (staged) {
             std::vector<ActFrame> af(n);
             for (int i = 0; i < n; ++i) {
@@ -724,8 +725,8 @@ public:
     }
 
     hipStream_t stream = nullptr;
-    TrackStageIface *stages[3] = {nullptr, nullptr, nullptr};   // the action, zone and heat map stage of the step being run, in launch order (set_actions, set_zones, set_heatmap; step_batch clears them)
-    const double *stage_times[3] = {nullptr, nullptr, nullptr};
+    TrackStageIface *stages[4] = {nullptr, nullptr, nullptr, nullptr};   // the action, zone, heat map and ground plane stage of the step being run, in launch order (set_actions, set_zones, set_heatmap, set_ground; step_batch clears them)
+    const double *stage_times[4] = {nullptr, nullptr, nullptr, nullptr};
     IdentityIface *ident = nullptr;               // the identity stage of the step being run (set_identities; step_batch clears it)
     std::vector<int> act_tag;                     // per frame that runs: its index in the step, its time
     std::vector<double> act_time;

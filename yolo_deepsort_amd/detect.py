@@ -554,7 +554,7 @@ class VideoDetector:
                 cv2.destroyAllWindows()
 
     def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False,
-                       identity_memory=None, zones=None, zone_max_age=30, heatmap=None, heatmap_max_age=30):
+                       identity_memory=None, zones=None, zone_max_age=30, heatmap=None, heatmap_max_age=30, ground=None, ground_max_age=30):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -599,6 +599,12 @@ class VideoDetector:
         frames, frame times are those of the action stage.  Read stream_heatmaps() between the yields; the yielded items and images
         do not change: blending a layer into a frame is the caller's (heatmap.render on the host; DeviceHeatMap.render is for
         frames kept in HBM).  ValueError naming heatmap for a spec the device refuses.
+        ground: the ground plane ON THE DEVICE inside the step (MultiStreamPipeline.set_ground) - one ground.GroundSpec for all
+        streams, a list with one (or None: that camera is skipped) per stream, a ground.GroundMap or a ground.DeviceGroundMap (their
+        specs, max_age and speed_window; never their grid): one fresh site grid on one floor plan for all cameras, entries leave
+        after ground_max_age unseen processed frames, frame times are those of the action stage.  Read stream_ground() (the step's
+        records: plan position, velocity, speed, cell per person) and site_map(layer) between the yields; the yielded items and
+        images do not change.  ValueError naming ground for a spec the device refuses.
         device_overlay (the constructor's flag, on by default; YDS_HOST_OVERLAY turns it off) runs the generator as a staged engine
         (_detect_streams_device): a reader thread forms the steps and uploads them from pinned staging blocks, the step runs on the
         caller's thread in lock-step with the yields and takes the next staged step along for its early detector pass, and the
@@ -651,6 +657,15 @@ class VideoDetector:
             elif isinstance(heatmap, hm.HeatMap):
                 heatmap, heatmap_max_age = heatmap.spec, heatmap.max_age
             heat_dev = hm.DeviceHeatMap(heatmap, heatmap_max_age, max(len(sources), 1))
+        ground_dev = None
+        if ground is not None:                           # (ValueError naming ground for what the device refuses)
+            from . import ground as gp
+            window = 8
+            if isinstance(ground, (gp.DeviceGroundMap, gp.GroundMap)):   # a fresh grid and fresh tables: never the caller's own
+                if ground.n_streams < len(sources):
+                    raise ValueError("ground: a map of %d streams for %d sources" % (ground.n_streams, len(sources)))
+                ground, ground_max_age, window = ground.specs[:max(len(sources), 1)], ground.max_age, ground.K
+            ground_dev = gp.DeviceGroundMap(ground, ground_max_age, window, max(len(sources), 1))
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -673,10 +688,13 @@ class VideoDetector:
             pipe.set_zones(zones_dev)
         if heat_dev is not None:
             pipe.set_heatmap(heat_dev)
+        if ground_dev is not None:
+            pipe.set_ground(ground_dev)
+        self._stream_ground = [[] for _ in range(S)]
         self._stream_zone_events = [[] for _ in range(S)]
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
-        on = dict(timed=actions_dev is not None or zones_dev is not None or heat_dev is not None, zones=zones_dev is not None,
-                  actions=actions_dev is not None)
+        on = dict(timed=actions_dev is not None or zones_dev is not None or heat_dev is not None or ground_dev is not None,
+                  zones=zones_dev is not None, actions=actions_dev is not None, ground=ground_dev is not None)
         try:
             if self.device_overlay:                          # staged uploads, look-ahead, the output stage on the device
                 yield from self._detect_streams_device(pipe, sources, F, show_fps, mixed_sizes, on, lookahead=not global_ids)
@@ -699,7 +717,8 @@ class VideoDetector:
     def _streams_step(self, pipe, plan, times, blk, ahead, on):
         """One MultiStreamPipeline step over the processed frames of a planned step (uniform or mixed; times: their frame times;
         ahead: the next step's HBM buffer for its early detector pass, or None), and what the bookkeeping reads after it:
-        (outs, actions per frame or None, detections per frame or None).  on: which device stages run (timed, zones, actions)."""
+        (outs, actions per frame or None, detections per frame or None).  on: which device stages run (timed, zones, actions,
+        ground)."""
         n, outs = plan["n_proc"], []
         if n:
             if on["timed"]:
@@ -714,6 +733,10 @@ class VideoDetector:
             self._stream_zone_events = [[] for _ in self._stream_zone_events]
             for s, evs in zip(plan["streams"], pipe.last_zone_events() if n else []):
                 self._stream_zone_events[s].append(evs)
+        if on.get("ground"):                             # the records of this step's processed frames, per stream in time order
+            self._stream_ground = [[] for _ in self._stream_ground]
+            for s, rows in zip(plan["streams"], pipe.last_ground() if n else []):
+                self._stream_ground[s].append(rows)
         return outs, step_acts, step_dets
 
     def _detect_streams_device(self, pipe, sources, F, show_fps, mixed_sizes, on, lookahead=True):
@@ -835,6 +858,31 @@ class VideoDetector:
         if getattr(pipe, "heat", None) is None:
             raise ValueError("VideoDetector.stream_heatmaps needs detect_streams(..., heatmap=...)")
         return pipe.heatmap(stream, layer)
+
+    def _ground_pipe(self, who):
+        pipe = self._live_streams_pipe(who)
+        if getattr(pipe, "ground", None) is None:
+            raise ValueError("VideoDetector.%s needs detect_streams(..., ground=...)" % who)
+        return pipe
+
+    def stream_ground(self, stream=None):
+        """The ground records of the last step of the running detect_streams(ground=...) generator, between two of its yields
+        (ValueError outside, and for a generator started without ground): for ``stream`` one entry per frame of it that the step
+        processed, in time order - int32 [m, 8] = track id, class, qx, qy, vx, vy, speed, cell, None where the detector returned
+        None - or a list of such lists, one per stream; MultiStreamPipeline.last_ground."""
+        self._ground_pipe("stream_ground")
+        per = self._stream_ground
+        if stream is None:
+            return [list(e) for e in per]
+        if int(stream) < 0 or int(stream) >= len(per):
+            raise ValueError("VideoDetector.stream_ground: stream %d outside [0, %d)" % (int(stream), len(per)))
+        return list(per[int(stream)])
+
+    def site_map(self, layer="presence"):
+        """The site grid of the running detect_streams(ground=...) generator, between two of its yields (ValueError outside, and
+        for a generator started without ground): ``layer`` as int64 [gh, gw], read from the device; layer=None: all five layers
+        [5, gh, gw]; MultiStreamPipeline.ground_layers."""
+        return self._ground_pipe("site_map").ground_layers(layer)
 
     def stream_identity_map(self):
         """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,

@@ -8,7 +8,7 @@ the definition every device test (csrc/heatmap.hip, ``DeviceHeatMap``) compares 
 integer arithmetic except one double subtraction and one double product per dwell credit.
 
 Limits: the layers only ever grow (no decay: ``reset`` or a fresh map starts a new period); cells are squares of image pixels
-(no ground plane); ``VideoDetector.detect()`` has no heat map; ``detect_streams`` accumulates on the device but leaves rendering
+(the floor-plan form is ground.py); ``VideoDetector.detect()`` has no heat map; ``detect_streams`` accumulates on the device but leaves rendering
 to the caller (``render`` on the host) - the device render is for callers who keep their frames in HBM.
 """
 

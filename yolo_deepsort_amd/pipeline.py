@@ -232,6 +232,48 @@ class Pipeline:
             raise ValueError("heatmap: stream %d outside [0, %d)" % (int(stream), n))
         return one(int(stream))
 
+    def set_ground(self, ground=None, max_age=30):
+        """The ground plane stage of every following step: ``ground`` is a ground.DeviceGroundMap of at least as many streams as the
+        pipeline (its site grid and tables are used as they are), a ground.GroundMap (its specs, max_age and speed_window go to the
+        device, a fresh grid), one ground.GroundSpec for all streams or a list with one (or None: that stream is skipped) per stream;
+        None switches the stage off.  A step then adds one launch behind the heat map launch, ``last_ground()`` holds its records
+        and ``ground_layers()`` reads the site grid; the step's own return value does not change.  ValueError naming ground for
+        anything the device refuses; refused (YdsError) while a look-ahead pass is in flight."""
+        from .ground import as_device_ground
+        dev = None if ground is None else as_device_ground(ground, getattr(self, "n_streams", 1), max_age)
+        _lib.check(_lib.load().yds_pipeline_set_ground(self._h, None if dev is None else dev.handle))
+        self.ground = dev                                   # (keeps the handle alive while the pipeline names it)
+        return dev
+
+    def last_ground(self, stream=None):
+        """The ground records of the last step, int32 [m, 8] = track id, class, qx, qy, vx, vy, speed, cell (cell -1: outside the
+        grid, -2: off plane): a list with one array per frame of the step (None where the frame's rows were None), or with
+        ``stream`` the records of that stream's frames of the step in time order as one array.  Already on the host; None when the
+        stage is off or no step ran."""
+        dev, counts = getattr(self, "ground", None), getattr(self, "_last_counts", None)
+        if dev is None or counts is None:
+            return None
+        n = C.c_int(0)
+        lib = _lib.load()
+        lib.yds_pipeline_last_ground(self._h, None, None, 0, C.byref(n))       # (asks for the count; refuses to copy when it is not 0)
+        rows, frame = np.zeros((max(n.value, 1), 8), np.int32), np.zeros(max(n.value, 1), np.int32)
+        _lib.check(lib.yds_pipeline_last_ground(self._h, _lib.ptr(rows), _lib.ptr(frame), len(rows), C.byref(n)))
+        rows, frame = rows[:n.value], frame[:n.value]
+        per = [None if counts[b] < 0 else rows[frame == b].copy() for b in range(len(counts))]
+        if stream is None:
+            return per
+        streams = getattr(self, "_zone_streams", None) or [0] * len(counts)
+        mine = [per[b] for b in range(len(counts)) if streams[b] == int(stream) and per[b] is not None]
+        return np.concatenate(mine) if mine else np.zeros((0, 8), np.int32)
+
+    def ground_layers(self, layer=None):
+        """The site grid as the last step left it, read from the device: int64 [5, gh, gw], or [gh, gw] for a named ``layer``.  None
+        when the stage is off."""
+        dev = getattr(self, "ground", None)
+        if dev is None:
+            return None
+        return dev.layers() if layer is None else dev.layer(layer)
+
     def _search_trackers(self):
         return getattr(self, "deepsorts", None) or [self.ds]
 
