@@ -16,6 +16,8 @@ from __future__ import annotations
 import time
 from collections import deque
 
+from .track_stage import TrackStage
+
 
 class Orbit:
     """Recent foot points ((x1+x2)/2, y2) and their timestamps for one track id."""
@@ -189,103 +191,67 @@ def pack_actions(actions, max_age=30, max_size=4):
     return kind, cls, param, names
 
 
-class DeviceActionIdentify:
+class DeviceActionIdentify(TrackStage):
     """``ActionIdentify`` for ``n_streams`` video streams with every orbit cache in HBM: one launch advances the caches of all
     streams over the frames of a call, and the rows equal the host module's fed the same rows and times (double arithmetic in the
     same operation order).  One difference: two sightings with the same time make FastCrossing divide by zero - Python raises,
     the device follows IEEE (x / 0 = inf passes, 0 / 0 fails)."""
+    NAME, LIB = "action_id", "actions"
+    PER_STREAM = False              # (the streams share the actions: fresh(n) may make more caches than this object has)
+    _check_max_age = staticmethod(int)      # (pack_actions has refused what is no integer; the host module sets no lower bound)
 
     def __init__(self, actions, max_age=30, max_size=4, n_streams=1):
         self.kind, self.class_ids, self.param, self.names = pack_actions(actions, max_age, max_size)
-        self.actions = list(actions)
-        self.max_age, self.max_size, self.n_streams = int(max_age), int(max_size), int(n_streams)
-        self._h = None
+        self.actions, self.max_size = list(actions), int(max_size)
+        super().__init__(n_streams, max_age)
+
+    def _settings(self, n_streams):
+        return self.actions, self.max_age, self.max_size, n_streams
 
     def clone(self, n_streams=None):
-        return DeviceActionIdentify(self.actions, self.max_age, self.max_size, self.n_streams if n_streams is None else n_streams)
+        return self.fresh(self.n_streams if n_streams is None else n_streams)
 
-    @property
-    def handle(self):
-        """The yds_act handle, created on first use (the descriptor itself needs no GPU)."""
-        if self._h is None:
-            from . import _lib
-            _lib.init()
-            self._h = _lib.check_ptr(_lib.load().yds_actions_create(
-                self.n_streams, _lib.ptr(self.kind), _lib.ptr(self.class_ids), _lib.ptr(self.param), len(self.names), self.max_age,
-                self.max_size))
-        return self._h
+    def _create(self, lib):
+        from . import _lib
+        return lib.yds_actions_create(self.n_streams, _lib.ptr(self.kind), _lib.ptr(self.class_ids), _lib.ptr(self.param), len(self.names),
+                                      self.max_age, self.max_size)
 
     def name_rows(self, rows4):
         return [(int(r[1]), int(r[2]), self.names[int(r[3])]) for r in rows4]
 
     def update_batch(self, frames_rows, stream_of, times):
         """Frames in the order given (a stream's frames in time order), frame f of stream ``stream_of[f]``; ``times[f]`` is a number
-        for the frame or a sequence with one number per row.  Returns one ``[(track_id, class_id, name), ...]`` per frame."""
+        for the frame or a sequence with one number per row.  Returns one ``[(track_id, class_id, name), ...]`` per frame (None
+        for a frame whose rows are None: it is not seen).  A stream outside the handle's is refused by the library (YdsError)."""
         import ctypes as C
         import numpy as np
         from . import _lib
-        n = len(frames_rows)
-        rows = [np.asarray(r, dtype=np.int64).reshape(-1, 6) if len(r) else np.zeros((0, 6), np.int64) for r in frames_rows]
-        first = np.zeros(n + 1, np.int32)
-        first[1:] = np.cumsum([len(r) for r in rows])
-        rows6 = np.ascontiguousarray(np.concatenate(rows) if n else np.zeros((0, 6)), dtype=np.int32)
-        row_time = np.zeros(int(first[-1]), np.float64)
-        for f in range(n):
-            row_time[first[f]:first[f + 1]] = np.asarray(times[f], np.float64)
-        sof = np.ascontiguousarray(stream_of, dtype=np.int32)
-        cap = max(int(first[-1]) * len(self.names), 1)
+        live, rows6, first, sof, row_time = self.pack(frames_rows, stream_of, times, per_row=True, check_streams=False)
+        per = [None] * len(frames_rows)
+        if not live:
+            return per
+        cap = max(len(rows6) * len(self.names), 1)
         out = np.zeros((cap, 4), np.int32)
         m = C.c_int(0)
-        _lib.check(_lib.load().yds_actions_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(row_time), n,
+        _lib.check(_lib.load().yds_actions_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(row_time), len(live),
                                                   _lib.ptr(out), cap, C.byref(m)))
-        per = [[] for _ in range(n)]
+        for f in live:
+            per[f] = []
         for r in out[:m.value]:
-            per[int(r[0])].append((int(r[1]), int(r[2]), self.names[int(r[3])]))
+            per[live[int(r[0])]] += self.name_rows([r])
         return per
-
-    def update(self, stream, rows, timestamp):
-        """One frame of one stream: ``ActionIdentify.update(rows, timestamp)`` (None in, None out, nothing touched)."""
-        if rows is None:
-            return None
-        return self.update_batch([rows], [stream], [timestamp])[0]
 
     def orbits(self, stream=0):
         """[(track_id, age, points held), ...] of one stream's cache in insertion order."""
-        import ctypes as C
         import numpy as np
-        from . import _lib
-        n = C.c_int(0)
-        lib = _lib.load()
-        _lib.check(lib.yds_actions_get_orbits(self.handle, int(stream), None, None, None, 1 << 30, C.byref(n)))
-        ids, ages, lens = (np.zeros(max(n.value, 1), np.int32) for _ in range(3))
-        _lib.check(lib.yds_actions_get_orbits(self.handle, int(stream), _lib.ptr(ids), _lib.ptr(ages), _lib.ptr(lens), len(ids), C.byref(n)))
-        return [(int(ids[k]), int(ages[k]), int(lens[k])) for k in range(n.value)]
+        ids, ages, lens = self._read_table("orbits", stream, [(np.int32, ())] * 3)
+        return list(zip(ids.tolist(), ages.tolist(), lens.tolist()))
 
-    def reset(self, stream=None):
-        from . import _lib
-        if self._h is not None:
-            _lib.check(_lib.load().yds_actions_reset(self._h, -1 if stream is None else int(stream)))
-
-    def close(self):
-        if self._h is not None:
-            from . import _lib
-            _lib.load().yds_actions_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @classmethod
+    def _from_host(cls, x, n_streams, max_age):
+        if not isinstance(x, ActionIdentify):
+            raise ValueError(f"action_id must be an ActionIdentify or a DeviceActionIdentify, got {type(x).__name__}")
+        return x.to_device(n_streams)
 
 
-def as_device_actions(action_id, n_streams):
-    """``action_id`` (an ActionIdentify or a DeviceActionIdentify) as a DeviceActionIdentify of at least ``n_streams`` streams;
-    ValueError naming ``action_id`` for anything else."""
-    if isinstance(action_id, DeviceActionIdentify):
-        if action_id.n_streams < n_streams:
-            raise ValueError(f"action_id: a DeviceActionIdentify of {action_id.n_streams} streams for {n_streams} streams")
-        return action_id
-    if isinstance(action_id, ActionIdentify):
-        return action_id.to_device(n_streams)
-    raise ValueError(f"action_id must be an ActionIdentify or a DeviceActionIdentify, got {type(action_id).__name__}")
+as_device_actions = DeviceActionIdentify.as_device      # (the name Pipeline.set_actions and callers import; track_stage.TrackStage.as_device is the rule)

@@ -219,10 +219,10 @@ public:
     }
 
     void collect() override {
-        rows4.clear();
+        report.rows.clear();
         collect_counts("rows", [&](int i, int m) {
             const int *r = res_host.p + pending_rows[i];
-            rows4.insert(rows4.end(), r, r + (size_t)m * 4);
+            report.rows.insert(report.rows.end(), r, r + (size_t)m * 4);
         });
     }
 
@@ -266,8 +266,8 @@ int yds_actions_update(yds_act *a, const int32_t *rows6_host, const int32_t *fir
     const size_t n_rows = first[n_frames];
     A->enqueue_ex(fr.data(), n_frames, A->own_stream, rows6_host, n_rows, row_time, n_rows);
     A->finish_alone();
-    const int m = A->give_count("action rows", (int)(A->rows4.size() / 4), cap, n_out);
-    if (m) memcpy(out4_host, A->rows4.data(), (size_t)m * 4 * sizeof(int32_t));
+    const int m = A->give_count("action rows", (int)(A->report.rows.size() / 4), cap, n_out);
+    if (m) memcpy(out4_host, A->report.rows.data(), (size_t)m * 4 * sizeof(int32_t));
     YDS_API_END
 }
 int yds_actions_get_orbits(yds_act *a, int stream, int32_t *ids, int32_t *ages, int32_t *lens, int cap, int *n) {

@@ -282,47 +282,52 @@ struct ActFrame {
     double t;
     const double *row_time;
 };
-// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps, ground plane; their shared frame is track_stage.h):
+// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps, ground plane; their shared frame is
+// track_stage.h, their Python front yolo_deepsort_amd/track_stage.py).  The slots of a step, in launch order:
+enum StageSlot { STAGE_ACTIONS, STAGE_ZONES, STAGE_HEAT, STAGE_GROUND, N_STAGES };
+// What a call reported, frame k = items [first[k], first[k + 1]): `rows` holds `width` int32 per item (a stage names its width and
+// columns below), `tags` one frame tag per item and `times` doubles per item where the stage has them.
+struct StageReport {
+    std::vector<int32_t> rows, tags;
+    std::vector<double> times;
+};
 struct TrackStageIface {
     virtual ~TrackStageIface() {}
     virtual int streams() const = 0;
+    // what a pipeline of n_streams streams asks of a handle before it accepts it; noun: the handle in its words ("a zones")
+    virtual void check_for(int n_streams, const char *noun) const {
+        if (streams() < n_streams) fail("pipeline: %s handle of %d streams for a pipeline of %d", noun, streams(), n_streams);
+    }
     // asynchronous on s: grows the tables, one launch; what the stage reports lands in pinned host memory
     virtual void enqueue(const ActFrame *fr, int n, hipStream_t s) = 0;
-    // after the caller synchronised s: the report of that call, frame k = items [first[k], first[k + 1]) of the stage's vectors
+    // after the caller synchronised s: the report of that call
     virtual void collect() = 0;
     std::vector<int32_t> first;
+    StageReport report;
 };
-struct ActionsIface : TrackStageIface {
-    std::vector<int32_t> rows4;                   // [m][4] tag, id, class, action
-};
+struct ActionsIface : TrackStageIface {};         // report.rows [m][4] tag, id, class, action
 
 // --------------------------------------------------------------------------------------------- zones
 // Implemented in zones.hip: per stream a table of tracks with, per zone, an inside bit, a debounce streak and an enter time, advanced
 // over the frames of a call by ONE launch over the same frame descriptors as the action stage (row_time is not read: every row of a
 // frame carries the frame's time t).
-struct ZonesIface : TrackStageIface {
-    std::vector<int32_t> ev6;                     // [m][6] tag, id, class, kind, zone or line, 0
-    std::vector<double> evt2;                     // [m][2] t, dwell
-};
+struct ZonesIface : TrackStageIface {};           // report.rows [m][6] tag, id, class, kind, zone or line, 0; report.times [m][2] t, dwell
 
 // --------------------------------------------------------------------------------------------- heat maps
 // Implemented in heatmap.hip: per stream a grid of int64 layers and a table of tracks with the cell, time and foot point of their last
 // sighting, advanced over the frames of a call by ONE launch over the same frame descriptors as the zone stage.  It reports nothing
-// per event: `counted` and `first` only say how many rows of each frame were of the stream's class.
+// per event: `counted` and `first` only say how many rows of each frame were of the stream's class.  Its check_for also refuses a
+// stream without a spec (yds_heatmap_set_stream).
 struct HeatmapIface : TrackStageIface {
-    virtual bool has_spec(int stream) const = 0;  // yds_heatmap_set_stream has been called for it
     std::vector<int32_t> counted;                 // [n] rows counted per frame
 };
 
 // --------------------------------------------------------------------------------------------- ground plane
 // Implemented in ground.hip: ONE site grid of int64 layers on a floor plan shared by all streams, per stream a homography and a table
 // of tracks with a ring of their last plan positions, advanced over the frames of a call by ONE launch over the same frame
-// descriptors as the zone stage.  It reports one int32[8] record per counted row: id, class, qx, qy, vx, vy, speed, cell.
-struct GroundIface : TrackStageIface {
-    virtual bool has_spec(int stream) const = 0;  // yds_ground_set_stream has been called for it (a stream without one is skipped)
-    std::vector<int32_t> rows8;                   // [m][8]
-    std::vector<int32_t> frame_of;                // [m] the tag of the frame every record belongs to
-};
+// descriptors as the zone stage.  It reports one int32[8] record per counted row: id, class, qx, qy, vx, vy, speed, cell.  A stream
+// without a spec (yds_ground_set_stream) is skipped.
+struct GroundIface : TrackStageIface {};          // report.rows [m][8]; report.tags [m] the tag of the frame every record belongs to
 
 // --------------------------------------------------------------------------------------------- tracker
 // Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
@@ -377,18 +382,10 @@ struct TrackerGroupIface {
     // the identity stage of the NEXT step_batch (nullptr: none): one small launch behind the action stage, ahead of the step's one
     // synchronisation, and the resolve sequence behind it in the steps that admit a new track.  Cleared by the step.
     virtual void set_identities(IdentityIface *ident) = 0;
-    // the action stage of the NEXT step_batch (nullptr: none): one more launch behind the last round, before the step's one
-    // synchronisation; frame_times[b] = time of frame b of that step.  Cleared by the step.
-    virtual void set_actions(ActionsIface *act, const double *frame_times) = 0;
-    // the zone stage of the NEXT step_batch (nullptr: none): one more launch behind the action launch (if there is one), ahead of the
-    // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
-    virtual void set_zones(ZonesIface *zones, const double *frame_times) = 0;
-    // the heat map stage of the NEXT step_batch (nullptr: none): one more launch behind the zone launch (if there is one), ahead of the
-    // identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
-    virtual void set_heatmap(HeatmapIface *heat, const double *frame_times) = 0;
-    // the ground plane stage of the NEXT step_batch (nullptr: none): one more launch behind the heat map launch (if there is one),
-    // ahead of the identity collect launch and of the step's one synchronisation; frame_times as for set_actions.  Cleared by the step.
-    virtual void set_ground(GroundIface *ground, const double *frame_times) = 0;
+    // the table stages of the NEXT step_batch by slot (nullptr: none), N_STAGES of them: one more launch each, in slot order, behind
+    // the last round and ahead of the identity collect launch and of the step's one synchronisation; frame_times[b] = time of frame b
+    // of that step, the same for every stage.  Cleared by the step.
+    virtual void set_stages(TrackStageIface *const *by_slot, const double *frame_times) = 0;
     virtual void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first,
                             const float *feats_dev, const float *payload_host, const char *skip, int32_t *out6_host, int cap, int32_t *counts) = 0;
     // the next step_batch starts behind `ev` on the driver's stream (features produced on another stream: no host wait)

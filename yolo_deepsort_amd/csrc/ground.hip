@@ -349,7 +349,6 @@ public:
             copy_live(nt.trav, t.trav, n);
         });
     }
-    bool has_spec(int stream) const override { return stream >= 0 && stream < S && specs[stream].set; }
     const Spec &spec_of(int stream) const {
         check_stream(stream);
         if (!specs[stream].set) fail("ground: stream %d has no spec (yds_ground_set_stream)", stream);
@@ -425,12 +424,12 @@ public:
     }
 
     void collect() override {
-        rows8.clear();
-        frame_of.clear();
+        report.rows.clear();
+        report.tags.clear();
         collect_counts("ground rows", [&](int i, int m) {
             const int *r = res_host.p + pending_rows[i];
-            rows8.insert(rows8.end(), r, r + (size_t)m * 8);
-            frame_of.insert(frame_of.end(), (size_t)m, pending_tag[i]);
+            report.rows.insert(report.rows.end(), r, r + (size_t)m * 8);
+            report.tags.insert(report.tags.end(), (size_t)m, pending_tag[i]);
         });
     }
 
@@ -577,10 +576,10 @@ int yds_ground_update(yds_ground *g, const int32_t *rows6_host, const int32_t *f
     if (fr.empty()) return 0;
     G->enqueue_ex(fr.data(), n_frames, G->own_stream, rows6_host, (size_t)first[n_frames]);
     G->finish_alone();
-    const int m = G->give_count("ground rows", (int)(G->rows8.size() / 8), cap, n_out);
+    const int m = G->give_count("ground rows", (int)(G->report.rows.size() / 8), cap, n_out);
     if (m) {
         if (!out8_host) yds::fail("ground: NULL argument");
-        memcpy(out8_host, G->rows8.data(), (size_t)m * 8 * sizeof(int32_t));
+        memcpy(out8_host, G->report.rows.data(), (size_t)m * 8 * sizeof(int32_t));
     }
     if (first_out) memcpy(first_out, G->first.data(), ((size_t)n_frames + 1) * sizeof(int32_t));
     YDS_API_END

@@ -262,7 +262,11 @@ public:
             copy_live(nt.pt, t.pt, n);
         });
     }
-    bool has_spec(int stream) const override { return stream >= 0 && stream < S && grids[stream].cell != 0; }
+    void check_for(int n_streams, const char *noun) const override {
+        HeatmapIface::check_for(n_streams, noun);
+        for (int s = 0; s < n_streams; ++s)
+            if (grids[s].cell == 0) fail("pipeline: stream %d of the heatmap handle has no spec (yds_heatmap_set_stream)", s);
+    }
     const Grid &grid_of(int stream) const {
         check_stream(stream);
         if (!grids[stream].cell) fail("heatmap: stream %d has no spec (yds_heatmap_set_stream)", stream);

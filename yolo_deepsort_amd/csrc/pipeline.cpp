@@ -569,35 +569,26 @@ public:
         std::vector<char> skip(batch, 0);
         for (int b = 0; b < batch; ++b) skip[b] = cur.n_det[b] == 0;  // detector returned None: tracker not called (video_detect.py:137)
         if (!multi) stream_of.assign(batch, 0);
-        // the action, zone, heat map and ground plane stages (set_actions, set_zones, set_heatmap, set_ground): frame b carries the caller's time for it, else its stream's frame
-        // count / 25
+        // the table stages (set_stage): frame b carries the caller's time for it, else its stream's frame count / 25
         std::vector<double> times;
         if ((int)frames_seen.size() < (int)trks.size()) frames_seen.resize(trks.size(), 0);
         const std::vector<double> given = std::move(next_times);      // (they name this step's frames, whatever becomes of it)
         next_times.clear();
-        if (actions || zones || heat || ground) {
+        if (std::any_of(stages, stages + N_STAGES, [](const TrackStageIface *sg) { return sg != nullptr; })) {
             if (!given.empty() && (int)given.size() != batch)
                 fail("pipeline: %zu frame times for a step of %d frames (yds_pipeline_set_frame_times)", given.size(), batch);
             times.resize(batch);
             std::vector<int64_t> seen(frames_seen);
             for (int b = 0; b < batch; ++b) times[b] = given.empty() ? (double)seen[stream_of[b]]++ / 25.0 : given[b];
-            if (actions) group->set_actions(actions, times.data());
-            if (zones) group->set_zones(zones, times.data());
-            if (heat) group->set_heatmap(heat, times.data());
-            if (ground) group->set_ground(ground, times.data());
+            group->set_stages(stages, times.data());
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
-        last_actions.clear();
-        last_zone_ev6.clear();
-        last_zone_evt2.clear();
-        last_ground_rows8.clear();
-        last_ground_frame.clear();
+        for (StageReport &r : last) r = StageReport();
         if (identities) group->set_identities(identities);
         group->step_batch(trks.data(), (int)trks.size(), batch, stream_of.data(), cur.tlwh.data(), cur.first.data(), feat_cur.p,
                           cur.payload.data(), skip.data(), out6, cap, counts);
-        if (actions) last_actions = actions->rows4;
-        if (zones) { last_zone_ev6 = zones->ev6; last_zone_evt2 = zones->evt2; }
-        if (ground) { last_ground_rows8 = ground->rows8; last_ground_frame = ground->frame_of; }
+        for (int k = 0; k < N_STAGES; ++k)
+            if (stages[k]) last[k] = stages[k]->report;   // (a copy: a stand-alone update on the handle between two steps leaves it alone)
         auto t_end = clk::now();
         stage_us[2] = us(t_begin, t_nms); stage_us[3] = us(t_nms, t_reid); stage_us[4] = us(t_reid, t_end);
         // a steady-state step of a chip-filling ReID pass counts towards the schedule trial of its entry
@@ -615,44 +606,30 @@ public:
         stream_of.assign(stream_of_frame, stream_of_frame + n);
     }
 
-    // ---- the action stage (yds_pipeline_set_actions; video_detect.py:151-152 for every stream of a step) ----
-    void set_actions(ActionsIface *a) {
-        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_actions while a look-ahead pass is in flight (consume it with a step first)");
-        if (a && a->streams() < (int)trks.size()) fail("pipeline: an action handle of %d streams for a pipeline of %zu", a->streams(), trks.size());
-        actions = a;
-        last_actions.clear();
+    // ---- the table stages (yds_pipeline_set_actions / _set_zones / _set_heatmap / _set_ground; video_detect.py:151-152 for every
+    //      stream of a step): a handle of at least as many streams as the pipeline, geometry in each stream's own frame pixels;
+    //      nullptr switches the stage off ----
+    void set_stage(StageSlot slot, TrackStageIface *sg) {
+        static const char *const setter[N_STAGES] = {"set_actions", "set_zones", "set_heatmap", "set_ground"};
+        static const char *const noun[N_STAGES] = {"an action", "a zones", "a heatmap", "a ground"};
+        if (pending.frames || ahead.reid_in_flight) fail("pipeline: %s while a look-ahead pass is in flight (consume it with a step first)", setter[slot]);
+        if (sg) sg->check_for((int)trks.size(), noun[slot]);
+        stages[slot] = sg;
+        last[slot] = StageReport();
     }
-    // ---- the zone stage (yds_pipeline_set_zones): zones and counting lines of every stream, in that stream's own frame pixels ----
-    void set_zones(ZonesIface *z) {
-        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_zones while a look-ahead pass is in flight (consume it with a step first)");
-        if (z && z->streams() < (int)trks.size()) fail("pipeline: a zones handle of %d streams for a pipeline of %zu", z->streams(), trks.size());
-        zones = z;
-        last_zone_ev6.clear();
-        last_zone_evt2.clear();
+    // m items of a stage's last report for a caller with room for cap: rows of `width` int32, then the tags / times the stage has
+    void give_last(StageSlot slot, const char *noun, int width, int32_t *rows_out, int32_t *tags_out, double *times_out, int cap, int *n_out) const {
+        const StageReport &r = last[slot];
+        const int m = (int)(r.rows.size() / width);
+        if (n_out) *n_out = m;
+        if (m > cap) fail("pipeline: %d %s exceed the caller's capacity %d", m, noun, cap);
+        if (!m) return;
+        memcpy(rows_out, r.rows.data(), r.rows.size() * sizeof(int32_t));
+        if (tags_out) memcpy(tags_out, r.tags.data(), r.tags.size() * sizeof(int32_t));
+        if (times_out) memcpy(times_out, r.times.data(), r.times.size() * sizeof(double));
     }
-    // ---- the heat map stage (yds_pipeline_set_heatmap): every stream's grid in that stream's own frame pixels ----
-    void set_heatmap(HeatmapIface *h) {
-        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_heatmap while a look-ahead pass is in flight (consume it with a step first)");
-        if (h && h->streams() < (int)trks.size()) fail("pipeline: a heatmap handle of %d streams for a pipeline of %zu", h->streams(), trks.size());
-        for (int s = 0; h && s < (int)trks.size(); ++s)
-            if (!h->has_spec(s)) fail("pipeline: stream %d of the heatmap handle has no spec (yds_heatmap_set_stream)", s);
-        heat = h;
-    }
-    HeatmapIface *heat = nullptr;
-    // ---- the ground plane stage (yds_pipeline_set_ground): every stream's rows onto one floor plan; a stream without a spec is skipped ----
-    void set_ground(GroundIface *g) {
-        if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_ground while a look-ahead pass is in flight (consume it with a step first)");
-        if (g && g->streams() < (int)trks.size()) fail("pipeline: a ground handle of %d streams for a pipeline of %zu", g->streams(), trks.size());
-        ground = g;
-        last_ground_rows8.clear();
-        last_ground_frame.clear();
-    }
-    GroundIface *ground = nullptr;
-    std::vector<int32_t> last_ground_rows8;       // ground records of the last step [m][8]: id, class, qx, qy, vx, vy, speed, cell
-    std::vector<int32_t> last_ground_frame;       //                                 [m]: frame of the step
-    ZonesIface *zones = nullptr;
-    std::vector<int32_t> last_zone_ev6;           // zone events of the last step [m][6]: frame of the step, id, class, kind, zone or line, 0
-    std::vector<double> last_zone_evt2;           //                              [m][2]: t, dwell
+    TrackStageIface *stages[N_STAGES] = {};       // the table stages of every following step, by slot
+    StageReport last[N_STAGES];                   // what each reported in the last step, tagged with the frame of the step
     // ---- the identity stage (yds_pipeline_set_identities): global ids over the streams' trackers, updated behind every step ----
     void set_identities(IdentityIface *i) {
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: set_identities while a look-ahead pass is in flight (consume it with a step first)");
@@ -667,10 +644,8 @@ public:
     }
     IdentityIface *identities = nullptr;
     std::shared_ptr<void *> self = std::make_shared<void *>(this);      // what a map bound to this pipeline asks; cleared by ~Pipeline
-    ActionsIface *actions = nullptr;
     std::vector<double> next_times;               // set_frame_times: times of the next step's frames (empty: count / 25)
     std::vector<int64_t> frames_seen;             // frames every stream was handed since the pipeline was made
-    std::vector<int32_t> last_actions;            // action rows of the last step [m][4]: frame of the step, id, class, action
 
     Darknet *net;
     ReidNet *reid;
@@ -823,7 +798,7 @@ int yds_pipeline_set_stream_windows(yds_pipe *p, int stream, int win_w, int win_
 }
 int yds_pipeline_set_actions(yds_pipe *p, yds_act *a) {
     YDS_API_BEGIN
-    p->p->set_actions(a ? a->a : nullptr);
+    p->p->set_stage(yds::STAGE_ACTIONS, a ? a->a : nullptr);
     YDS_API_END
 }
 int yds_pipeline_set_frame_times(yds_pipe *p, const double *t_host, int n) {
@@ -834,11 +809,7 @@ int yds_pipeline_set_frame_times(yds_pipe *p, const double *t_host, int n) {
 }
 int yds_pipeline_last_actions(yds_pipe *p, int32_t *out4_host, int cap, int *n_out) {
     YDS_API_BEGIN
-    const std::vector<int32_t> &r = p->p->last_actions;
-    const int m = (int)(r.size() / 4);
-    if (n_out) *n_out = m;
-    if (m > cap) yds::fail("pipeline: %d action rows exceed the caller's capacity %d", m, cap);
-    if (m) memcpy(out4_host, r.data(), r.size() * sizeof(int32_t));
+    p->p->give_last(yds::STAGE_ACTIONS, "action rows", 4, out4_host, nullptr, nullptr, cap, n_out);
     YDS_API_END
 }
 int yds_pipeline_last_detections(yds_pipe *p, float *rows5_host, int cap, int32_t *counts_host) {
@@ -863,41 +834,27 @@ int yds_pipeline_last_detections(yds_pipe *p, float *rows5_host, int cap, int32_
 }
 int yds_pipeline_set_zones(yds_pipe *p, yds_zones *z) {
     YDS_API_BEGIN
-    p->p->set_zones(z ? z->z : nullptr);
+    p->p->set_stage(yds::STAGE_ZONES, z ? z->z : nullptr);
     YDS_API_END
 }
 int yds_pipeline_set_heatmap(yds_pipe *p, yds_heatmap *h) {
     YDS_API_BEGIN
-    p->p->set_heatmap(h ? h->h : nullptr);
+    p->p->set_stage(yds::STAGE_HEAT, h ? h->h : nullptr);
     YDS_API_END
 }
 int yds_pipeline_set_ground(yds_pipe *p, yds_ground *g) {
     YDS_API_BEGIN
-    p->p->set_ground(g ? g->g : nullptr);
+    p->p->set_stage(yds::STAGE_GROUND, g ? g->g : nullptr);
     YDS_API_END
 }
 int yds_pipeline_last_ground(yds_pipe *p, int32_t *rows8_host, int32_t *frame_host, int cap, int *n_out) {
     YDS_API_BEGIN
-    const std::vector<int32_t> &r = p->p->last_ground_rows8;
-    const int m = (int)(r.size() / 8);
-    if (n_out) *n_out = m;
-    if (m > cap) yds::fail("pipeline: %d ground rows exceed the caller's capacity %d", m, cap);
-    if (m) {
-        memcpy(rows8_host, r.data(), r.size() * sizeof(int32_t));
-        memcpy(frame_host, p->p->last_ground_frame.data(), (size_t)m * sizeof(int32_t));
-    }
+    p->p->give_last(yds::STAGE_GROUND, "ground rows", 8, rows8_host, frame_host, nullptr, cap, n_out);
     YDS_API_END
 }
 int yds_pipeline_last_zone_events(yds_pipe *p, int32_t *ev6_host, double *evt2_host, int cap, int *n_out) {
     YDS_API_BEGIN
-    const std::vector<int32_t> &r = p->p->last_zone_ev6;
-    const int m = (int)(r.size() / 6);
-    if (n_out) *n_out = m;
-    if (m > cap) yds::fail("pipeline: %d zone events exceed the caller's capacity %d", m, cap);
-    if (m) {
-        memcpy(ev6_host, r.data(), r.size() * sizeof(int32_t));
-        memcpy(evt2_host, p->p->last_zone_evt2.data(), p->p->last_zone_evt2.size() * sizeof(double));
-    }
+    p->p->give_last(yds::STAGE_ZONES, "zone events", 6, ev6_host, nullptr, evt2_host, cap, n_out);
     YDS_API_END
 }
 int yds_pipeline_set_identities(yds_pipe *p, yds_ident *i) {

@@ -8,6 +8,9 @@
 //   host half:   TrackStage, the bookkeeping that does not depend on what a table holds - frames bucketed by stream, table growth,
 //                the input / result blocks, the counts that come back - and the front of the stand-alone C entries
 // A stage adds its device structs, its kernel, its table layout and its result layout.
+// Above this frame a stage is a slot of a step (engine.h: StageSlot, TrackStageIface, StageReport; pipeline.cpp: set_stage) and, in
+// Python, a subclass of the front that mirrors this header: yolo_deepsort_amd/track_stage.py (handle, frame table of a call, table
+// read, reset / timing / close).
 #pragma once
 #include "tracker_dev.h"
 

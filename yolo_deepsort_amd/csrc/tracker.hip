@@ -510,10 +510,10 @@ public:
         if (stream) (void)hipStreamDestroy(stream);
     }
     void wait_for(hipEvent_t ev) override { YDS_HIP(hipStreamWaitEvent(stream, ev, 0)); }
-    void set_actions(ActionsIface *a, const double *frame_times) override { stages[0] = a; stage_times[0] = frame_times; }
-    void set_zones(ZonesIface *z, const double *frame_times) override { stages[1] = z; stage_times[1] = frame_times; }
-    void set_heatmap(HeatmapIface *h, const double *frame_times) override { stages[2] = h; stage_times[2] = frame_times; }
-    void set_ground(GroundIface *g, const double *frame_times) override { stages[3] = g; stage_times[3] = frame_times; }
+    void set_stages(TrackStageIface *const *by_slot, const double *times) override {
+        std::copy(by_slot, by_slot + N_STAGES, stages);
+        frame_times = times;
+    }
     void set_identities(IdentityIface *i) override { ident = i; }
 
     void step_batch(TrackerIface *const *trk, int S, int n, const int *stream_of, const float *tlwh_host, const int *first, const float *feats_dev,
@@ -526,12 +526,12 @@ public:
         struct ClearStages {
             TrackerGroup &g;
             ~ClearStages() {
-                for (int k = 0; k < 4; ++k) { g.stages[k] = nullptr; g.stage_times[k] = nullptr; }
+                std::fill(g.stages, g.stages + N_STAGES, nullptr);
+                g.frame_times = nullptr;
                 g.act_tag.clear(); g.act_time.clear();
             }
         } clear_stages{*this};
-        const bool staged = stages[0] || stages[1] || stages[2] || stages[3];
-        const double *times_in = stages[0] ? stage_times[0] : stages[1] ? stage_times[1] : stages[2] ? stage_times[2] : stage_times[3];   // (the pipeline hands every stage the same times)
+        const bool staged = any_stage();
         struct ClearIdentities { TrackerGroup &g; ~ClearIdentities() { g.ident = nullptr; } } clear_identities{*this};
         if (ident && !ident->bound_to(trk, S)) fail("tracker group: the identity map was not made over this step's trackers in this order");
         for (int b = 0; b < n; ++b) {
@@ -543,7 +543,7 @@ public:
             caps.push_back(cap);
             which.push_back(b);
             st.push_back(stream_of[b]);
-            if (staged) { act_tag.push_back(b); act_time.push_back(times_in ? times_in[b] : 0.0); }
+            if (staged) { act_tag.push_back(b); act_time.push_back(frame_times ? frame_times[b] : 0.0); }
         }
         cnt.assign(fr.size(), 0);
         for (TrackStageIface *sg : stages)
@@ -694,10 +694,10 @@ public:
             if (maxD) hipLaunchKernelGGL(trk_back_kernel, dim3(maxD, Sr), dim3(128), 0, stream, g);
         }
         YDS_HIP(hipGetLastError());
-        // ---- the table stages (set_actions, set_zones, set_heatmap, then set_ground): one launch each over the step's frames, reading each frame's row count and
+        // ---- the table stages (set_stages), in slot order: one launch each over the step's frames, reading each frame's row count and
         //      rows where the association kernels stored them (the pinned result blocks), their own reports behind the same
         //      synchronisation
-        const bool staged = (stages[0] || stages[1] || stages[2] || stages[3]) && (int)act_tag.size() == n;
+        const bool staged = any_stage() && (int)act_tag.size() == n;
         if (staged) {
             std::vector<ActFrame> af(n);
             for (int i = 0; i < n; ++i) {
@@ -725,8 +725,9 @@ public:
     }
 
     hipStream_t stream = nullptr;
-    TrackStageIface *stages[4] = {nullptr, nullptr, nullptr, nullptr};   // the action, zone, heat map and ground plane stage of the step being run, in launch order (set_actions, set_zones, set_heatmap, set_ground; step_batch clears them)
-    const double *stage_times[4] = {nullptr, nullptr, nullptr, nullptr};
+    TrackStageIface *stages[N_STAGES] = {};       // the table stages of the step being run, in launch order (set_stages; step_batch clears them)
+    const double *frame_times = nullptr;          // the time of every frame of that step (nullptr: 0)
+    bool any_stage() const { return std::any_of(stages, stages + N_STAGES, [](const TrackStageIface *sg) { return sg != nullptr; }); }
     IdentityIface *ident = nullptr;               // the identity stage of the step being run (set_identities; step_batch clears it)
     std::vector<int> act_tag;                     // per frame that runs: its index in the step, its time
     std::vector<double> act_time;

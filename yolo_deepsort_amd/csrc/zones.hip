@@ -347,13 +347,13 @@ public:
     }
 
     void collect() override {
-        ev6.clear();
-        evt2.clear();
+        report.rows.clear();
+        report.times.clear();
         collect_counts("events", [&](int i, int m) {
             const int *r = res_host.p + pending_base + pending_off[i] * 6;
             const double *t = res_t_host.p + pending_off[i] * 2;
-            ev6.insert(ev6.end(), r, r + (size_t)m * 6);
-            evt2.insert(evt2.end(), t, t + (size_t)m * 2);
+            report.rows.insert(report.rows.end(), r, r + (size_t)m * 6);
+            report.times.insert(report.times.end(), t, t + (size_t)m * 2);
         });
     }
 
@@ -403,10 +403,10 @@ int yds_zones_update(yds_zones *z, const int32_t *rows6_host, const int32_t *fir
     if (fr.empty()) return 0;
     Zn->enqueue_ex(fr.data(), n_frames, Zn->own_stream, rows6_host, (size_t)first[n_frames]);
     Zn->finish_alone();
-    const int m = Zn->give_count("events", (int)(Zn->ev6.size() / 6), cap, n_out);
+    const int m = Zn->give_count("events", (int)(Zn->report.rows.size() / 6), cap, n_out);
     if (m) {
-        memcpy(ev6_host, Zn->ev6.data(), (size_t)m * 6 * sizeof(int32_t));
-        memcpy(evt2_host, Zn->evt2.data(), (size_t)m * 2 * sizeof(double));
+        memcpy(ev6_host, Zn->report.rows.data(), (size_t)m * 6 * sizeof(int32_t));
+        memcpy(evt2_host, Zn->report.times.data(), (size_t)m * 2 * sizeof(double));
     }
     YDS_API_END
 }

@@ -11,10 +11,15 @@ from functools import reduce
 
 import numpy as np
 
+from .action import as_device_actions
+from .ground import as_device_ground
+from .heatmap import as_device_heatmap
 from .label_draw import LabelDrawer, put_text
 from .loaders import load_classes
 from .staging import (NOTHING, STAGE_ALIGN, Bookkeeper, give, same_composition, shut_down, skip_gate, stage_plan,  # noqa: F401 - part of this
                       stage_steps, stream_groups, take)                                                            # module's interface
+from .track_stage import TrackStage
+from .zones import as_device_zones
 
 
 def p1p2Toxywh(x):
@@ -211,6 +216,18 @@ def _transform(frame):
 def _is_frame_iterable(source):
     """An iterable of already-decoded RGB frames - not a path, not a capture."""
     return hasattr(source, "__iter__") and not isinstance(source, (str, bytes)) and not hasattr(source, "isOpened")
+
+
+STAGE_FRONTS = dict(actions=as_device_actions, zones=as_device_zones, heatmap=as_device_heatmap, ground=as_device_ground)
+
+
+def fresh_stage(name, x, n_sources, *max_age):
+    """``x`` as the table stage ``name`` of a detect_streams run over n_sources sources: converted as Pipeline.set_<name> converts
+    it (a host comparator that names its streams keeps them), then ``fresh`` - the first n_sources specs and the settings in a new
+    object, so that every stream starts with empty tables whatever the caller handed over."""
+    if not isinstance(x, TrackStage):
+        x = STAGE_FRONTS[name](x, getattr(x, "n_streams", max(n_sources, 1)), *max_age)
+    return x.fresh(n_sources)
 
 
 class VideoDetector:
@@ -629,43 +646,11 @@ class VideoDetector:
         stream_win_sizes = pl.check_stream_win_sizes(len(sources), self.image_detector.win_size, stream_win_sizes, "VideoDetector.detect_streams")
         if self.tracker is None:
             raise ValueError("VideoDetector.detect_streams needs a tracker (each stream runs a clone of it)")
-        actions_dev = None
-        if self.action_id is not None:                   # (ValueError naming action_id for what the device cannot run)
-            from .action import DeviceActionIdentify, as_device_actions
-            actions_dev = as_device_actions(self.action_id, 0)
-            if isinstance(self.action_id, DeviceActionIdentify):     # fresh caches, one per stream: never the caller's own
-                actions_dev = actions_dev.clone(max(len(sources), 1))
-            else:
-                actions_dev = self.action_id.to_device(max(len(sources), 1))
-        zones_dev = None
-        if zones is not None:                            # (ValueError naming zones for what the device refuses)
-            from . import zones as zn
-            if isinstance(zones, zn.DeviceZoneMonitor):      # fresh tables, one per stream: never the caller's own
-                if zones.n_streams < len(sources):
-                    raise ValueError("zones: a DeviceZoneMonitor of %d streams for %d sources" % (zones.n_streams, len(sources)))
-                zones, zone_max_age = zones.geometry[:max(len(sources), 1)], zones.max_age
-            elif isinstance(zones, zn.ZoneMonitor):
-                zones, zone_max_age = zones.geometry, zones.max_age
-            zones_dev = zn.DeviceZoneMonitor(zones, zone_max_age, max(len(sources), 1))
-        heat_dev = None
-        if heatmap is not None:                          # (ValueError naming heatmap for what the device refuses)
-            from . import heatmap as hm
-            if isinstance(heatmap, hm.DeviceHeatMap):        # fresh layers and tables, one per stream: never the caller's own
-                if heatmap.n_streams < len(sources):
-                    raise ValueError("heatmap: a DeviceHeatMap of %d streams for %d sources" % (heatmap.n_streams, len(sources)))
-                heatmap, heatmap_max_age = heatmap.specs[:max(len(sources), 1)], heatmap.max_age
-            elif isinstance(heatmap, hm.HeatMap):
-                heatmap, heatmap_max_age = heatmap.spec, heatmap.max_age
-            heat_dev = hm.DeviceHeatMap(heatmap, heatmap_max_age, max(len(sources), 1))
-        ground_dev = None
-        if ground is not None:                           # (ValueError naming ground for what the device refuses)
-            from . import ground as gp
-            window = 8
-            if isinstance(ground, (gp.DeviceGroundMap, gp.GroundMap)):   # a fresh grid and fresh tables: never the caller's own
-                if ground.n_streams < len(sources):
-                    raise ValueError("ground: a map of %d streams for %d sources" % (ground.n_streams, len(sources)))
-                ground, ground_max_age, window = ground.specs[:max(len(sources), 1)], ground.max_age, ground.K
-            ground_dev = gp.DeviceGroundMap(ground, ground_max_age, window, max(len(sources), 1))
+        # the table stages (track_stage.py): fresh tables for this run, one per stream, never the caller's own; ValueError naming the
+        # stage for what the device refuses
+        stages = {name: fresh_stage(name, x, len(sources), *age)
+                  for name, x, *age in (("actions", self.action_id), ("zones", zones, zone_max_age), ("heatmap", heatmap, heatmap_max_age),
+                                        ("ground", ground, ground_max_age)) if x is not None}
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -680,21 +665,14 @@ class VideoDetector:
             det.model.set_batch_max(S * F)
         pipe = pl.MultiStreamPipeline(det.model, [self.tracker.clone() for _ in range(S)], det.thres, det.nms_thres, class_mask=self.class_mask,
                                       win_size=det.win_size, overlap=det.overlap, stream_win_sizes=stream_win_sizes)
-        if actions_dev is not None:
-            pipe.set_actions(actions_dev)
+        for name, dev in stages.items():
+            getattr(pipe, "set_" + name)(dev)
         if global_ids:
             pipe.set_identities(True, **memory)
-        if zones_dev is not None:
-            pipe.set_zones(zones_dev)
-        if heat_dev is not None:
-            pipe.set_heatmap(heat_dev)
-        if ground_dev is not None:
-            pipe.set_ground(ground_dev)
         self._stream_ground = [[] for _ in range(S)]
         self._stream_zone_events = [[] for _ in range(S)]
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
-        on = dict(timed=actions_dev is not None or zones_dev is not None or heat_dev is not None or ground_dev is not None,
-                  zones=zones_dev is not None, actions=actions_dev is not None, ground=ground_dev is not None)
+        on = dict({name: name in stages for name in STAGE_FRONTS}, timed=bool(stages))
         try:
             if self.device_overlay:                          # staged uploads, look-ahead, the output stage on the device
                 yield from self._detect_streams_device(pipe, sources, F, show_fps, mixed_sizes, on, lookahead=not global_ids)
@@ -717,8 +695,8 @@ class VideoDetector:
     def _streams_step(self, pipe, plan, times, blk, ahead, on):
         """One MultiStreamPipeline step over the processed frames of a planned step (uniform or mixed; times: their frame times;
         ahead: the next step's HBM buffer for its early detector pass, or None), and what the bookkeeping reads after it:
-        (outs, actions per frame or None, detections per frame or None).  on: which device stages run (timed, zones, actions,
-        ground)."""
+        (outs, actions per frame or None, detections per frame or None).  on: which device stages run (the stages' names, and
+        timed: any of them)."""
         n, outs = plan["n_proc"], []
         if n:
             if on["timed"]:
@@ -733,7 +711,7 @@ class VideoDetector:
             self._stream_zone_events = [[] for _ in self._stream_zone_events]
             for s, evs in zip(plan["streams"], pipe.last_zone_events() if n else []):
                 self._stream_zone_events[s].append(evs)
-        if on.get("ground"):                             # the records of this step's processed frames, per stream in time order
+        if on["ground"]:                                 # the records of this step's processed frames, per stream in time order
             self._stream_ground = [[] for _ in self._stream_ground]
             for s, rows in zip(plan["streams"], pipe.last_ground() if n else []):
                 self._stream_ground[s].append(rows)
@@ -826,63 +804,55 @@ class VideoDetector:
             raise ValueError("VideoDetector.stream_identities needs detect_streams(..., global_ids=True)")
         return pipe.last_identities(stream)
 
-    def _zones_pipe(self, who):
+    def _stage_pipe(self, who, name):
+        """The pipe of the running generator for a reader of the stage ``name``: ValueError outside the generator, and for one
+        started without the stage."""
         pipe = self._live_streams_pipe(who)
-        if getattr(pipe, "zones", None) is None:
-            raise ValueError("VideoDetector.%s needs detect_streams(..., zones=...)" % who)
+        if getattr(pipe, "heat" if name == "heatmap" else name, None) is None:
+            raise ValueError("VideoDetector.%s needs detect_streams(..., %s=...)" % (who, name))
         return pipe
+
+    def _stage_report(self, who, name, kept, stream):
+        """The last step's report of the stage as _streams_step kept it (attribute ``kept``: per stream an entry per processed
+        frame): one stream's list or all."""
+        self._stage_pipe(who, name)
+        per = getattr(self, kept)
+        if stream is None:
+            return [list(e) for e in per]
+        if int(stream) < 0 or int(stream) >= len(per):
+            raise ValueError("VideoDetector.%s: stream %d outside [0, %d)" % (who, int(stream), len(per)))
+        return list(per[int(stream)])
 
     def stream_zone_events(self, stream=None):
         """The zone events of the last step of the running detect_streams(zones=...) generator, between two of its yields
         (ValueError outside, and for a generator started without zones): for ``stream`` one entry per frame of it that the step
         processed, in time order - that frame's ``[(track_id, class_id, kind, zone or line name, t, dwell), ...]``, None where
         the detector returned None - or a list of such lists, one per stream; MultiStreamPipeline.last_zone_events."""
-        self._zones_pipe("stream_zone_events")
-        per = self._stream_zone_events
-        if stream is None:
-            return [list(e) for e in per]
-        if int(stream) < 0 or int(stream) >= len(per):
-            raise ValueError("VideoDetector.stream_zone_events: stream %d outside [0, %d)" % (int(stream), len(per)))
-        return list(per[int(stream)])
+        return self._stage_report("stream_zone_events", "zones", "_stream_zone_events", stream)
 
     def stream_zone_counts(self, stream=None):
         """The zone and line counters of the running detect_streams(zones=...) generator, between two of its yields (ValueError
         outside, and for a generator started without zones): MultiStreamPipeline.zone_counts."""
-        return self._zones_pipe("stream_zone_counts").zone_counts(stream)
+        return self._stage_pipe("stream_zone_counts", "zones").zone_counts(stream)
 
     def stream_heatmaps(self, layer="presence", stream=None):
         """The heat maps of the running detect_streams(heatmap=...) generator, between two of its yields (ValueError outside, and
         for a generator started without heatmap): ``layer`` of ``stream`` as int64 [gh, gw], read from the device, or a list with
         one grid per stream; layer=None: all five layers [5, gh, gw]; MultiStreamPipeline.heatmap."""
-        pipe = self._live_streams_pipe("stream_heatmaps")
-        if getattr(pipe, "heat", None) is None:
-            raise ValueError("VideoDetector.stream_heatmaps needs detect_streams(..., heatmap=...)")
-        return pipe.heatmap(stream, layer)
-
-    def _ground_pipe(self, who):
-        pipe = self._live_streams_pipe(who)
-        if getattr(pipe, "ground", None) is None:
-            raise ValueError("VideoDetector.%s needs detect_streams(..., ground=...)" % who)
-        return pipe
+        return self._stage_pipe("stream_heatmaps", "heatmap").heatmap(stream, layer)
 
     def stream_ground(self, stream=None):
         """The ground records of the last step of the running detect_streams(ground=...) generator, between two of its yields
         (ValueError outside, and for a generator started without ground): for ``stream`` one entry per frame of it that the step
         processed, in time order - int32 [m, 8] = track id, class, qx, qy, vx, vy, speed, cell, None where the detector returned
         None - or a list of such lists, one per stream; MultiStreamPipeline.last_ground."""
-        self._ground_pipe("stream_ground")
-        per = self._stream_ground
-        if stream is None:
-            return [list(e) for e in per]
-        if int(stream) < 0 or int(stream) >= len(per):
-            raise ValueError("VideoDetector.stream_ground: stream %d outside [0, %d)" % (int(stream), len(per)))
-        return list(per[int(stream)])
+        return self._stage_report("stream_ground", "ground", "_stream_ground", stream)
 
     def site_map(self, layer="presence"):
         """The site grid of the running detect_streams(ground=...) generator, between two of its yields (ValueError outside, and
         for a generator started without ground): ``layer`` as int64 [gh, gw], read from the device; layer=None: all five layers
         [5, gh, gw]; MultiStreamPipeline.ground_layers."""
-        return self._ground_pipe("site_map").ground_layers(layer)
+        return self._stage_pipe("site_map", "ground").ground_layers(layer)
 
     def stream_identity_map(self):
         """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,

@@ -14,10 +14,12 @@ distortion model; the layers only ever grow (no decay).
 from __future__ import annotations
 
 import math
+from functools import partial
 
 import numpy as np
 
 from .heatmap import LAYERS, MAX_CELLS, check_alpha, check_lut, levels, render as _heat_render
+from .track_stage import GridStage, as_int, check_max_age, per_stream
 
 Q_LIMIT = 1 << 29                   # |px * scale| beyond this is off plane
 MAX_WINDOW = 16                     # YDS_GROUND_MAX_WINDOW
@@ -26,16 +28,8 @@ SAT = (1 << 31) - 1                 # vx, vy, speed saturate to +-SAT
 OUTSIDE, OFF_PLANE = -1, -2
 
 
-def _as_int(v, what):
-    if isinstance(v, (bool, float)) and int(v) != v or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"ground: {what} {v!r} is no integer")
-    return int(v)
-
-
-def _check_max_age(max_age):
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 1:
-        raise ValueError(f"ground: max_age {max_age!r} is no integer >= 1")
-    return int(max_age)
+_as_int = partial(as_int, "ground")
+_check_max_age = partial(check_max_age, "ground")
 
 
 def _quanta(v, scale, what):
@@ -146,14 +140,8 @@ def stream_specs(specs, n_streams):
     n_streams; all specs must share one plan.  ValueError naming ground otherwise."""
     if isinstance(specs, GroundMap):
         specs = specs.specs
-    if isinstance(specs, GroundSpec):
-        specs = [specs] * n_streams
-    try:
-        per = list(specs)
-    except TypeError:
-        per = None
-    if per is None or len(per) != n_streams or not all(s is None or isinstance(s, GroundSpec) for s in per):
-        raise ValueError(f"ground: specs is one GroundSpec or a list of {n_streams}, one (or None) per stream")
+    per = per_stream(specs, n_streams, lambda s: isinstance(s, GroundSpec),
+                     "ground: specs is one GroundSpec or a list of %d, one (or None) per stream", or_none=True)
     given = [s for s in per if s is not None]
     if not given:
         raise ValueError("ground: no stream has a spec")
@@ -364,80 +352,59 @@ def site_people(rows_by_stream, ids_by_stream):
     return out
 
 
-class DeviceGroundMap:
+class DeviceGroundMap(GridStage):
     """``GroundMap`` with the site grid and every table in HBM: one launch advances all streams over the frames of a call,
     ``render_plan`` / ``render_view`` blend a site layer into a canvas / into camera frames resident in HBM.  ``specs``: one
     GroundSpec for all streams, or a list with one (or None) per stream."""
+    NAME = LIB = "ground"
+    HOST = GroundMap
+    LAYERS = LAYERS
 
     def __init__(self, specs, max_age=30, speed_window=8, n_streams=None):
         if n_streams is None:
             n_streams = 1 if isinstance(specs, GroundSpec) else len(specs.specs if isinstance(specs, GroundMap) else specs)
-        self.n_streams = int(n_streams)
-        if self.n_streams < 1:
-            raise ValueError(f"ground: {n_streams} streams")
-        self.max_age, self.K = _check_max_age(max_age), _check_window(speed_window)
+        super().__init__(n_streams, max_age)
+        self.K = _check_window(speed_window)
         self.specs = stream_specs(specs, self.n_streams)
         self.plan = next(s for s in self.specs if s is not None)
         self.gw, self.gh = self.plan.gw, self.plan.gh
-        self._h = None
+
+    def _settings(self, n_streams):
+        return self.specs[:n_streams], self.max_age, self.K, n_streams
+
+    def _what(self):
+        return "a map"
 
     def host(self):
         """A fresh GroundMap of these specs, max_age and speed_window: the comparator."""
         return GroundMap(self.specs, self.max_age, self.K)
 
-    @property
-    def handle(self):
-        """The yds_ground handle, created on first use."""
-        if self._h is None:
-            from . import _lib
-            _lib.init()
-            lib = _lib.load()
-            p = self.plan
-            h = _lib.check_ptr(lib.yds_ground_create(self.n_streams, self.max_age, self.K, p.ox_q, p.oy_q, p.cell_q, p.gw, p.gh, p.scale))
-            try:
-                for s, sp in enumerate(self.specs):
-                    if sp is not None:
-                        _lib.check(lib.yds_ground_set_stream(h, s, _lib.ptr(np.ascontiguousarray(sp.H.reshape(9))), sp.class_id))
-            except Exception:
-                lib.yds_ground_destroy(h)
-                raise
-            self._h = h
-        return self._h
+    def _create(self, lib):
+        p = self.plan
+        return lib.yds_ground_create(self.n_streams, self.max_age, self.K, p.ox_q, p.oy_q, p.cell_q, p.gw, p.gh, p.scale)
 
-    def _stream(self, stream):
-        s = int(stream)
-        if s < 0 or s >= self.n_streams:
-            raise ValueError(f"ground: stream {s} outside [0, {self.n_streams})")
-        return s
+    def _setup(self, lib, h):
+        from . import _lib
+        for s, sp in enumerate(self.specs):
+            if sp is not None:
+                _lib.check(lib.yds_ground_set_stream(h, s, _lib.ptr(np.ascontiguousarray(sp.H.reshape(9))), sp.class_id))
 
     def update_batch(self, frames_rows, stream_of, times):
         """Frames in the order given (a stream's frames in time order), frame f of stream ``stream_of[f]`` at time ``times[f]``;
         a frame whose rows are None is not seen.  Returns per frame its records int32 [m][8] (None for a None frame)."""
         import ctypes as C
         from . import _lib
-        live = [f for f in range(len(frames_rows)) if frames_rows[f] is not None]
+        live, rows6, first, sof, tm = self.pack(frames_rows, stream_of, times)
         out = [None] * len(frames_rows)
         if not live:
             return out
-        rows = [np.asarray(frames_rows[f], dtype=np.int64).reshape(-1, 6) if len(frames_rows[f]) else np.zeros((0, 6), np.int64) for f in live]
-        if any(r.size and np.abs(r).max() >= 2 ** 31 for r in rows):
-            raise ValueError("ground: a row value does not fit 32 bits")
         n = len(live)
-        first = np.zeros(n + 1, np.int32)
-        first[1:] = np.cumsum([len(r) for r in rows])
-        rows6 = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32)
-        sof = np.ascontiguousarray([self._stream(stream_of[f]) for f in live], dtype=np.int32)
-        tm = np.ascontiguousarray([times[f] for f in live], dtype=np.float64)
         out8, first_out, m = np.zeros((max(len(rows6), 1), 8), np.int32), np.zeros(n + 1, np.int32), C.c_int(0)
         _lib.check(_lib.load().yds_ground_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(tm), n, _lib.ptr(out8),
                                                  _lib.ptr(first_out), len(out8), C.byref(m)))
         for k, f in enumerate(live):
             out[f] = out8[first_out[k]:first_out[k + 1]].copy()
         return out
-
-    def update(self, stream, rows, t):
-        """One frame of one stream: ``GroundMap.update(stream, rows, t)``."""
-        return self.update_batch([rows], [stream], [t])[0]
 
     def layers(self):
         """GroundMap.layers(), read from the device."""
@@ -447,102 +414,41 @@ class DeviceGroundMap:
         return out
 
     def layer(self, name):
-        if name not in LAYERS:
-            raise ValueError(f"ground: layer {name!r} is not one of {LAYERS}")
-        return self.layers()[LAYERS.index(name)]
+        k = self._layer(name)
+        return self.layers()[k]
 
     def max(self, name):
         """GroundMap.max(name), reduced on the device."""
-        import ctypes as C
-        from . import _lib
-        if name not in LAYERS:
-            raise ValueError(f"ground: layer {name!r} is not one of {LAYERS}")
-        v = C.c_int64(0)
-        _lib.check(_lib.load().yds_ground_get_max(self.handle, LAYERS.index(name), C.byref(v)))
-        return int(v.value)
+        return self._read_max(name)
 
     def tracks(self, stream=0):
         """GroundMap.tracks(stream), read from the device."""
-        import ctypes as C
-        from . import _lib
-        lib, n, s, K = _lib.load(), C.c_int(0), self._stream(stream), self.K
-        _lib.check(lib.yds_ground_get_tracks(self.handle, s, None, None, None, None, None, None, None, None, 1 << 30, C.byref(n)))
-        m = max(n.value, 1)
-        ids, ages, cells, lens = (np.zeros(m, np.int32) for _ in range(4))
-        trav, tl, rxy, rt = np.zeros(m, np.int64), np.zeros(m), np.zeros((m, K, 2), np.int32), np.zeros((m, K))
-        _lib.check(lib.yds_ground_get_tracks(self.handle, s, _lib.ptr(ids), _lib.ptr(ages), _lib.ptr(cells), _lib.ptr(lens), _lib.ptr(trav),
-                                             _lib.ptr(tl), _lib.ptr(rxy), _lib.ptr(rt), m, C.byref(n)))
+        i32, K = (np.int32, ()), self.K
+        ids, ages, cells, lens, trav, tl, rxy, rt = self._read_table("tracks", stream, [i32, i32, i32, i32, (np.int64, ()), (np.float64, ()),
+                                                                                        (np.int32, (K, 2)), (np.float64, (K,))])
         return [(int(ids[k]), int(ages[k]), int(cells[k]), int(trav[k]), float(tl[k]),
-                 tuple((int(rxy[k, i, 0]), int(rxy[k, i, 1]), float(rt[k, i])) for i in range(int(lens[k])))) for k in range(n.value)]
-
-    def reset(self, stream=None):
-        """An empty table for one stream (the site grid stands), or all tables and a zero grid."""
-        from . import _lib
-        if self._h is not None:
-            _lib.check(_lib.load().yds_ground_reset(self._h, -1 if stream is None else int(stream)))
+                 tuple((int(rxy[k, i, 0]), int(rxy[k, i, 1]), float(rt[k, i])) for i in range(int(lens[k])))) for k in range(len(ids))]
 
     def render_plan(self, canvas_dev, cell_px=8, layer="presence", vmax=0, alpha=256, lut=None):
         """canvas_dev: device pointer of a uint8 canvas of gh * cell_px x gw * cell_px x 3 bytes.  Bit-equal to
         heatmap.render(canvas, layer grid, cell_px, ...).  Synchronous."""
         from . import _lib
-        if layer not in LAYERS:
-            raise ValueError(f"ground: layer {layer!r} is not one of {LAYERS}")
-        _lib.check(_lib.load().yds_ground_render_plan(self.handle, canvas_dev, _as_int(cell_px, "cell_px"), LAYERS.index(layer), _as_int(vmax, "vmax"),
+        _lib.check(_lib.load().yds_ground_render_plan(self.handle, canvas_dev, _as_int(cell_px, "cell_px"), self._layer(layer), _as_int(vmax, "vmax"),
                                                       _as_int(alpha, "alpha"), _lib.ptr(check_lut(lut))))
 
     def render_view(self, frames_dev, slots, stream_of, h, w, layer="presence", vmax=0, alpha=128, lut=None, n_frames=None):
         """frames_dev: device pointer of uint8 frames h*w*3 bytes apart; frame slots[i] is a picture of camera stream_of[i] and takes
         the site layer onto its floor.  Slots must be distinct and inside [0, n_frames) (default: max slot + 1).  Bit-equal to
         render_view() with that stream's spec.  Synchronous."""
-        from . import _lib
-        slots_a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        sof = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
-        if len(slots_a) != len(sof):
-            raise ValueError("ground: %d slots for %d streams" % (len(slots_a), len(sof)))
-        if layer not in LAYERS:
-            raise ValueError(f"ground: layer {layer!r} is not one of {LAYERS}")
-        if len(slots_a) == 0:
-            return
-        n_src = int(slots_a.max()) + 1 if n_frames is None else int(n_frames)
-        _lib.check(_lib.load().yds_ground_render_view(self.handle, frames_dev, n_src, _lib.ptr(slots_a), _lib.ptr(sof), len(slots_a), int(h), int(w),
-                                                      LAYERS.index(layer), _as_int(vmax, "vmax"), _as_int(alpha, "alpha"), _lib.ptr(check_lut(lut))))
+        self._render("render_view", frames_dev, slots, stream_of, h, w, layer, vmax, alpha, lut, n_frames)
 
-    def set_timing(self, on=True):
-        from . import _lib
-        _lib.check(_lib.load().yds_ground_set_timing(self.handle, 1 if on else 0))
-
-    def last_us(self, what="update"):
-        """Device time of the last timed update launch or render (levels + pixels) in microseconds (set_timing first)."""
-        import ctypes as C
-        from . import _lib
-        if what not in ("update", "render"):
-            raise ValueError("ground: last_us of 'update' or 'render'")
-        us = C.c_float(0)
-        _lib.check(_lib.load().yds_ground_last_us(self.handle, 0 if what == "update" else 1, C.byref(us)))
-        return us.value
-
-    def close(self):
-        if self._h is not None:
-            from . import _lib
-            _lib.load().yds_ground_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    @classmethod
+    def _from_host(cls, x, n_streams, max_age):
+        if isinstance(x, GroundMap):
+            if x.n_streams != n_streams:
+                raise ValueError(f"ground: a GroundMap of {x.n_streams} streams for {n_streams} streams")
+            return cls(x.specs, x.max_age, x.K, n_streams)
+        return cls(x, max_age, n_streams=n_streams)
 
 
-def as_device_ground(x, n_streams, max_age=30):
-    """``x`` (a DeviceGroundMap of at least n_streams streams, a GroundMap, one GroundSpec or a list of them / None) as a
-    DeviceGroundMap; ValueError naming ground for anything else."""
-    if isinstance(x, DeviceGroundMap):
-        if x.n_streams < n_streams:
-            raise ValueError(f"ground: a DeviceGroundMap of {x.n_streams} streams for {n_streams} streams")
-        return x
-    if isinstance(x, GroundMap):
-        if x.n_streams != n_streams:
-            raise ValueError(f"ground: a GroundMap of {x.n_streams} streams for {n_streams} streams")
-        return DeviceGroundMap(x.specs, x.max_age, x.K, n_streams)
-    return DeviceGroundMap(x, max_age, n_streams=n_streams)
+as_device_ground = DeviceGroundMap.as_device      # (the name Pipeline.set_ground and callers import; track_stage.TrackStage.as_device is the rule)

@@ -14,8 +14,11 @@ to the caller (``render`` on the host) - the device render is for callers who ke
 
 from __future__ import annotations
 
+from functools import partial
+
 import numpy as np
 
+from .track_stage import GridStage, as_int, check_max_age, per_stream
 from .zones import anchor
 
 CELLS = (4, 8, 16, 32, 64, 128)     # allowed cell edges in pixels
@@ -25,10 +28,8 @@ RENDERABLE = LAYERS[:3]
 VMAX_LIMIT = 1 << 47                # YDS_HEATMAP_VMAX_LIMIT: a level is (v * 65535) // vmax in int64
 
 
-def _as_int(v, what):
-    if isinstance(v, (bool, float)) and int(v) != v or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"heatmap: {what} {v!r} is no integer")
-    return int(v)
+_as_int = partial(as_int, "heatmap")
+_check_max_age = partial(check_max_age, "heatmap")
 
 
 class HeatSpec:
@@ -58,12 +59,6 @@ class HeatSpec:
 
     def __repr__(self):
         return "HeatSpec(h=%d, w=%d, cell=%d, class_id=%d)" % self.astuple()
-
-
-def _check_max_age(max_age):
-    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 1:
-        raise ValueError(f"heatmap: max_age {max_age!r} is no integer >= 1")
-    return int(max_age)
 
 
 class HeatMap:
@@ -247,84 +242,50 @@ def stream_specs(specs, n_streams):
     n_streams specs; ValueError naming heatmap otherwise."""
     if isinstance(specs, HeatMap):
         specs = specs.spec
-    if isinstance(specs, HeatSpec):
-        return [specs] * n_streams
-    try:
-        per = list(specs)
-    except TypeError:
-        per = None
-    if per is None or len(per) != n_streams or not all(isinstance(s, HeatSpec) for s in per):
-        raise ValueError(f"heatmap: specs is one HeatSpec or a list of {n_streams}, one per stream")
-    return per
+    return per_stream(specs, n_streams, lambda s: isinstance(s, HeatSpec), "heatmap: specs is one HeatSpec or a list of %d, one per stream")
 
 
-class DeviceHeatMap:
+class DeviceHeatMap(GridStage):
     """``HeatMap`` for ``n_streams`` video streams with every layer and table in HBM: one launch advances the maps of all streams
     over the frames of a call, and ``render`` blends a layer into frames that are resident in HBM.  ``specs``: one HeatSpec for
     all streams, or a list with one per stream."""
+    NAME = LIB = "heatmap"
+    HOST = HeatMap
+    LAYERS = LAYERS
 
     def __init__(self, specs, max_age=30, n_streams=1):
-        self.n_streams = int(n_streams)
-        if self.n_streams < 1:
-            raise ValueError(f"heatmap: {n_streams} streams")
-        self.max_age = _check_max_age(max_age)
+        super().__init__(n_streams, max_age)
         self.specs = stream_specs(specs, self.n_streams)
-        self._h = None
+
+    def _settings(self, n_streams):
+        return self.specs[:n_streams], self.max_age, n_streams
 
     def host(self, stream=0):
         """A fresh HeatMap of one stream's spec and this max_age: the comparator."""
         return HeatMap(self.specs[stream], self.max_age)
 
-    @property
-    def handle(self):
-        """The yds_heatmap handle, created (and its grids allocated) on first use."""
-        if self._h is None:
-            from . import _lib
-            _lib.init()
-            lib = _lib.load()
-            h = _lib.check_ptr(lib.yds_heatmap_create(self.n_streams, self.max_age))
-            try:
-                for s, sp in enumerate(self.specs):
-                    _lib.check(lib.yds_heatmap_set_stream(h, s, sp.h, sp.w, sp.cell, sp.class_id))
-            except Exception:
-                lib.yds_heatmap_destroy(h)
-                raise
-            self._h = h
-        return self._h
+    def _create(self, lib):
+        return lib.yds_heatmap_create(self.n_streams, self.max_age)
 
-    def _stream(self, stream):
-        s = int(stream)
-        if s < 0 or s >= self.n_streams:
-            raise ValueError(f"heatmap: stream {s} outside [0, {self.n_streams})")
-        return s
+    def _setup(self, lib, h):
+        from . import _lib
+        for s, sp in enumerate(self.specs):
+            _lib.check(lib.yds_heatmap_set_stream(h, s, sp.h, sp.w, sp.cell, sp.class_id))
 
     def update_batch(self, frames_rows, stream_of, times):
         """Frames in the order given (a stream's frames in time order), frame f of stream ``stream_of[f]`` at time ``times[f]``;
         a frame whose rows are None is not seen.  Returns per frame the number of rows counted (None for a None frame)."""
         from . import _lib
-        live = [f for f in range(len(frames_rows)) if frames_rows[f] is not None]
+        live, rows6, first, sof, tm = self.pack(frames_rows, stream_of, times)
         out = [None] * len(frames_rows)
         if not live:
             return out
-        rows = [np.asarray(frames_rows[f], dtype=np.int64).reshape(-1, 6) if len(frames_rows[f]) else np.zeros((0, 6), np.int64) for f in live]
-        if any(r.size and np.abs(r).max() >= 2 ** 31 for r in rows):
-            raise ValueError("heatmap: a row value does not fit 32 bits")
-        n = len(live)
-        first = np.zeros(n + 1, np.int32)
-        first[1:] = np.cumsum([len(r) for r in rows])
-        rows6 = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32)
-        sof = np.ascontiguousarray([self._stream(stream_of[f]) for f in live], dtype=np.int32)
-        tm = np.ascontiguousarray([times[f] for f in live], dtype=np.float64)
-        counted = np.zeros(n, np.int32)
-        _lib.check(_lib.load().yds_heatmap_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(tm), n,
+        counted = np.zeros(len(live), np.int32)
+        _lib.check(_lib.load().yds_heatmap_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(tm), len(live),
                                                   _lib.ptr(counted)))
         for k, f in enumerate(live):
             out[f] = int(counted[k])
         return out
-
-    def update(self, stream, rows, t):
-        """One frame of one stream: ``HeatMap.update(rows, t)`` (None in, None out, nothing touched)."""
-        return self.update_batch([rows], [stream], [t])[0]
 
     def layers(self, stream=0):
         """HeatMap.layers() of one stream, read from the device."""
@@ -335,89 +296,24 @@ class DeviceHeatMap:
         return out
 
     def layer(self, stream, name):
-        if name not in LAYERS:
-            raise ValueError(f"heatmap: layer {name!r} is not one of {LAYERS}")
-        return self.layers(stream)[LAYERS.index(name)]
+        k = self._layer(name)
+        return self.layers(stream)[k]
 
     def max(self, stream, name):
         """HeatMap.max(name) of one stream, reduced on the device."""
-        import ctypes as C
-        from . import _lib
-        if name not in LAYERS:
-            raise ValueError(f"heatmap: layer {name!r} is not one of {LAYERS}")
-        v = C.c_int64(0)
-        _lib.check(_lib.load().yds_heatmap_get_max(self.handle, self._stream(stream), LAYERS.index(name), C.byref(v)))
-        return int(v.value)
+        return self._read_max(name, self._stream(stream))
 
     def tracks(self, stream=0):
         """HeatMap.tracks() of one stream, read from the device."""
-        import ctypes as C
-        from . import _lib
-        lib, n, s = _lib.load(), C.c_int(0), self._stream(stream)
-        _lib.check(lib.yds_heatmap_get_tracks(self.handle, s, None, None, None, None, None, 1 << 30, C.byref(n)))
-        m = max(n.value, 1)
-        ids, ages, cells, xy, t = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 2), np.int32), np.zeros(m)
-        _lib.check(lib.yds_heatmap_get_tracks(self.handle, s, _lib.ptr(ids), _lib.ptr(ages), _lib.ptr(cells), _lib.ptr(xy), _lib.ptr(t), m,
-                                              C.byref(n)))
-        return [(int(ids[k]), int(ages[k]), int(cells[k]), int(xy[k, 0]), int(xy[k, 1]), float(t[k])) for k in range(n.value)]
-
-    def reset(self, stream=None):
-        """Zero layers and an empty table for one stream, or all of them."""
-        from . import _lib
-        if self._h is not None:
-            _lib.check(_lib.load().yds_heatmap_reset(self._h, -1 if stream is None else int(stream)))
+        i32 = (np.int32, ())
+        ids, ages, cells, xy, t = self._read_table("tracks", stream, [i32, i32, i32, (np.int32, (2,)), (np.float64, ())])
+        return [(int(ids[k]), int(ages[k]), int(cells[k]), int(xy[k, 0]), int(xy[k, 1]), float(t[k])) for k in range(len(ids))]
 
     def render(self, frames_dev, slots, stream_of, h, w, layer="presence", vmax=0, alpha=128, lut=None, n_frames=None):
         """frames_dev: device pointer of uint8 frames h*w*3 bytes apart; frame slots[i] takes the grid of stream stream_of[i],
         whose spec must be of h x w.  Slots must be distinct and inside [0, n_frames) (default: max slot + 1).  Bit-equal to
         render() of the same layer; the LUT's bytes as they land in memory.  Synchronous."""
-        from . import _lib
-        slots_a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        sof = np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
-        if len(slots_a) != len(sof):
-            raise ValueError("heatmap: %d slots for %d streams" % (len(slots_a), len(sof)))
-        if layer not in LAYERS:
-            raise ValueError(f"heatmap: layer {layer!r} is not one of {LAYERS}")
-        if len(slots_a) == 0:
-            return
-        n_src = int(slots_a.max()) + 1 if n_frames is None else int(n_frames)
-        _lib.check(_lib.load().yds_heatmap_render(self.handle, frames_dev, n_src, _lib.ptr(slots_a), _lib.ptr(sof), len(slots_a), int(h), int(w),
-                                                  LAYERS.index(layer), _as_int(vmax, "vmax"), _as_int(alpha, "alpha"), _lib.ptr(check_lut(lut))))
-
-    def set_timing(self, on=True):
-        from . import _lib
-        _lib.check(_lib.load().yds_heatmap_set_timing(self.handle, 1 if on else 0))
-
-    def last_us(self, what="update"):
-        """Device time of the last timed update launch or render (levels + pixels) in microseconds (set_timing first)."""
-        import ctypes as C
-        from . import _lib
-        if what not in ("update", "render"):
-            raise ValueError("heatmap: last_us of 'update' or 'render'")
-        us = C.c_float(0)
-        _lib.check(_lib.load().yds_heatmap_last_us(self.handle, 0 if what == "update" else 1, C.byref(us)))
-        return us.value
-
-    def close(self):
-        if self._h is not None:
-            from . import _lib
-            _lib.load().yds_heatmap_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._render("render", frames_dev, slots, stream_of, h, w, layer, vmax, alpha, lut, n_frames)
 
 
-def as_device_heatmap(x, n_streams, max_age=30):
-    """``x`` (a DeviceHeatMap of at least n_streams streams, a HeatMap, one HeatSpec or a list of them) as a DeviceHeatMap;
-    ValueError naming heatmap for anything else."""
-    if isinstance(x, DeviceHeatMap):
-        if x.n_streams < n_streams:
-            raise ValueError(f"heatmap: a DeviceHeatMap of {x.n_streams} streams for {n_streams} streams")
-        return x
-    if isinstance(x, HeatMap):
-        return DeviceHeatMap(x.spec, x.max_age, n_streams)
-    return DeviceHeatMap(x, max_age, n_streams)
+as_device_heatmap = DeviceHeatMap.as_device      # (the name Pipeline.set_heatmap and callers import; track_stage.TrackStage.as_device is the rule)

@@ -87,8 +87,8 @@ class Pipeline:
 
     def _run(self, n, select_next, call, streams=None):
         """One step of n frames: call(out, counts) is the library entry that fills int32 out [n,cap,6] and counts [n]; streams: the
-        stream of every frame (a multi-stream step), kept for last_zone_events()."""
-        self._zone_streams = None if streams is None else [int(v) for v in streams]
+        stream of every frame (a multi-stream step), kept for the per-stream readers of the stages' reports."""
+        self._step_streams = None if streams is None else [int(v) for v in streams]
         out = np.zeros((n, self.cap, 6), np.int32)
         counts = np.zeros(n, np.int32)
         if select_next is not None:
@@ -105,6 +105,37 @@ class Pipeline:
         return self._run(batch, select_next, lambda out, counts: _lib.load().yds_pipeline_step_host(
             self._h, _lib.ptr(frames), _lib.ptr(next_frames), h, w, batch, out, self.cap, counts))
 
+    def _set_stage(self, name, as_device, x, *max_age):
+        """One table stage of every following step (yds_pipeline_set_<name>): x as the stage's device object (track_stage.py
+        as_device), None = off.  The object is kept as self.actions / .zones / .heat / .ground: the handle lives while the
+        pipeline names it."""
+        dev = None if x is None else as_device(x, getattr(self, "n_streams", 1), *max_age)
+        _lib.check(getattr(_lib.load(), "yds_pipeline_set_" + name)(self._h, None if dev is None else dev.handle))
+        setattr(self, "heat" if name == "heatmap" else name, dev)
+        return dev
+
+    def _last_report(self, dev, entry, columns):
+        """The two-call read of a stage's report of the last step (yds_pipeline_last_<entry>: ask the count, then copy).  columns:
+        (dtype, width) each; returns (counts of the step, the columns cut to the items reported), or None when the stage is off
+        or no step ran."""
+        counts = getattr(self, "_last_counts", None)
+        if dev is None or counts is None:
+            return None
+        n, call = C.c_int(0), getattr(_lib.load(), "yds_pipeline_last_" + entry)
+        call(self._h, *[None] * len(columns), 0, C.byref(n))      # (asks for the count; refuses to copy when it is not 0)
+        cols = [np.zeros((max(n.value, 1), w) if w > 1 else max(n.value, 1), t) for t, w in columns]
+        _lib.check(call(self._h, *[_lib.ptr(c) for c in cols], len(cols[0]), C.byref(n)))
+        return counts, [c[:n.value] for c in cols]
+
+    def _per_stream(self, who, stream, one):
+        """one(s) for ``stream``, or for every stream as a list (the single-stream Pipeline: its one value)."""
+        n = getattr(self, "n_streams", 1)
+        if stream is None:
+            return [one(s) for s in range(n)] if hasattr(self, "n_streams") else one(0)
+        if int(stream) < 0 or int(stream) >= n:
+            raise ValueError("%s: stream %d outside [0, %d)" % (who, int(stream), n))
+        return one(int(stream))
+
     def set_actions(self, action_id=None):
         """The action stage of every following step (video_detect.py:151-152 on the device): ``action_id`` is an
         action.ActionIdentify (its actions and settings go to the device, fresh orbit caches, one per stream) or an
@@ -113,9 +144,7 @@ class Pipeline:
         return value does not change.  ValueError naming action_id for anything the device cannot run; refused (YdsError) while
         a look-ahead pass is in flight."""
         from .action import as_device_actions
-        dev = None if action_id is None else as_device_actions(action_id, getattr(self, "n_streams", 1))
-        _lib.check(_lib.load().yds_pipeline_set_actions(self._h, None if dev is None else dev.handle))
-        self.actions = dev                                  # (keeps the handle alive while the pipeline names it)
+        self._set_stage("actions", as_device_actions, action_id)
 
     def set_frame_times(self, times):
         """Times (seconds) of the frames of the NEXT step, one per frame: every row of a frame carries its frame's time in the
@@ -126,17 +155,14 @@ class Pipeline:
     def last_actions(self):
         """Per frame of the last step: ``[(track_id, class_id, name), ...]`` as ActionIdentify.update returns it, ``[]`` where
         nothing fired, None where the frame's rows were None (the stage did not see that frame).  Already on the host."""
-        dev, counts = getattr(self, "actions", None), getattr(self, "_last_counts", None)
-        if dev is None or counts is None:
+        dev = getattr(self, "actions", None)
+        got = self._last_report(dev, "actions", [(np.int32, 4)])
+        if got is None:
             return None
-        n = C.c_int(0)
-        lib = _lib.load()
-        lib.yds_pipeline_last_actions(self._h, None, 0, C.byref(n))      # (asks for the count; refuses to copy when it is not 0)
-        rows = np.zeros((max(n.value, 1), 4), np.int32)
-        _lib.check(lib.yds_pipeline_last_actions(self._h, _lib.ptr(rows), len(rows), C.byref(n)))
+        counts, (rows,) = got
         per = [None if counts[b] < 0 else [] for b in range(len(counts))]
-        for r in rows[:n.value]:
-            per[int(r[0])].append((int(r[1]), int(r[2]), dev.names[int(r[3])]))
+        for r in rows:
+            per[int(r[0])] += dev.name_rows([r])
         return per
 
     def last_detections(self):
@@ -166,27 +192,20 @@ class Pipeline:
         ``last_zone_events()`` holds its events; the step's own return value does not change.  ValueError naming zones for
         anything the device refuses; refused (YdsError) while a look-ahead pass is in flight."""
         from .zones import as_device_zones
-        dev = None if zones is None else as_device_zones(zones, getattr(self, "n_streams", 1), max_age)
-        _lib.check(_lib.load().yds_pipeline_set_zones(self._h, None if dev is None else dev.handle))
-        self.zones = dev                                    # (keeps the handle alive while the pipeline names it)
-        self._zone_streams = None
-        return dev
+        return self._set_stage("zones", as_device_zones, zones, max_age)
 
     def last_zone_events(self):
         """Per frame of the last step: ``[(track_id, class_id, kind, zone or line name (index without one), t, dwell), ...]`` as
         ZoneMonitor.update returns it, ``[]`` where nothing happened, None where the frame's rows were None (the stage did not
         see that frame).  Already on the host."""
-        dev, counts = getattr(self, "zones", None), getattr(self, "_last_counts", None)
-        if dev is None or counts is None:
+        dev = getattr(self, "zones", None)
+        got = self._last_report(dev, "zone_events", [(np.int32, 6), (np.float64, 2)])
+        if got is None:
             return None
-        n = C.c_int(0)
-        lib = _lib.load()
-        lib.yds_pipeline_last_zone_events(self._h, None, None, 0, C.byref(n))      # (asks for the count; refuses to copy when it is not 0)
-        ev6, evt2 = np.zeros((max(n.value, 1), 6), np.int32), np.zeros((max(n.value, 1), 2), np.float64)
-        _lib.check(lib.yds_pipeline_last_zone_events(self._h, _lib.ptr(ev6), _lib.ptr(evt2), len(ev6), C.byref(n)))
-        streams = getattr(self, "_zone_streams", None) or [0] * len(counts)
+        counts, (ev6, evt2) = got
+        streams = self._step_streams or [0] * len(counts)
         per = [None if counts[b] < 0 else [] for b in range(len(counts))]
-        for r, t in zip(ev6[:n.value], evt2[:n.value]):
+        for r, t in zip(ev6, evt2):
             b = int(r[0])
             per[b] += dev.name_events(streams[b], [r], [t])
         return per
@@ -195,14 +214,7 @@ class Pipeline:
         """(per zone [occupancy, entries, exits, lost], per line [forward, backward]) of ``stream``, read from the device, or a
         list of such pairs for all streams; None when the stage is off."""
         dev = getattr(self, "zones", None)
-        if dev is None:
-            return None
-        n = getattr(self, "n_streams", 1)
-        if stream is None:
-            return [dev.counts(s) for s in range(n)] if hasattr(self, "n_streams") else dev.counts(0)
-        if int(stream) < 0 or int(stream) >= n:
-            raise ValueError("zone_counts: stream %d outside [0, %d)" % (int(stream), n))
-        return dev.counts(int(stream))
+        return None if dev is None else self._per_stream("zone_counts", stream, dev.counts)
 
     def set_heatmap(self, heatmap=None, max_age=30):
         """The heat map stage of every following step: ``heatmap`` is a heatmap.DeviceHeatMap of at least as many streams as the
@@ -212,25 +224,14 @@ class Pipeline:
         does not change.  ValueError naming heatmap for anything the device refuses; refused (YdsError) while a look-ahead pass is
         in flight."""
         from .heatmap import as_device_heatmap
-        dev = None if heatmap is None else as_device_heatmap(heatmap, getattr(self, "n_streams", 1), max_age)
-        _lib.check(_lib.load().yds_pipeline_set_heatmap(self._h, None if dev is None else dev.handle))
-        self.heat = dev                                     # (keeps the handle alive while the pipeline names it)
-        return dev
+        return self._set_stage("heatmap", as_device_heatmap, heatmap, max_age)
 
     def heatmap(self, stream=None, layer=None):
         """The layers of ``stream`` as the last step left them, read from the device: int64 [5, gh, gw], or [gh, gw] for a named
         ``layer``; stream=None: a list with one such array per stream (the single-stream Pipeline: its one array).  None when the
         stage is off."""
         dev = getattr(self, "heat", None)
-        if dev is None:
-            return None
-        n = getattr(self, "n_streams", 1)
-        one = (lambda s: dev.layers(s)) if layer is None else (lambda s: dev.layer(s, layer))
-        if stream is None:
-            return [one(s) for s in range(n)] if hasattr(self, "n_streams") else one(0)
-        if int(stream) < 0 or int(stream) >= n:
-            raise ValueError("heatmap: stream %d outside [0, %d)" % (int(stream), n))
-        return one(int(stream))
+        return None if dev is None else self._per_stream("heatmap", stream, dev.layers if layer is None else (lambda s: dev.layer(s, layer)))
 
     def set_ground(self, ground=None, max_age=30):
         """The ground plane stage of every following step: ``ground`` is a ground.DeviceGroundMap of at least as many streams as the
@@ -240,29 +241,21 @@ class Pipeline:
         and ``ground_layers()`` reads the site grid; the step's own return value does not change.  ValueError naming ground for
         anything the device refuses; refused (YdsError) while a look-ahead pass is in flight."""
         from .ground import as_device_ground
-        dev = None if ground is None else as_device_ground(ground, getattr(self, "n_streams", 1), max_age)
-        _lib.check(_lib.load().yds_pipeline_set_ground(self._h, None if dev is None else dev.handle))
-        self.ground = dev                                   # (keeps the handle alive while the pipeline names it)
-        return dev
+        return self._set_stage("ground", as_device_ground, ground, max_age)
 
     def last_ground(self, stream=None):
         """The ground records of the last step, int32 [m, 8] = track id, class, qx, qy, vx, vy, speed, cell (cell -1: outside the
         grid, -2: off plane): a list with one array per frame of the step (None where the frame's rows were None), or with
         ``stream`` the records of that stream's frames of the step in time order as one array.  Already on the host; None when the
         stage is off or no step ran."""
-        dev, counts = getattr(self, "ground", None), getattr(self, "_last_counts", None)
-        if dev is None or counts is None:
+        got = self._last_report(getattr(self, "ground", None), "ground", [(np.int32, 8), (np.int32, 1)])
+        if got is None:
             return None
-        n = C.c_int(0)
-        lib = _lib.load()
-        lib.yds_pipeline_last_ground(self._h, None, None, 0, C.byref(n))       # (asks for the count; refuses to copy when it is not 0)
-        rows, frame = np.zeros((max(n.value, 1), 8), np.int32), np.zeros(max(n.value, 1), np.int32)
-        _lib.check(lib.yds_pipeline_last_ground(self._h, _lib.ptr(rows), _lib.ptr(frame), len(rows), C.byref(n)))
-        rows, frame = rows[:n.value], frame[:n.value]
+        counts, (rows, frame) = got
         per = [None if counts[b] < 0 else rows[frame == b].copy() for b in range(len(counts))]
         if stream is None:
             return per
-        streams = getattr(self, "_zone_streams", None) or [0] * len(counts)
+        streams = self._step_streams or [0] * len(counts)
         mine = [per[b] for b in range(len(counts)) if streams[b] == int(stream) and per[b] is not None]
         return np.concatenate(mine) if mine else np.zeros((0, 8), np.int32)
 
@@ -404,14 +397,8 @@ class MultiStreamPipeline(Pipeline):
         from .identity import _read_ids
         lib = _lib.load()
 
-        def one(s):
-            return _read_ids(lambda t, g, cap, n: lib.yds_pipeline_last_identities(self._h, s, t, g, cap, n))
-        if stream is None:
-            return [one(s) for s in range(self.n_streams)]
-        stream = int(stream)
-        if stream < 0 or stream >= self.n_streams:
-            raise ValueError("MultiStreamPipeline: stream %d outside [0, %d)" % (stream, self.n_streams))
-        return one(stream)
+        return self._per_stream("MultiStreamPipeline", stream, lambda s: _read_ids(
+            lambda t, g, cap, n: lib.yds_pipeline_last_identities(self._h, s, t, g, cap, n)))
 
     def _streams(self, stream_of_frame):
         s = np.ascontiguousarray(stream_of_frame, dtype=np.int32).reshape(-1)

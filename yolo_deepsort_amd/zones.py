@@ -12,6 +12,12 @@ Geometry is in the stream's frame pixels.  A row ``(x1, y1, x2, y2, id, class)``
 
 from __future__ import annotations
 
+from functools import partial
+
+from .track_stage import TrackStage, as_int, per_stream
+
+_as_int = partial(as_int, "zones")
+
 ENTER, EXIT, LOST, CROSS_FWD, CROSS_BACK = 0, 1, 2, 3, 4          # YDS_ZONE_* of include/ydsort.h
 KIND_NAMES = ("enter", "exit", "lost", "cross_fwd", "cross_back")
 MAX_ZONES = 32                  # YDS_ZONE_MAX_ZONES
@@ -37,16 +43,6 @@ class Line:
     def __init__(self, a, b, class_id=-1, name=None):
         self.a, self.b = tuple(a), tuple(b)
         self.class_id, self.name = class_id, name
-
-
-def _as_int(v, what):
-    try:
-        ok = int(v) == v
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"zones: {what} is {v!r}, not an integer")
-    return int(v)
 
 
 def _as_point(p, what):
@@ -285,55 +281,38 @@ def stream_geometries(geometry, n_streams):
     as a list of n_streams pairs; ValueError naming ``zones`` otherwise."""
     if isinstance(geometry, ZoneMonitor):
         geometry = geometry.geometry
-    if _is_pair(geometry):
-        return [(list(geometry[0]), list(geometry[1]))] * n_streams
-    try:
-        per = list(geometry)
-    except TypeError:
-        per = None
-    if per is None or len(per) != n_streams or not all(_is_pair(g) for g in per):
-        raise ValueError(f"zones: geometry is one (zones, lines) pair or a list of {n_streams} pairs, one per stream")
+    per = per_stream(geometry, n_streams, _is_pair, "zones: geometry is one (zones, lines) pair or a list of %d pairs, one per stream")
     return [(list(g[0]), list(g[1])) for g in per]
 
 
-class DeviceZoneMonitor:
+class DeviceZoneMonitor(TrackStage):
     """``ZoneMonitor`` for ``n_streams`` video streams with every table and counter in HBM: one launch advances the tables of all
     streams over the frames of a call.  ``geometry``: one (zones, lines) pair for all streams, or a list with one pair per
     stream; it travels to the device once, when the handle is made."""
+    NAME = LIB = "zones"
+    HOST = ZoneMonitor
 
     def __init__(self, geometry, max_age=30, n_streams=1):
-        self.n_streams = int(n_streams)
-        if self.n_streams < 1:
-            raise ValueError(f"zones: {n_streams} streams")
-        if int(max_age) != max_age or max_age < 1:
-            raise ValueError(f"zones: max_age {max_age!r} is no integer >= 1")
-        self.max_age = int(max_age)
+        super().__init__(n_streams, max_age)
         self.geometry = stream_geometries(geometry, self.n_streams)
         self.packed = [pack_geometry(z, ln) for z, ln in self.geometry]
-        self._h = None
+
+    def _settings(self, n_streams):
+        return self.geometry[:n_streams], self.max_age, n_streams
 
     def host(self, stream=0):
         """A fresh ZoneMonitor of one stream's geometry and this max_age: the comparator."""
         z, ln = self.geometry[stream]
         return ZoneMonitor(z, ln, self.max_age)
 
-    @property
-    def handle(self):
-        """The yds_zones handle, created (and its geometry uploaded) on first use."""
-        if self._h is None:
-            from . import _lib
-            _lib.init()
-            lib = _lib.load()
-            h = _lib.check_ptr(lib.yds_zones_create(self.n_streams, self.max_age))
-            try:
-                for s, g in enumerate(self.packed):
-                    _lib.check(lib.yds_zones_set_stream(h, s, _lib.ptr(g[0]), _lib.ptr(g[1]), _lib.ptr(g[2]), _lib.ptr(g[3]), len(g[2]),
-                                                        _lib.ptr(g[4]), _lib.ptr(g[5]), len(g[5])))
-            except Exception:
-                lib.yds_zones_destroy(h)
-                raise
-            self._h = h
-        return self._h
+    def _create(self, lib):
+        return lib.yds_zones_create(self.n_streams, self.max_age)
+
+    def _setup(self, lib, h):
+        from . import _lib
+        for s, g in enumerate(self.packed):
+            _lib.check(lib.yds_zones_set_stream(h, s, _lib.ptr(g[0]), _lib.ptr(g[1]), _lib.ptr(g[2]), _lib.ptr(g[3]), len(g[2]),
+                                                _lib.ptr(g[4]), _lib.ptr(g[5]), len(g[5])))
 
     def name_events(self, stream, ev6, evt2):
         """Event rows of one stream's frame as ZoneMonitor.update returns them."""
@@ -347,36 +326,22 @@ class DeviceZoneMonitor:
         import ctypes as C
         import numpy as np
         from . import _lib
-        live = [f for f in range(len(frames_rows)) if frames_rows[f] is not None]
+        live, rows6, first, sof, tm = self.pack(frames_rows, stream_of, times)
         out = [None] * len(frames_rows)
         if not live:
             return out
-        rows = [np.asarray(frames_rows[f], dtype=np.int64).reshape(-1, 6) if len(frames_rows[f]) else np.zeros((0, 6), np.int64) for f in live]
-        if any(r.size and np.abs(r).max() >= 2 ** 31 for r in rows):
-            raise ValueError("zones: a row value does not fit 32 bits")
-        n = len(live)
-        first = np.zeros(n + 1, np.int32)
-        first[1:] = np.cumsum([len(r) for r in rows])
-        rows6 = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32)
-        sof = np.ascontiguousarray([stream_of[f] for f in live], dtype=np.int32)
-        tm = np.ascontiguousarray([times[f] for f in live], dtype=np.float64)
-        lib, h = _lib.load(), self.handle
         # the most events the call can emit: every entry a frame can meet (the table before the call + the rows so far), at each
         # of its stream's zones and lines
-        held, cap = {}, 1
+        n, held, cap = len(live), {}, 1
         for k in range(n):
             s = int(sof[k])
-            if s < 0 or s >= self.n_streams:
-                raise ValueError(f"zones: frame {live[k]} names stream {s} outside [0, {self.n_streams})")
             if s not in held:
-                c = C.c_int(0)
-                _lib.check(lib.yds_zones_get_tracks(h, s, None, None, None, 1 << 30, C.byref(c)))
-                held[s] = c.value
-            held[s] += len(rows[k])
+                held[s] = self._table_count("tracks", s, 3)
+            held[s] += int(first[k + 1] - first[k])
             cap += held[s] * (len(self.packed[s][2]) + len(self.packed[s][5]))
         ev6, evt2, m = np.zeros((cap, 6), np.int32), np.zeros((cap, 2), np.float64), C.c_int(0)
-        _lib.check(lib.yds_zones_update(h, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(tm), n, _lib.ptr(ev6), _lib.ptr(evt2),
-                                        cap, C.byref(m)))
+        _lib.check(_lib.load().yds_zones_update(self.handle, _lib.ptr(rows6), _lib.ptr(first), _lib.ptr(sof), _lib.ptr(tm), n, _lib.ptr(ev6),
+                                                _lib.ptr(evt2), cap, C.byref(m)))
         per = [([], []) for _ in range(n)]
         for r, t in zip(ev6[:m.value], evt2[:m.value]):
             per[int(r[0])][0].append(r)
@@ -384,10 +349,6 @@ class DeviceZoneMonitor:
         for k, f in enumerate(live):
             out[f] = self.name_events(int(sof[k]), *per[k])
         return out
-
-    def update(self, stream, rows, t):
-        """One frame of one stream: ``ZoneMonitor.update(rows, t)`` (None in, None out, nothing touched)."""
-        return self.update_batch([rows], [stream], [t])[0]
 
     def counts(self, stream=0):
         """ZoneMonitor.counts() of one stream, read from the device."""
@@ -400,56 +361,12 @@ class DeviceZoneMonitor:
 
     def tracks(self, stream=0):
         """ZoneMonitor.tracks() of one stream, read from the device."""
-        import ctypes as C
         import numpy as np
-        from . import _lib
-        lib, n = _lib.load(), C.c_int(0)
-        _lib.check(lib.yds_zones_get_tracks(self.handle, int(stream), None, None, None, 1 << 30, C.byref(n)))
-        ids, ages, mask = (np.zeros(max(n.value, 1), np.int32) for _ in range(3))
-        _lib.check(lib.yds_zones_get_tracks(self.handle, int(stream), _lib.ptr(ids), _lib.ptr(ages), _lib.ptr(mask), len(ids), C.byref(n)))
-        return [(int(ids[k]), int(ages[k]), int(mask.view(np.uint32)[k])) for k in range(n.value)]
-
-    def reset(self, stream=None):
-        """Empty tables and zero counters for one stream, or all of them."""
-        from . import _lib
-        if self._h is not None:
-            _lib.check(_lib.load().yds_zones_reset(self._h, -1 if stream is None else int(stream)))
-
-    def set_timing(self, on=True):
-        from . import _lib
-        _lib.check(_lib.load().yds_zones_set_timing(self.handle, 1 if on else 0))
-
-    def last_us(self):
-        """Device time of the last timed launch in microseconds (set_timing first)."""
-        import ctypes as C
-        from . import _lib
-        us = C.c_float(0)
-        _lib.check(_lib.load().yds_zones_last_us(self.handle, C.byref(us)))
-        return us.value
-
-    def close(self):
-        if self._h is not None:
-            from . import _lib
-            _lib.load().yds_zones_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ids, ages, mask = self._read_table("tracks", stream, [(np.int32, ())] * 3)
+        return list(zip(ids.tolist(), ages.tolist(), mask.view(np.uint32).tolist()))
 
 
-def as_device_zones(zones, n_streams, max_age=30):
-    """``zones`` (a DeviceZoneMonitor of at least n_streams streams, a ZoneMonitor, one (zones, lines) pair or a list of pairs)
-    as a DeviceZoneMonitor; ValueError naming ``zones`` for anything else."""
-    if isinstance(zones, DeviceZoneMonitor):
-        if zones.n_streams < n_streams:
-            raise ValueError(f"zones: a DeviceZoneMonitor of {zones.n_streams} streams for {n_streams} streams")
-        return zones
-    if isinstance(zones, ZoneMonitor):
-        return DeviceZoneMonitor(zones.geometry, zones.max_age, n_streams)
-    return DeviceZoneMonitor(zones, max_age, n_streams)
+as_device_zones = DeviceZoneMonitor.as_device      # (the name Pipeline.set_zones and callers import; track_stage.TrackStage.as_device is the rule)
 
 
 class VisitorLog:
