@@ -153,3 +153,46 @@ def test_fused_half_construction_is_exact():
             for f16 in (False, True):
                 with pytest.raises(AssertionError, match="above mut / 16"):
                     G._hold(G._FusedWorst(), hr.kind, hr.case, R.x_hat(mutant) if f16 else mutant, a, f16=f16)
+
+
+# ---- the fused kernels in half mode on generic operands (test_fused_half_mode_on_generic_operands) -------------------------------------
+_GENERIC = [(kind, i) for kind in ("stem2", "block1") for i in range(len(R.FUSED_GENERIC_CASES[kind]))]
+
+
+@pytest.mark.parametrize("kind,i", _GENERIC, ids=[kind + "-" + "x".join(str(c) for c in R.FUSED_GENERIC_CASES[kind][i][:4]) for kind, i in _GENERIC])
+def test_fused_generic_bound_admits_the_kernel_and_no_mutant(kind, i):
+    """conv_ref.FusedHalfGenericRef, every case, both tensor formats.
+    (a) The emulated kernel - stage one by the fp32 CPU convolution, activation, rounded to fp32 and then to the hi half; stage two in
+        float64 on the rounded operands, rounded to fp32 and, for F16, into that format - passes `_hold_bound`, and every intermediate
+        it rounds to the other neighbour is one the reference calls ambiguous.
+    (b) Every mutant fails `_hold_bound` on its bound: as the float64 tensor against the H16 bound, stored as F16 against the F16 one.
+    (c) The widening stays rare, which is what keeps it from hiding a failure: at most 10 % of the outputs have a bound above mut / 2
+        (an F16 output's own half spacing aside), at most 25 % of the intermediates are ambiguous.  Conditions on the inputs, no tolerances.
+    (d) Stem: fp16 holds the layer-0 bias in at most 2 of 32 channels, and the kernel that adds the fp32 bias is one of the mutants."""
+    import test_gpu_conv_fused as G
+    r = R.fused_generic_refs(kind)[i]
+    assert r.case == R.FUSED_GENERIC_CASES[kind][i]
+    flips, outside = r.flips()
+    over = float((r.mut / 16 + r.widen > r.mut / 2).mean())
+    print(f"{kind} {r.case}: mut {r.mut:.2e}, {r.amb.mean():.1%} ambiguous, {over:.1%} of the outputs bounded above mut/2, the emulation flips {flips} "
+          f"intermediates ({outside} outside the ambiguous set) | mutants / mut " + ", ".join(f"{k} {v / r.mut:.1f}" for k, v in r.mutant_err.items()))
+    assert r.mut > 0 and np.isfinite(r.mut)
+    assert outside == 0, (kind, r.case, outside)                                                       # (a)
+    assert over <= 0.10 and r.amb.mean() <= 0.25, (kind, r.case, over, r.amb.mean())                   # (c)
+    assert set(r.mutant_err) == set(r.mutants) and ("ba fp32" in r.mutants) == (kind == "stem2")       # (d)
+    if kind == "stem2":
+        assert (R._f16(r.ba) != r.ba).sum() >= 30 and not np.array_equal(r.bias1, r.ba)
+    else:
+        assert np.array_equal(r.bias1, r.ba)
+    cores = {name: r.mutant_core(name) for name in r.mutants}
+    for fmt in (R.FMT_AUTO, R.FMT_F16):
+        a = r.half(fmt)
+        assert r.mut < 1e-3 * a.scale                                   # every mutant's smallest error passes the older bar
+        worst = G._BoundWorst()
+        G._hold_bound(worst, kind, r.case, a.fp32, a)                                                  # (a)
+        print(f"  fmt {fmt}: the emulation at {worst.rows[kind][0]:.2f} of the bound; mutants' violations / worst ratio " +
+              ", ".join(f"{k} {a.violations(v + r.shortcut(fmt)):.0%} / {a.ratio(v + r.shortcut(fmt)):.1f}" for k, v in cores.items()))
+        for name, core in cores.items():                                                               # (b)
+            m = core + r.shortcut(fmt)
+            with pytest.raises(AssertionError, match="above their bound"):
+                G._hold_bound(G._BoundWorst(), kind, (r.case, name), R.x_hat(m) if fmt == R.FMT_F16 else m, a)

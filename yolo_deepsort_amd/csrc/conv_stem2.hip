@@ -53,6 +53,9 @@ __device__ __forceinline__ int patch_row(int ry, int rc) {      // LDS row of la
 
 // HALF (Darknet.half(), round 4): single-term fp16 operands in both layers - one MFMA per product block instead of three, the
 // patch rows carry hi halves only (no lo encode in phase A: 7 instead of 14 vector instructions per layer-0 value).
+// The bias rule in HALF: layer 0's bias is an MFMA operand (w0h / w0l below), and only the hi product runs, so layer 0 adds the
+// SINGLE-TERM fp16(bias) (|bias| < 65504), not the fp32 bias; layer 1's bias is added in fp32 by the shared epilogue, as conv_block1.hip
+// adds both of its biases.  tests/conv_ref.py (FusedHalfGenericRef) restates this, and the stem with an fp32 bias is one of its mutants.
 template <int ACT0, int ACT1, bool HALF>
 __global__ __launch_bounds__(NT, 1) void conv_stem2_f16x3(ConvKernelArgs p0, ConvKernelArgs p1, int tiles_y, int tiles_x, int n_tiles) {
     fp16_saturate_on();
