@@ -849,6 +849,77 @@ int yds_ground_last_us(yds_ground *, int what, float *us);
 int yds_pipeline_set_ground(yds_pipe *, yds_ground *);
 int yds_pipeline_last_ground(yds_pipe *, int32_t *rows8_host, int32_t *frame_host, int cap, int *n_out);
 
+/* ---- track snapshots: each track's best crop, kept and chosen on the device --------------------------------------------------------
+ * No reference counterpart; yolo_deepsort_amd/snapshot.py (SnapshotBook) restates the rules below in numpy and Python ints and every
+ * comparison with it is exact equality.  All integer after the resize.
+ * 1. Spec.  Per handle: max_age >= 1 and archive in [0, YDS_SNAP_MAX_ARCHIVE], the ring slots PER STREAM (0: closed snapshots are
+ *    dropped).  Per stream: class_id >= -1 (-1 = any class; rows of another class are ignored entirely: no entry, no age effect),
+ *    min_w >= 1, min_h >= 1.  A stream without a spec is skipped: its frames report nothing and touch nothing.
+ * 2. Clipped box of a row (x1, y1, x2, y2), x2 and y2 exclusive, in a frame of H x W: xa = max(x1, 0), ya = max(y1, 0),
+ *    xb = min(x2, W), yb = min(y2, H); vw = xb - xa, vh = yb - ya; full = (x2 - x1) * (y2 - y1), vis = vw * vh, in 64 bits.  The row is
+ *    a CANDIDATE iff vw >= min_w, vh >= min_h and full > 0.  A row that is no candidate still counts as a sighting: it registers its
+ *    track and resets its age.
+ * 3. Thumbnail T[128][64][3]: the 8-bit bilinear resize of the ReID front end (csrc/resize_dev.h resize_px: cv2.resize INTER_LINEAR
+ *    bit for bit, its copy at equal sizes and the 2 x 2 mean at exactly twice the size included) of the region [ya, yb) x [xa, xb) to
+ *    128 rows x 64 columns.  Channels are stored R, G, B whatever the frame's order: a call's bgr flag swaps them.
+ * 4. Score.  Luma Y = (77 R + 150 G + 29 B + 128) >> 8; sharp = sum over 1 <= y <= 126, 1 <= x <= 62 of
+ *    |4 Y[y][x] - Y[y-1][x] - Y[y+1][x] - Y[y][x-1] - Y[y][x+1]| (at most 8.1e6); score = (sharp * vis) // full (64-bit product; the
+ *    result fits int32).  A box cut by the frame edge is discounted by its visible share.
+ * 5. Decision.  A stream's frames in time order, rows within a frame in row order.  An unknown id becomes a new entry at the end of
+ *    the table: score -1, no picture (an all-zero thumbnail, a zero box, tag_best -1, t_best 0), t_first = t.  Every sighting sets
+ *    age 0, t_last = t, class = the row's class and n_seen += 1.  A candidate replaces the entry's picture iff its score is STRICTLY
+ *    greater (a tie keeps the earlier sighting); a replacement sets score, box (the UNCLIPPED row box), t_best = t and tag_best = the
+ *    frame's tag.
+ * 6. Closing.  After a frame, entries not seen in it age by one (a frame the tracker was not called for is not seen by the stage; a
+ *    frame with zero rows ages every entry); an entry with age > max_age closes, in entry order, the others keeping their order.  With
+ *    a picture and archive > 0 it takes ring position closed_count[stream] % archive (overwriting what is there) and closed_count
+ *    advances; otherwise it vanishes.  An id that returns later is a new entry.
+ * 7. Report, per frame int32[6] items: tag, id, class, kind, score, aux.  YDS_SNAP_BEST: the entry's picture changed, aux = n_seen;
+ *    YDS_SNAP_CLOSED: aux = the ring position, -1 if the snapshot was dropped.  Within a frame BEST items in row order, then CLOSED
+ *    items in entry order.
+ * yds_snap_create       <- streams without a spec.          yds_snap_set_stream <- the spec of one stream; an empty table and ring.
+ * yds_snap_reset        <- an empty table, an empty ring and closed_count 0 for one stream, or for all (-1).
+ * yds_snap_update       <- n_frames frames in THREE launches (score, decide, commit) and one synchronisation: the frame table as for
+ *                          yds_ground_update plus the pixels - frame f is frame_hw[f] = (h, w) x 3 bytes at frames_dev + frame_off[f]
+ *                          inside a buffer of frames_bytes (refused before anything runs when a frame ends past it), bgr != 0: B, G, R
+ *                          bytes; out6 [m][6] items, first_out [n_frames + 1] (may be NULL) their split by frame, cap in items.
+ * yds_snap_get_tracks   <- the table of one stream in entry order (each array may be NULL): ids, classes, scores, n_seen, box4
+ *                          [m][4], tag_best, t_first, t_best, t_last, thumbs [m][128][64][3].  Call with cap 0 for the count.
+ * yds_snap_get_archive  <- the ring of one stream, oldest first: the same columns and t_closed.
+ * yds_snap_get_pool     <- the picture pool of one stream: its free slots and all its slots (capacity of the table + archive); at any
+ *                          time free + live entries with a picture + ring occupants = slots.
+ * yds_snap_set_timing / _last_us: HIP events around the launches: what = 0 score, 1 decide, 2 commit.
+ * yds_pipeline_set_snapshots: with a handle of at least as many streams as the pipeline every step adds the three launches behind the
+ *   ground launch (if there is one), ahead of the identity collect launch and of the step's one synchronisation, in every entry
+ *   (plain, window, mixed sizes, per-stream windows), over the frames of the step being associated, in their byte order
+ *   (yds_pipeline_set_frame_order); tracker rows are in whole-frame pixels in all of them.  NULL switches it off.  Refused while a
+ *   look-ahead pass is in flight.
+ * yds_pipeline_last_snapshots: the items of the last step (tag = the frame of the step); already on the host.
+ * Limits: the box is the tracker's posterior box; thumbnails are taken from the frames as they were handed over, BEFORE any output
+ *   stage, so anonymisation does not mask them; the score knows nothing about pose or occlusion; no face detection, no JPEG. */
+typedef struct yds_snap yds_snap;
+#define YDS_SNAP_H 128
+#define YDS_SNAP_W 64
+#define YDS_SNAP_MAX_ARCHIVE 4096
+#define YDS_SNAP_BEST 0
+#define YDS_SNAP_CLOSED 1
+yds_snap *yds_snap_create(int n_streams, int max_age, int archive);
+void yds_snap_destroy(yds_snap *);
+int yds_snap_set_stream(yds_snap *, int stream, int class_id, int min_w, int min_h);
+int yds_snap_reset(yds_snap *, int stream);
+int yds_snap_update(yds_snap *, const int32_t *rows6_host, const int32_t *first, const int32_t *stream_of, const double *frame_time,
+                    int n_frames, const uint8_t *frames_dev, const uint64_t *frame_off, const int32_t *frame_hw, size_t frames_bytes, int bgr,
+                    int32_t *out6_host, int32_t *first_out, int cap, int *n_out);
+int yds_snap_get_tracks(yds_snap *, int stream, int32_t *ids, int32_t *classes, int32_t *scores, int32_t *n_seen, int32_t *box4,
+                        int32_t *tag_best, double *t_first, double *t_best, double *t_last, uint8_t *thumbs, int cap, int *n);
+int yds_snap_get_archive(yds_snap *, int stream, int32_t *ids, int32_t *classes, int32_t *scores, int32_t *n_seen, int32_t *box4,
+                         int32_t *tag_best, double *t_first, double *t_best, double *t_last, double *t_closed, uint8_t *thumbs, int cap, int *n);
+int yds_snap_get_pool(yds_snap *, int stream, int *n_free, int *n_slots);
+int yds_snap_set_timing(yds_snap *, int on);
+int yds_snap_last_us(yds_snap *, int what, float *us);
+int yds_pipeline_set_snapshots(yds_pipe *, yds_snap *);
+int yds_pipeline_last_snapshots(yds_pipe *, int32_t *items6_host, int32_t *frame_host, int cap, int *n_out);
+
 /* ---- cross-camera identities: one global id per person, kept on the device ---------------------------------------------------------
  * No reference counterpart (the reference tracks one camera); tests/identity_ref.py restates the rules below in numpy / scipy.
  * An identity map is bound to an ordered list of S trackers (stream = index), all with the cosine metric and a finite nn_budget.  It

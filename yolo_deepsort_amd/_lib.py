@@ -230,6 +230,18 @@ SIGNATURES = {
     "yds_ground_last_us": (_I, [_P, _I, _P]),
     "yds_pipeline_set_ground": (_I, [_P, _P]),
     "yds_pipeline_last_ground": (_I, [_P, _P, _P, _I, _P]),
+    "yds_snap_create": (_P, [_I, _I, _I]),
+    "yds_snap_destroy": (None, [_P]),
+    "yds_snap_set_stream": (_I, [_P, _I, _I, _I, _I]),
+    "yds_snap_reset": (_I, [_P, _I]),
+    "yds_snap_update": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _SZ, _I, _P, _P, _I, _P]),
+    "yds_snap_get_tracks": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "yds_snap_get_archive": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "yds_snap_get_pool": (_I, [_P, _I, _P, _P]),
+    "yds_snap_set_timing": (_I, [_P, _I]),
+    "yds_snap_last_us": (_I, [_P, _I, _P]),
+    "yds_pipeline_set_snapshots": (_I, [_P, _P]),
+    "yds_pipeline_last_snapshots": (_I, [_P, _P, _P, _I, _P]),
     "yds_overlay_tracks_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P, _P]),
     "yds_overlay_tracks_bgr_masked": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32, _P]),
     "yds_anonymize_frames": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, C.c_uint32]),

@@ -282,9 +282,9 @@ struct ActFrame {
     double t;
     const double *row_time;
 };
-// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps, ground plane; their shared frame is
+// What the driver of a step needs of a per-stream table stage (actions, zones, heat maps, ground plane, snapshots; their shared frame is
 // track_stage.h, their Python front yolo_deepsort_amd/track_stage.py).  The slots of a step, in launch order:
-enum StageSlot { STAGE_ACTIONS, STAGE_ZONES, STAGE_HEAT, STAGE_GROUND, N_STAGES };
+enum StageSlot { STAGE_ACTIONS, STAGE_ZONES, STAGE_HEAT, STAGE_GROUND, STAGE_SNAP, N_STAGES };
 // What a call reported, frame k = items [first[k], first[k + 1]): `rows` holds `width` int32 per item (a stage names its width and
 // columns below), `tags` one frame tag per item and `times` doubles per item where the stage has them.
 struct StageReport {
@@ -328,6 +328,17 @@ struct HeatmapIface : TrackStageIface {
 // descriptors as the zone stage.  It reports one int32[8] record per counted row: id, class, qx, qy, vx, vy, speed, cell.  A stream
 // without a spec (yds_ground_set_stream) is skipped.
 struct GroundIface : TrackStageIface {};          // report.rows [m][8]; report.tags [m] the tag of the frame every record belongs to
+
+// --------------------------------------------------------------------------------------------- snapshots
+// Implemented in snapshot.hip: per stream a table of tracks with the best thumbnail (uint8 RGB 128 x 64) seen of each, its score, box
+// and time, and an archive ring of the snapshots of tracks that left, advanced over the frames of a call by THREE launches (score,
+// decide, commit) over the same frame descriptors as the zone stage.  The one stage that reads pixels: ActFrame carries none, so the
+// driver of a step hands them over before enqueue - frame tag k of the call is geom_by_tag[k].h x .w x 3 bytes at frames +
+// geom_by_tag[k].off, bgr: the bytes are B, G, R.  The table is copied; the pixels must stay device-readable until the call has been
+// collected, and serve that one call.  A stream without a spec (yds_snap_set_stream) is skipped.
+struct SnapIface : TrackStageIface {              // report.rows [m][6] tag, id, class, kind, score, aux; report.tags [m] = column 0
+    virtual void set_pixels(const uint8_t *frames, const FrameGeom *geom_by_tag, int n, bool bgr) = 0;
+};
 
 // --------------------------------------------------------------------------------------------- tracker
 // Implemented in tracker.hip.  A tracker is state; the association driver (TrackerGroupIface) advances it.
@@ -404,3 +415,4 @@ struct yds_ident { yds::IdentityIface *i; };
 struct yds_zones { yds::ZonesIface *z; };
 struct yds_heatmap { yds::HeatmapIface *h; };
 struct yds_ground { yds::GroundIface *g; };
+struct yds_snap { yds::SnapIface *s; };

@@ -581,6 +581,12 @@ public:
             std::vector<int64_t> seen(frames_seen);
             for (int b = 0; b < batch; ++b) times[b] = given.empty() ? (double)seen[stream_of[b]]++ / 25.0 : given[b];
             group->set_stages(stages, times.data());
+            if (SnapIface *snap = static_cast<SnapIface *>(stages[STAGE_SNAP])) {      // the one stage that reads pixels: this step's frames
+                std::vector<FrameGeom> by_frame(cur.geo.frames);
+                if (!cur.geo.mixed())
+                    for (int b = 0; b < batch; ++b) by_frame.push_back(FrameGeom{(uint64_t)b * cur.geo.h * cur.geo.w * 3, cur.geo.h, cur.geo.w});
+                snap->set_pixels(cur.frames, by_frame.data(), batch, frames_bgr);
+            }
         }
         for (int b = 0; b < batch; ++b) ++frames_seen[stream_of[b]];
         for (StageReport &r : last) r = StageReport();
@@ -606,12 +612,12 @@ public:
         stream_of.assign(stream_of_frame, stream_of_frame + n);
     }
 
-    // ---- the table stages (yds_pipeline_set_actions / _set_zones / _set_heatmap / _set_ground; video_detect.py:151-152 for every
+    // ---- the table stages (yds_pipeline_set_actions / _set_zones / _set_heatmap / _set_ground / _set_snapshots; video_detect.py:151-152 for every
     //      stream of a step): a handle of at least as many streams as the pipeline, geometry in each stream's own frame pixels;
     //      nullptr switches the stage off ----
     void set_stage(StageSlot slot, TrackStageIface *sg) {
-        static const char *const setter[N_STAGES] = {"set_actions", "set_zones", "set_heatmap", "set_ground"};
-        static const char *const noun[N_STAGES] = {"an action", "a zones", "a heatmap", "a ground"};
+        static const char *const setter[N_STAGES] = {"set_actions", "set_zones", "set_heatmap", "set_ground", "set_snapshots"};
+        static const char *const noun[N_STAGES] = {"an action", "a zones", "a heatmap", "a ground", "a snapshots"};
         if (pending.frames || ahead.reid_in_flight) fail("pipeline: %s while a look-ahead pass is in flight (consume it with a step first)", setter[slot]);
         if (sg) sg->check_for((int)trks.size(), noun[slot]);
         stages[slot] = sg;
@@ -845,6 +851,16 @@ int yds_pipeline_set_heatmap(yds_pipe *p, yds_heatmap *h) {
 int yds_pipeline_set_ground(yds_pipe *p, yds_ground *g) {
     YDS_API_BEGIN
     p->p->set_stage(yds::STAGE_GROUND, g ? g->g : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_set_snapshots(yds_pipe *p, yds_snap *g) {
+    YDS_API_BEGIN
+    p->p->set_stage(yds::STAGE_SNAP, g ? g->s : nullptr);
+    YDS_API_END
+}
+int yds_pipeline_last_snapshots(yds_pipe *p, int32_t *items6_host, int32_t *frame_host, int cap, int *n_out) {
+    YDS_API_BEGIN
+    p->p->give_last(yds::STAGE_SNAP, "snapshot items", 6, items6_host, frame_host, nullptr, cap, n_out);
     YDS_API_END
 }
 int yds_pipeline_last_ground(yds_pipe *p, int32_t *rows8_host, int32_t *frame_host, int cap, int *n_out) {

@@ -13,6 +13,7 @@ import numpy as np
 
 from .action import as_device_actions
 from .ground import as_device_ground
+from .snapshot import as_device_snapshots
 from .heatmap import as_device_heatmap
 from .label_draw import LabelDrawer, put_text
 from .loaders import load_classes
@@ -218,7 +219,8 @@ def _is_frame_iterable(source):
     return hasattr(source, "__iter__") and not isinstance(source, (str, bytes)) and not hasattr(source, "isOpened")
 
 
-STAGE_FRONTS = dict(actions=as_device_actions, zones=as_device_zones, heatmap=as_device_heatmap, ground=as_device_ground)
+STAGE_FRONTS = dict(actions=as_device_actions, zones=as_device_zones, heatmap=as_device_heatmap, ground=as_device_ground,
+                    snapshots=as_device_snapshots)
 
 
 def fresh_stage(name, x, n_sources, *max_age):
@@ -571,7 +573,8 @@ class VideoDetector:
                 cv2.destroyAllWindows()
 
     def detect_streams(self, sources, frames_per_stream=None, show_fps=True, mixed_sizes=False, stream_win_sizes=None, global_ids=False,
-                       identity_memory=None, zones=None, zone_max_age=30, heatmap=None, heatmap_max_age=30, ground=None, ground_max_age=30):
+                       identity_memory=None, zones=None, zone_max_age=30, heatmap=None, heatmap_max_age=30, ground=None, ground_max_age=30,
+                       snapshots=None, snapshot_max_age=30):
         """Many sources (cameras, files, iterables of RGB frames) on one GPU: a generator that yields, per step, a list of
         (stream_index, bgr_image, hold_detections, actions) for every frame read in that step, streams in the order given, each
         stream's frames in time order.  Each stream gets its own self.tracker.clone() (one tracker per stream, the Extractor shared:
@@ -622,6 +625,13 @@ class VideoDetector:
         after ground_max_age unseen processed frames, frame times are those of the action stage.  Read stream_ground() (the step's
         records: plan position, velocity, speed, cell per person) and site_map(layer) between the yields; the yielded items and
         images do not change.  ValueError naming ground for a spec the device refuses.
+        snapshots: each track's best crop ON THE DEVICE inside the step (MultiStreamPipeline.set_snapshots) - one snapshot.SnapSpec
+        for all streams, a list with one (or None: that camera is skipped) per stream, a snapshot.SnapshotBook or a
+        snapshot.DeviceSnapshotBook (their specs and max_age; never their tables): every stream starts with an empty table and an
+        empty archive ring, entries close after snapshot_max_age unseen processed frames, frame times are those of the action
+        stage.  Read stream_snapshots() (the records with their 128 x 64 RGB thumbnails) and stream_snapshot_events() between the
+        yields; the yielded items and images do not change.  The thumbnails are taken from the frames as they were read, before the
+        output stage: anonymize= does not mask them.  ValueError naming snapshots for a spec the device refuses.
         device_overlay (the constructor's flag, on by default; YDS_HOST_OVERLAY turns it off) runs the generator as a staged engine
         (_detect_streams_device): a reader thread forms the steps and uploads them from pinned staging blocks, the step runs on the
         caller's thread in lock-step with the yields and takes the next staged step along for its early detector pass, and the
@@ -650,7 +660,7 @@ class VideoDetector:
         # stage for what the device refuses
         stages = {name: fresh_stage(name, x, len(sources), *age)
                   for name, x, *age in (("actions", self.action_id), ("zones", zones, zone_max_age), ("heatmap", heatmap, heatmap_max_age),
-                                        ("ground", ground, ground_max_age)) if x is not None}
+                                        ("ground", ground, ground_max_age), ("snapshots", snapshots, snapshot_max_age)) if x is not None}
         if not (self._batchable() or self._batchable_windows()):
             raise ValueError("VideoDetector.detect_streams needs this package's DeepSort with its Extractor and nms_max_overlap=1")
         if mixed_sizes and self.image_detector.win_size is not None:
@@ -670,6 +680,7 @@ class VideoDetector:
         if global_ids:
             pipe.set_identities(True, **memory)
         self._stream_ground = [[] for _ in range(S)]
+        self._stream_snap_events = [[] for _ in range(S)]
         self._stream_zone_events = [[] for _ in range(S)]
         self._streams_pipe = pipe                        # search_streams / link_stream_track reach the trackers between the yields
         on = dict({name: name in stages for name in STAGE_FRONTS}, timed=bool(stages))
@@ -715,6 +726,10 @@ class VideoDetector:
             self._stream_ground = [[] for _ in self._stream_ground]
             for s, rows in zip(plan["streams"], pipe.last_ground() if n else []):
                 self._stream_ground[s].append(rows)
+        if on["snapshots"]:                              # the items of this step's processed frames, per stream in time order
+            self._stream_snap_events = [[] for _ in self._stream_snap_events]
+            for s, items in zip(plan["streams"], pipe.last_snapshot_events() if n else []):
+                self._stream_snap_events[s].append(items)
         return outs, step_acts, step_dets
 
     def _detect_streams_device(self, pipe, sources, F, show_fps, mixed_sizes, on, lookahead=True):
@@ -808,7 +823,7 @@ class VideoDetector:
         """The pipe of the running generator for a reader of the stage ``name``: ValueError outside the generator, and for one
         started without the stage."""
         pipe = self._live_streams_pipe(who)
-        if getattr(pipe, "heat" if name == "heatmap" else name, None) is None:
+        if getattr(pipe, {"heatmap": "heat", "snapshots": "snap"}.get(name, name), None) is None:
             raise ValueError("VideoDetector.%s needs detect_streams(..., %s=...)" % (who, name))
         return pipe
 
@@ -853,6 +868,20 @@ class VideoDetector:
         for a generator started without ground): ``layer`` as int64 [gh, gw], read from the device; layer=None: all five layers
         [5, gh, gw]; MultiStreamPipeline.ground_layers."""
         return self._stage_pipe("site_map", "ground").ground_layers(layer)
+
+    def stream_snapshots(self, stream=None, archive=False):
+        """The snapshots of the running detect_streams(snapshots=...) generator, between two of its yields (ValueError outside, and
+        for a generator started without snapshots): the records of ``stream`` - dicts of id, cls, score, n_seen, box, tag_best,
+        t_first, t_best, t_last and thumb (uint8 [128, 64, 3] RGB) in table order, read from the device; archive=True: the archive
+        ring, oldest first, with t_closed - or a list of such lists, one per stream; MultiStreamPipeline.snapshots."""
+        return self._stage_pipe("stream_snapshots", "snapshots").snapshots(stream, archive)
+
+    def stream_snapshot_events(self, stream=None):
+        """The snapshot items of the last step of the running detect_streams(snapshots=...) generator, between two of its yields
+        (ValueError outside, and for a generator started without snapshots): for ``stream`` one entry per frame of it that the
+        step processed, in time order - int32 [m, 6] = frame of the step, track id, class, kind, score, aux, None where the
+        detector returned None - or a list of such lists, one per stream; MultiStreamPipeline.last_snapshot_events."""
+        return self._stage_report("stream_snapshot_events", "snapshots", "_stream_snap_events", stream)
 
     def stream_identity_map(self):
         """The IdentityMap of the running detect_streams(global_ids=True) generator, between two of its yields (ValueError outside,

@@ -107,11 +107,11 @@ class Pipeline:
 
     def _set_stage(self, name, as_device, x, *max_age):
         """One table stage of every following step (yds_pipeline_set_<name>): x as the stage's device object (track_stage.py
-        as_device), None = off.  The object is kept as self.actions / .zones / .heat / .ground: the handle lives while the
+        as_device), None = off.  The object is kept as self.actions / .zones / .heat / .ground / .snap: the handle lives while the
         pipeline names it."""
         dev = None if x is None else as_device(x, getattr(self, "n_streams", 1), *max_age)
         _lib.check(getattr(_lib.load(), "yds_pipeline_set_" + name)(self._h, None if dev is None else dev.handle))
-        setattr(self, "heat" if name == "heatmap" else name, dev)
+        setattr(self, {"heatmap": "heat", "snapshots": "snap"}.get(name, name), dev)
         return dev
 
     def _last_report(self, dev, entry, columns):
@@ -266,6 +266,39 @@ class Pipeline:
         if dev is None:
             return None
         return dev.layers() if layer is None else dev.layer(layer)
+
+    def set_snapshots(self, snapshots=None, max_age=30):
+        """The snapshot stage of every following step: ``snapshots`` is a snapshot.DeviceSnapshotBook of at least as many streams as
+        the pipeline (its tables, rings and pictures are used as they are), a snapshot.SnapshotBook (its specs and max_age go to the
+        device, fresh tables), one snapshot.SnapSpec for all streams or a list with one (or None: that stream is skipped) per stream;
+        None switches the stage off.  A step then adds three launches behind the ground launch, over the frames of the step where
+        they lie in HBM (before any output stage: anonymisation does not mask the pictures); ``last_snapshot_events()`` holds its
+        items and ``snapshots(stream)`` reads the pictures; the step's own return value does not change.  ValueError naming
+        snapshots for anything the device refuses; refused (YdsError) while a look-ahead pass is in flight."""
+        from .snapshot import as_device_snapshots
+        return self._set_stage("snapshots", as_device_snapshots, snapshots, max_age)
+
+    def last_snapshot_events(self, stream=None):
+        """The snapshot items of the last step, int32 [m, 6] = frame of the step, track id, class, kind (snapshot.BEST: the picture
+        changed, aux = n_seen; snapshot.CLOSED: aux = the ring position or -1), score, aux: a list with one array per frame of the
+        step (None where the frame's rows were None), or with ``stream`` the items of that stream's frames of the step in time
+        order as one array.  Already on the host; None when the stage is off or no step ran."""
+        got = self._last_report(getattr(self, "snap", None), "snapshots", [(np.int32, 6), (np.int32, 1)])
+        if got is None:
+            return None
+        counts, (rows, frame) = got
+        per = [None if counts[b] < 0 else rows[frame == b].copy() for b in range(len(counts))]
+        if stream is None:
+            return per
+        streams = self._step_streams or [0] * len(counts)
+        mine = [per[b] for b in range(len(counts)) if streams[b] == int(stream) and per[b] is not None]
+        return np.concatenate(mine) if mine else np.zeros((0, 6), np.int32)
+
+    def snapshots(self, stream=None, archive=False):
+        """The snapshot records of ``stream`` as the last step left them, read from the device (snapshot.DeviceSnapshotBook.tracks;
+        archive=True: the archive ring instead), or a list of such lists for all streams; None when the stage is off."""
+        dev = getattr(self, "snap", None)
+        return None if dev is None else self._per_stream("snapshots", stream, dev.archive if archive else dev.tracks)
 
     def _search_trackers(self):
         return getattr(self, "deepsorts", None) or [self.ds]
